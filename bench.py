@@ -2,12 +2,17 @@
 """bench.py — audio-hours/sec of one full Conformer-Transducer train step on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus 1 --steps K --warmup W --full   (+ rooflines, three timed regions, box calibration, sub-lines, CPU baseline)
 
 A "step" = log-mel + SpecAugment + Conformer encoder + LSTM prediction net + joint + RNN-T loss + full backward +
 (RCCL gradient all-reduce) + Adam, on one batch of synthetic 16 kHz utterances already resident in HBM.
 Workload (BASELINE.json metric "audio-hours/sec (train step) Conformer-M RNN-T"): Conformer-M, 32 utterances per GPU
 (weak scaling: global batch = 32 x N), LibriSpeech-shaped durations (lognormal, mean ~12.3 s, clipped to [1.3, 29.7] s,
 ~3.7 BPE tokens/s), padded to the batch maximum.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line.  Everything else the line can carry (see
+--full) runs only with --full.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (inputs are seeded:
+two builds run with the same arguments can be compared output for output).
 """
 import argparse
 import json
@@ -147,7 +152,7 @@ def sub_line(argv, timeout_s=150):
     """One more bench line (another workload of BASELINE.json's metric) from a child process: its JSON line parsed, the bulky keys dropped."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-extras", "--regions", "1"] + argv
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-extras", "--regions", "1"] + argv
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
         for line in reversed(r.stdout.splitlines()):
@@ -306,7 +311,8 @@ def dp_route_line(argv_model, steps=10, warmup=3, timeout_s=150):
     multi-GPU job does except the wire time, so the cost of the route is visible in every default run."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--dp-hooks", "--no-cpu-baseline", "--no-extras", "--steps", str(steps), "--warmup", str(warmup)] + argv_model
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--dp-hooks", "--no-cpu-baseline", "--no-extras", "--steps", str(steps),
+           "--warmup", str(warmup)] + argv_model
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
         for line in reversed(r.stdout.splitlines()):
@@ -432,6 +438,33 @@ def cpu_baseline(size, vocab, batch=32, timeout_s=300):
         return {"value": None, "unit": "audio-hours/sec", "error": f"CPU baseline exceeded {timeout_s} s"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_PARAM_SAMPLE = 1 << 20  # elements of the parameters / gradients written by --dump-outputs (4 MiB each in f32)
+
+
+def param_sample(W, names, seed=0):
+    """A fixed, seeded sample of a parameter-shaped buffer exported under the reference's (Keras) variable names and shapes
+    (ParamStore.export_keras), so independent of the device layout (padding, ordering): the variables of `names` concatenated in
+    name order, at DUMP_PARAM_SAMPLE distinct positions in sorted order."""
+    vec = torch.cat([W[k].reshape(-1) for k in names])
+    idx = np.sort(np.random.default_rng(seed).choice(vec.numel(), min(vec.numel(), DUMP_PARAM_SAMPLE), replace=False))
+    return vec[torch.from_numpy(idx)]
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 stays float64), at most DUMP_MAX_BYTES in all."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte bound")
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def bench_decode(args, model, cfg, dev):
     """Greedy transducer search (Transducer.recognize, base_transducer.py:474-575) RTF = wall time / audio duration on
     32 x 10 s synthetic utterances.  Headline = the token-exact mode (tests/test_parity_baseline_gpu.py: a bf16-trained model
@@ -474,7 +507,8 @@ def bench_decode(args, model, cfg, dev):
     bias, ntok = best if best is not None else (hi, -1)
     ntok, sat = probe(bias)
     res, toks = {}, {}
-    for prec in ("f32", "bf16") if args.dtype == "bf16" else ("f32",):
+    # the headline is the token-exact mode; the bf16-encoder mode is a second precision (--full)
+    for prec in ("f32", "bf16") if args.dtype == "bf16" and args.full else ("f32",):
         for _ in range(args.warmup):
             out = model.recognize(inp, precision=prec)
         torch.cuda.synchronize()
@@ -484,6 +518,18 @@ def bench_decode(args, model, cfg, dev):
         torch.cuda.synchronize()
         res[prec] = ((time.perf_counter() - t0) / args.steps, int((out.tokens != 0).sum().item()), int((out.tokens != 0).sum(1).max().item()))
         toks[prec] = out.tokens.clone()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"tokens": toks["f32"]})
+    dt, ntok, max_row_tokens = res["f32"]
+    line = {"metric": "greedy-decode RTF Conformer-%s RNN-T" % args.model, "value": round(dt / (B * secs), 6), "unit": "RTF (wall s / audio s)",
+            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": False,
+            "dtype": "f32", "data": "synthetic", "vs_baseline": None,
+            "config": {"workload": f"greedy search (recognize_batch) over {B} x {secs:.0f} s utterances incl. log-mel + encoder; token-exact mode "
+                                   f"(f32 master weights, exact-f32 MFMA encoder; search arithmetic f32), blank bias +{bias:.3f} (calibrated)",
+                       "tokens_emitted": ntok, "global_batch": B, "training_storage": args.dtype}}
+    if not args.full:
+        print(json.dumps(line))
+        return
     # breakdown of the token-exact mode: front end + encoder vs the greedy search, HIP events around each half
     twin = model.inference_twin() if model.dtype != torch.float32 else model
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -504,13 +550,6 @@ def bench_decode(args, model, cfg, dev):
     rows = B * T_enc
     enc_flop = 2.0 * (cfg.num_blocks * (rows * (2 * (2 * d * 4 * d) + d * 3 * H * dh + H * dh * d + d * 2 * d + d * d) + 2 * T_enc * H * dh * d
                                         + B * H * T_enc * T_enc * dh * 3) + rows * F2 * 9 * C * C + rows * F2 * C * d)
-    dt, ntok, max_row_tokens = res["f32"]
-    line = {"metric": "greedy-decode RTF Conformer-%s RNN-T" % args.model, "value": round(dt / (B * secs), 6), "unit": "RTF (wall s / audio s)",
-            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": False,
-            "dtype": "f32", "data": "synthetic", "vs_baseline": None,
-            "config": {"workload": f"greedy search (recognize_batch) over {B} x {secs:.0f} s utterances incl. log-mel + encoder; token-exact mode "
-                                   f"(f32 master weights, exact-f32 MFMA encoder; search arithmetic f32), blank bias +{bias:.3f} (calibrated)",
-                       "tokens_emitted": ntok, "global_batch": B, "training_storage": args.dtype}}
     line["breakdown"] = {"frontend_encoder_ms": round(enc_ms, 3), "search_ms": round(srch_ms, 3),
                          "encoder_f32_tflops": round(enc_flop / (enc_ms * 1e-3) / 1e12, 1), "encoder_f32_mfma_frac": round(enc_flop / (enc_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
                          "search_us_per_token": round(srch_ms * 1e3 / max(ntok, 1), 2),
@@ -555,7 +594,8 @@ def bench_ctc_decode(args, dev, dtype):
     sig = torch.from_numpy(np.clip(rng.standard_normal((B, int(secs * 16000))).astype(np.float32) * 0.1, -1, 1)).to(dev)
     inp = PredictInput(sig, torch.full((B,), int(secs * 16000), dtype=torch.int32))
     res = {}
-    for name, fn in (("greedy", lambda: model.recognize(inp)), ("beam10", lambda: model.recognize_beam(inp, beam_width=10))):
+    modes = (("greedy", lambda: model.recognize(inp)), ("beam10", lambda: model.recognize_beam(inp, beam_width=10)))
+    for name, fn in modes if args.full else modes[:1]:  # the headline is greedy; the beam search is a line extra (--full)
         for _ in range(args.warmup):
             out = fn()
         torch.cuda.synchronize()
@@ -564,13 +604,15 @@ def bench_ctc_decode(args, dev, dtype):
             out = fn()
         torch.cuda.synchronize()
         res[name] = (time.perf_counter() - t0) / args.steps
+        if name == "greedy" and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"tokens": out.tokens})
     dt = res["greedy"]
+    config = {"workload": f"CtcModel.recognize over {B} x {secs:.0f} s utterances incl. log-mel + encoder (random weights)", "global_batch": B}
+    if "beam10" in res:
+        config.update(beam_search_width10_rtf=round(res["beam10"] / (B * secs), 6), beam_search_ms=round(res["beam10"] * 1e3, 2))
     print(json.dumps({"metric": "CTC greedy-decode RTF Conformer-CTC(S)", "value": round(dt / (B * secs), 6), "unit": "RTF (wall s / audio s)",
                       "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": False,
-                      "dtype": args.dtype, "data": "synthetic", "vs_baseline": None,
-                      "config": {"workload": f"CtcModel.recognize over {B} x {secs:.0f} s utterances incl. log-mel + encoder (random weights)",
-                                 "global_batch": B, "beam_search_width10_rtf": round(res["beam10"] / (B * secs), 6),
-                                 "beam_search_ms": round(res["beam10"] * 1e3, 2)}}))
+                      "dtype": args.dtype, "data": "synthetic", "vs_baseline": None, "config": config}))
 
 
 def relaunch_cmd(gpus, argv, env):
@@ -600,11 +642,14 @@ class _StubModel:
     def __init__(self, dp):
         self.dp, self.ps, self.timers, self.timer_work, self.time_sections = dp, self._PS(), {}, {}, False
         self.buf = torch.ones(1024)
+        self.calls = 0
 
     def train_step(self, data):
         if self.dp:
             self.dp.allreduce_stats_(self.buf.clone())
-        return {"loss": None}
+        self.calls += 1
+        # placeholder loss = the number of train steps so far: what --dump-outputs writes shows which step it came from
+        return {"loss": torch.full((len(data.labels.labels_length),), float(self.calls))}
 
 
 def main():
@@ -621,11 +666,18 @@ def main():
     ap.add_argument("--workload", default=None, help="'S-10s' = BASELINE cfg2 (10 s utterances); default LibriSpeech-shaped")
     ap.add_argument("--mode", default="train", choices=["train", "decode", "ctc-decode"],
                     help="decode = transducer greedy-search RTF (second half of BASELINE.json's metric); ctc-decode = Conformer-CTC greedy / beam RTF")
-    ap.add_argument("--regions", type=int, default=3,
+    ap.add_argument("--regions", type=int, default=None,
                     help="timed regions of --steps steps each, every one bracketed by barrier + synchronize; the line reports the MEDIAN region "
-                         "(ms_per_step / value) plus every region, the minimum and the spread")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the reference-padding second measurement of the default run")
+                         "(ms_per_step / value) plus every region, the minimum and the spread (default 1; 3 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: rooflines (event timers inside the timed steps), three timed regions, the box "
+                         "calibration, the reference-padding / joint-recompute / data-parallel-route legs, the sub-lines of the other "
+                         "configurations, the CPU baseline; the bf16-encoder mode of --mode decode, the beam search of --mode ctc-decode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): train = per-utterance "
+                         "losses + a fixed seeded sample of the parameters and gradients after it; decode = tokens")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the extra legs and sub-lines")
     ap.add_argument("--no-specaugment", action="store_true")
     ap.add_argument("--dp-hooks", action="store_true",
                     help="with --gpus 1: run the DATA-PARALLEL code path (split block phases around the sync-BN all-reduces, bucketed gradient "
@@ -710,7 +762,9 @@ def main():
     # the global batch is padded as one (datasets.py:102-138,342-365) - and no rank waits for a longer batch on another.
     batches = [make_batch(cfg, 2 if stub else args.batch, seed=10 + 13 * i, padding=args.padding, size="S-10s" if stub else size) for i in range(nb)]
     data = [to_train_data(b, dev) for b in batches]
-    model.timers = {}
+    # HIP events around the joint projection and the loss inside the timed steps feed the rooflines (--full) and the section table
+    timed = args.full or bool(os.environ.get("TFASR_BENCH_SECTIONS"))
+    model.timers = {} if timed else None
     model.time_sections = bool(os.environ.get("TFASR_BENCH_SECTIONS"))
     if not stub:
         torch.cuda.synchronize()
@@ -720,18 +774,18 @@ def main():
         return model.train_step(data[i % nb])
 
     box = None
-    if not stub and rank == 0 and world == 1 and not args.no_extras:
+    if args.full and not stub and rank == 0 and world == 1 and not args.no_extras:
         box = {"before": box_snapshot(local_rank)}
     for i in range(args.warmup):
         one_step(i)
     flush_c_stdio()  # RCCL's start-up banner (C stdio) leaves every rank's buffer now, long before rank 0's JSON line
-    model.timers, model.timer_work = {}, {}
+    model.timers, model.timer_work = ({} if timed else None), {}
     n_launch0 = 0
     if not stub:
         from tensorflowasr_amd import kernels as _K
 
     # `--regions` timed regions of EXACTLY --steps steps, each bracketed by barrier + synchronize on both sides and reduced with MAX over
-    # the ranks; the reported step time is the MEDIAN region's (one region = the contract's single timed region: --regions 1)
+    # the ranks; the reported step time is the MEDIAN region's (one region = the contract's single timed region: the default of a plain run)
     region_ms, region_host_ms, region_secs = [], [], []
     launches_per_step = None
     step_no = 0
@@ -739,7 +793,9 @@ def main():
     if dp_acc is not None:
         dp_acc.enable()
     rank_ms = []
-    for r in range(max(1, args.regions)):
+    regions = args.regions if args.regions is not None else (3 if args.full else 1)
+    last = None
+    for r in range(max(1, regions)):
         torch.cuda.synchronize()
         if dp:
             dp.barrier()
@@ -748,7 +804,7 @@ def main():
         t0 = time.perf_counter()
         secs_local = 0.0
         for i in range(args.steps):
-            one_step(step_no)
+            last = one_step(step_no)
             secs_local += batches[step_no % nb]["seconds"]
             step_no += 1
         t_host = time.perf_counter() - t0  # host-side enqueue time (the GPU may still be running)
@@ -773,6 +829,15 @@ def main():
     dt = ms_per_step * 1e-3 * args.steps
     secs_total = region_secs[med]
     value = (secs_total / 3600.0) / dt
+    if args.dump_outputs and rank == 0 and last is not None:
+        # what the last timed step handed its caller (per-utterance losses) and left in the model: a fixed sample of the f32 master
+        # weights after its optimizer update and of the gradients it computed (the legs of --full run more steps: dumped before them)
+        outs = {} if last["loss"] is None else {"loss": last["loss"]}
+        if not stub:
+            G, P = model.ps.export_keras(model.ps.grad), model.ps.export_keras(model.ps.flat)
+            names = sorted(G)  # the trainable variables (the parameter export also holds the BatchNorm moving statistics)
+            outs.update(params_sample=param_sample(P, names), grads_sample=param_sample(G, names))
+        dump_outputs(args.dump_outputs, outs)
     dp_report = None
     if dp_acc is not None:
         # where this rank's compute stream waited for the wire (dp.Accounting), rank 0's figures and the worst rank's
@@ -792,8 +857,8 @@ def main():
             sys.stderr.write(f"[section] {name:18s} {sum(a.elapsed_time(b) for a, b in tm) / args.steps:8.3f} ms/step over {len(tm) // args.steps} calls\n")
     if rank == 0:
         roof = None
-        tm = model.timers.get("joint_vocab_gemm") or []
-        cn = model.timers.get("cn_dwconv_fwd") or []
+        tm = (model.timers.get("joint_vocab_gemm") or []) if args.full else []
+        cn = (model.timers.get("cn_dwconv_fwd") or []) if args.full else []
         if args.model == "contextnet" and cn:
             # ContextNet is depthwise-conv / BatchNorm heavy: report the HBM roofline of its depthwise convolution (all launches of
             # the timed region: achieved = algorithmic bytes (read x + write y) / measured time)
@@ -826,7 +891,7 @@ def main():
         # RNN-T loss kernels (statistics finalize + alpha/beta lattice + gradient) against the HBM roofline: algorithmic bytes =
         # cells x V x (logit + gradient), time = HIP events around exactly those launches in the timed region
         roof_rnnt = None
-        tl_ = model.timers.get("rnnt_loss") or []
+        tl_ = (model.timers.get("rnnt_loss") or []) if args.full else []
         if tl_ and args.model != "contextnet":
             ms = float(np.mean([a.elapsed_time(b) for a, b in tl_]))
             by = float(np.mean(model.timer_work["rnnt_loss"]))
@@ -844,8 +909,6 @@ def main():
             "config": {"workload": "STUB (launch-logic test, not a measurement)" if stub else f"{'ContextNet' if args.model == 'contextnet' else 'Conformer-' + args.model} transducer full train step (fwd+RNN-T loss+bwd+Adam), {size} 16 kHz utterances, "
                                    f"{args.batch}/GPU, padding={args.padding}, SpecAugment {'off' if args.no_specaugment else 'on'}, dropout {cfg.dropout}",
                        "global_batch": args.batch * world, "parallelism": f"dp{world}" + (" (data-parallel hooks on, one-rank RCCL group)" if args.dp_hooks and world == 1 else ""), "params": model.ps.num_trainable()},
-            "roofline": roof,
-            "roofline_rnnt": roof_rnnt,
             # kernels this library queued per step (host-side count, tfasr_launch_count; torch's own fills / copies are not in it)
             "launches_per_step": None if launches_per_step is None else round(launches_per_step, 1),
             "dp": dp_report,
@@ -856,10 +919,13 @@ def main():
                         "note": "host_enqueue = wall time the host needs to queue one step's launches; when it approaches ms_per_step the host "
                                 "(its cores shared with other tenants of the node), not the GPU, sets the step time"},
         }
+        if args.full:
+            out.update(roofline=roof, roofline_rnnt=roof_rnnt)
+        extras = args.full and not args.no_extras  # everything below: --full only
         # (this leg runs FIRST of the extra legs, straight behind the timed region: behind the reference-padding leg - other shapes, a
         # differently filled allocator - the same ten steps measured 3 ms slower than as a run of their own, behind the 874 MiB of rotating
         # operand sets of the roofline_by_time probe 9 ms slower; profiles/r05_ab/recompute_leg_order.txt)
-        if world == 1 and not args.no_extras and args.model in ("M", "S") and not stub and dtype == torch.bfloat16:
+        if world == 1 and extras and args.model in ("M", "S") and not stub and dtype == torch.bfloat16:
             # SURVEY section 8(d) "report both": the joint + loss WITHOUT materialised lattice logits (statistics-only projection, gradient
             # epilogue on a re-computed logit tile; TFASR_JOINT_RECOMPUTE=1) next to the default materialised route, same batches
             try:
@@ -890,7 +956,7 @@ def main():
             finally:
                 model.joint_recompute = False
                 model.timers = None
-        if not stub and args.model in ("M", "S") and dtype == torch.bfloat16 and not args.no_extras:
+        if extras and not stub and args.model in ("M", "S") and dtype == torch.bfloat16:
             try:
                 rows_list = [args.batch * int(-(-(-(-(-(-int(np.asarray(b["nsamp"], np.int64).max()) // cfg.frame_step)) // 2)) // 2)) for b in batches]
                 # in-step duration of the grouped weight gradients: a few more steps with the executor's event probe on
@@ -908,7 +974,7 @@ def main():
                 out["roofline_by_time"] = wgrad_group_roofline(cfg, rows_list, dev, in_step=(ms_in, n_in, fl_in))
             except Exception as e:
                 out["roofline_by_time"] = {"value": None, "error": repr(e)[:200]}
-        if world == 1 and not args.no_extras and args.model == "M" and args.padding == "batch" and size == "LibriSpeech-shaped":
+        if world == 1 and extras and args.model == "M" and args.padding == "batch" and size == "LibriSpeech-shaped":
             # BASELINE.md section 2 "report both": the same step with the reference's dataset-maximum padding (every utterance padded
             # to 475 760 samples / 230 labels, datasets.py:342-365).  The packed lattice and the length-aware kernels make the
             # padded LABEL positions free; the padded encoder frames are computed like the reference computes them.
@@ -932,7 +998,7 @@ def main():
                 del rd, rb
             except Exception as e:  # the headline number must still be reported
                 out["reference_padding"] = {"value": None, "error": repr(e)[:200]}
-        if world == 1 and not stub and not args.no_extras and not args.dp_hooks and args.model in ("M", "S") and dtype == torch.bfloat16:
+        if world == 1 and not stub and extras and not args.dp_hooks and args.model in ("M", "S") and dtype == torch.bfloat16:
             # the data-parallel route at one rank: what a rank of an N-GPU job runs, wire time excluded
             dpm = dp_route_line(["--model", args.model, "--batch", str(args.batch), "--padding", args.padding] + (["--workload", args.workload] if args.workload else []))
             out["dp_route_ms"] = None if dpm is None else round(dpm, 3)
@@ -953,7 +1019,7 @@ def main():
             except Exception as e:
                 box["calibration"] = {"value": None, "error": repr(e)[:200]}
             out["box"] = box
-        if world == 1 and not stub and not args.no_extras and not args.dp_hooks and args.model == "M" and args.mode == "train" and dtype == torch.bfloat16 \
+        if world == 1 and not stub and extras and not args.dp_hooks and args.model == "M" and args.mode == "train" and dtype == torch.bfloat16 \
                 and args.padding == "batch" and size == "LibriSpeech-shaped":
             # the rest of BASELINE.json's metric and its other single-GPU configurations, as short lines of their own (child processes,
             # this process idle meanwhile): greedy-decode RTF (M and S), configs[1] (Conformer-S, 32 x 10 s), configs[3] (ContextNet-L)
@@ -963,7 +1029,7 @@ def main():
                              "S": sub_line(["--mode", "decode", "--model", "S", "--steps", "5", "--warmup", "2"])}
             out["cfg2_conformer_S_10s"] = sub_line(["--model", "S", "--steps", "20", "--warmup", "5"])
             out["cfg4_contextnet_L"] = sub_line(["--model", "contextnet", "--steps", "10", "--warmup", "3"])
-        if not args.no_cpu_baseline and world == 1 and not stub:
+        if args.full and not args.no_cpu_baseline and world == 1 and not stub:
             try:
                 if args.model != "contextnet":  # the CPU port baseline is the Conformer oracle
                     out["cpu_baseline"] = cpu_baseline(size if args.model.startswith("S") else "M", cfg.vocab_size, args.batch)

@@ -1,13 +1,13 @@
 """Label-side data format: the tokenizer drop-in against the reference's documented behaviour
-(tensorflow_asr/tokenizers.py) and, when /root/reference is present (build container), its shipped vocabularies."""
+(tensorflow_asr/tokenizers.py) and its shipped LibriSpeech vocabularies (examples/datasets/librispeech: characters/english.vocab,
+sentencepiece/train_bpe_{1000,256}.model), stored as data fixtures under tests/golden/librispeech."""
 import os
 
 import numpy as np
-import pytest
 
 from tensorflowasr_amd import tokenizers as tk
 
-REF = "/root/reference/examples/datasets/librispeech"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "librispeech")
 
 
 def test_normalize_text_rules():
@@ -44,7 +44,6 @@ def test_wordpiece_greedy_longest_match(tmp_path):
     assert t.detokenize(np.array([2, 3, 4, 5, 6])) == ["unaffable running"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference vocabularies only exist in the build container")
 def test_reference_vocabularies_round_trip():
     chars = tk.get({"type": "characters", "blank_index": 0, "vocabulary": f"{REF}/characters/english.vocab"})
     assert chars.num_classes == 29

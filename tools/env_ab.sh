@@ -10,7 +10,7 @@ mkdir -p $O
 cd $R
 run() {  # run "<env assignments>"
   local ms
-  ms=$(env $1 timeout 200 python bench.py --steps ${STEPS:-40} --warmup 8 --no-cpu-baseline --no-extras 2>>$O/err.txt | tail -1 | python -c "import sys,json; print(json.loads(sys.stdin.read())['ms_per_step'])" 2>/dev/null)
+  ms=$(env $1 timeout 200 python bench.py --full --steps ${STEPS:-40} --warmup 8 --no-cpu-baseline --no-extras 2>>$O/err.txt | tail -1 | python -c "import sys,json; print(json.loads(sys.stdin.read())['ms_per_step'])" 2>/dev/null)
   echo "${ms:-FAILED}  ${1:-<default>}" | tee -a $O/results.txt
 }
 : > $O/results.txt

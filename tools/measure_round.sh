@@ -5,15 +5,15 @@ TAG=${1:-round}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-timeout 400 python bench.py > $O/bench_M.json 2> $O/bench_M.err
-timeout 300 python bench.py --model S > $O/bench_S.json 2> $O/bench_S.err
-timeout 200 python bench.py --model S-streaming --no-cpu-baseline --steps 50 > $O/bench_S_streaming.json 2>> $O/bench_S.err
-timeout 200 python bench.py --dp-hooks --no-cpu-baseline --no-extras > $O/bench_M_dp_hooks.json 2>> $O/bench_M.err
-timeout 200 python bench.py --model S --dp-hooks --no-cpu-baseline --no-extras > $O/bench_S_dp_hooks.json 2>> $O/bench_S.err
-timeout 200 python bench.py --mode decode --model S --steps 10 --warmup 2 > $O/decode_S.json 2> $O/decode.err
-timeout 200 python bench.py --mode decode --model M --steps 10 --warmup 2 > $O/decode_M.json 2>> $O/decode.err
-timeout 200 python bench.py --mode ctc-decode --steps 5 --warmup 2 > $O/ctc_decode.json 2>> $O/decode.err
-timeout 300 python bench.py --model contextnet --alpha 2 --steps 20 --warmup 3 --no-cpu-baseline > $O/contextnet_L.json 2> $O/contextnet.err
+timeout 400 python bench.py --full > $O/bench_M.json 2> $O/bench_M.err
+timeout 300 python bench.py --full --model S > $O/bench_S.json 2> $O/bench_S.err
+timeout 200 python bench.py --full --model S-streaming --no-cpu-baseline --steps 50 > $O/bench_S_streaming.json 2>> $O/bench_S.err
+timeout 200 python bench.py --full --dp-hooks --no-cpu-baseline --no-extras > $O/bench_M_dp_hooks.json 2>> $O/bench_M.err
+timeout 200 python bench.py --full --model S --dp-hooks --no-cpu-baseline --no-extras > $O/bench_S_dp_hooks.json 2>> $O/bench_S.err
+timeout 200 python bench.py --full --mode decode --model S --steps 10 --warmup 2 > $O/decode_S.json 2> $O/decode.err
+timeout 200 python bench.py --full --mode decode --model M --steps 10 --warmup 2 > $O/decode_M.json 2>> $O/decode.err
+timeout 200 python bench.py --full --mode ctc-decode --steps 5 --warmup 2 > $O/ctc_decode.json 2>> $O/decode.err
+timeout 300 python bench.py --full --model contextnet --alpha 2 --steps 20 --warmup 3 --no-cpu-baseline > $O/contextnet_L.json 2> $O/contextnet.err
 python tools/lstm_bench.py 32 111 640 > $O/lstm_persist.txt 2>&1
 python tools/lstm_bench.py 32 65 320 >> $O/lstm_persist.txt 2>&1
 python tools/nccl_selfcheck.py > $O/nccl_selfcheck.txt 2>&1

@@ -8,7 +8,7 @@ cd $R
 : > $O/results.txt
 for i in $(seq 1 $ROUNDS); do
   for e in "$@"; do
-    ms=$(env $e timeout 200 python bench.py --steps ${STEPS:-40} --warmup 8 --no-cpu-baseline --no-extras $BENCH_ARGS 2>>$O/err.txt | tail -1 | python -c "import sys,json; print(json.loads(sys.stdin.read())['ms_per_step'])" 2>/dev/null)
+    ms=$(env $e timeout 200 python bench.py --full --steps ${STEPS:-40} --warmup 8 --no-cpu-baseline --no-extras $BENCH_ARGS 2>>$O/err.txt | tail -1 | python -c "import sys,json; print(json.loads(sys.stdin.read())['ms_per_step'])" 2>/dev/null)
     echo "${ms:-FAILED}  $e" | tee -a $O/results.txt
   done
 done
