@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define TFASR_ABI_VERSION 43
+#define TFASR_ABI_VERSION 44
 
 typedef enum {
   TFASR_STATUS_SUCCESS = 0,
@@ -624,6 +624,16 @@ int tfasr_add_act_bwd(const void* a, const void* b, const void* dy, void* d, lon
  * class V-1 as blank (TF's decoder convention) although the model's blank is 0 - pass V-1 to reproduce it. */
 int tfasr_ctc_beam_search_host(const float* logits, const int32_t* logit_len, int B, int T, int V, int beam_width,
                                int blank_index, int32_t* tokens, int32_t* tokens_len, float* log_prob);
+
+/* The same search on the device, stream ordered, with n-best output: tokens [B,P,T] (0-padded), tokens_len [B,P], log_prob [B,P]
+ * hold the top P = top_paths paths of the final beam, best first (exact ties: the smaller label sequence first); paths past the
+ * last live beam are empty with log_prob -inf.  All pointers are device pointers; logits [B,T,V] `dtype` (f32 arithmetic),
+ * logit_len [B].  1 <= beam_width <= 64, 1 <= top_paths <= beam_width, 0 <= blank_index < V, V >= 2.  The workspace size depends
+ * only on (B, T, V, beam_width); nothing synchronises with the host. */
+int tfasr_ctc_beam_search_workspace_size(int B, int T, int V, int beam_width, size_t* bytes);
+int tfasr_ctc_beam_search(const void* logits, const int32_t* logit_len, int B, int T, int V, int beam_width, int top_paths,
+                          int blank_index, int dtype, int32_t* tokens, int32_t* tokens_len, float* log_prob, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Native executor of one Conformer block (ConformerBlock.call, encoders/conformer.py:430-520, and its backward):

@@ -153,7 +153,7 @@ def load(build_if_missing=True):
     return lib
 
 
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 
 STATUS_UNSUPPORTED = 3

@@ -166,3 +166,412 @@ extern "C" int tfasr_ctc_beam_search_host(const float* logits, const int32_t* lo
   }
   return TFASR_STATUS_SUCCESS;
 }
+
+// ================================================================================================================================
+// Device prefix beam search (tfasr_ctc_beam_search): the same decoder as tfasr_ctc_beam_search_host above, stream ordered, with the
+// top `top_paths` paths of the final beam.  Two launches:
+//
+// 1. ctc_beam_frame_kernel, one wave per (b, t) row: the row's log-sum-exp (f32 max + f64 sum, the host routine's arithmetic, so
+//    lp = x - lse comes out as the host's value) and the row's top K = min(2W, V-1) NON-blank classes by (lp desc, class asc).
+//    Why 2W classes are enough: beam i extended by class c scores ptot_i + lp[c], monotone in lp[c], except for the classes that
+//    are "special" to row i: its own last label (a repeat adds pb_i, not ptot_i) and the merge targets (the labels of the beams
+//    whose parent is beam i: their "stay" mass joins the extension).  Row i has at most nb <= W specials, computed explicitly from
+//    logits - lse.  So at least W of the global top 2W classes are regular for row i, and they are row i's best W regular
+//    extensions; an extension outside them is beaten by W candidates of its own row and cannot enter a beam of width W.  The
+//    per-frame search is O(W^2) candidates instead of O(W*V).
+// 2. ctc_beam_search_kernel, one workgroup per utterance, all frames in one launch.  Per frame: stays (merged into their parent's
+//    extension when the parent is a beam, as in the host routine), specials, and each row's first W regular extensions from the
+//    top-K list become candidates in LDS (<= W^2 + 3W); each candidate counts the candidates better than it (early exit at W), the
+//    first W by (total desc, label sequence asc) are the next beam.  Label sequences live in a per-utterance trie in the workspace
+//    with an open-addressing (parent, label) -> node table: one node per label sequence for the whole utterance, so a prefix that
+//    leaves the beam and comes back keeps its mass.  The comparator walks the trie only on an exact tie of totals.
+// ================================================================================================================================
+namespace {
+
+constexpr int BEAM_MAXW = 64;
+constexpr int BEAM_MAXK = 2 * BEAM_MAXW;
+constexpr int BEAM_MAXC = BEAM_MAXW * BEAM_MAXW + 3 * BEAM_MAXW;  // stays + specials (<= 2 per beam) + W regulars per beam
+constexpr int BEAM_THREADS = 256;
+constexpr unsigned long long BEAM_EMPTY = ~0ull;
+
+__device__ __forceinline__ float dlse2(float a, float b) {  // lse2 above, same operation order
+  if (a == -INFINITY) return b;
+  if (b == -INFINITY) return a;
+  const float m = a > b ? a : b;
+  return m + log1pf(expf(-fabsf(a - b)));
+}
+
+// (lp, c) comes before (lq, d) in the frame's class order
+__device__ __forceinline__ bool cls_before(float lp, int c, float lq, int d) { return lp > lq || (lp == lq && c < d); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void ctc_beam_frame_kernel(const T* __restrict__ logits, const int32_t* __restrict__ logit_len,
+                                                             float* __restrict__ lse, float* __restrict__ lp_blank,
+                                                             int32_t* __restrict__ top_c, float* __restrict__ top_lp, int B, int Tm,
+                                                             int V, int K, int blank) {
+  const int lane = threadIdx.x & 63;
+  const long rows = (long)B * Tm;
+  const long w0 = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (long)gridDim.x * (blockDim.x >> 6);
+  for (long r = w0; r < rows; r += nw) {
+    const int b = (int)(r / Tm), t = (int)(r % Tm);
+    if (t >= min(max(logit_len[b], 0), Tm)) continue;  // frames past the utterance are never read
+    const T* row = logits + r * V;
+    float m = -INFINITY;
+    for (int v = lane; v < V; v += 64) m = fmaxf(m, Num<T>::ld(row + v));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    double s = 0.0;
+    for (int v = lane; v < V; v += 64) s += exp((double)Num<T>::ld(row + v) - (double)m);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const float lz = m + (float)log(s);
+    // K rounds of a wave arg-max, each restricted to the classes after the previous winner in (lp desc, class asc) order
+    float plp = INFINITY;
+    int pc = -1;
+    for (int k = 0; k < K; ++k) {
+      float bl = -INFINITY;
+      int bc = 0x7fffffff;
+      for (int v = lane; v < V; v += 64) {
+        if (v == blank) continue;
+        const float l = Num<T>::ld(row + v) - lz;
+        if (cls_before(plp, pc, l, v) && cls_before(l, v, bl, bc)) { bl = l; bc = v; }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ol = __shfl_xor(bl, o, 64);
+        const int oc = __shfl_xor(bc, o, 64);
+        if (cls_before(ol, oc, bl, bc)) { bl = ol; bc = oc; }
+      }
+      if (lane == 0) { top_c[r * K + k] = min(bc, V - 1); top_lp[r * K + k] = bl; }  // clamp: only NaN rows leave bc unset
+      plp = bl;
+      pc = bc;
+    }
+    if (lane == 0) { lse[r] = lz; lp_blank[r] = Num<T>::ld(row + blank) - lz; }
+  }
+}
+
+// Trie of one utterance (node 0 = the empty prefix).  Written and read by one workgroup inside one launch: plain (non-restrict)
+// pointers, ordered by __syncthreads.
+struct Trie { int* parent; int* label; int* depth; };
+
+// A label sequence given as (node, extra): the node's sequence, followed by `extra` when extra >= 0.
+struct Seq { int n, x; };
+__device__ __forceinline__ int seq_len(const Trie& tr, Seq s) { return tr.depth[s.n] + (s.x >= 0); }
+__device__ __forceinline__ int seq_last(const Trie& tr, Seq s) { return s.x >= 0 ? s.x : tr.label[s.n]; }
+__device__ __forceinline__ Seq seq_up(const Trie& tr, Seq s) { return s.x >= 0 ? Seq{s.n, -1} : Seq{tr.parent[s.n], -1}; }
+__device__ __forceinline__ bool seq_eq(const Trie& tr, Seq a, Seq b) {
+  if ((a.x >= 0) == (b.x >= 0)) return a.n == b.n && a.x == b.x;
+  if (a.x >= 0) { Seq t = a; a = b; b = t; }  // a real node, b = (node, extra)
+  return tr.parent[a.n] == b.n && tr.label[a.n] == b.x;
+}
+// lexicographic a < b (a proper prefix is smaller), as std::vector's operator< in the host routine
+__device__ bool seq_less(const Trie& tr, Seq a, Seq b) {
+  int la = seq_len(tr, a), lb = seq_len(tr, b);
+  const bool b_longer = lb > la;
+  for (; la > lb; --la) a = seq_up(tr, a);
+  for (; lb > la; --lb) b = seq_up(tr, b);
+  if (seq_eq(tr, a, b)) return b_longer;  // one is a prefix of the other (or they are equal)
+  int ea = 0, eb = 0;
+  while (!seq_eq(tr, a, b)) { ea = seq_last(tr, a); eb = seq_last(tr, b); a = seq_up(tr, a); b = seq_up(tr, b); }
+  return ea < eb;
+}
+
+__device__ __forceinline__ unsigned beam_hash(int par, int c, unsigned mask) {
+  return ((unsigned)par * 0x9E3779B1u ^ ((unsigned)c + 0x7F4A7C15u) * 0x85EBCA77u) & mask;
+}
+
+template <typename T>
+__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
+    const T* __restrict__ logits, const int32_t* __restrict__ logit_len, const float* __restrict__ lse_ws,
+    const float* __restrict__ lpb_ws, const int32_t* __restrict__ top_c, const float* __restrict__ top_lp, int* trie_parent,
+    int* trie_label, int* trie_depth, unsigned long long* hkeys, int* hvals, int Tm, int V, int W, int K, int P, long nmax,
+    unsigned hcap, int32_t* __restrict__ tokens, int32_t* __restrict__ tokens_len, float* __restrict__ log_prob) {
+  // beam state (node, its parent / last label / depth, probabilities) and per-frame scratch
+  __shared__ int bnode[BEAM_MAXW], bpar[BEAM_MAXW], blab[BEAM_MAXW], bdep[BEAM_MAXW], merged[BEAM_MAXW];
+  __shared__ float bpb[BEAM_MAXW], bpnb[BEAM_MAXW], bptot[BEAM_MAXW], lpl[BEAM_MAXW], spb[BEAM_MAXW], spnb[BEAM_MAXW];
+  __shared__ int nnode[BEAM_MAXW], npar[BEAM_MAXW], nlab[BEAM_MAXW], ndep[BEAM_MAXW], win[BEAM_MAXW];
+  __shared__ float npb[BEAM_MAXW], npnb[BEAM_MAXW];
+  __shared__ int kc[BEAM_MAXK];
+  __shared__ float klp[BEAM_MAXK];
+  __shared__ float ctot[BEAM_MAXC];
+  __shared__ unsigned ccode[BEAM_MAXC];  // src | (label + 1) << 6; label -1 = the beam itself ("stay")
+  __shared__ int s_nc, s_nb, s_ntrie;
+
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int Tb = min(max(logit_len[b], 0), Tm);
+  const Trie tr{trie_parent + (long)b * nmax, trie_label + (long)b * nmax, trie_depth + (long)b * nmax};
+  unsigned long long* hk = hkeys + (long)b * hcap;
+  int* hv = hvals + (long)b * hcap;
+  const unsigned hmask = hcap - 1;
+  for (unsigned i = tid; i < hcap; i += BEAM_THREADS) hk[i] = BEAM_EMPTY;
+  if (tid == 0) {
+    tr.parent[0] = -1; tr.label[0] = -1; tr.depth[0] = 0;
+    bnode[0] = 0; bpar[0] = -1; blab[0] = -1; bdep[0] = 0; bpb[0] = 0.f; bpnb[0] = -INFINITY;
+    s_nb = 1; s_ntrie = 1;
+  }
+  if (tid < BEAM_MAXW) win[tid] = 0;
+  __syncthreads();
+
+  for (int t = 0; t < Tb; ++t) {
+    const long r = (long)b * Tm + t;
+    const T* row = logits + r * V;
+    const float lz = lse_ws[r], lpblank = lpb_ws[r];
+    const int nb = s_nb;
+    if (tid < K) { kc[tid] = top_c[r * K + tid]; klp[tid] = top_lp[r * K + tid]; }
+    if (tid < nb) {
+      bptot[tid] = dlse2(bpb[tid], bpnb[tid]);
+      lpl[tid] = bpar[tid] >= 0 ? Num<T>::ld(row + blab[tid]) - lz : -INFINITY;
+    }
+    if (tid < BEAM_MAXW) win[tid] = 0;
+    if (tid == 0) s_nc = 0;
+    __syncthreads();
+    if (tid < nb) {
+      int m = -1;
+      if (bpar[tid] >= 0)
+        for (int j = 0; j < nb; ++j)
+          if (bnode[j] == bpar[tid]) { m = j; break; }
+      merged[tid] = m;
+      spb[tid] = bptot[tid] + lpblank;
+      spnb[tid] = bpar[tid] >= 0 ? bpnb[tid] + lpl[tid] : -INFINITY;
+    }
+    __syncthreads();
+    // --- candidates: stays not merged into a parent's extension
+    if (tid < nb && merged[tid] < 0) {
+      const int q = atomicAdd(&s_nc, 1);
+      ctot[q] = dlse2(spb[tid], spnb[tid]);
+      ccode[q] = (unsigned)tid;
+    }
+    // --- specials: pair (i, j): beam j's stay merged into (beam i, label of j); (i, i): beam i repeating its own last label
+    for (int pq = tid; pq < nb * nb; pq += BEAM_THREADS) {
+      const int i = pq / nb, j = pq % nb;
+      int c = -1, child = -1;
+      if (j != i && merged[j] == i) { c = blab[j]; child = j; }
+      if (j == i && bpar[i] >= 0) {
+        c = blab[i];
+        for (int k = 0; k < nb; ++k)
+          if (merged[k] == i && blab[k] == c) c = -1;  // counted with that child
+      }
+      if (c < 0) continue;
+      const bool rep = bpar[i] >= 0 && c == blab[i];
+      const float add = rep ? bpb[i] : bptot[i];
+      const float lpc = child >= 0 ? lpl[child] : lpl[i];
+      float ext = add != -INFINITY ? add + lpc : -INFINITY, ext_pb = -INFINITY;
+      if (child < 0)
+        for (int k = 0; k < nb; ++k)
+          if (merged[k] == i && blab[k] == c) child = k;
+      if (child >= 0) { ext_pb = spb[child]; ext = dlse2(ext, spnb[child]); }
+      const float tot = dlse2(ext_pb, ext);
+      if (tot != -INFINITY) {
+        const int q = atomicAdd(&s_nc, 1);
+        ctot[q] = tot;
+        ccode[q] = (unsigned)i | ((unsigned)(c + 1) << 6);
+      }
+    }
+    // --- regulars: wave per beam, lane per top-K class; the first W classes of the row that are not special to it
+    for (int i = wid; i < nb; i += BEAM_THREADS / 64) {
+      int seen = 0;
+      for (int k0 = 0; k0 < K; k0 += 64) {
+        const int k = k0 + lane;
+        bool reg = false;
+        int c = -1;
+        if (k < K) {
+          c = kc[k];
+          reg = !(bpar[i] >= 0 && c == blab[i]);
+          for (int j = 0; j < nb && reg; ++j)
+            if (merged[j] == i && blab[j] == c) reg = false;
+        }
+        const unsigned long long mask = __ballot(reg);
+        const int rank = seen + __popcll(mask & ((1ull << lane) - 1ull));
+        seen += __popcll(mask);
+        if (reg && rank < W && bptot[i] != -INFINITY) {
+          const float tot = bptot[i] + klp[k];
+          if (tot != -INFINITY) {
+            const int q = atomicAdd(&s_nc, 1);
+            ctot[q] = tot;
+            ccode[q] = (unsigned)i | ((unsigned)(c + 1) << 6);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // --- the best `keep` candidates: rank = number of better candidates (exact order, so ranks are distinct)
+    const int nc = s_nc, keep = min(W, nc);
+    for (int q = tid; q < nc; q += BEAM_THREADS) {
+      const float tq = ctot[q];
+      const unsigned cq = ccode[q];
+      const Seq sq{bnode[cq & 63], (int)(cq >> 6) - 1};
+      int rank = 0;
+      for (int p = 0; p < nc && rank < keep; ++p) {
+        const float tp = ctot[p];
+        if (tp > tq) ++rank;
+        else if (tp == tq && p != q) {
+          const unsigned cp = ccode[p];
+          if (seq_less(tr, Seq{bnode[cp & 63], (int)(cp >> 6) - 1}, sq)) ++rank;
+        }
+      }
+      if (rank < keep) win[rank] = q;
+    }
+    __syncthreads();
+    // --- the next beam: probabilities and (parent, label) of each winner; look the extended prefix up in the table
+    bool fresh = false;
+    if (tid < keep) {
+      const unsigned code = ccode[win[tid]];
+      const int i = code & 63, c = (int)(code >> 6) - 1;
+      if (c < 0) {
+        nnode[tid] = bnode[i]; npar[tid] = bpar[i]; nlab[tid] = blab[i]; ndep[tid] = bdep[i];
+        npb[tid] = spb[i]; npnb[tid] = spnb[i];
+      } else {
+        const bool rep = bpar[i] >= 0 && c == blab[i];
+        const float add = rep ? bpb[i] : bptot[i];
+        float ext = add != -INFINITY ? add + (Num<T>::ld(row + c) - lz) : -INFINITY, ext_pb = -INFINITY;
+        for (int k = 0; k < nb; ++k)
+          if (merged[k] == i && blab[k] == c) { ext_pb = spb[k]; ext = dlse2(ext, spnb[k]); }
+        npb[tid] = ext_pb; npnb[tid] = ext;
+        npar[tid] = bnode[i]; nlab[tid] = c; ndep[tid] = bdep[i] + 1;
+        const unsigned long long key = ((unsigned long long)(unsigned)bnode[i] << 32) | (unsigned)c;
+        int node = -1;
+        unsigned h = beam_hash(bnode[i], c, hmask);
+        for (unsigned probe = 0; probe < hcap; ++probe, h = (h + 1) & hmask) {
+          const unsigned long long kk = hk[h];
+          if (kk == key) { node = hv[h]; break; }
+          if (kk == BEAM_EMPTY) break;
+        }
+        nnode[tid] = node;
+        fresh = node < 0;
+      }
+    }
+    // new nodes numbered in rank order (keep <= 64: wave 0 holds every winner)
+    int nfresh = 0;
+    if (wid == 0) {
+      const unsigned long long mask = __ballot(fresh);
+      nfresh = __popcll(mask);
+      if (fresh) {
+        const int node = s_ntrie + __popcll(mask & ((1ull << lane) - 1ull));
+        nnode[tid] = node;
+        tr.parent[node] = npar[tid]; tr.label[node] = nlab[tid]; tr.depth[node] = ndep[tid];
+        const unsigned long long key = ((unsigned long long)(unsigned)npar[tid] << 32) | (unsigned)nlab[tid];
+        unsigned h = beam_hash(npar[tid], nlab[tid], hmask);
+        for (unsigned probe = 0; probe < hcap; ++probe, h = (h + 1) & hmask)
+          if (atomicCAS(&hk[h], BEAM_EMPTY, key) == BEAM_EMPTY) { hv[h] = node; break; }
+      }
+    }
+    __syncthreads();
+    if (tid < keep) {
+      bnode[tid] = nnode[tid]; bpar[tid] = npar[tid]; blab[tid] = nlab[tid]; bdep[tid] = ndep[tid];
+      bpb[tid] = npb[tid]; bpnb[tid] = npnb[tid];
+    }
+    if (tid == 0) {
+      s_nb = keep;
+      s_ntrie += nfresh;
+    }
+    __syncthreads();
+  }
+
+  // final beam, best first (ties: smaller label sequence); top P paths, dense and 0 padded
+  const int nb = s_nb;
+  if (tid < nb) {
+    const float tq = dlse2(bpb[tid], bpnb[tid]);
+    int rank = 0;
+    for (int p = 0; p < nb; ++p) {
+      const float tp = dlse2(bpb[p], bpnb[p]);
+      if (tp > tq || (tp == tq && p != tid && seq_less(tr, Seq{bnode[p], -1}, Seq{bnode[tid], -1}))) ++rank;
+    }
+    if (rank < P) {
+      win[rank] = tid;
+      npb[rank] = tq;
+    }
+  }
+  __syncthreads();
+  const long obase = (long)b * P;
+  for (int p = tid; p < P; p += BEAM_THREADS) {
+    tokens_len[obase + p] = p < nb ? bdep[win[p]] : 0;
+    log_prob[obase + p] = p < nb ? npb[p] : -INFINITY;
+  }
+  for (long e = tid; e < (long)P * Tm; e += BEAM_THREADS) {
+    const int p = (int)(e / Tm), pos = (int)(e % Tm);
+    if (p >= nb || pos >= bdep[win[p]]) tokens[obase * Tm + e] = 0;
+  }
+  if (tid < min(nb, P)) {
+    int32_t* out = tokens + (obase + tid) * Tm;
+    for (int n = bnode[win[tid]], d = bdep[win[tid]]; n > 0; n = tr.parent[n]) out[--d] = tr.label[n];
+  }
+}
+
+inline size_t beam_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct BeamLayout {
+  int K;
+  long nmax;
+  unsigned hcap;
+  size_t off_lse, off_lpb, off_tc, off_tlp, off_par, off_lab, off_dep, off_hk, off_hv, total;
+};
+
+inline BeamLayout beam_layout(int B, int T, int V, int W) {
+  BeamLayout L;
+  L.K = std::min(2 * W, V - 1);
+  L.nmax = 1 + (long)W * T;  // at most W new nodes per frame
+  unsigned long long cap = 64;
+  while (cap < 2ull * (unsigned long long)L.nmax) cap <<= 1;
+  L.hcap = (unsigned)cap;
+  const size_t rows = (size_t)B * T;
+  size_t o = 0;
+  L.off_lse = o; o += beam_align(rows * 4);
+  L.off_lpb = o; o += beam_align(rows * 4);
+  L.off_tc = o; o += beam_align(rows * L.K * 4);
+  L.off_tlp = o; o += beam_align(rows * L.K * 4);
+  L.off_par = o; o += beam_align((size_t)B * L.nmax * 4);
+  L.off_lab = o; o += beam_align((size_t)B * L.nmax * 4);
+  L.off_dep = o; o += beam_align((size_t)B * L.nmax * 4);
+  L.off_hk = o; o += beam_align((size_t)B * L.hcap * 8);
+  L.off_hv = o; o += beam_align((size_t)B * L.hcap * 4);
+  L.total = o;
+  return L;
+}
+
+inline bool beam_shape_ok(int B, int T, int V, int W) {
+  // T * W bounded so that node ids and table sizes stay in int / unsigned range; V bounded by the candidate code's label field
+  return B > 0 && T > 0 && V >= 2 && V < (1 << 25) && W >= 1 && W <= BEAM_MAXW && (long)T * W < (1L << 28);
+}
+
+}  // namespace
+
+extern "C" int tfasr_ctc_beam_search_workspace_size(int B, int T, int V, int beam_width, size_t* bytes) {
+  if (!bytes || !beam_shape_ok(B, T, V, beam_width)) return TFASR_STATUS_INVALID_VALUE;
+  *bytes = beam_layout(B, T, V, beam_width).total;
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_search(const void* logits, const int32_t* logit_len, int B, int T, int V, int beam_width, int top_paths,
+                                     int blank_index, int dtype, int32_t* tokens, int32_t* tokens_len, float* log_prob, void* workspace,
+                                     size_t workspace_bytes, void* stream_) {
+  if (!logits || !logit_len || !tokens || !tokens_len || !log_prob || !workspace) return TFASR_STATUS_INVALID_VALUE;
+  if (!beam_shape_ok(B, T, V, beam_width) || top_paths < 1 || top_paths > beam_width || blank_index < 0 || blank_index >= V)
+    return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
+  const BeamLayout L = beam_layout(B, T, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t s = (hipStream_t)stream_;
+  char* ws = (char*)workspace;
+  float* lse = (float*)(ws + L.off_lse);
+  float* lpb = (float*)(ws + L.off_lpb);
+  int32_t* tc = (int32_t*)(ws + L.off_tc);
+  float* tlp = (float*)(ws + L.off_tlp);
+  int* par = (int*)(ws + L.off_par);
+  int* lab = (int*)(ws + L.off_lab);
+  int* dep = (int*)(ws + L.off_dep);
+  unsigned long long* hk = (unsigned long long*)(ws + L.off_hk);
+  int* hv = (int*)(ws + L.off_hv);
+  const long rows = (long)B * T;
+  const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
+  if (dtype == TFASR_F32) {
+    TFASR_KLAUNCH(ctc_beam_frame_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)logits, logit_len, lse, lpb, tc, tlp, B, T, V, L.K, blank_index);
+    TFASR_KLAUNCH(ctc_beam_search_kernel<float>, dim3(B), dim3(BEAM_THREADS), 0, s, (const float*)logits, logit_len, lse, lpb, tc, tlp, par, lab, dep,
+                  hk, hv, T, V, beam_width, L.K, top_paths, L.nmax, L.hcap, tokens, tokens_len, log_prob);
+  } else {
+    TFASR_KLAUNCH(ctc_beam_frame_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)logits, logit_len, lse, lpb, tc, tlp, B, T, V, L.K, blank_index);
+    TFASR_KLAUNCH(ctc_beam_search_kernel<bf16_t>, dim3(B), dim3(BEAM_THREADS), 0, s, (const bf16_t*)logits, logit_len, lse, lpb, tc, tlp, par, lab,
+                  dep, hk, hv, T, V, beam_width, L.K, top_paths, L.nmax, L.hcap, tokens, tokens_len, log_prob);
+  }
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}

@@ -8,7 +8,9 @@ Mirrors  tensorflow_asr.models.ctc.conformer.Conformer      (models/ctc/conforme
 The log-mel frontend, SpecAugment, subsampling, Conformer blocks (native block executor), optimizer, gradient accumulation
 and the data-parallel hooks are inherited from ConformerTransducer; this class replaces the prediction / joint networks and the
 RNN-T loss by the Dense decoder and tfasr_ctc_loss, with a hand-written backward.  Decoding: tfasr_ctc_greedy_decode (device)
-and tfasr_ctc_beam_search_host (host routine, as tf.nn.ctc_beam_search_decoder is).  No CPU fallback.
+and tfasr_ctc_beam_search_host (host routine, as tf.nn.ctc_beam_search_decoder is; the default of recognize_beam) or
+tfasr_ctc_beam_search (the same search on the device, with the n-best list: recognize_beam(device_search=True), recognize_nbest).
+No CPU fallback.
 """
 import torch
 
@@ -92,13 +94,25 @@ class ConformerCTC(ConformerTransducer):
         return PredictOutput(tokens=tokens[:, :width], next_tokens=None, next_encoder_states=None, next_decoder_states=None)
 
     @torch.no_grad()
-    def recognize_beam(self, inputs: PredictInput, beam_width=10, **kwargs):
+    def recognize_beam(self, inputs: PredictInput, beam_width=10, device_search=False, **kwargs):
         """CtcModel.recognize_beam (base_ctc.py:128-149): tf.nn.ctc_beam_search_decoder(beam_width) - top path, dense.  TF's beam
-        search decoder treats the LAST class as blank (the reference does not pass blank_index there): reproduced."""
+        search decoder treats the LAST class as blank (the reference does not pass blank_index there): reproduced.
+        device_search=True runs the same search on the GPU (tfasr_ctc_beam_search) instead of the host routine."""
         logits, elen = self._infer_logits(inputs)
-        toks, n, _ = K.ctc_beam_search(logits, torch.tensor(elen, dtype=torch.int32), beam_width=beam_width, blank_index=None)
+        if device_search:
+            toks, n, _ = K.ctc_beam_search_device(logits, self._h2d(elen), beam_width=beam_width, top_paths=1, blank_index=None)
+            toks, n = toks[:, 0], n[:, 0]
+        else:
+            toks, n, _ = K.ctc_beam_search(logits, torch.tensor(elen, dtype=torch.int32), beam_width=beam_width, blank_index=None)
         width = max(int(n.max().item()), 1)
         return PredictOutput(tokens=toks[:, :width].to(self.device), next_tokens=None, next_encoder_states=None, next_decoder_states=None)
+
+    @torch.no_grad()
+    def recognize_nbest(self, inputs: PredictInput, beam_width=10, top_paths=4):
+        """n-best list of the beam search (tf.nn.ctc_beam_search_decoder's top_paths), on the GPU: tokens [B, P, T'] (0 padded),
+        lengths [B, P], log_prob [B, P], best first; P = top_paths <= beam_width."""
+        logits, elen = self._infer_logits(inputs)
+        return K.ctc_beam_search_device(logits, self._h2d(elen), beam_width=beam_width, top_paths=top_paths, blank_index=None)
 
     def recognize_encoded(self, *a, **k):
         raise NotImplementedError("transducer greedy search does not apply to a CTC model")

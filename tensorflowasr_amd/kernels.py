@@ -954,6 +954,35 @@ def ctc_beam_search(logits, logit_len, beam_width=10, blank_index=None):
     return torch.from_numpy(toks), torch.from_numpy(n), torch.from_numpy(lp)
 
 
+def ctc_beam_search_device(logits, logit_len, beam_width=10, top_paths=1, blank_index=None):
+    """The prefix beam search of ctc_beam_search on the device (tfasr_ctc_beam_search), stream ordered, with the n-best list:
+    logits [B,T,V] f32 / bf16 on the GPU, logit_len [B] -> device tensors tokens [B,P,T] (0 padded), lengths [B,P], log_prob [B,P],
+    best first; paths past the last live beam are empty with log_prob -inf.  blank_index=None: class V-1 (TF's convention)."""
+    B, T, V = logits.shape
+    beam_width, top_paths = int(beam_width), int(top_paths)
+    bi = V - 1 if blank_index is None else int(blank_index)
+    if not 1 <= beam_width <= 64:
+        raise ValueError(f"tfasr_ctc_beam_search: beam_width {beam_width} outside [1, 64] (the beam lives in one workgroup's LDS)")
+    if not 1 <= top_paths <= beam_width:
+        raise ValueError(f"tfasr_ctc_beam_search: top_paths {top_paths} outside [1, beam_width = {beam_width}]")
+    if V < 2 or not 0 <= bi < V:
+        raise ValueError(f"tfasr_ctc_beam_search: blank_index {bi} outside [0, V = {V}) or V < 2")
+    logits = logits.contiguous()
+    dev = logits.device
+    if not torch.is_tensor(logit_len):
+        logit_len = torch.tensor(logit_len, dtype=torch.int32)
+    logit_len = logit_len.to(device=dev, dtype=torch.int32).contiguous()
+    n = ctypes.c_size_t(0)
+    check(_L().tfasr_ctc_beam_search_workspace_size(B, T, V, beam_width, ctypes.byref(n)), "ctc_beam_ws")
+    ws = workspace(n.value, dev, "ctc_beam")
+    tokens = torch.empty(B, top_paths, T, dtype=torch.int32, device=dev)
+    lengths = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
+    log_prob = torch.empty(B, top_paths, dtype=torch.float32, device=dev)
+    check(_L().tfasr_ctc_beam_search(_p(logits), _p(logit_len), B, T, V, beam_width, top_paths, bi, _dt(logits), _p(tokens), _p(lengths),
+                                     _p(log_prob), _p(ws), ws.numel(), _stream()), "ctc_beam_search_device")
+    return tokens, lengths, log_prob
+
+
 def ctc_greedy_decode(logits, logit_len, blank=0):
     B, T, V = logits.shape
     am = torch.empty(B * T, dtype=torch.int32, device=logits.device)
