@@ -635,6 +635,36 @@ int tfasr_ctc_beam_search(const void* logits, const int32_t* logit_len, int B, i
                           int blank_index, int dtype, int32_t* tokens, int32_t* tokens_len, float* log_prob, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* Transducer beam search on the device (ABI 44 addition; csrc/rnnt_beam.hip): the batched "modified beam search", at most one
+ * symbol per frame, candidates with equal label sequences merged by log-add-exp, the next beam = the first W candidates by
+ * (total desc, label sequence asc).  Utterance b starts from one empty hypothesis with prediction input init_tok[b] (NULL: blank)
+ * and state init_h / init_c [B,U] (NULL: zeros), and runs nframes[b] <= T frames of encj [B,T,J] f32 (the joint's encoder
+ * projection).  Weights as tfasr_decode_step takes them (U = prediction units, ln_g / ln_b NULL: no prediction LayerNorm); `packed`
+ * (optional, from tfasr_decode_pack) supplies G = emb @ lstm_k.  Products f32 on the f32 weights; lse per row as the CTC device search
+ * (f32 max, f64 sum, f32 log); log-probabilities, totals and merges f64; scores f32.  Outputs, best first, NP = top_paths: tokens
+ * [B,NP,T] (blank padded), tokens_len [B,NP], score [B,NP], next_tok [B,NP] (the path's last label, or the initial token) and
+ * next_h / next_c [B,NP,U] (the prediction state before next_tok is fed: a greedy PredictInput continues the path).  Paths past
+ * the last live hypothesis are empty with score -inf, next_tok = blank, zero state.  1 <= beam_width <= 64, 1 <= top_paths <=
+ * beam_width, V >= 2, 0 <= blank < V.  All pointers are device pointers; one host call queues the whole search, nothing
+ * synchronises with the host.  The workspace size depends only on (B, T, U, J, V, beam_width).
+ * Test seam on the same workspace (the search is built from it): _begin = one empty hypothesis per utterance (no prediction
+ * network); _select = one frame t from caller-supplied f32 logits [B,W,V] of the current beam rows (utterances with t >= nframes[b]
+ * are left as they are; a workspace takes at most T frames); _nbest = the best top_paths rows as tokens / tokens_len / score. */
+int tfasr_rnnt_beam_workspace_size(int B, int T, int U, int J, int V, int beam_width, size_t* bytes);
+int tfasr_rnnt_beam_search(const float* emb, const float* lstm_k, const float* lstm_rk, const float* lstm_b, const float* ln_g,
+                           const float* ln_b, const float* joint_pred_w, const float* joint_pred_b, const float* vocab_w,
+                           const float* vocab_b, const float* packed, const float* encj, const int32_t* nframes,
+                           const int32_t* init_tok, const float* init_h, const float* init_c, int B, int T, int E, int U, int J,
+                           int V, int beam_width, int top_paths, int blank, float ln_eps, int32_t* tokens, int32_t* tokens_len,
+                           float* score, int32_t* next_tok, float* next_h, float* next_c, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int tfasr_rnnt_beam_begin(const int32_t* init_tok, int B, int T, int U, int J, int V, int beam_width, int blank, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int tfasr_rnnt_beam_select(const float* logits, const int32_t* nframes, int t, int B, int T, int U, int J, int V, int beam_width,
+                           int blank, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_rnnt_beam_nbest(int B, int T, int U, int J, int V, int beam_width, int top_paths, int blank, int32_t* tokens,
+                          int32_t* tokens_len, float* score, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Native executor of one Conformer block (ConformerBlock.call, encoders/conformer.py:430-520, and its backward):
  * queues every kernel of FFModule -> MHSAModule -> ConvModule -> FFModule -> LayerNorm on `stream` with one host call.

@@ -1575,9 +1575,57 @@ class ConformerTransducer(BaseModel):
         return self.recognize_encoded(enc, elen, inputs.previous_tokens, inputs.previous_decoder_states, max_tokens_per_frame,
                                       check_every)
 
-    def recognize_beam(self, inputs: PredictInput, beam_width=10, **kw):
-        """The reference's recognize_beam falls back to greedy (base_transducer.py:841-842)."""
-        return self.recognize(inputs, **kw)
+    def recognize_beam(self, inputs: PredictInput, beam_width=10, device_search=False, precision=None, **kw):
+        """The reference's recognize_beam falls back to greedy (base_transducer.py:841-842), and so does this one by default.
+        device_search=True runs the modified beam search on the device (csrc/rnnt_beam.hip: at most one symbol per frame, equal label
+        sequences merged) and returns its best path: tokens [B, T'] blank padded, next_tokens [B, 1], next_decoder_states [B, 1, 2, P]."""
+        if not device_search:
+            return self.recognize(inputs, precision=precision, **kw)
+        enc, elen = self.encode(inputs.inputs, inputs.inputs_length, precision)
+        tokens, _, _, next_tok, states = self.recognize_beam_encoded(enc, elen, beam_width, 1, inputs.previous_tokens,
+                                                                     inputs.previous_decoder_states)
+        return PredictOutput(tokens=tokens[:, 0], next_tokens=next_tok[:, :1], next_encoder_states=None, next_decoder_states=states[:, 0])
+
+    def recognize_nbest(self, inputs: PredictInput, beam_width=10, top_paths=4, precision=None):
+        """n-best list of the device beam search: (tokens [B, NP, T'] blank padded, lengths [B, NP], scores [B, NP]), best first; paths
+        past the last live hypothesis are empty with score -inf (the shapes of ConformerCTC.recognize_nbest)."""
+        enc, elen = self.encode(inputs.inputs, inputs.inputs_length, precision)
+        tokens, lengths, scores, _, _ = self.recognize_beam_encoded(enc, elen, beam_width, top_paths, inputs.previous_tokens,
+                                                                    inputs.previous_decoder_states)
+        return tokens, lengths, scores
+
+    @torch.no_grad()
+    def recognize_beam_encoded(self, enc, elen, beam_width=10, top_paths=1, previous_tokens=None, previous_decoder_states=None):
+        """The device beam search on encoder output enc [B, T', dmodel] with lengths elen: (tokens [B, NP, T'], lengths [B, NP], scores
+        [B, NP] f32, next_tokens [B, NP], next_decoder_states [B, NP, 1, 2, P]).  Path p continues from next_tokens[:, p:p+1] and
+        next_decoder_states[:, p] (the greedy search's convention: the path's last label, or the initial token, and the prediction
+        state before it is fed).  f32 on the f32 master weights whatever the model's storage type, as recognize_encoded."""
+        ps, c, dev = self.ps, self.cfg, self.device
+        B, T, d = enc.shape
+        P, J = c.rnn_units, c.joint_dim
+        f32 = torch.float32
+        lens = [min(max(int(v), 0), T) for v in elen]
+        Tm = max(max(lens), 1)  # frames past every utterance are never searched
+        enc32 = enc[:, :Tm].reshape(B * Tm, d)
+        if enc32.dtype != f32 or not enc32.is_contiguous():
+            enc32 = K.cast(enc32.contiguous(), torch.empty(B * Tm, d, dtype=f32, device=dev))
+        encj = K.matmul(enc32, ps.p2d("joint/enc/w"), bias=ps.p("joint/enc/b")).view(B, Tm, J)
+        init_tok = None if previous_tokens is None else previous_tokens.to(dev).to(torch.int32).reshape(B).contiguous()
+        init_h = init_c = None
+        if previous_decoder_states is not None:
+            st = previous_decoder_states.to(dev)
+            init_h, init_c = st[:, 0, 0].float().contiguous(), st[:, 0, 1].float().contiguous()
+        lng, lnb = (ps.p("pred/ln/g"), ps.p("pred/ln/b")) if c.prediction_layer_norm else (None, None)
+        Wk, Wrk, Wjp, Wv = ps.p2d("pred/lstm/k"), ps.p2d("pred/lstm/rk"), ps.p2d("joint/pred/w"), ps.p2d("joint/vocab/w")
+        toks, lengths, scores, next_tok, next_h, next_c = K.rnnt_beam_search(
+            ps.p("pred/emb"), Wk, Wrk, ps.p("pred/lstm/b"), lng, lnb, Wjp, ps.p("joint/pred/b"), Wv, ps.p("joint/vocab/b"), encj,
+            torch.tensor(lens, dtype=torch.int32), beam_width, top_paths, self.blank, init_tok, init_h, init_c)
+        if Tm < T:
+            full = torch.full((B, toks.shape[1], T), self.blank, dtype=torch.int32, device=dev)
+            full[:, :, :Tm] = toks
+            toks = full
+        states = torch.stack([next_h, next_c], dim=2).unsqueeze(2)  # [B, NP, 1, 2, P]
+        return toks, lengths, scores, next_tok, states
 
     @torch.no_grad()
     def recognize_encoded(self, enc, elen, previous_tokens=None, previous_decoder_states=None, max_tokens_per_frame=3,

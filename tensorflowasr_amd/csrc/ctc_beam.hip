@@ -7,6 +7,7 @@
 // base's blank is 0 (base_ctc.py passes no blank index to the beam decoder) - so `blank_index` is a parameter and the Python
 // host passes V-1 to reproduce recognize_beam, 0 for a self-consistent decoder.
 #include "common.h"
+#include "beam_trie.h"
 #include <algorithm>
 #include <cmath>
 #include <unordered_map>
@@ -192,7 +193,6 @@ constexpr int BEAM_MAXW = 64;
 constexpr int BEAM_MAXK = 2 * BEAM_MAXW;
 constexpr int BEAM_MAXC = BEAM_MAXW * BEAM_MAXW + 3 * BEAM_MAXW;  // stays + specials (<= 2 per beam) + W regulars per beam
 constexpr int BEAM_THREADS = 256;
-constexpr unsigned long long BEAM_EMPTY = ~0ull;
 
 __device__ __forceinline__ float dlse2(float a, float b) {  // lse2 above, same operation order
   if (a == -INFINITY) return b;
@@ -250,35 +250,9 @@ __global__ __launch_bounds__(256) void ctc_beam_frame_kernel(const T* __restrict
   }
 }
 
-// Trie of one utterance (node 0 = the empty prefix).  Written and read by one workgroup inside one launch: plain (non-restrict)
-// pointers, ordered by __syncthreads.
-struct Trie { int* parent; int* label; int* depth; };
-
-// A label sequence given as (node, extra): the node's sequence, followed by `extra` when extra >= 0.
-struct Seq { int n, x; };
-__device__ __forceinline__ int seq_len(const Trie& tr, Seq s) { return tr.depth[s.n] + (s.x >= 0); }
-__device__ __forceinline__ int seq_last(const Trie& tr, Seq s) { return s.x >= 0 ? s.x : tr.label[s.n]; }
-__device__ __forceinline__ Seq seq_up(const Trie& tr, Seq s) { return s.x >= 0 ? Seq{s.n, -1} : Seq{tr.parent[s.n], -1}; }
-__device__ __forceinline__ bool seq_eq(const Trie& tr, Seq a, Seq b) {
-  if ((a.x >= 0) == (b.x >= 0)) return a.n == b.n && a.x == b.x;
-  if (a.x >= 0) { Seq t = a; a = b; b = t; }  // a real node, b = (node, extra)
-  return tr.parent[a.n] == b.n && tr.label[a.n] == b.x;
-}
-// lexicographic a < b (a proper prefix is smaller), as std::vector's operator< in the host routine
-__device__ bool seq_less(const Trie& tr, Seq a, Seq b) {
-  int la = seq_len(tr, a), lb = seq_len(tr, b);
-  const bool b_longer = lb > la;
-  for (; la > lb; --la) a = seq_up(tr, a);
-  for (; lb > la; --lb) b = seq_up(tr, b);
-  if (seq_eq(tr, a, b)) return b_longer;  // one is a prefix of the other (or they are equal)
-  int ea = 0, eb = 0;
-  while (!seq_eq(tr, a, b)) { ea = seq_last(tr, a); eb = seq_last(tr, b); a = seq_up(tr, a); b = seq_up(tr, b); }
-  return ea < eb;
-}
-
-__device__ __forceinline__ unsigned beam_hash(int par, int c, unsigned mask) {
-  return ((unsigned)par * 0x9E3779B1u ^ ((unsigned)c + 0x7F4A7C15u) * 0x85EBCA77u) & mask;
-}
+using beam_trie::Seq;
+using beam_trie::Trie;
+using beam_trie::seq_less;
 
 template <typename T>
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
@@ -302,8 +276,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
   const Trie tr{trie_parent + (long)b * nmax, trie_label + (long)b * nmax, trie_depth + (long)b * nmax};
   unsigned long long* hk = hkeys + (long)b * hcap;
   int* hv = hvals + (long)b * hcap;
-  const unsigned hmask = hcap - 1;
-  for (unsigned i = tid; i < hcap; i += BEAM_THREADS) hk[i] = BEAM_EMPTY;
+  for (unsigned i = tid; i < hcap; i += BEAM_THREADS) hk[i] = beam_trie::EMPTY;
   if (tid == 0) {
     tr.parent[0] = -1; tr.label[0] = -1; tr.depth[0] = 0;
     bnode[0] = 0; bpar[0] = -1; blab[0] = -1; bdep[0] = 0; bpb[0] = 0.f; bpnb[0] = -INFINITY;
@@ -428,14 +401,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
           if (merged[k] == i && blab[k] == c) { ext_pb = spb[k]; ext = dlse2(ext, spnb[k]); }
         npb[tid] = ext_pb; npnb[tid] = ext;
         npar[tid] = bnode[i]; nlab[tid] = c; ndep[tid] = bdep[i] + 1;
-        const unsigned long long key = ((unsigned long long)(unsigned)bnode[i] << 32) | (unsigned)c;
-        int node = -1;
-        unsigned h = beam_hash(bnode[i], c, hmask);
-        for (unsigned probe = 0; probe < hcap; ++probe, h = (h + 1) & hmask) {
-          const unsigned long long kk = hk[h];
-          if (kk == key) { node = hv[h]; break; }
-          if (kk == BEAM_EMPTY) break;
-        }
+        const int node = beam_trie::lookup(hk, hv, hcap, bnode[i], c);
         nnode[tid] = node;
         fresh = node < 0;
       }
@@ -449,10 +415,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
         const int node = s_ntrie + __popcll(mask & ((1ull << lane) - 1ull));
         nnode[tid] = node;
         tr.parent[node] = npar[tid]; tr.label[node] = nlab[tid]; tr.depth[node] = ndep[tid];
-        const unsigned long long key = ((unsigned long long)(unsigned)npar[tid] << 32) | (unsigned)nlab[tid];
-        unsigned h = beam_hash(npar[tid], nlab[tid], hmask);
-        for (unsigned probe = 0; probe < hcap; ++probe, h = (h + 1) & hmask)
-          if (atomicCAS(&hk[h], BEAM_EMPTY, key) == BEAM_EMPTY) { hv[h] = node; break; }
+        beam_trie::insert(hk, hv, hcap, npar[tid], nlab[tid], node);
       }
     }
     __syncthreads();
@@ -510,9 +473,7 @@ inline BeamLayout beam_layout(int B, int T, int V, int W) {
   BeamLayout L;
   L.K = std::min(2 * W, V - 1);
   L.nmax = 1 + (long)W * T;  // at most W new nodes per frame
-  unsigned long long cap = 64;
-  while (cap < 2ull * (unsigned long long)L.nmax) cap <<= 1;
-  L.hcap = (unsigned)cap;
+  L.hcap = beam_trie::table_cap(L.nmax);
   const size_t rows = (size_t)B * T;
   size_t o = 0;
   L.off_lse = o; o += beam_align(rows * 4);

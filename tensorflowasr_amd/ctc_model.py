@@ -116,3 +116,6 @@ class ConformerCTC(ConformerTransducer):
 
     def recognize_encoded(self, *a, **k):
         raise NotImplementedError("transducer greedy search does not apply to a CTC model")
+
+    def recognize_beam_encoded(self, *a, **k):
+        raise NotImplementedError("transducer beam search does not apply to a CTC model")

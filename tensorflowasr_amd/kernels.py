@@ -983,6 +983,100 @@ def ctc_beam_search_device(logits, logit_len, beam_width=10, top_paths=1, blank_
     return tokens, lengths, log_prob
 
 
+def _rnnt_beam_args(V, beam_width, top_paths, blank):
+    beam_width, top_paths, blank = int(beam_width), int(top_paths), int(blank)
+    if not 1 <= beam_width <= 64:
+        raise ValueError(f"tfasr_rnnt_beam_search: beam_width {beam_width} outside [1, 64] (a beam lives in one workgroup's LDS)")
+    if not 1 <= top_paths <= beam_width:
+        raise ValueError(f"tfasr_rnnt_beam_search: top_paths {top_paths} outside [1, beam_width = {beam_width}]")
+    if V < 2 or not 0 <= blank < V:
+        raise ValueError(f"tfasr_rnnt_beam_search: blank {blank} outside [0, V = {V}) or V < 2")
+    return beam_width, top_paths, blank
+
+
+def _i32(x, dev):
+    if not torch.is_tensor(x):
+        x = torch.tensor(x, dtype=torch.int32)
+    return x.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def rnnt_beam_workspace_size(B, T, U, J, V, beam_width):
+    n = ctypes.c_size_t(0)
+    check(_L().tfasr_rnnt_beam_workspace_size(B, T, U, J, V, int(beam_width), ctypes.byref(n)), "rnnt_beam_ws")
+    return n.value
+
+
+def rnnt_beam_search(emb, lstm_k, lstm_rk, lstm_b, ln_g, ln_b, wjp, bjp, wv, bv, encj, nframes, beam_width=10, top_paths=1, blank=0,
+                     init_tok=None, init_h=None, init_c=None, ln_eps=1e-3, packed=None):
+    """Transducer modified beam search (tfasr_rnnt_beam_search), the whole search queued by one call: f32 weights as decode_step takes
+    them, encj [B,T,J] f32, nframes [B] (<= T) -> device tensors tokens [B,NP,T] (blank padded), lengths [B,NP], scores [B,NP] f32,
+    next_tok [B,NP], next_h / next_c [B,NP,U], best first; paths past the last live hypothesis are empty with score -inf."""
+    B, T, J = encj.shape
+    V, E = emb.shape
+    U = lstm_rk.shape[0]
+    beam_width, top_paths, blank = _rnnt_beam_args(V, beam_width, top_paths, blank)
+    dev = encj.device
+    nframes = _i32(nframes, dev)
+    if init_tok is not None:
+        init_tok = _i32(init_tok, dev).reshape(B)
+    ws = workspace(rnnt_beam_workspace_size(B, T, U, J, V, beam_width), dev, "rnnt_beam")
+    tokens = torch.empty(B, top_paths, T, dtype=torch.int32, device=dev)
+    lengths = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, top_paths, dtype=torch.float32, device=dev)
+    next_tok = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
+    next_h = torch.empty(B, top_paths, U, dtype=torch.float32, device=dev)
+    next_c = torch.empty(B, top_paths, U, dtype=torch.float32, device=dev)
+    check(_L().tfasr_rnnt_beam_search(_p(emb), _p(lstm_k), _p(lstm_rk), _p(lstm_b), _p(ln_g), _p(ln_b), _p(wjp), _p(bjp), _p(wv), _p(bv),
+                                      _p(packed), _p(encj), _p(nframes), _p(init_tok), _p(init_h), _p(init_c), B, T, E, U, J, V, beam_width,
+                                      top_paths, blank, ln_eps, _p(tokens), _p(lengths), _p(scores), _p(next_tok), _p(next_h), _p(next_c),
+                                      _p(ws), ws.numel(), _stream()), "rnnt_beam_search")
+    return tokens, lengths, scores, next_tok, next_h, next_c
+
+
+class RnntBeamSeam:
+    """A beam search driven from outside (tfasr_rnnt_beam_begin / _select / _nbest): the caller supplies the logits of every frame,
+    which is how a test replaces the joint network by a model of its own."""
+
+    def __init__(self, B, T, V, beam_width, blank=0, init_tok=None, device="cuda"):
+        self.beam_width, _, self.blank = _rnnt_beam_args(V, beam_width, 1, blank)
+        self.B, self.T, self.V, self.U, self.J = int(B), int(T), int(V), 1, 1
+        self.ws = torch.empty(rnnt_beam_workspace_size(self.B, self.T, 1, 1, self.V, self.beam_width), dtype=torch.uint8, device=device)
+        tok = None if init_tok is None else _i32(init_tok, self.ws.device)
+        check(_L().tfasr_rnnt_beam_begin(_p(tok), self.B, self.T, 1, 1, self.V, self.beam_width, self.blank, _p(self.ws), self.ws.numel(),
+                                         _stream()), "rnnt_beam_begin")
+
+    def select(self, logits, nframes, t):
+        """one frame t from logits [B, beam_width, V] f32 of the current beam rows"""
+        logits = logits.to(self.ws.device, torch.float32).contiguous()
+        if tuple(logits.shape) != (self.B, self.beam_width, self.V):
+            raise ValueError(f"rnnt_beam_select: logits {tuple(logits.shape)}, expected {(self.B, self.beam_width, self.V)}")
+        check(_L().tfasr_rnnt_beam_select(_p(logits), _p(_i32(nframes, self.ws.device)), int(t), self.B, self.T, self.U, self.J, self.V,
+                                          self.beam_width, self.blank, _p(self.ws), self.ws.numel(), _stream()), "rnnt_beam_select")
+
+    def nbest(self, top_paths=None):
+        """the best top_paths rows (default: all) -> tokens [B,NP,T], lengths [B,NP], scores [B,NP]"""
+        _, top_paths, _ = _rnnt_beam_args(self.V, self.beam_width, top_paths or self.beam_width, self.blank)
+        dev = self.ws.device
+        tokens = torch.empty(self.B, top_paths, self.T, dtype=torch.int32, device=dev)
+        lengths = torch.empty(self.B, top_paths, dtype=torch.int32, device=dev)
+        scores = torch.empty(self.B, top_paths, dtype=torch.float32, device=dev)
+        check(_L().tfasr_rnnt_beam_nbest(self.B, self.T, self.U, self.J, self.V, self.beam_width, top_paths, self.blank, _p(tokens),
+                                         _p(lengths), _p(scores), _p(self.ws), self.ws.numel(), _stream()), "rnnt_beam_nbest")
+        return tokens, lengths, scores
+
+
+def rnnt_beam_begin(B, T, V, beam_width, blank=0, init_tok=None, device="cuda"):
+    return RnntBeamSeam(B, T, V, beam_width, blank, init_tok, device)
+
+
+def rnnt_beam_select(seam, logits, nframes, t):
+    seam.select(logits, nframes, t)
+
+
+def rnnt_beam_nbest(seam, top_paths=None):
+    return seam.nbest(top_paths)
+
+
 def ctc_greedy_decode(logits, logit_len, blank=0):
     B, T, V = logits.shape
     am = torch.empty(B * T, dtype=torch.int32, device=logits.device)
