@@ -665,6 +665,51 @@ int tfasr_rnnt_beam_select(const float* logits, const int32_t* nframes, int t, i
 int tfasr_rnnt_beam_nbest(int B, int T, int U, int J, int V, int beam_width, int top_paths, int blank, int32_t* tokens,
                           int32_t* tokens_len, float* score, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Forced alignment on the device (ABI 44 addition; csrc/align.hip): the best single path through the lattice the loss sums over,
+ * and when it emits each label.  All pointers are device pointers, label_len / logit_len [B] int32 are clamped to the padded
+ * sizes, nothing synchronises with the host, and every argument is checked on the host before any launch.
+ *
+ * Transducer, with the lattice log-probabilities blank[t,u] / truth[t,u] of tfasr_rnnt_loss, Tl = min(logit_len[b], T) (NOT raised to
+ * the label length), Ul = min(label_len[b], U1-1):
+ *   v[0,0] = 0,  v[t,u] = max(v[t-1,u] + blank[t-1,u], v[t,u-1] + truth[t,u-1]),  score[b] = v[Tl-1,Ul] + blank[Tl-1,Ul]
+ * in f32, one addition per term.  On an exact tie a label is emitted as late as possible: going forward the path prefers the blank
+ * move, so the back-trace from (Tl-1, Ul) takes the label move into (t,u) when both give the same f32 value.  frames [B,U1-1]:
+ * the frame at which label u is emitted (non-decreasing; -1 for u >= Ul); label_lp [B,U1-1] = truth[frames[u],u] (0 past Ul);
+ * Tl <= 0: score -inf, frames -1.  Lattice layouts as the loss: dense [B,T,U1] (cell_off NULL, total_cells ignored) or packed
+ * (tfasr_rnnt_loss_packed).  U1 > TFASR_ALIGN_MAX_U1: TFASR_STATUS_UNSUPPORTED.  blank must be 0, as for the loss.
+ *   _align_lattice : the walk alone on caller-supplied blank / truth log-probabilities (f32, either layout).
+ *   _align         : the loss's log-probability pass over dense [B,T,U1,V] or packed [total_cells,V] logits (f32 | bf16), then the walk.
+ *   _align_stats   : the same from the vocabulary GEMM's statistics epilogue (tfasr_gemm_args.lse_part / pick, as
+ *                    tfasr_rnnt_loss_packed_coef takes them): the logits never exist.
+ * tfasr_rnnt_align_workspace_size(B, T, U1, V) answers for all three and both layouts (the packed lattice is never larger than the
+ * dense one); V does not enter.
+ *
+ * CTC, over the states s = 0..2Ul of the extended label sequence (even: blank, odd: label s/2; labels clamped to [0,V) as the loss
+ * clamps them), lp[t,s] = logit[t,lab_s] - lse[t] in f32, or the logit itself with normalized != 0 (the input holds
+ * log-probabilities already: no lse pass):
+ *   v[0,s] = lp[0,s] for s <= 1, else -inf;  v[t,s] = max(v[t-1,s], v[t-1,s-1], v[t-1,s-2] if s odd and lab_s != lab_{s-2}) + lp[t,s]
+ *   score[b] = max(v[Tl-1,2Ul], v[Tl-1,2Ul-1])
+ * An exact tie takes the smallest move (stay, then s-1, then s-2), and the final blank state at the end.  start / end [B,U]: the
+ * first frame and one past the last frame spent in label u's state (-1 for u >= Ul); label_lp [B,U]: the sum of lp over those
+ * frames, added in frame order.  Labels that do not fit their frames, or Tl <= 0: score -inf and -1 everywhere.
+ * U > TFASR_ALIGN_CTC_MAX_U: TFASR_STATUS_UNSUPPORTED. */
+#define TFASR_ALIGN_MAX_U1 1024
+#define TFASR_ALIGN_CTC_MAX_U 511
+int tfasr_rnnt_align_workspace_size(int B, int T, int U1, int V, size_t* bytes);
+int tfasr_rnnt_align_lattice(const float* blank_lp, const float* truth_lp, const int32_t* label_len, const int32_t* logit_len,
+                             const long* cell_off, long total_cells, int B, int T, int U1, int32_t* frames, float* label_lp,
+                             float* score, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_rnnt_align(const void* logits, const int32_t* labels, const int32_t* label_len, const int32_t* logit_len,
+                     const long* cell_off, long total_cells, int B, int T, int U1, int V, int blank, int dtype, int32_t* frames,
+                     float* label_lp, float* score, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_rnnt_align_stats(const float* lse_part, int lse_parts, const float* pick, const int32_t* labels, const int32_t* label_len,
+                           const int32_t* logit_len, const long* cell_off, long total_cells, int B, int T, int U1, int V, int blank,
+                           int32_t* frames, float* label_lp, float* score, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_ctc_align_workspace_size(int B, int T, int U, int V, size_t* bytes);
+int tfasr_ctc_align(const void* logits, const int32_t* labels, const int32_t* label_len, const int32_t* logit_len, int B, int T,
+                    int U, int V, int blank, int dtype, int normalized, int32_t* start, int32_t* end, float* label_lp, float* score,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Native executor of one Conformer block (ConformerBlock.call, encoders/conformer.py:430-520, and its backward):
  * queues every kernel of FFModule -> MHSAModule -> ConvModule -> FFModule -> LayerNorm on `stream` with one host call.

@@ -19,7 +19,7 @@ from . import kernels as K
 from .base_model import BaseModel
 from .kernels import ACT_NONE, ACT_SWISH, ACT_TANH_OUT
 from .params import ParamStore
-from .schemas import PredictInput, PredictOutput, TrainData, TrainInput, TrainOutput
+from .schemas import AlignOutput, PredictInput, PredictOutput, TrainData, TrainInput, TrainOutput
 
 
 class SingleProcess:
@@ -1566,6 +1566,83 @@ class ConformerTransducer(BaseModel):
         feats, flen = self.frontend(sig, slen, training=False)
         enc, T, elen, _ = self.encoder_fwd(feats, flen, False, None)
         return enc.view(sig.shape[0], T, self.cfg.dmodel), elen
+
+    @property
+    def seconds_per_frame(self):
+        return self.cfg.time_reduction_factor * self.cfg.stride_ms / 1000.0
+
+    @torch.no_grad()
+    def align(self, data: TrainData, precision=None):
+        """Forced alignment of data.labels to the audio: the best path through the lattice the loss sums over (csrc/align.hip) and the
+        encoder frame at which it emits each label -> AlignOutput.  Inference mode; `precision` as in encode.  On a tie a
+        label is emitted as late as possible.  Unlike the loss, the number of frames is NOT raised to the label length."""
+        if (precision or self.decode_precision) == "f32" and self.dtype != torch.float32:
+            return self.inference_twin().align(data, "f32")
+        enc, elen = self.encode(data.inputs.inputs, data.inputs.inputs_length, "f32" if self.dtype == torch.float32 else "bf16")
+        return self.align_encoded(enc, elen, data.inputs.predictions, data.labels.labels, data.labels.labels_length)
+
+    @torch.no_grad()
+    def align_encoded(self, enc, elen, predictions, labels, labels_length):
+        """align() on encoder output enc [B, T', dmodel] (this model's storage type) with lengths elen: prediction network over the
+        blank-prepended labels `predictions` [B, U+1], the joint network on the valid lattice nodes only, then the walk.  A bf16 model
+        takes the log-probabilities from the vocabulary product's statistics epilogue (where its 256-row kernel applies the logits never
+        exist); f32, or a shape that epilogue does not hold, walks materialised logits: the choices loss_and_backward makes."""
+        ps, c, dev = self.ps, self.cfg, self.device
+        B, T, d = enc.shape
+        J, V = c.joint_dim, c.vocab_size
+        tokens = predictions.to(dev).to(torch.int32).contiguous()
+        no_labels = tokens.shape[1] == 1  # nothing to align anywhere: one padding column keeps the label arrays non-empty
+        if no_labels:
+            tokens = torch.cat([tokens, torch.full((B, 1), self.blank, dtype=torch.int32, device=dev)], 1)
+        U1 = tokens.shape[1]
+        lab = labels.to(dev).to(torch.int32)
+        if lab.shape[1] != U1 - 1:  # labels padded to another width than the predictions
+            fit = torch.zeros(B, U1 - 1, dtype=torch.int32, device=dev)
+            w = min(U1 - 1, lab.shape[1])
+            fit[:, :w] = lab[:, :w]
+            lab = fit
+        lab = lab.contiguous()
+        tl = [min(max(int(v), 0), T) for v in elen]
+        ul = [min(max(int(v), 0), U1 - 1) for v in labels_length.tolist()]
+        tl_dev, ul_dev = self._h2d(tl), self._h2d(ul)
+        plen = self._h2d([u + 1 for u in ul])
+        enc2 = enc.reshape(B * T, d)
+        if enc2.dtype != self.dtype or not enc2.is_contiguous():
+            enc2 = K.cast(enc2.contiguous(), torch.empty(B * T, d, dtype=self.dtype, device=dev))
+        pred = self.prediction_fwd(tokens, plen, None)
+        off = np.zeros(B + 1, np.int64)
+        off[1:] = np.cumsum([t * (u + 1) for t, u in zip(tl, ul)])
+        total = int(off[-1])
+        if total == 0:  # no utterance has a frame
+            return AlignOutput(torch.full((B, U1 - 1), -1, dtype=torch.int32, device=dev), None, torch.zeros(B, U1 - 1, device=dev),
+                               torch.full((B,), float("-inf"), device=dev), self.seconds_per_frame)
+        off_dev = self._h2d(off, torch.int64)
+        e = K.matmul(enc2, ps.w2d("joint/enc/w"), bias=ps.p("joint/enc/b"))
+        p = K.matmul(pred, ps.w2d("joint/pred/w"), bias=ps.p("joint/pred/b"))
+        h = K.joint_fwd_packed(e.view(B, T, J), p.view(B, U1, J), off_dev, ul_dev, total)
+        out = None
+        if self.dtype == torch.bfloat16 and self.fuse_joint_stats:
+            parts = -(-V // 128) * 2
+            lse_part = torch.empty(total, parts, 2, dtype=torch.float32, device=dev)
+            pick = torch.empty(total, 2, dtype=torch.float32, device=dev)
+            row_label = K.rnnt_row_labels(lab, ul_dev, tl_dev, off_dev, total, T, V)
+            # statistics only (the 256-row kernel), else statistics beside materialised logits (the 128-row kernel: the walk still skips its
+            # pass over them), else the plain route below: the order loss_and_backward tries them in
+            for materialise in (False, True):
+                try:
+                    logits = torch.empty(total, V, dtype=self.dtype, device=dev) if materialise else None
+                    K.gemm(h, ps.w2d("joint/vocab/w"), logits, total, V, J, J, V, V, bias=ps.p("joint/vocab/b"), lse=(lse_part, row_label, pick))
+                    out = K.rnnt_align_stats((lse_part, pick), lab, ul_dev, tl_dev, T, V, cell_off=off_dev, blank=self.blank)
+                    break
+                except K._lib.TfasrUnsupported:
+                    out = None
+        if out is None:
+            logits = K.matmul(h, ps.w2d("joint/vocab/w"), bias=ps.p("joint/vocab/b"))  # [total, V]
+            out = K.rnnt_align(logits, lab, ul_dev, tl_dev, T=T, cell_off=off_dev, blank=self.blank)
+        frames, label_lp, score = out
+        if no_labels:
+            frames, label_lp = frames[:, :0], label_lp[:, :0]
+        return AlignOutput(frames, None, label_lp, score, self.seconds_per_frame)
 
     @torch.no_grad()
     def recognize(self, inputs: PredictInput, max_tokens_per_frame=3, check_every=16, precision=None):

@@ -10,6 +10,7 @@
 // (utterance, {alpha|beta}), one thread per state, T sequential steps through a double-buffered LDS row), the gradient
 // (one workgroup per frame; per-label occupancies combined with LDS atomics, then one pass over V).
 #include "common.h"
+#include "lattice_lp.h"
 #include <algorithm>
 
 namespace {
@@ -161,6 +162,16 @@ __global__ void ctc_collapse_kernel(const int32_t* __restrict__ amax, const int3
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
+
+// The per-frame pass of the loss, shared with the forced alignment (csrc/align.hip).
+int tfasr_detail::ctc_row_lse(const void* logits, float* lse, long rows, int V, int dtype, hipStream_t stream) {
+  const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
+  if (dtype == TFASR_F32) TFASR_KLAUNCH(ctc_lse_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)logits, lse, (int32_t*)nullptr, rows, V);
+  else if (dtype == TFASR_BF16) TFASR_KLAUNCH(ctc_lse_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (const bf16_t*)logits, lse, (int32_t*)nullptr, rows, V);
+  else return TFASR_STATUS_INVALID_VALUE;
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
 
 extern "C" int tfasr_ctc_loss_workspace_size(int B, int T, int U, int V, size_t* bytes) {
   if (!bytes || B <= 0 || T <= 0 || U < 0 || V <= 0) return TFASR_STATUS_INVALID_VALUE;

@@ -18,6 +18,7 @@
 //                      anti-diagonals, neighbours exchanged through a double-buffered LDS row
 //   3. rnnt_grad     : one wave per lattice node, rewrites the row with the gradient
 #include "common.h"
+#include "lattice_lp.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -599,6 +600,28 @@ extern "C" int tfasr_rnnt_loss_workspace_size(int B, int T, int U1, int V, size_
   return TFASR_STATUS_SUCCESS;
 }
 
+// The first pass of the loss, shared with the forced alignment (csrc/align.hip).
+int tfasr_detail::rnnt_lattice_logprobs(const void* logits, const int32_t* labels, const int32_t* label_len, const int32_t* logit_len,
+                                        const long* cell_off, long nrows, int B, int T, int U1, int V, int dtype, const float* lse_part,
+                                        int lse_parts, const float* pick, float* lse, float* blank_lp, float* truth_lp, hipStream_t stream) {
+  const int wpb = 4;
+  const int grid = (int)std::min<long>((nrows + wpb - 1) / wpb, 256L * 32);
+  if (lse_part) {
+    const int fg = (int)std::min<long>(((lse_parts == 16 ? nrows * 16 : nrows) + 255) / 256, 256L * 16);
+    TFASR_KLAUNCH(rnnt_stats_finalize_kernel, dim3(fg), dim3(256), 0, stream, (const float2*)lse_part, lse_parts, pick, label_len, logit_len,
+                       cell_off, nrows, B, T, U1, lse, blank_lp, truth_lp);
+  } else if (dtype == TFASR_F32)
+    TFASR_KLAUNCH(rnnt_logprobs_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)logits, labels,
+                       label_len, logit_len, cell_off, nrows, B, T, U1, V, lse, blank_lp, truth_lp);
+  else if (dtype == TFASR_BF16)
+    TFASR_KLAUNCH(rnnt_logprobs_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (const bf16_t*)logits, labels,
+                       label_len, logit_len, cell_off, nrows, B, T, U1, V, lse, blank_lp, truth_lp);
+  else
+    return TFASR_STATUS_INVALID_VALUE;
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
 static int rnnt_impl(const void* logits, void* grads, const int32_t* labels, const int32_t* label_len,
                      const int32_t* logit_len, const float* grad_scale, const long* cell_off, long nrows, int B, int T, int U1,
                      int V, int blank, int dtype, float* costs, void* workspace, size_t workspace_bytes, void* stream_,
@@ -618,19 +641,9 @@ static int rnnt_impl(const void* logits, void* grads, const int32_t* labels, con
   float* beta = (float*)(ws + 4 * seg);
   const int wpb = 4;
   int grid = (int)std::min<long>((nrows + wpb - 1) / wpb, 256L * 32);
-  if (lse_part) {
-    const int fg = (int)std::min<long>(((lse_parts == 16 ? nrows * 16 : nrows) + 255) / 256, 256L * 16);
-    TFASR_KLAUNCH(rnnt_stats_finalize_kernel, dim3(fg), dim3(256), 0, stream, (const float2*)lse_part, lse_parts, pick, label_len, logit_len,
-                       cell_off, nrows, B, T, U1, lse, blank_lp, truth_lp);
-  } else if (dtype == TFASR_F32)
-    TFASR_KLAUNCH(rnnt_logprobs_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)logits, labels,
-                       label_len, logit_len, cell_off, nrows, B, T, U1, V, lse, blank_lp, truth_lp);
-  else if (dtype == TFASR_BF16)
-    TFASR_KLAUNCH(rnnt_logprobs_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (const bf16_t*)logits, labels,
-                       label_len, logit_len, cell_off, nrows, B, T, U1, V, lse, blank_lp, truth_lp);
-  else
-    return TFASR_STATUS_INVALID_VALUE;
-  TFASR_CHECK_LAUNCH();
+  const int lp_status = tfasr_detail::rnnt_lattice_logprobs(logits, labels, label_len, logit_len, cell_off, nrows, B, T, U1, V, dtype, lse_part,
+                                                            lse_parts, pick, lse, blank_lp, truth_lp, stream);
+  if (lp_status != TFASR_STATUS_SUCCESS) return lp_status;
   const int nthr = ((U1 + 63) / 64) * 64;
   static const bool wave_off = false;  // A/B probe: the workgroup kernel
   static const bool fast = !(false);

@@ -16,7 +16,7 @@ import torch
 
 from . import kernels as K
 from .conformer import ConformerTransducer
-from .schemas import PredictInput, PredictOutput, TrainData, TrainInput, TrainOutput
+from .schemas import AlignOutput, PredictInput, PredictOutput, TrainData, TrainInput, TrainOutput
 
 
 class ConformerCTC(ConformerTransducer):
@@ -113,6 +113,22 @@ class ConformerCTC(ConformerTransducer):
         lengths [B, P], log_prob [B, P], best first; P = top_paths <= beam_width."""
         logits, elen = self._infer_logits(inputs)
         return K.ctc_beam_search_device(logits, self._h2d(elen), beam_width=beam_width, top_paths=top_paths, blank_index=None)
+
+    @torch.no_grad()
+    def align(self, data: TrainData, precision=None):
+        """CTC forced alignment of data.labels over the f32 logits of _infer_logits (csrc/align.hip) -> AlignOutput: label u holds the
+        frames [frames[b, u], ends[b, u]).  Ties take the smallest move, and the final blank at the end; labels that do not fit their
+        frames give score -inf and -1 everywhere."""
+        logits, elen = self._infer_logits(PredictInput(data.inputs.inputs, data.inputs.inputs_length))
+        B, T, V = logits.shape
+        lab = data.labels.labels.to(self.device).to(torch.int32).contiguous()
+        tl = [min(max(int(v), 0), T) for v in elen]
+        ul = [min(max(int(v), 0), lab.shape[1]) for v in data.labels.labels_length.tolist()]
+        start, end, label_lp, score = K.ctc_align(logits, lab, self._h2d(ul), self._h2d(tl), blank=self.blank)
+        return AlignOutput(start, end, label_lp, score, self.seconds_per_frame)
+
+    def align_encoded(self, *a, **k):
+        raise NotImplementedError("the transducer lattice does not apply to a CTC model: use align")
 
     def recognize_encoded(self, *a, **k):
         raise NotImplementedError("transducer greedy search does not apply to a CTC model")

@@ -136,6 +136,107 @@ def rnnt_loss_packed_coef(labels, label_len, logit_len, cell_off, total_cells, T
     return costs, coef
 
 
+# ------------------------------------------------------------------------------------ forced alignment
+def rnnt_align_workspace_size(B, T, U1, V):
+    n = ctypes.c_size_t(0)
+    check(_lib.load().tfasr_rnnt_align_workspace_size(B, T, U1, V, ctypes.byref(n)), "rnnt_align_workspace_size")
+    return n.value
+
+
+def ctc_align_workspace_size(B, T, U, V):
+    n = ctypes.c_size_t(0)
+    check(_lib.load().tfasr_ctc_align_workspace_size(B, T, U, V, ctypes.byref(n)), "ctc_align_workspace_size")
+    return n.value
+
+
+def _align_check(st, what):
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported(f"{what}: shape outside what the alignment kernels hold (see include/tfasr_hip.h)")
+    check(st, what)
+
+
+def _rnnt_align_io(labels_shape, label_len, logit_len, cell_off, dev):
+    B, U = labels_shape
+    assert label_len.dtype == torch.int32 and logit_len.dtype == torch.int32 and label_len.shape == (B,) and logit_len.shape == (B,)
+    assert cell_off is None or (cell_off.dtype == torch.int64 and cell_off.numel() >= B)
+    frames = torch.empty(B, U, dtype=torch.int32, device=dev)
+    label_lp = torch.empty(B, U, dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    return frames, label_lp, score
+
+
+def rnnt_align_lattice(blank_lp, truth_lp, label_len, logit_len, T=None, U1=None, cell_off=None):
+    """Viterbi walk over caller-supplied lattice log-probabilities (f32): dense [B,T,U1], or packed [total_cells] with cell_off [B(+1)]
+    int64 and the padded T / U1 given.  -> (frames [B,U1-1] i32, label_lp [B,U1-1] f32, score [B] f32); on a tie a label is emitted as late as possible."""
+    assert blank_lp.dtype == torch.float32 and truth_lp.dtype == torch.float32 and blank_lp.shape == truth_lp.shape
+    if cell_off is None:
+        assert blank_lp.dim() == 3
+        B, T, U1 = blank_lp.shape
+        total = B * T * U1
+    else:
+        assert blank_lp.dim() == 1 and T is not None and U1 is not None
+        B, total = label_len.shape[0], blank_lp.shape[0]
+    frames, label_lp, score = _rnnt_align_io((B, U1 - 1), label_len, logit_len, cell_off, blank_lp.device)
+    ws = workspace(rnnt_align_workspace_size(B, T, U1, 2), blank_lp.device, "align")
+    _align_check(_lib.load().tfasr_rnnt_align_lattice(_p(blank_lp), _p(truth_lp), _p(label_len), _p(logit_len), _p(cell_off), total, B, T, U1,
+                                                      _p(frames), _p(label_lp), _p(score), _p(ws), ws.numel(), _stream()), "rnnt_align_lattice")
+    return frames, label_lp, score
+
+
+def rnnt_align(logits, labels, label_len, logit_len, T=None, cell_off=None, blank=0):
+    """Forced alignment from logits (f32 | bf16): dense [B,T,U1,V], or packed [total_cells,V] with cell_off and the padded T.
+    labels [B,U1-1] i32.  -> (frames, label_lp, score) as rnnt_align_lattice."""
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 2
+    B, U = labels.shape
+    if cell_off is None:
+        assert logits.dim() == 4 and logits.shape[0] == B and logits.shape[2] == U + 1
+        T, V = logits.shape[1], logits.shape[3]
+        total = B * T * (U + 1)
+    else:
+        assert logits.dim() == 2 and T is not None
+        total, V = logits.shape
+    frames, label_lp, score = _rnnt_align_io((B, U), label_len, logit_len, cell_off, logits.device)
+    ws = workspace(rnnt_align_workspace_size(B, T, U + 1, V), logits.device, "align")
+    _align_check(_lib.load().tfasr_rnnt_align(_p(logits), _p(labels), _p(label_len), _p(logit_len), _p(cell_off), total, B, T, U + 1, V, blank,
+                                              _dt(logits), _p(frames), _p(label_lp), _p(score), _p(ws), ws.numel(), _stream()), "rnnt_align")
+    return frames, label_lp, score
+
+
+def rnnt_align_stats(stats, labels, label_len, logit_len, T, V, cell_off=None, blank=0):
+    """Forced alignment from the vocabulary GEMM's statistics epilogue (stats = (lse_part [rows,parts,2], pick [rows,2]) of
+    gemm(..., out=None, lse=...)): the logits never exist.  Rows are the lattice nodes, dense or packed (cell_off)."""
+    part, pick = stats
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 2
+    B, U = labels.shape
+    total = part.shape[0]
+    assert cell_off is not None or total == B * T * (U + 1)
+    frames, label_lp, score = _rnnt_align_io((B, U), label_len, logit_len, cell_off, part.device)
+    ws = workspace(rnnt_align_workspace_size(B, T, U + 1, V), part.device, "align")
+    _align_check(_lib.load().tfasr_rnnt_align_stats(_p(part), part.shape[1], _p(pick), _p(labels), _p(label_len), _p(logit_len), _p(cell_off), total,
+                                                    B, T, U + 1, V, blank, _p(frames), _p(label_lp), _p(score), _p(ws), ws.numel(), _stream()),
+                 "rnnt_align_stats")
+    return frames, label_lp, score
+
+
+def ctc_align(logits, labels, label_len, logit_len, blank=0, normalized=False):
+    """CTC forced alignment of logits [B,T,V] (f32 | bf16; normalized=True: log-probabilities already) to labels [B,U] i32.
+    -> (start [B,U] i32, end [B,U] i32, label_lp [B,U] f32, score [B] f32); ties take the smallest move, the final blank at the end."""
+    assert logits.dim() == 3 and labels.dim() == 2 and labels.dtype == torch.int32 and labels.is_contiguous()
+    B, T, V = logits.shape
+    U = labels.shape[1]
+    assert labels.shape[0] == B and label_len.dtype == torch.int32 and logit_len.dtype == torch.int32
+    dev = logits.device
+    start = torch.empty(B, U, dtype=torch.int32, device=dev)
+    end = torch.empty(B, U, dtype=torch.int32, device=dev)
+    label_lp = torch.empty(B, U, dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = workspace(ctc_align_workspace_size(B, T, U, V), dev, "align")
+    _align_check(_lib.load().tfasr_ctc_align(_p(logits), _p(labels) if U else None, _p(label_len), _p(logit_len), B, T, U, V, blank, _dt(logits),
+                                             1 if normalized else 0, _p(start) if U else None, _p(end) if U else None, _p(label_lp) if U else None,
+                                             _p(score), _p(ws), ws.numel(), _stream()), "ctc_align")
+    return start, end, label_lp, score
+
+
 # ---------------------------------------------------------------------------------------------- GEMM
 def gemm(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, bias=None, res=None, dact_z=None,
          prez=None, alpha=1.0, beta=1.0, act=ACT_NONE, dact=ACT_NONE, nb1=1, nb2=1, sA=(0, 0), sB=(0, 0), sD=(0, 0),

@@ -118,6 +118,12 @@ class Tokenizer:
     def detokenize_unicode_points(self, indices):
         raise NotImplementedError
 
+    def word_spans(self, indices):
+        """One transcript's ids [U] -> [(word, first_token_index, last_token_index)], in order: which tokens spell which word, so that
+        the per-token frames of a forced alignment (AlignOutput.frames) become word times.  The words joined by single spaces equal
+        detokenize(indices)[0]; separators and dropped ids (spaces, blank, padding) belong to no span."""
+        raise NotImplementedError(f"{type(self).__name__} has no word_spans")
+
     def _rows(self, indices):
         a = np.asarray(indices, dtype=np.int64)
         return a[None] if a.ndim == 1 else a
@@ -162,6 +168,23 @@ class CharTokenizer(Tokenizer):
             out.append(self.normalize_text(s))
         return out
 
+    def word_spans(self, indices):
+        ids = self.normalize_indices(np.asarray(indices).reshape(-1))
+        blank_tok = self.tokens[self.blank] if 0 <= self.blank < len(self.tokens) else ""
+        spans, cur = [], None  # cur = [text, first, last]
+        for k, i in enumerate(ids):
+            raw = self.tokens[i] if 0 <= i < len(self.tokens) else blank_tok
+            tok = self.normalize_text(raw)
+            if tok:
+                if cur is None:
+                    cur = [tok, k, k]
+                    spans.append(cur)
+                else:
+                    cur[0], cur[2] = cur[0] + tok, k
+            elif raw:  # a space ends the word; an empty token (blank, padding) spells nothing and splits nothing
+                cur = None
+        return [tuple(s) for s in spans]
+
     def detokenize_unicode_points(self, indices):
         ids = self.normalize_indices(np.asarray(indices).reshape(-1))
         pts = [ord(self.tokens[i][0]) for i in ids if 0 <= i < len(self.tokens) and self.tokens[i]]
@@ -190,6 +213,22 @@ class SentencePieceTokenizer(Tokenizer):
         rows = self._rows(self.normalize_indices(indices))
         n = self.num_classes
         return [self.normalize_text(self.tokenizer.DecodeIds([int(i) for i in r if 0 <= i < n])) for r in rows]
+
+    def word_spans(self, indices):
+        ids = self.normalize_indices(np.asarray(indices).reshape(-1))
+        n = self.num_classes
+        groups = []  # [ids, first, last]: a piece that starts with U+2581 opens a word
+        for k, i in enumerate(ids):
+            i = int(i)
+            if not 0 <= i < n or i == self.blank:
+                continue
+            if not groups or self.tokenizer.IdToPiece(i).startswith("\u2581"):
+                groups.append([[i], k, k])
+            else:
+                groups[-1][0].append(i)
+                groups[-1][2] = k
+        spans = [(self.normalize_text(self.tokenizer.DecodeIds(g)), a, b) for g, a, b in groups]
+        return [(w, a, b) for w, a, b in spans if w]
 
     def detokenize_unicode_points(self, indices):
         s = self.detokenize(np.asarray(indices).reshape(1, -1))[0]
