@@ -844,6 +844,43 @@ int tfasr_block_ln_fold_all(void* const* ctx, int n, int d, void* stream);
 int tfasr_block_dwconv_wgrad_all(const tfasr_block_cfg* cfg, const tfasr_block_params* const* params, void* const* ctx, const void* const* dcv,
                                  int n, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Streaming recognition (csrc/stream.hip; declarations added under ABI 44, nothing existing changes): one step = B streams x at most
+ * C = chunk_size encoder frames with state carried on the device.  seen [B] = encoder frames a stream consumed before this chunk,
+ * nvalid [B] = real rows of this chunk (0 .. C; 0 = the stream is idle in this step and NONE of its state is written).
+ *
+ * tfasr_stream_attn_fwd: qkv [B*C, 3*H*dh] (q | k | v column blocks, the fused projection's layout), ubias / vbias [H*dh] f32,
+ *   pos [hist + 2C - 1, H*dh] = the projected relative-position table, row r <-> position hist + C - 1 - r (a constant of the session),
+ *   kcache / vcache [B, hist, H*dh] rings (frame f in slot f % hist; may be NULL with hist == 0), out [B*C, H*dh]: context of the valid
+ *   rows against min(seen, hist) + nvalid keys, score ((q+u).k + (q+v).p(i-j)) * scale, softmax, times V; rows >= nvalid are zero.
+ * tfasr_stream_kv_append: the chunk's valid k / v rows into the rings; queue it AFTER the attention of the same layer.
+ * tfasr_stream_glu_dwconv_fwd: glu_x [B*C, 2d] -> GLU -> causal depthwise conv (w [K, d], bias [d] f32, K <= 32) over
+ *   state [B, K-1, d] ++ the valid rows -> y [B*C, d] (rows >= nvalid zero); state = the last K-1 rows of that concatenation, in place.
+ * UNSUPPORTED beyond the limits below. */
+#define TFASR_STREAM_MAX_CHUNK 32
+#define TFASR_STREAM_MAX_KEYS 512 /* hist + C */
+#define TFASR_STREAM_MAX_HEAD 128
+int tfasr_stream_attn_fwd(const void* qkv, const float* ubias, const float* vbias, const void* pos, const void* kcache, const void* vcache,
+                          const int32_t* seen, const int32_t* nvalid, void* out, int B, int C, int H, int dh, int hist, float scale,
+                          int dtype, void* stream);
+int tfasr_stream_kv_append(const void* qkv, void* kcache, void* vcache, const int32_t* seen, const int32_t* nvalid, int B, int C, int H,
+                           int dh, int hist, int dtype, void* stream);
+int tfasr_stream_glu_dwconv_fwd(const void* glu_x, void* state, const float* w, const float* bias, const int32_t* nvalid, void* y, int B,
+                                int C, int d, int K, int dtype, void* stream);
+/* tfasr_logmel for a stream: signal [B, N] holds the unconsumed samples of every stream from column 0, nlen [B] how many of them are
+ * real (the rest of a frame is zero padding: ask for frames past nlen only when flushing), prev [B] / has_prev [B] the last sample
+ * consumed before column 0 (pre-emphasis of sample 0; has_prev == 0: start of the utterance).  out [B, T0, F]. */
+int tfasr_logmel_stream(const float* signal, const int32_t* nlen, const float* prev, const int32_t* has_prev, int B, int N, float preemph,
+                        const float* window, int frame_len, int frame_step, int nfft, const float* melw, const int32_t* band, int F,
+                        float eps, void* out, int T0, int dtype, void* stream);
+/* Greedy search, `mode` 2 of tfasr_decode_prepare / _step / _steps / _update: the rule of mode 1 (recognize_single: every frame decoded,
+ * at most max_tokens_per_frame symbols each) applied to every row independently.  per_frame is [B] (symbols of the row's CURRENT frame),
+ * tokens [B, max_tokens] with tok_idx [B] starting at -1, a row is active while frame_idx[b] < nframes[b] (nframes[b] == 0 allowed).
+ * tfasr_ctc_greedy_decode_carry: tfasr_ctc_greedy_decode whose merge of repeated classes looks across a chunk boundary: last_class [B]
+ * (in / out; -1 = none yet) is the arg-max class of the stream's previous frame; rows with logit_len == 0 keep theirs. */
+int tfasr_ctc_greedy_decode_carry(const void* logits, const int32_t* logit_len, int32_t* last_class, int32_t* workspace_argmax,
+                                  int32_t* tokens, int32_t* tokens_len, int B, int T, int V, int blank, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1649,8 +1649,31 @@ class ConformerTransducer(BaseModel):
         """Transducer.recognize (base_transducer.py:474-494): batch size 1 -> recognize_single (<=3 symbols per frame),
         otherwise recognize_batch — the two variants are NOT equivalent in the reference and both are reproduced."""
         enc, elen = self.encode(inputs.inputs, inputs.inputs_length, precision)
-        return self.recognize_encoded(enc, elen, inputs.previous_tokens, inputs.previous_decoder_states, max_tokens_per_frame,
-                                      check_every)
+        out = self.recognize_encoded(enc, elen, inputs.previous_tokens, inputs.previous_decoder_states, max_tokens_per_frame,
+                                     check_every)
+        if inputs.previous_encoder_states is not None:  # a streaming session's encoder state (streaming.StreamState.export) rides along
+            out = out._replace(next_encoder_states=inputs.previous_encoder_states)
+        return out
+
+    # =================================================================================== streaming (streaming.py, csrc/stream.hip)
+    def stream_state(self, batch_size=1, precision=None):
+        """Encoder state of `batch_size` streams for encode_chunk.  precision as encode: "f32" (default) = the inference twin."""
+        from . import streaming
+
+        return streaming.StreamState(streaming._twin(self, precision), batch_size)
+
+    def encode_chunk(self, state, feats, nframes):
+        """One chunk of the streaming encoder: feats [B, n <= 4 chunk_size, F], nframes [B] -> (enc [B, chunk_size, dmodel], nvalid [B])."""
+        from . import streaming
+
+        return streaming.encode_chunk(state, feats, nframes)
+
+    def stream(self, batch_size=1, precision=None, max_tokens_per_frame=3):
+        """Incremental recognition session (streaming.StreamingRecognizer): accept(pcm) ... finish().  Refused, with the reason, for a
+        full-context config, unlimited history, and sizes beyond the streaming attention kernel."""
+        from . import streaming
+
+        return streaming.StreamingRecognizer(self, batch_size, precision, max_tokens_per_frame)
 
     def recognize_beam(self, inputs: PredictInput, beam_width=10, device_search=False, precision=None, **kw):
         """The reference's recognize_beam falls back to greedy (base_transducer.py:841-842), and so does this one by default.

@@ -34,6 +34,11 @@ class ContextNetTransducer(ConformerTransducer):
         self.blocks = contextnet_modules(cfg)
         self.native_blocks = False  # the native executor (csrc/block.hip) is the Conformer block
 
+    def stream(self, *a, **k):
+        raise NotImplementedError("ContextNet cannot stream: its squeeze-and-excite is a mean over the whole utterance")
+
+    stream_state = encode_chunk = stream
+
     def _encoder_length(self, t):
         for blk in self.blocks:
             t = -(-int(t) // int(blk["stride"]))

@@ -145,11 +145,11 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const T* logits, T* grads
 
 // merge repeated + drop blanks (tf.nn.ctc_greedy_decoder); one thread per utterance
 __global__ void ctc_collapse_kernel(const int32_t* __restrict__ amax, const int32_t* __restrict__ logit_len, int32_t* __restrict__ out,
-                                    int32_t* __restrict__ out_len, int B, int Tm, int blank) {
+                                    int32_t* __restrict__ out_len, int B, int Tm, int blank, int32_t* __restrict__ last = nullptr) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const int Tl = min(logit_len[b], Tm);
-  int prev = -1, n = 0;
+  int prev = last ? last[b] : -1, n = 0;  // last: the class of the stream's previous frame (tfasr_ctc_greedy_decode_carry)
   for (int t = 0; t < Tl; ++t) {
     const int c = amax[(long)b * Tm + t];
     if (c != prev && c != blank) out[(long)b * Tm + n++] = c;
@@ -157,6 +157,7 @@ __global__ void ctc_collapse_kernel(const int32_t* __restrict__ amax, const int3
   }
   for (int i = n; i < Tm; ++i) out[(long)b * Tm + i] = blank;
   out_len[b] = n;
+  if (last && Tl > 0) last[b] = prev;
 }
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -220,6 +221,21 @@ extern "C" int tfasr_ctc_greedy_decode(const void* logits, const int32_t* logit_
   else if (dtype == TFASR_BF16) TFASR_KLAUNCH(ctc_lse_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)logits, (float*)nullptr, workspace_argmax, rows, V);
   else return TFASR_STATUS_INVALID_VALUE;
   TFASR_KLAUNCH(ctc_collapse_kernel, dim3((B + 63) / 64), dim3(64), 0, s, workspace_argmax, logit_len, tokens, tokens_len, B, T, blank);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_greedy_decode_carry(const void* logits, const int32_t* logit_len, int32_t* last_class, int32_t* workspace_argmax,
+                                             int32_t* tokens, int32_t* tokens_len, int B, int T, int V, int blank, int dtype, void* stream_) {
+  if (!logits || !logit_len || !last_class || !workspace_argmax || !tokens || !tokens_len || B <= 0 || T <= 0 || V <= 0)
+    return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t s = (hipStream_t)stream_;
+  const long rows = (long)B * T;
+  const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
+  if (dtype == TFASR_F32) TFASR_KLAUNCH(ctc_lse_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)logits, (float*)nullptr, workspace_argmax, rows, V);
+  else if (dtype == TFASR_BF16) TFASR_KLAUNCH(ctc_lse_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)logits, (float*)nullptr, workspace_argmax, rows, V);
+  else return TFASR_STATUS_INVALID_VALUE;
+  TFASR_KLAUNCH(ctc_collapse_kernel, dim3((B + 63) / 64), dim3(64), 0, s, workspace_argmax, logit_len, tokens, tokens_len, B, T, blank, last_class);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }

@@ -9,7 +9,8 @@
 
 namespace {
 
-// mode 0 = recognize_batch, 1 = recognize_single (B == 1)
+// mode 0 = recognize_batch, 1 = recognize_single (B == 1), 2 = the rule of mode 1 for every row on its own (streaming sessions:
+// per_frame is [B], the symbols of the row's current frame; a row takes part while frame_idx[b] < nframes[b])
 template <typename T>
 __global__ void decode_prepare_kernel(const T* __restrict__ encj, const int32_t* __restrict__ nframes,
                                       const int32_t* __restrict__ frame_idx, const int32_t* __restrict__ tok_idx,
@@ -93,6 +94,21 @@ __global__ __launch_bounds__(256) void decode_update_kernel(
       if (!eq_blank) { tok_idx[b] = nxt; prev_tok[b] = cur; }
       else frame_idx[b] = fi + 1;
       s_keep = eq_blank ? 1 : 0;
+    } else if (mode == 2) {
+      const int fi = frame_idx[b];
+      s_keep = 1;
+      if (fi < nframes[b]) {
+        const bool is_blank = (cur == blank);
+        int nf = per_frame[b];
+        if (!is_blank) nf += 1;
+        const bool next = is_blank || nf >= max_tokens_per_frame;
+        per_frame[b] = next ? 0 : nf;
+        if (next) frame_idx[b] = fi + 1;
+        const int ti = tok_idx[b] + 1;
+        if (!is_blank && ti < max_tokens) { tok_idx[b] = ti; tokens[(long)b * max_tokens + ti] = cur; }
+        if (!is_blank) prev_tok[b] = cur;
+        s_keep = is_blank ? 1 : 0;
+      }
     } else {
       const int fi = frame_idx[b];
       const bool is_blank = (cur == blank);
@@ -138,6 +154,7 @@ __global__ __launch_bounds__(256) void decode_update_regs_kernel(
   const int act = active[0];
   int nf = 0;
   if (mode == 1) nf = per_frame[fi];  // (second round trip, single-utterance variant only)
+  else if (mode == 2) nf = per_frame[b];
   if (!act) return;
   float m = -INFINITY;
 #pragma unroll
@@ -185,6 +202,18 @@ __global__ __launch_bounds__(256) void decode_update_regs_kernel(
       if (!eq_blank) { tok_idx[b] = nxt; prev_tok[b] = cur; }
       else frame_idx[b] = fi + 1;
       s_keep = eq_blank ? 1 : 0;
+    } else if (mode == 2) {
+      s_keep = 1;
+      if (fi < nfr) {
+        const bool is_blank = (cur == blank);
+        if (!is_blank) nf += 1;
+        const bool next = is_blank || nf >= max_tokens_per_frame;
+        per_frame[b] = next ? 0 : nf;
+        if (next) frame_idx[b] = fi + 1;
+        if (!is_blank && ti + 1 < max_tokens) { tok_idx[b] = ti + 1; tokens[(long)b * max_tokens + ti + 1] = cur; }
+        if (!is_blank) prev_tok[b] = cur;
+        s_keep = is_blank ? 1 : 0;
+      }
     } else {
       const bool is_blank = (cur == blank);
       if (!is_blank) { nf += 1; per_frame[fi] = nf; }
@@ -227,7 +256,7 @@ extern "C" int tfasr_decode_update(const void* logits, const int32_t* active, co
                                    int max_tokens, int blank, int mode, int max_tokens_per_frame, int dtype, void* stream_) {
   if (!logits || !active || !nframes || !frame_idx || !prev_tok || !tok_idx || !tokens || !h_new || !c_new || !h || !c)
     return TFASR_STATUS_INVALID_VALUE;
-  if (B <= 0 || V <= 0 || P <= 0 || (mode == 1 && (B != 1 || !per_frame))) return TFASR_STATUS_INVALID_VALUE;
+  if (B <= 0 || V <= 0 || P <= 0 || (mode == 1 && (B != 1 || !per_frame)) || (mode == 2 && !per_frame)) return TFASR_STATUS_INVALID_VALUE;
   hipStream_t s = (hipStream_t)stream_;
   if (dtype == TFASR_F32 && P <= 1024 && V <= 4096) {
 #define TFASR_DU(NV) TFASR_KLAUNCH(decode_update_regs_kernel<NV>, dim3(B), dim3(256), 0, s, (const float*)logits, active, nframes, frame_idx, prev_tok, \

@@ -65,11 +65,14 @@ __device__ __forceinline__ int pw_index(int f) { return f + 4 * (f >> 5); }  // 
 //   pass 3: DFT over a            -> X[k2 + 8 b2 + 64 a2]
 // Real and imaginary parts live in separate f64 images; exchange addresses in 8-byte units: write 72 k2 + l / read 72 k2 + a + 8 b,
 // then write 72 k2 + 9 a + b2 / read 72 k2 + 9 a + b2: inside every 32-lane group each access hits 32 different bank pairs.
-template <typename T>
-__global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ sig, int B, int N, float preemph,
-                                                     const float* __restrict__ window, int frame_len, int frame_step,
-                                                     const float* __restrict__ melw, const int32_t* __restrict__ band,
-                                                     int F, float eps, T* __restrict__ out, int T0) {
+// STREAM (tfasr_logmel_stream): row b holds nlen[b] real samples (zero padding behind them), and the sample in front of column 0 is
+// prev[b] where has_prev[b] is set - the pre-emphasis of a stream's first unconsumed sample.  The plain instantiation ignores the three.
+template <typename T, bool STREAM>
+__device__ __forceinline__ void logmel_body(const float* __restrict__ sig, int B, int N, float preemph,
+                                            const float* __restrict__ window, int frame_len, int frame_step,
+                                            const float* __restrict__ melw, const int32_t* __restrict__ band,
+                                            int F, float eps, T* __restrict__ out, int T0, const int32_t* __restrict__ nlen,
+                                            const float* __restrict__ sprev, const int32_t* __restrict__ has_prev) {
   __shared__ __attribute__((aligned(16))) double ex[4][2][EX_PTS];   // first the block's twiddle table (512 x 2 doubles), then the exchange images
   __shared__ float pw[4][PW_LEN];
   __shared__ int snq[MAX_PASS];                                      // tap quads the widest band of each 64-bin pass needs
@@ -138,11 +141,17 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ s
   // pre-emphasis + window in f32 as the reference does, widened to f64 for the transform
   auto prepare = [&](int fr, const float (&c)[8], const float (&pv)[8], double (&o)[8]) {
     const int g0 = (fr % T0) * frame_step + lane;
+    int nl = N;
+    float p0 = 0.f;
+    bool hp = false;
+    if (STREAM) { const int b = fr / T0; nl = min(nlen[b], N); hp = has_prev[b] != 0; p0 = sprev[b]; }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int g = g0 + 64 * k;
-      const bool ok = ((rows_ok >> k) & 1) && g < N;
-      const float cc = ok ? c[k] : 0.f, pp = (ok && g > 0 && preemph > 0.f) ? pv[k] : 0.f;
+      const bool ok = ((rows_ok >> k) & 1) && g < nl;
+      const float cc = ok ? c[k] : 0.f;
+      float pp = (ok && g > 0 && preemph > 0.f) ? pv[k] : 0.f;
+      if (STREAM && ok && g == 0 && hp && preemph > 0.f) pp = p0;
       o[k] = (double)((cc - preemph * pp) * win[k]);
     }
   };
@@ -205,6 +214,23 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ s
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ sig, int B, int N, float preemph,
+                                                     const float* __restrict__ window, int frame_len, int frame_step,
+                                                     const float* __restrict__ melw, const int32_t* __restrict__ band,
+                                                     int F, float eps, T* __restrict__ out, int T0) {
+  logmel_body<T, false>(sig, B, N, preemph, window, frame_len, frame_step, melw, band, F, eps, out, T0, nullptr, nullptr, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void logmel_stream_kernel(const float* __restrict__ sig, int B, int N, float preemph,
+                                                            const float* __restrict__ window, int frame_len, int frame_step,
+                                                            const float* __restrict__ melw, const int32_t* __restrict__ band,
+                                                            int F, float eps, T* __restrict__ out, int T0, const int32_t* __restrict__ nlen,
+                                                            const float* __restrict__ sprev, const int32_t* __restrict__ has_prev) {
+  logmel_body<T, true>(sig, B, N, preemph, window, frame_len, frame_step, melw, band, F, eps, out, T0, nlen, sprev, has_prev);
+}
+
 }  // namespace
 
 extern "C" int tfasr_logmel(const float* signal, int B, int N, float preemph, const float* window, int frame_len,
@@ -236,6 +262,29 @@ extern "C" int tfasr_logmel(const float* signal, int B, int N, float preemph, co
     TFASR_KLAUNCH(logmel_kernel<bf16_t>, dim3(grid), dim3(256), dyn, s, signal, B, N, preemph, window, frame_len,
                        frame_step, melw, band, F, eps, (bf16_t*)out, T0);
   else return TFASR_STATUS_INVALID_VALUE;
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_logmel_stream(const float* signal, const int32_t* nlen, const float* prev, const int32_t* has_prev, int B, int N,
+                                   float preemph, const float* window, int frame_len, int frame_step, int nfft, const float* melw,
+                                   const int32_t* band, int F, float eps, void* out, int T0, int dtype, void* stream_) {
+  if (!signal || !nlen || !prev || !has_prev || !window || !melw || !band || !out || B <= 0 || N <= 0 || F <= 0 || T0 <= 0)
+    return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
+  if (nfft != NFFT || frame_len > NFFT || frame_len <= 0 || frame_step <= 0) return TFASR_STATUS_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream_;
+  const long nframes = (long)B * T0;
+  if (nframes > 0x7fffffffL - (1L << 20) || (long)N > 0x7fffffffL - 1024 || (long)T0 * frame_step > 0x7fffffffL - 1024) return TFASR_STATUS_UNSUPPORTED;
+  const size_t dyn = (size_t)F * TAP_PITCH * sizeof(float) + (size_t)F * 2 * sizeof(int);
+  if (dyn > 48 * 1024) return TFASR_STATUS_UNSUPPORTED;
+  const int grid = (int)std::max<long>(1, std::min<long>((nframes + 3) / 4, 1024));  // a chunk is a few hundred frames: one wave each
+  if (dtype == TFASR_F32)
+    TFASR_KLAUNCH(logmel_stream_kernel<float>, dim3(grid), dim3(256), dyn, s, signal, B, N, preemph, window, frame_len, frame_step, melw, band, F,
+                  eps, (float*)out, T0, nlen, prev, has_prev);
+  else
+    TFASR_KLAUNCH(logmel_stream_kernel<bf16_t>, dim3(grid), dim3(256), dyn, s, signal, B, N, preemph, window, frame_len, frame_step, melw, band,
+                  F, eps, (bf16_t*)out, T0, nlen, prev, has_prev);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }

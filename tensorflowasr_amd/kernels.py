@@ -1315,3 +1315,60 @@ def add_act_bwd(a, b, dy, act=ACT_NONE):
     d = torch.empty_like(a)
     check(_L().tfasr_add_act_bwd(_p(a), _p(b), _p(dy), _p(d), a.numel(), act, _dt(a), _stream()), "add_act_bwd")
     return d
+
+
+# ------------------------------------------------------------------------------------------- streaming (csrc/stream.hip)
+STREAM_MAX_CHUNK, STREAM_MAX_KEYS, STREAM_MAX_HEAD = 32, 512, 128  # TFASR_STREAM_MAX_* of include/tfasr_hip.h
+
+
+def stream_attn_fwd(qkv, ubias, vbias, pos, kcache, vcache, seen, nvalid, B, C, H, dh, hist, scale, out=None):
+    """Chunk attention against the key / value rings: qkv [B*C, 3*H*dh], pos [hist + 2C - 1, H*dh], kcache / vcache [B, hist, H*dh],
+    seen / nvalid [B] int32 on the device -> context [B*C, H*dh] (rows >= nvalid zero)."""
+    if out is None:
+        out = torch.empty(B * C, H * dh, dtype=qkv.dtype, device=qkv.device)
+    st = _L().tfasr_stream_attn_fwd(_p(qkv), _p(ubias), _p(vbias), _p(pos), _p(kcache), _p(vcache), _p(seen), _p(nvalid), _p(out), B, C, H, dh,
+                                    hist, scale, _dt(qkv), _stream())
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported(f"stream_attn_fwd: chunk {C} / keys {hist + C} / head {dh} beyond the kernel's limits "
+                                    f"({STREAM_MAX_CHUNK}, {STREAM_MAX_KEYS}, {STREAM_MAX_HEAD})")
+    check(st, "stream_attn_fwd")
+    return out
+
+
+def stream_kv_append(qkv, kcache, vcache, seen, nvalid, B, C, H, dh, hist):
+    """The chunk's valid key / value rows into ring slots (seen + r) % hist; queue after stream_attn_fwd of the same layer."""
+    check(_L().tfasr_stream_kv_append(_p(qkv), _p(kcache), _p(vcache), _p(seen), _p(nvalid), B, C, H, dh, hist, _dt(qkv), _stream()),
+          "stream_kv_append")
+
+
+def stream_glu_dwconv_fwd(glu_x, state, w, bias, nvalid, B, C, out=None):
+    """GLU + causal depthwise conv over state [B, K-1, d] ++ the chunk's valid rows; glu_x [B*C, 2d] -> [B*C, d]; state updated in place."""
+    d = glu_x.shape[-1] // 2
+    if out is None:
+        out = torch.empty(B * C, d, dtype=glu_x.dtype, device=glu_x.device)
+    check(_L().tfasr_stream_glu_dwconv_fwd(_p(glu_x), _p(state), _p(w), _p(bias), _p(nvalid), _p(out), B, C, d, w.shape[0], _dt(glu_x),
+                                           _stream()), "stream_glu_dwconv_fwd")
+    return out
+
+
+def logmel_stream(signal, nlen, prev, has_prev, T0, window, melw, band, frame_step, nfft, preemph, eps, out_dtype):
+    """tfasr_logmel on the unconsumed samples of B streams: signal [B, N] f32, nlen [B] real samples per row, prev / has_prev [B] the sample
+    in front of column 0 -> [B, T0, F]."""
+    B, N = signal.shape
+    F = melw.shape[1]
+    out = torch.empty(B, T0, F, dtype=out_dtype, device=signal.device)
+    assert signal.dtype == torch.float32 and prev.dtype == torch.float32
+    check(_L().tfasr_logmel_stream(_p(signal), _p(nlen), _p(prev), _p(has_prev), B, N, preemph, _p(window), window.numel(), frame_step, nfft,
+                                   _p(melw), _p(band), F, eps, _p(out), T0, _dt(out), _stream()), "logmel_stream")
+    return out
+
+
+def ctc_greedy_decode_carry(logits, logit_len, last_class, blank=0):
+    """ctc_greedy_decode of one chunk per stream; last_class [B] int32 (in / out, -1 = none) carries the merge of repeats over the boundary."""
+    B, T, V = logits.shape
+    ws = torch.empty(B * T, dtype=torch.int32, device=logits.device)
+    tokens = torch.empty(B, T, dtype=torch.int32, device=logits.device)
+    tlen = torch.empty(B, dtype=torch.int32, device=logits.device)
+    check(_L().tfasr_ctc_greedy_decode_carry(_p(logits), _p(logit_len), _p(last_class), _p(ws), _p(tokens), _p(tlen), B, T, V, blank,
+                                             _dt(logits), _stream()), "ctc_greedy_decode_carry")
+    return tokens, tlen

@@ -1,0 +1,376 @@
+"""Incremental recognition with the streaming Conformer (chunked attention mask, causal convolutions): chunk-by-chunk encoder with
+state carried on the device, and the greedy searches continued across chunks.
+
+The contract ("Streaming"): stream b of a session produces the encoder frames and the tokens that `model.encode` /
+`model.recognize` produce for that utterance run ALONE (batch size 1), however the samples arrive and whatever the other streams of the
+session do.  State carried per stream:
+    frontend      unconsumed samples (host side, < frame_length + frame_step + one chunk) and the last consumed raw sample
+    subsampling   the last 2 feature frames and the last 2 frames of the first convolution's activation (zeros = the causal padding)
+    each block    K and V of the last `history_size` frames (rings), the last kernel_size - 1 GLU outputs of the conv module
+    search        last token, LSTM h / c (transducer); the class of the last frame (CTC)
+The kernels that touch carried state are csrc/stream.hip; the dense pieces are the forward kernels of training with T = chunk_size.
+"""
+import math
+import typing
+
+import numpy as np
+import torch
+
+from . import kernels as K
+from .kernels import ACT_SWISH
+
+
+class StreamOutput(typing.NamedTuple):
+    tokens: torch.Tensor  # [B, W] int32 on the host: the tokens NEW in this call, blank padded
+    tokens_length: torch.Tensor  # [B] int32
+    frames: torch.Tensor  # [B] int32: encoder frames emitted so far
+
+
+class StreamState:
+    """Encoder state of `batch_size` streams (device tensors) plus the per-layer constant position tables."""
+
+    def __init__(self, model, batch_size):
+        c, ps, dev, dt = model.cfg, model.ps, model.device, model.dtype
+        check_streamable(model)
+        self.model, self.B = model, int(batch_size)
+        B, C, hist = self.B, int(c.chunk_size), int(c.history_size)
+        HD = c.num_heads * ps.head_phys
+        F1 = (c.num_feature_bins + 1) // 2
+        self.seen = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.feat_carry = torch.zeros(B, 2, c.num_feature_bins, dtype=dt, device=dev)
+        self.conv_carry = torch.zeros(B, 2, F1, ps.filt_phys, dtype=dt, device=dev)
+        nb = c.num_blocks
+        self.kcache = [torch.zeros(B, hist, HD, dtype=dt, device=dev) for _ in range(nb)]
+        self.vcache = [torch.zeros(B, hist, HD, dtype=dt, device=dev) for _ in range(nb)]
+        self.dwstate = [torch.zeros(B, c.kernel_size - 1, c.dmodel, dtype=dt, device=dev) for _ in range(nb)]
+        # alone, key j seen from query i sits at position i - j in [-(C-1), hist + C - 1]: one constant table per layer
+        pos = np.arange(hist + C - 1, -C, -1).astype(np.float32)
+        d = c.dmodel
+        ts = np.power(np.float32(1.0 / 10000.0), (2 * (np.arange(d, dtype=np.float32) // 2)) / np.float32(d)).astype(np.float32)
+        ang = pos[:, None] * ts[None, :]
+        pe = np.where((np.arange(d) % 2 == 1)[None, :], np.cos(ang), np.sin(ang)).astype(np.float32)
+        pe = torch.from_numpy(pe).to(dev).to(dt).contiguous()
+        self.pext = [K.matmul(pe, ps.w2d(f"enc/block{i}/mhsa/pos/w"), bias=ps.p(f"enc/block{i}/mhsa/pos/b")) for i in range(nb)]
+
+    def _tensors(self):
+        return [self.seen, self.feat_carry, self.conv_carry] + self.kcache + self.vcache + self.dwstate
+
+    def reset(self, rows=None):
+        for t in self._tensors():
+            if rows is None:
+                t.zero_()
+            else:
+                t[torch.as_tensor(list(rows), dtype=torch.long, device=t.device)] = 0
+
+    def export(self):
+        """The carried tensors as one flat list (a copy): what PredictOutput.next_encoder_states holds."""
+        return [t.clone() for t in self._tensors()]
+
+    def load(self, tensors):
+        mine = self._tensors()
+        if len(tensors) != len(mine):
+            raise ValueError("encoder state of another model")
+        for a, b in zip(mine, tensors):
+            a.copy_(b)
+
+
+def check_streamable(model):
+    c = model.cfg
+    if getattr(c, "encoder", "conformer") != "conformer":
+        raise ValueError("streaming needs a Conformer encoder: ContextNet's squeeze-and-excite is a mean over the whole utterance")
+    if c.chunk_size is None:
+        raise ValueError("streaming needs a streaming config: chunk_size is None (full-context attention sees the whole utterance)")
+    if c.history_size is None or int(c.history_size) < 0:
+        raise ValueError("streaming needs history_size >= 0: unlimited history would need an unbounded key / value cache")
+    C, hist = int(c.chunk_size), int(c.history_size)
+    if C < 1 or C > K.STREAM_MAX_CHUNK or hist + C > K.STREAM_MAX_KEYS or model.ps.head_phys > K.STREAM_MAX_HEAD or c.kernel_size > 32:
+        raise ValueError(f"chunk_size {C} / history_size {hist} / head {model.ps.head_phys} / kernel {c.kernel_size} beyond the streaming "
+                         f"kernels' limits (chunk <= {K.STREAM_MAX_CHUNK}, history + chunk <= {K.STREAM_MAX_KEYS}, head <= "
+                         f"{K.STREAM_MAX_HEAD}, kernel <= 32)")
+
+
+def _twin(model, precision):
+    return model.inference_twin() if (precision or model.decode_precision) == "f32" else model
+
+
+@torch.no_grad()
+def encode_chunk(state, feats, nframes):
+    """One encoder step: feats [B, n <= 4C, F] (compute dtype, device), nframes [B] int32 feature frames that are real per stream: 0
+    (idle), 4C (a full chunk) or in between for a stream's last chunk -> (enc [B, C, dmodel], nvalid [B] int32 device); advances state."""
+    m = state.model
+    c, ps, dev = m.cfg, m.ps, m.device
+    B, C, hist = state.B, int(c.chunk_size), int(c.history_size)
+    H, dh, d = c.num_heads, ps.head_phys, c.dmodel
+    n0 = 4 * C
+    nf = nframes.to(dev).to(torch.int32) if isinstance(nframes, torch.Tensor) else m._h2d(list(nframes))
+    if feats.shape[0] != B or feats.shape[1] > n0:
+        raise ValueError(f"encode_chunk takes [B = {B}, <= {n0}, F] feature frames")
+    cat = torch.zeros(B, n0 + 2, c.num_feature_bins, dtype=m.dtype, device=dev)
+    cat[:, :2] = state.feat_carry
+    cat[:, 2:2 + feats.shape[1]] = feats
+    n1 = (nf + 1) // 2
+    nvalid = ((n1 + 1) // 2).to(torch.int32).contiguous()
+    two = torch.arange(2, device=dev)
+    # the carries move to the last two VALID rows (rows nf, nf + 1 of carry ++ new; nf == 0 picks the carry itself)
+    idx = (nf.long()[:, None] + two[None, :])
+    state.feat_carry.copy_(torch.gather(cat, 1, idx[:, :, None].expand(B, 2, cat.shape[2])))
+    # causal 3x3 stride-2 convs on carry(2) ++ new(n): output 0 belongs to the previous chunk, outputs 1.. are the originals
+    Cp = ps.filt_phys
+    c1 = K.conv1_fwd(cat, ps.p("enc/sub/conv0/w"), ps.p("enc/sub/conv0/b"))  # [B, 2C + 1, F1, Cp]
+    T1, F1 = c1.shape[1], c1.shape[2]
+    a1, _ = m._sub_norm_fwd(c1.view(-1, Cp), "enc/sub/bn0", False)
+    a1 = a1.view(B, T1, F1, Cp)
+    cat1 = torch.cat([state.conv_carry, a1[:, 1:]], 1).contiguous()  # [B, 2C + 2, F1, Cp]
+    idx1 = (n1.long()[:, None] + two[None, :])
+    state.conv_carry.copy_(torch.gather(cat1, 1, idx1[:, :, None, None].expand(B, 2, F1, Cp)))
+    col = K.im2col_3x3s2(cat1)
+    T2, F2 = (cat1.shape[1] + 1) // 2, (F1 + 1) // 2  # C + 1
+    c2 = K.matmul(col, ps.w2d("enc/sub/conv1/w"), bias=ps.p("enc/sub/conv1/b"))
+    a2, _ = m._sub_norm_fwd(c2, "enc/sub/bn1", False)
+    merged = a2.view(B, T2, F2 * Cp)[:, 1:].reshape(B * C, F2 * Cp)
+    x = K.matmul(merged, ps.w2d("enc/linear/w"), bias=ps.p("enc/linear/b"))  # [B*C, d]
+    scale = 1.0 / math.sqrt(c.head_size)
+    for i in range(c.num_blocks):
+        p = f"enc/block{i}/"
+        x = m._ffm_fwd(x, p + "ff1/", None, 0, False)
+        pfx = p + "mhsa/"
+        ln, _, _ = K.layernorm_fwd(x, ps.p(pfx + "ln/g"), ps.p(pfx + "ln/b"))
+        qkv = K.matmul(ln, ps.w2d(pfx + "qkv/w"), bias=ps.p(pfx + "qkv/b"))
+        ub, vb = m._uv(pfx)
+        att = K.stream_attn_fwd(qkv, ub, vb, state.pext[i], state.kcache[i], state.vcache[i], state.seen, nvalid, B, C, H, dh, hist, scale)
+        K.stream_kv_append(qkv, state.kcache[i], state.vcache[i], state.seen, nvalid, B, C, H, dh, hist)  # after every head has read the ring
+        x = K.matmul(att, ps.w2d(pfx + "o/w"), bias=ps.p(pfx + "o/b"), res=x, beta=c.mhsam_residual)
+        pfx = p + "conv/"
+        ln, _, _ = K.layernorm_fwd(x, ps.p(pfx + "ln/g"), ps.p(pfx + "ln/b"))
+        a = K.matmul(ln, ps.w2d(pfx + "pw1/w"), bias=ps.p(pfx + "pw1/b"))
+        cv = K.stream_glu_dwconv_fwd(a, state.dwstate[i], ps.p(pfx + "dw/w"), ps.p(pfx + "dw/b"), nvalid, B, C)
+        if c.convm_dw_norm == "layer":
+            yn, _, _ = K.layernorm_fwd(cv, ps.p(pfx + "bn/g"), ps.p(pfx + "bn/b"))
+            sw = K.add_act_fwd(yn, None, ACT_SWISH)
+        else:
+            sw, _ = m._bn_fwd(cv, pfx + "bn", False, ACT_SWISH)
+        x = K.matmul(sw, ps.w2d(pfx + "pw2/w"), bias=ps.p(pfx + "pw2/b"), res=x, beta=c.convm_residual)
+        x = m._ffm_fwd(x, p + "ff2/", None, 0, False)
+        x, _, _ = K.layernorm_fwd(x, ps.p(p + "ln/g"), ps.p(p + "ln/b"))
+    state.seen += nvalid
+    return x.view(B, C, d), nvalid
+
+
+class StreamingRecognizer:
+    """model.stream(): accept() PCM as it arrives, get the new tokens back; finish() flushes a stream's tail."""
+
+    def __init__(self, model, batch_size=1, precision=None, max_tokens_per_frame=3):
+        self.model = model
+        self.enc_model = _twin(model, precision)
+        self.state = StreamState(self.enc_model, batch_size)
+        self.B = int(batch_size)
+        self.max_tokens_per_frame = int(max_tokens_per_frame)
+        c = model.cfg
+        self.C = int(c.chunk_size)
+        self.step, self.flen = int(c.frame_step), int(c.frame_length)
+        self.chunk_frames = 4 * self.C
+        self.chunk_samples = self.step * (self.chunk_frames - 1) + self.flen  # samples a full chunk's feature frames cover
+        self.ctc = c.head == "ctc"
+        self.encoded_log = None  # a list here receives (enc [B, C, d], nvalid host list) of every chunk (callers that want the frames)
+        self.chunks_run = 0
+        self._init_rows(range(self.B), first=True)
+
+    # ------------------------------------------------------------------------------------------- state
+    def _init_rows(self, rows, first=False):
+        m, dev, B = self.model, self.model.device, self.B
+        if first:
+            self.buf = [np.zeros(0, np.float32) for _ in range(B)]
+            self.prev = np.zeros(B, np.float32)
+            self.has_prev = np.zeros(B, np.int32)
+            self.total = [0] * B  # samples received
+            self.emitted = [0] * B  # feature frames consumed
+            self.frames = [0] * B  # encoder frames emitted
+            self.finished = [False] * B
+            if self.ctc:
+                self.last_class = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            else:
+                P = m.cfg.rnn_units
+                self.prev_tok = torch.full((B,), m.blank, dtype=torch.int32, device=dev)
+                self.h = torch.zeros(B, P, dtype=torch.float32, device=dev)
+                self.c = torch.zeros(B, P, dtype=torch.float32, device=dev)
+                self._packed = None
+            return
+        rows = list(rows)
+        for b in rows:
+            self.buf[b] = np.zeros(0, np.float32)
+            self.prev[b], self.has_prev[b] = 0.0, 0
+            self.total[b] = self.emitted[b] = self.frames[b] = 0
+            self.finished[b] = False
+        r = torch.as_tensor(rows, dtype=torch.long, device=dev)
+        if self.ctc:
+            self.last_class[r] = -1
+        else:
+            self.prev_tok[r] = m.blank
+            self.h[r] = 0
+            self.c[r] = 0
+
+    def reset(self, rows=None):
+        """Zero the state of some or all streams: the slot takes the next utterance."""
+        rows = list(range(self.B)) if rows is None else list(rows)
+        self.state.reset(None if len(rows) == self.B else rows)
+        self._init_rows(rows)
+
+    def encoder_state(self):
+        return self.state.export()
+
+    def set_encoder_state(self, tensors):
+        self.state.load(tensors)
+
+    # ------------------------------------------------------------------------------------------- steps
+    def _ready(self, b, flush):
+        """feature frames stream b can give to the next chunk, and the samples they consume"""
+        n = len(self.buf[b])
+        if n >= self.chunk_samples:
+            return self.chunk_frames
+        if flush and not self.finished[b]:
+            left = -(-self.total[b] // self.step) - self.emitted[b]
+            return min(left, self.chunk_frames)
+        return 0
+
+    @torch.no_grad()
+    def _run(self, flush_rows=()):
+        m, em, dev, B = self.model, self.enc_model, self.model.device, self.B
+        c = m.cfg
+        new = [[] for _ in range(B)]
+        window, melw, band = em._frontend_consts()
+        while True:
+            take = [self._ready(b, b in flush_rows) for b in range(B)]
+            if max(take) == 0:
+                break
+            # one front-end launch per chunk on exactly the samples the chunk's frames cover: the same frames whatever the arrival
+            sig = np.zeros((B, self.chunk_samples), np.float32)
+            nlen = np.zeros(B, np.int32)
+            for b in range(B):
+                if take[b]:
+                    seg = self.buf[b][:self.chunk_samples]
+                    sig[b, :len(seg)] = seg
+                    nlen[b] = len(seg)
+            feats = K.logmel_stream(em._h2d(torch.from_numpy(sig), torch.float32), em._h2d(nlen), em._h2d(torch.from_numpy(self.prev.copy()), torch.float32),
+                                    em._h2d(self.has_prev.copy()), self.chunk_frames, window, melw, band, c.frame_step, c.nfft, c.preemphasis,
+                                    c.epsilon, em.dtype)
+            for b in range(B):
+                if take[b]:
+                    used = take[b] * self.step
+                    if used <= len(self.buf[b]):
+                        self.prev[b], self.has_prev[b] = self.buf[b][used - 1], 1
+                    self.buf[b] = self.buf[b][used:]
+                    self.emitted[b] += take[b]
+            enc, nvalid = encode_chunk(self.state, feats, take)
+            nv = [-(-(-(-t // 2)) // 2) for t in take]
+            if self.encoded_log is not None:
+                self.encoded_log.append((enc, nv))
+            self.chunks_run += 1
+            toks = self._search_ctc(enc, nvalid) if self.ctc else self._search(enc, nvalid, nv)
+            for b in range(B):
+                self.frames[b] += nv[b]
+                new[b].extend(toks[b])
+        W = max(max(len(t) for t in new), 1)
+        out = torch.full((B, W), m.blank, dtype=torch.int32)
+        for b in range(B):
+            if new[b]:
+                out[b, :len(new[b])] = torch.tensor(new[b], dtype=torch.int32)
+        return StreamOutput(out, torch.tensor([len(t) for t in new], dtype=torch.int32), torch.tensor(self.frames, dtype=torch.int32))
+
+    def _enc32(self, enc):
+        B, C, d = enc.shape
+        e = enc.reshape(B * C, d)
+        if e.dtype != torch.float32:
+            e = K.cast(e.contiguous(), torch.empty(B * C, d, dtype=torch.float32, device=e.device))
+        return e
+
+    def _search(self, enc, nvalid, nv_host):
+        """The greedy search of recognize_single continued over this chunk for every stream on its own (mode 2 of csrc/decode.hip)."""
+        m = self.model
+        ps, c, dev = m.ps, m.cfg, m.device
+        B, C, _ = enc.shape
+        P, J, V = c.rnn_units, c.joint_dim, c.vocab_size
+        f32 = torch.float32
+        encj = K.matmul(self._enc32(enc), ps.p2d("joint/enc/w"), bias=ps.p("joint/enc/b")).view(B, C, J)
+        mtpf = self.max_tokens_per_frame
+        max_tokens = C * mtpf
+        tokens = torch.full((B, max_tokens), m.blank, dtype=torch.int32, device=dev)
+        frame_idx = torch.zeros(B, dtype=torch.int32, device=dev)
+        tok_idx = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        per_frame = torch.zeros(B, dtype=torch.int32, device=dev)
+        active = torch.ones(1, dtype=torch.int32, device=dev)
+        h_new, c_new = torch.empty(B, P, dtype=f32, device=dev), torch.empty(B, P, dtype=f32, device=dev)
+        zbuf, logits = torch.empty(B, J, dtype=f32, device=dev), torch.empty(B, V, dtype=f32, device=dev)
+        Wk, Wrk, Wjp, Wv = ps.p2d("pred/lstm/k"), ps.p2d("pred/lstm/rk"), ps.p2d("joint/pred/w"), ps.p2d("joint/vocab/w")
+        lng, lnb = (ps.p("pred/ln/g"), ps.p("pred/ln/b")) if c.prediction_layer_norm else (None, None)
+        fused = B <= 64 and m.decode_fused
+        if fused and self._packed is None:
+            self._packed = K.decode_pack(ps.p("pred/emb"), Wk, Wrk, Wjp, Wv)  # (inference session: the weights are constants)
+        it, max_iters = 0, max(nv_host) * mtpf + 1  # every iteration of an active row advances its frame or appends a token
+        need = max(nv_host)
+        while it < max_iters:
+            n = min(max(need, 4), max_iters - it)
+            if fused:
+                fused = K.decode_steps(ps.p("pred/emb"), Wk, Wrk, ps.p("pred/lstm/b"), lng, lnb, Wjp, ps.p("joint/pred/b"), Wv, ps.p("joint/vocab/b"),
+                                       encj, nvalid, frame_idx, tok_idx, self.prev_tok, self.h, self.c, active, h_new, c_new, zbuf, logits, tokens,
+                                       per_frame, max_tokens, m.blank, 2, mtpf, n, packed=self._packed)
+            if not fused:
+                ecur = torch.empty(B, J, dtype=f32, device=dev)
+                xg, hr, pj = torch.empty(B, 4 * P, dtype=f32, device=dev), torch.empty(B, 4 * P, dtype=f32, device=dev), torch.empty(B, J, dtype=f32, device=dev)
+                for _ in range(n):
+                    K.decode_prepare(encj, nvalid, frame_idx, tok_idx, active, ecur, max_tokens, 2)
+                    emb = K.embedding_fwd(self.prev_tok, ps.p("pred/emb"), f32)
+                    K.matmul(emb, Wk, bias=ps.p("pred/lstm/b"), out=xg)
+                    K.gemm(self.h, Wrk, hr, B, 4 * P, P, P, 4 * P, 4 * P)
+                    K.lstm_step_fwd(xg, hr, self.h, self.c, None, 0, None, c_new, h_new, None, B, P)
+                    y = K.layernorm_fwd(h_new, lng, lnb, save_stats=False)[0] if c.prediction_layer_norm else h_new
+                    K.matmul(y, Wjp, bias=ps.p("joint/pred/b"), out=pj)
+                    z = K.joint_fwd(ecur.view(B, 1, J), pj.view(B, 1, J))
+                    K.matmul(z.view(B, J), Wv, bias=ps.p("joint/vocab/b"), out=logits)
+                    K.decode_update(logits, active, nvalid, frame_idx, self.prev_tok, tok_idx, tokens, per_frame, h_new, c_new, self.h, self.c,
+                                    max_tokens, m.blank, 2, mtpf)
+            it += n
+            left = (nvalid - frame_idx).clamp_(min=0).max()
+            need = int(left.item())  # (one sync per batch of iterations)
+            if need == 0:
+                break
+        th, tl = tokens.cpu(), tok_idx.cpu()  # the fetch of the new tokens: the one host round trip of a chunk besides the loop check
+        return [th[b, :int(tl[b]) + 1].tolist() for b in range(B)]
+
+    def _search_ctc(self, enc, nvalid):
+        m = self.model
+        ps = m.ps
+        B, C, _ = enc.shape
+        logits = K.matmul(self._enc32(enc), ps.p2d("dec/logits/w"), bias=ps.p("dec/logits/b")).view(B, C, m.cfg.vocab_size)
+        tokens, tlen = K.ctc_greedy_decode_carry(logits, nvalid, self.last_class, blank=m.blank)
+        th, tl = tokens.cpu(), tlen.cpu()
+        return [th[b, :int(tl[b])].tolist() for b in range(B)]
+
+    # ------------------------------------------------------------------------------------------- public
+    def accept(self, pcm, lengths=None):
+        """pcm [B, n] f32 (or [n] with batch_size 1), lengths [B] real samples per row (default n): buffers them, runs every chunk that
+        is complete for at least one stream, continues the search -> StreamOutput."""
+        x = pcm.detach().cpu().numpy() if isinstance(pcm, torch.Tensor) else np.asarray(pcm)
+        x = np.asarray(x, np.float32)
+        if x.ndim == 1:
+            x = x[None]
+        if x.shape[0] != self.B:
+            raise ValueError(f"accept takes [{self.B}, n] samples")
+        lens = [x.shape[1]] * self.B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        for b in range(self.B):
+            if lens[b] > 0 and self.finished[b]:
+                raise RuntimeError(f"stream {b} is finished: reset it before it takes another utterance")
+        for b in range(self.B):
+            if lens[b] > 0:
+                self.buf[b] = np.concatenate([self.buf[b], x[b, :lens[b]]])
+                self.total[b] += lens[b]
+        return self._run()
+
+    def finish(self, rows=None):
+        """Pad the tail of the given streams (default: all) as pad_end=True does, run their last (partial) chunk -> StreamOutput; those
+        streams then refuse accept until reset."""
+        rows = [b for b in (range(self.B) if rows is None else rows) if not self.finished[b]]
+        out = self._run(flush_rows=set(rows))
+        for b in rows:
+            self.finished[b] = True
+            self.buf[b] = np.zeros(0, np.float32)
+        return out
