@@ -23,8 +23,14 @@ def swish(x):
     return x * torch.sigmoid(x)
 
 
-def conv_module(x, W, m, K, stride, act, stats=None):
-    """ConvModule.call (contextnet.py:76-90): x [B, T, Cin] -> [B, ceil(T/stride), Cout]."""
+def _identity(x):
+    return x
+
+
+def conv_module(x, W, m, K, stride, act, stats=None, store=_identity):
+    """ConvModule.call (contextnet.py:76-90): x [B, T, Cin] -> [B, ceil(T/stride), Cout].
+    store: applied to the module's output (default identity); a test passes a storage-format rounding to measure what one rounding
+    per stored tensor costs (tests/contextnet_parity.py)."""
     B, T, ci = x.shape
     dw = W[m + "/dw"]                                              # [K, Cin]
     xp = F.pad(x.transpose(1, 2), (K - 1, 0))                      # causal: left pad K-1
@@ -35,33 +41,37 @@ def conv_module(x, W, m, K, stride, act, stats=None):
     if stats is not None:
         stats[m + "/bn"] = (mean.detach(), var.detach())
     y = (y - mean) / torch.sqrt(var + 1e-3) * W[m + "/bn/g"] + W[m + "/bn/b"]
-    return swish(y) if act == "swish" else y
+    return store(swish(y) if act == "swish" else y)
 
 
-def se_module(x, lens, W, p):
+def se_module(x, lens, W, p, store=_identity):
     """SEModule.call after its conv module (contextnet.py:159-170): masked average pool -> fc1 -> swish -> fc2 -> sigmoid."""
     B, T, C = x.shape
     mask = (torch.arange(T)[None, :] < torch.as_tensor(lens)[:, None]).to(x.dtype)[..., None]
     pool = (x * mask).sum(1) / mask.sum(1).clamp(min=1.0)
     h = swish(pool @ W[p + "fc1/w"] + W[p + "fc1/b"])
     s = torch.sigmoid(h @ W[p + "fc2/w"] + W[p + "fc2/b"])
-    return x * s[:, None, :]
+    return store(x * s[:, None, :])
 
 
-def encoder_forward(feats, flen, W, blocks, stats=None):
-    """ContextNetEncoder.call (contextnet.py:313-318).  feats [B, T, F]; blocks = params.contextnet_modules(cfg)."""
+def encoder_forward(feats, flen, W, blocks, stats=None, store=_identity, keep=None):
+    """ContextNetEncoder.call (contextnet.py:313-318).  feats [B, T, F]; blocks = params.contextnet_modules(cfg).
+    store: applied to the output of every conv module, of the squeeze-excite scale and of every block (default identity);
+    keep: a list that receives (input, lengths) of every block."""
     x = feats
     lens = [int(n) for n in flen]
     for blk in blocks:
         x0 = x
+        if keep is not None:
+            keep.append((x, list(lens)))
         for (m, ci, co, K, s, act) in blk["convs"]:
-            x = conv_module(x, W, m, K, s, act, stats)
+            x = conv_module(x, W, m, K, s, act, stats, store)
         lens = [-(-n // blk["stride"]) for n in lens]              # conv_output_length(..., "causal") = ceil(L / stride)
-        x = se_module(x, lens, W, blk["prefix"] + "se/")
+        x = se_module(x, lens, W, blk["prefix"] + "se/", store)
         if blk["res"] is not None:
             m, ci, co, K, s, act = blk["res"]
-            x = x + conv_module(x0, W, m, K, s, act, stats)
-        x = swish(x)
+            x = x + conv_module(x0, W, m, K, s, act, stats, store)
+        x = store(swish(x))
     return x, lens
 
 

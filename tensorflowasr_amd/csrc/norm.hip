@@ -104,14 +104,16 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, 
   const long nw = (long)gridDim.x * (blockDim.x >> 6);
   float a0[MAXC_PER_LANE], a1[MAXC_PER_LANE], mean[MAXC_PER_LANE], rstd[MAXC_PER_LANE], sc[MAXC_PER_LANE],
       sh[MAXC_PER_LANE];
+  // blockIdx.y = slab of 64 * MAXC_PER_LANE channels (one slab up to C = 1024; ContextNet-L's last block is 1280 wide)
+  const int c_lo = blockIdx.y * (64 * MAXC_PER_LANE), c_hi = min(C, c_lo + 64 * MAXC_PER_LANE);
   int ncol = 0;
-  for (int c = lane; c < C; c += 64, ++ncol) {
+  for (int c = c_lo + lane; c < c_hi; c += 64, ++ncol) {
     a0[ncol] = 0.f; a1[ncol] = 0.f;
     if (MODE == 1) { mean[ncol] = fin[c]; rstd[ncol] = fin[C + c]; sc[ncol] = fin[2 * C + c]; sh[ncol] = fin[3 * C + c]; }
   }
   for (long r = w0; r < rows; r += nw) {
     int n = 0;
-    for (int c = lane; c < C; c += 64, ++n) {
+    for (int c = c_lo + lane; c < c_hi; c += 64, ++n) {
       const float xv = Num<T>::ld(x + r * C + c);
       if (MODE == 0) { a0[n] += xv; a1[n] += xv * xv; }
       else {
@@ -125,11 +127,12 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, 
   __shared__ float red[2][4][64 * MAXC_PER_LANE];
   const int w = threadIdx.x >> 6;
   int n = 0;
-  for (int c = lane; c < C; c += 64, ++n) { red[0][w][c] = a0[n]; red[1][w][c] = a1[n]; }
+  for (int c = c_lo + lane; c < c_hi; c += 64, ++n) { red[0][w][c - c_lo] = a0[n]; red[1][w][c - c_lo] = a1[n]; }
   __syncthreads();
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    atomicAdd(stats + c, red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c]);
-    atomicAdd(stats + C + c, red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c]);
+  for (int c = c_lo + threadIdx.x; c < c_hi; c += blockDim.x) {
+    const int cl = c - c_lo;
+    atomicAdd(stats + c, red[0][0][cl] + red[0][1][cl] + red[0][2][cl] + red[0][3][cl]);
+    atomicAdd(stats + C + c, red[1][0][cl] + red[1][1][cl] + red[1][2][cl] + red[1][3][cl]);
   }
 }
 
@@ -773,7 +776,7 @@ extern "C" int tfasr_layernorm_bwd(const void* dy, const void* x, const float* g
 }
 
 extern "C" int tfasr_bn_stats(const void* x, float* stats, long rows, int C, int dtype, void* stream_) {
-  if (!x || !stats || rows <= 0 || C <= 0 || (C > 64 * MAXC_PER_LANE && (dtype != TFASR_BF16 || (C % 8)))) return TFASR_STATUS_INVALID_VALUE;
+  if (!x || !stats || rows <= 0 || C <= 0) return TFASR_STATUS_INVALID_VALUE;
   hipStream_t s = (hipStream_t)stream_;
   if (dtype == TFASR_BF16 && (C % 8) == 0) {
     if (C <= 256) TFASR_KLAUNCH((bn_stats_vec_kernel<bf16_t, 0, 32>), dim3(fat_grid(rows, 2)), dim3(red_threads()), 0, s, (const bf16_t*)x, (const bf16_t*)nullptr, (const float*)nullptr, stats, rows, C, 0);
@@ -781,12 +784,12 @@ extern "C" int tfasr_bn_stats(const void* x, float* stats, long rows, int C, int
     TFASR_CHECK_LAUNCH();
     return TFASR_STATUS_SUCCESS;
   }
-  const int grid = (int)std::min<long>((rows + 3) / 4, 1024L);
+  const dim3 grid((unsigned)std::min<long>((rows + 3) / 4, 1024L), (C + 64 * MAXC_PER_LANE - 1) / (64 * MAXC_PER_LANE));
   if (dtype == TFASR_F32)
-    TFASR_KLAUNCH((bn_stats_kernel<float, 0>), dim3(grid), dim3(256), 0, s, (const float*)x, (const float*)nullptr,
+    TFASR_KLAUNCH((bn_stats_kernel<float, 0>), grid, dim3(256), 0, s, (const float*)x, (const float*)nullptr,
                        (const float*)nullptr, stats, rows, C, 0);
   else
-    TFASR_KLAUNCH((bn_stats_kernel<bf16_t, 0>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x,
+    TFASR_KLAUNCH((bn_stats_kernel<bf16_t, 0>), grid, dim3(256), 0, s, (const bf16_t*)x,
                        (const bf16_t*)nullptr, (const float*)nullptr, stats, rows, C, 0);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
@@ -856,7 +859,7 @@ extern "C" int tfasr_bn_finalize_apply_fwd(const void* x, const float* stats, fl
 
 extern "C" int tfasr_bn_bwd_stats(const void* x, const void* dy, const float* fin, float* bstats, long rows, int C,
                                   int act, int dtype, void* stream_) {
-  if (!x || !dy || !fin || !bstats || rows <= 0 || C <= 0 || (C > 64 * MAXC_PER_LANE && (dtype != TFASR_BF16 || (C % 8)))) return TFASR_STATUS_INVALID_VALUE;
+  if (!x || !dy || !fin || !bstats || rows <= 0 || C <= 0) return TFASR_STATUS_INVALID_VALUE;
   hipStream_t s = (hipStream_t)stream_;
   if (dtype == TFASR_BF16 && (C % 8) == 0) {
     if (C <= 256) TFASR_KLAUNCH((bn_stats_vec_kernel<bf16_t, 1, 32>), dim3(fat_grid(rows, 2)), dim3(red_threads()), 0, s, (const bf16_t*)x, (const bf16_t*)dy, fin, bstats, rows, C, act);
@@ -864,12 +867,12 @@ extern "C" int tfasr_bn_bwd_stats(const void* x, const void* dy, const float* fi
     TFASR_CHECK_LAUNCH();
     return TFASR_STATUS_SUCCESS;
   }
-  const int grid = (int)std::min<long>((rows + 3) / 4, 1024L);
+  const dim3 grid((unsigned)std::min<long>((rows + 3) / 4, 1024L), (C + 64 * MAXC_PER_LANE - 1) / (64 * MAXC_PER_LANE));
   if (dtype == TFASR_F32)
-    TFASR_KLAUNCH((bn_stats_kernel<float, 1>), dim3(grid), dim3(256), 0, s, (const float*)x, (const float*)dy, fin,
+    TFASR_KLAUNCH((bn_stats_kernel<float, 1>), grid, dim3(256), 0, s, (const float*)x, (const float*)dy, fin,
                        bstats, rows, C, act);
   else
-    TFASR_KLAUNCH((bn_stats_kernel<bf16_t, 1>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy,
+    TFASR_KLAUNCH((bn_stats_kernel<bf16_t, 1>), grid, dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy,
                        fin, bstats, rows, C, act);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;

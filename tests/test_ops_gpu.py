@@ -74,8 +74,6 @@ def test_layernorm_bwd_with_dropped_copy(dev, dtype, C):
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("C", [144, 1280])  # 1280 = ContextNet-L width: channel slabs in the statistics kernels
 def test_batchnorm_swish(dev, dtype, C):
-    if C > 1024 and dtype == torch.float32:
-        pytest.skip("the f32 (parity-mode) statistics kernels cover C <= 1024")
     g = torch.Generator().manual_seed(0)
     rows = 500
     x = rt(torch.randn(rows, C, generator=g) * 1.5 + 0.3, dtype)
