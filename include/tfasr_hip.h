@@ -881,6 +881,20 @@ int tfasr_logmel_stream(const float* signal, const int32_t* nlen, const float* p
 int tfasr_ctc_greedy_decode_carry(const void* logits, const int32_t* logit_len, int32_t* last_class, int32_t* workspace_argmax,
                                   int32_t* tokens, int32_t* tokens_len, int B, int T, int V, int blank, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scoring (csrc/edit_distance.hip; declarations added under ABI 44, nothing existing changes): edit distance with unit costs of P pairs
+ * of int32 sequences, hyp [P, N] against ref [P, M], and the counts behind WER / MER / WIL:
+ *   counts [P, 5] = distance, hits, substitutions, deletions, insertions   (distance = S + D + I, hits + S + D = |ref|, hits + S + I = |hyp|)
+ * Where several alignments reach the distance, the counts are those of the one with the most hits (the fewest substitutions).
+ * A row's sequence: with hyp_len (ref_len) given, its first clamp(len, 0, width) entries; with the pointer NULL, what is left of the row
+ * after dropping entries < 0 and entries == skip_id, order kept (blank-padded search output).  N = 0 and M = 0 are legal (the row pointer
+ * must still be non-null; it is never read).  Widths above TFASR_EDIT_MAX_LEN are UNSUPPORTED by both functions.  Device pointers,
+ * caller-owned workspace of at least the queried size, no allocation, no synchronisation. */
+#define TFASR_EDIT_MAX_LEN 4096
+int tfasr_edit_distance_workspace_size(int P, int N, int M, size_t* bytes);
+int tfasr_edit_distance(const int32_t* hyp, const int32_t* hyp_len, const int32_t* ref, const int32_t* ref_len, int P, int N, int M,
+                        int skip_id, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,120 @@ class BaseModel:
         _beam_tokens = self.recognize_beam(inputs=inputs).tokens
         return {"tokens": _tokens, "beam_tokens": _beam_tokens, "labels": y_true.labels}
 
+    # ----------------------------------------------------------------------------------------------- evaluation
+    def _evaluation_batches(self, data, batch_size):
+        """(TrainData, names or None) per batch.  A dataset is read through a copy of the object (its own settings and entry order stay
+        as they are): every entry once, in file order, the last short batch included, padded to the batch's own maxima."""
+        from .datasets import ASRSliceDataset, to_train_data
+
+        if not isinstance(data, ASRSliceDataset):
+            for batch in data:
+                yield batch, None
+            return
+        import copy
+
+        ds = copy.copy(data)
+        ds.shuffle, ds.entries = False, []
+        ds.read_entries()
+        bs = int(batch_size or self._per_replica_batch_size or 1)
+        for s in range(0, len(ds.entries), bs):
+            chunk = ds.entries[s : s + bs]
+            items = [ds.parse(e[0], e[2]) for e in chunk]
+            yield to_train_data(ds.padded_batch(items), self.device), [e[0] for e in chunk]
+
+    @torch.no_grad()
+    def evaluate(self, data, output_file_path=None, names=None, beam_width=0, top_paths=0, device_search=True, cer_unit="char",
+                 device_metrics=True, batch_size=None):
+        """What scripts/test.py does with predict + PredictLogger + evaluate_hypotheses, in one pass: recognise every batch of `data`
+        (an iterable of TrainData, or an ASRSliceDataset read in file order in batches of `batch_size`), score it, and optionally write
+        the results file (PATH, GROUND_TRUTH, GREEDY, BEAM_SEARCH; `names` defaults to the dataset's paths, else to running numbers).
+
+        Per batch: `recognize`; `recognize_beam(beam_width, device_search)` when beam_width > 0, otherwise the beam column repeats the
+        greedy one (what the reference's transducer recognize_beam gives); token-level counts on the device straight from the searches'
+        output (blank and -1 padding dropped there) against labels[:labels_length]; then `tokenizer.detokenize` on the host and the
+        word- and `cer_unit`-level ("char" | "byte") counts on the device again.  device_metrics=False scores on the host (metrics.
+        edit_distance_host) with identical results.  top_paths > 0 adds an "oracle" row from `recognize_nbest(max(beam_width, top_paths),
+        top_paths)`: per utterance the path with the smallest word distance (the lowest index on a tie; paths with score -inf are left
+        out), with that same path's character and token counts.
+
+        -> {"greedy": row, "beam": row[, "oracle": row]}, row = {wer, cer, mer, wil, wip, ter, words, chars, tokens, utterances}: rates as
+        metrics.ErrorStats defines them (not multiplied by 100; ter = token error rate), the three raw count sums, and the number of
+        utterances.  An utterance with an empty reference counts in the sums and cannot divide by zero on its own."""
+        import numpy as np
+
+        from . import metrics
+
+        tok = self.tokenizer
+        if tok is None:
+            raise ValueError("evaluate needs model.tokenizer (texts are scored, not only tokens)")
+        dev, blank = self.device, int(self.blank)
+        rows = ["greedy", "beam"] + (["oracle"] if top_paths > 0 else [])
+        stats = {r: {u: metrics.ErrorStats() for u in ("words", "chars", "tokens")} for r in rows}
+        names = None if names is None else list(names)
+
+        def count(hyp, ref, hyp_len=None, ref_len=None, skip_id=None):
+            if not device_metrics:
+                hyp, ref, hyp_len, ref_len = (None if t is None else t.cpu() for t in (hyp, ref, hyp_len, ref_len))
+            return metrics.edit_distance(hyp, ref, hyp_len, ref_len, skip_id)
+
+        def count_texts(hyps, refs, unit):
+            return metrics.score_texts(hyps, refs, unit, dev if device_metrics else None)
+
+        writer = metrics.ResultsWriter(output_file_path) if output_file_path else None
+        done = 0
+        try:
+            for (x, y), batch_names in self._evaluation_batches(data, batch_size):
+                B = int(x.inputs.shape[0])
+                inputs = PredictInput(inputs=x.inputs, inputs_length=x.inputs_length, previous_tokens=self.get_initial_tokens(batch_size=B),
+                                      previous_encoder_states=self.get_initial_encoder_states(batch_size=B),
+                                      previous_decoder_states=self.get_initial_decoder_states(batch_size=B))
+                labels = y.labels.to(dev).to(torch.int32).contiguous()
+                llen = y.labels_length.to(dev).to(torch.int32).clamp(0, labels.shape[1])
+                hyp = {"greedy": self.recognize(inputs).tokens.to(torch.int32).contiguous()}
+                hyp["beam"] = (self.recognize_beam(inputs, beam_width=beam_width, device_search=device_search).tokens.to(torch.int32).contiguous()
+                               if beam_width > 0 else hyp["greedy"])
+                for r in ("greedy", "beam"):
+                    stats[r]["tokens"].update(count(hyp[r], labels, None, llen, blank))
+                past = torch.arange(labels.shape[1], device=dev)[None] >= llen[:, None]
+                refs = tok.detokenize(labels.masked_fill(past, blank).cpu().numpy())
+                text = {r: tok.detokenize(hyp[r].cpu().numpy()) for r in ("greedy", "beam")}
+                for r in ("greedy", "beam"):
+                    stats[r]["words"].update(count_texts(text[r], refs, "word"))
+                    stats[r]["chars"].update(count_texts(text[r], refs, cer_unit))
+                if top_paths > 0:
+                    nb, nlen, score = self.recognize_nbest(inputs, beam_width=max(beam_width, top_paths), top_paths=top_paths)
+                    NP = nb.shape[1]
+                    nb = nb.to(torch.int32)
+                    nlen = nlen.to(dev).to(torch.int32)
+                    gone = torch.arange(nb.shape[2], device=dev)[None, None] >= nlen[:, :, None]
+                    nb = nb.masked_fill(gone, blank).reshape(B * NP, -1)
+                    paths = tok.detokenize(nb.cpu().numpy())
+                    words = count_texts(paths, [t for t in refs for _ in range(NP)], "word")
+                    dist = np.asarray(words.distance.cpu()).astype(np.int64).reshape(B, NP)
+                    dead = ~np.isfinite(np.asarray(score.detach().float().cpu()).reshape(B, NP))
+                    dead[:, 0] = False
+                    best = np.argmin(np.where(dead, np.iinfo(np.int64).max, dist), axis=1)  # the first minimum: the lowest index
+                    flat = torch.from_numpy(np.arange(B) * NP + best)
+                    stats["oracle"]["words"].update(metrics.EditCounts(*(c.cpu()[flat] for c in words)))
+                    stats["oracle"]["chars"].update(count_texts([paths[k] for k in flat.tolist()], refs, cer_unit))
+                    stats["oracle"]["tokens"].update(count(nb[flat.to(dev)].contiguous(), labels, None, llen, blank))
+                if writer is not None:
+                    if names is not None:
+                        ids = names[done : done + B]
+                    else:
+                        ids = batch_names if batch_names is not None else [str(done + k) for k in range(B)]
+                    writer.write(ids, refs, text["greedy"], text["beam"])
+                done += B
+        finally:
+            if writer is not None:
+                writer.close()
+        out = {}
+        for r in rows:
+            s = stats[r]
+            out[r] = dict(metrics.summary(s["words"], s["chars"]), ter=s["tokens"].error_rate, words=s["words"].counts(),
+                          chars=s["chars"].counts(), tokens=s["tokens"].counts(), utterances=done)
+        return out
+
     # ----------------------------------------------------------------------------------------------- states
     def get_initial_encoder_states(self, batch_size=1):
         return []

@@ -237,6 +237,40 @@ def ctc_align(logits, labels, label_len, logit_len, blank=0, normalized=False):
     return start, end, label_lp, score
 
 
+# ------------------------------------------------------------------------------------------ scoring
+def _edit_check(st, what):
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported(f"{what}: a sequence width above TFASR_EDIT_MAX_LEN (see include/tfasr_hip.h)")
+    check(st, what)
+
+
+def edit_distance_workspace_size(P, N, M):
+    n = ctypes.c_size_t(0)
+    _edit_check(_lib.load().tfasr_edit_distance_workspace_size(P, N, M, ctypes.byref(n)), "edit_distance_workspace_size")
+    return n.value
+
+
+def edit_distance(hyp, ref, hyp_len=None, ref_len=None, skip_id=-1):
+    """Edit distance of hyp [P,N] against ref [P,M] (i32, device) -> counts [P,5] i32: distance, hits, substitutions, deletions,
+    insertions (of the minimum-distance alignment with the most hits).  A side without lengths is compacted on the device: entries
+    < 0 and entries == skip_id are dropped.  Widths above TFASR_EDIT_MAX_LEN raise TfasrUnsupported."""
+    for t in (hyp, ref, hyp_len, ref_len):
+        if t is not None and not t.is_cuda:
+            raise _lib.TfasrError("tensorflowasr_amd ops need HIP device tensors (no CPU fallback on the product path)")
+    assert hyp.dim() == 2 and ref.dim() == 2 and hyp.shape[0] == ref.shape[0] and hyp.dtype == torch.int32 and ref.dtype == torch.int32
+    P, N, M = hyp.shape[0], hyp.shape[1], ref.shape[1]
+    for ln in (hyp_len, ref_len):
+        assert ln is None or (ln.dtype == torch.int32 and ln.shape == (P,))
+    counts = torch.empty(P, 5, dtype=torch.int32, device=hyp.device)
+    if P == 0:
+        return counts
+    ws = workspace(edit_distance_workspace_size(P, N, M), hyp.device, "edit")
+    # an empty tensor has no storage: a width of 0 is never read, the pointer only has to be non-null
+    _edit_check(_lib.load().tfasr_edit_distance(_p(hyp) if N else _p(counts), _p(hyp_len), _p(ref) if M else _p(counts), _p(ref_len), P, N, M,
+                                                 int(skip_id), _p(counts), _p(ws), ws.numel(), _stream()), "edit_distance")
+    return counts
+
+
 # ---------------------------------------------------------------------------------------------- GEMM
 def gemm(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, bias=None, res=None, dact_z=None,
          prez=None, alpha=1.0, beta=1.0, act=ACT_NONE, dact=ACT_NONE, nb1=1, nb2=1, sA=(0, 0), sB=(0, 0), sD=(0, 0),
