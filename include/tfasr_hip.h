@@ -665,6 +665,50 @@ int tfasr_rnnt_beam_select(const float* logits, const int32_t* nframes, int t, i
 int tfasr_rnnt_beam_nbest(int B, int T, int U, int J, int V, int beam_width, int top_paths, int blank, int32_t* tokens,
                           int32_t* tokens_len, float* score, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The beam searches in pieces (declarations added under ABI 44, nothing existing changes): streaming sessions that carry whole beams
+ * from chunk to chunk.  The frame loops are those of tfasr_rnnt_beam_search / tfasr_ctc_beam_search, which are reset + one advance
+ * over all T frames + n-best on the same code, so stream b holds after any sequence of advances exactly (bit for bit) the beam the
+ * one-shot search holds after the same frames, whatever the other streams do.  All pointers are device pointers, nothing synchronises
+ * with the host, every argument is checked on the host before any launch.
+ *
+ * Transducer.  The carried state of B streams is the search workspace of tfasr_rnnt_beam_workspace_size with T = Tcap, the most frames
+ * one stream consumes between resets (its trie holds 1 + beam_width * Tcap nodes).
+ *   _reset    streams with mask[b] != 0 (mask NULL: all) hold one empty hypothesis: total 0, the trie root, an empty table, zeroed
+ *             counters, blank as prediction input, zero state.  The other streams are not touched.
+ *   _advance  C frames of encj [B,C,J] f32; frame t is searched for the streams with t < nvalid[b] (nvalid 0: the stream's beam keeps
+ *             every bit).  Weights and `packed` as tfasr_rnnt_beam_search.  frames_max_after = the largest frame count any stream
+ *             reaches with this call: INVALID_VALUE when it exceeds Tcap (the device also refuses frames past Tcap).
+ *   _commit   per stream the labels between depth committed[b] (in / out) and the deepest trie node that is an ancestor-or-self of every
+ *             live row -> tokens [B,width] (blank padded), ntokens [B]; streams with final_mask[b] != 0 (NULL: none) commit their whole
+ *             best row.  At most `width` labels per call (the rest comes with the next).  The committed prefix never shrinks.
+ *   _nbest_states  the current beams as tfasr_rnnt_beam_search returns them, token rows `width` <= Tcap wide (>= the frames consumed
+ *             holds every label).  tfasr_rnnt_beam_nbest with T = Tcap serves as well when the states are not needed. */
+int tfasr_rnnt_beam_reset(const int32_t* mask, int B, int Tcap, int U, int J, int V, int beam_width, int blank, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int tfasr_rnnt_beam_advance(const float* emb, const float* lstm_k, const float* lstm_rk, const float* lstm_b, const float* ln_g,
+                            const float* ln_b, const float* joint_pred_w, const float* joint_pred_b, const float* vocab_w,
+                            const float* vocab_b, const float* packed, const float* encj, const int32_t* nvalid, int B, int C,
+                            int Tcap, int E, int U, int J, int V, int beam_width, int blank, float ln_eps, int frames_max_after,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_rnnt_beam_commit(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens, int B, int Tcap, int U,
+                           int J, int V, int beam_width, int width, int blank, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_rnnt_beam_nbest_states(int B, int Tcap, int U, int J, int V, int beam_width, int top_paths, int blank, int width,
+                                 int32_t* tokens, int32_t* tokens_len, float* score, int32_t* next_tok, float* next_h, float* next_c,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* CTC, the same contracts.  The workspace holds the per-frame scratch of a chunk of at most C frames, a trie for Tcap frames per
+ * stream, and the beam rows the search kernel keeps in LDS (node, parent, label, depth, p_blank, p_nonblank), the live count and
+ * the node count: loaded when an advance starts, stored when it ends.  _advance takes logits [B,Cn,V] (f32 / bf16), Cn <= C;
+ * _commit pads with 0 and _nbest writes 0 padded rows `width` <= Tcap wide, as tfasr_ctc_beam_search. */
+int tfasr_ctc_beam_stream_workspace_size(int B, int C, int Tcap, int V, int beam_width, size_t* bytes);
+int tfasr_ctc_beam_reset(const int32_t* mask, int B, int C, int Tcap, int V, int beam_width, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int tfasr_ctc_beam_advance(const void* logits, const int32_t* nvalid, int B, int C, int Cn, int Tcap, int V, int beam_width,
+                           int blank_index, int dtype, int frames_max_after, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_ctc_beam_commit(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens, int B, int C, int Tcap,
+                          int V, int beam_width, int width, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_ctc_beam_nbest(int B, int C, int Tcap, int V, int beam_width, int top_paths, int width, int32_t* tokens, int32_t* tokens_len,
+                         float* log_prob, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Forced alignment on the device (ABI 44 addition; csrc/align.hip): the best single path through the lattice the loss sums over,
  * and when it emits each label.  All pointers are device pointers, label_len / logit_len [B] int32 are clamped to the padded
  * sizes, nothing synchronises with the host, and every argument is checked on the host before any launch.

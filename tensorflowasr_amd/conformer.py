@@ -1668,12 +1668,14 @@ class ConformerTransducer(BaseModel):
 
         return streaming.encode_chunk(state, feats, nframes)
 
-    def stream(self, batch_size=1, precision=None, max_tokens_per_frame=3):
+    def stream(self, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
         """Incremental recognition session (streaming.StreamingRecognizer): accept(pcm) ... finish().  Refused, with the reason, for a
-        full-context config, unlimited history, and sizes beyond the streaming attention kernel."""
+        full-context config, unlimited history, and sizes beyond the streaming attention kernel.  beam_width >= 1: every stream carries
+        a whole beam (the device beam search, one symbol per frame at most) for up to max_frames encoder frames; the outputs are the
+        committed tokens and rec.hypotheses() the n-best (see StreamingRecognizer for the memory per stream)."""
         from . import streaming
 
-        return streaming.StreamingRecognizer(self, batch_size, precision, max_tokens_per_frame)
+        return streaming.StreamingRecognizer(self, batch_size, precision, max_tokens_per_frame, beam_width, max_frames)
 
     def recognize_beam(self, inputs: PredictInput, beam_width=10, device_search=False, precision=None, **kw):
         """The reference's recognize_beam falls back to greedy (base_transducer.py:841-842), and so does this one by default.

@@ -56,6 +56,37 @@ __device__ inline void insert(unsigned long long* hk, int* hv, unsigned hcap, in
     if (atomicCAS(&hk[h], EMPTY, k) == EMPTY) { hv[h] = node; return; }
 }
 
+// ---- the stable prefix of a carried beam (the chunked searches' commit), run by ONE wave: lane i holds the node of live row i ----
+// The deepest node that is an ancestor-or-self of every live lane's node.  Lane 0 must be live.  Every lane walks up to the smallest
+// depth, then all walk up together until a ballot says they agree: O(depth below the answer) parent reads per lane.
+__device__ inline int common_ancestor(const Trie& tr, int node, bool live) {
+  int dmin = live ? tr.depth[node] : 0x7fffffff;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) dmin = min(dmin, __shfl_xor(dmin, o, 64));
+  if (live)
+    for (int d = tr.depth[node]; d > dmin; --d) node = tr.parent[node];
+  for (;;) {
+    const int first = __shfl(node, 0, 64);
+    if (__ballot(live && node != first) == 0ull) return first;
+    if (live) node = tr.parent[node];  // (all at one depth > 0 here: the root is common to all)
+  }
+}
+// Labels of `target`'s sequence from depth *committed on -> out[0 .. n), n = min(depth(target) - *committed, width) >= 0, the rest of
+// out[0 .. width) = pad; *count = n, *committed += n (labels that did not fit come with the next commit).  `target` is wave uniform.
+__device__ inline void commit_labels(const Trie& tr, int target, int lane, int32_t* committed, int32_t* out, int32_t* count, int width,
+                                     int pad) {
+  const int have = max(*committed, 0);
+  const int n = max(min(tr.depth[target] - have, width), 0), upto = have + n;
+  for (int pos = n + lane; pos < width; pos += 64) out[pos] = pad;
+  if (lane == 0) {
+    int t = target;
+    for (int d = tr.depth[t]; d > upto; --d) t = tr.parent[t];
+    for (int d = upto; d > have; --d, t = tr.parent[t]) out[d - have - 1] = tr.label[t];
+    *count = n;
+    *committed = upto;
+  }
+}
+
 // table slots for an utterance of at most `nmax` nodes (load factor <= 1/2)
 inline unsigned table_cap(long nmax) {
   unsigned long long cap = 64;

@@ -186,6 +186,10 @@ extern "C" int tfasr_ctc_beam_search_host(const float* logits, const int32_t* lo
 //    first W by (total desc, label sequence asc) are the next beam.  Label sequences live in a per-utterance trie in the workspace
 //    with an open-addressing (parent, label) -> node table: one node per label sequence for the whole utterance, so a prefix that
 //    leaves the beam and comes back keeps its mass.  The comparator walks the trie only on an exact tie of totals.
+//
+// The search in pieces (tfasr_ctc_beam_reset / _advance / _commit / _nbest, streaming sessions) is the same two kernels: the search
+// kernel loads its LDS beam from the workspace's carry area instead of starting from the empty prefix, runs the chunk's frames and
+// stores the beam back; the n-best of a carried beam is the same kernel over zero frames.
 // ================================================================================================================================
 namespace {
 
@@ -254,12 +258,20 @@ using beam_trie::Seq;
 using beam_trie::Trie;
 using beam_trie::seq_less;
 
+// the beam of every stream between two advances: what the search kernel holds in LDS, [B][W] each, and [B][CC_N] counters
+struct CtcCarry { int *node, *par, *lab, *dep; float *pb, *pnb; int* cnt; };
+enum { CC_LIVE = 0, CC_NODES = 1, CC_FRAMES = 2, CC_N = 4 };
+enum { BEAM_LOAD = 1, BEAM_STORE = 2, BEAM_OUTPUT = 4 };  // one-shot search: BEAM_OUTPUT alone
+
 template <typename T>
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
     const T* __restrict__ logits, const int32_t* __restrict__ logit_len, const float* __restrict__ lse_ws,
     const float* __restrict__ lpb_ws, const int32_t* __restrict__ top_c, const float* __restrict__ top_lp, int* trie_parent,
     int* trie_label, int* trie_depth, unsigned long long* hkeys, int* hvals, int Tm, int V, int W, int K, int P, long nmax,
-    unsigned hcap, int32_t* __restrict__ tokens, int32_t* __restrict__ tokens_len, float* __restrict__ log_prob) {
+    unsigned hcap, int32_t* __restrict__ tokens, int32_t* __restrict__ tokens_len, float* __restrict__ log_prob, CtcCarry cy, int mode,
+    int Tcap, int OW) {
+  // Tm = frames per utterance of `logits` (the whole utterance or one chunk), OW = the row width of `tokens`, Tcap = the most frames a
+  // carried beam takes (its trie holds 1 + W * Tcap nodes)
   // beam state (node, its parent / last label / depth, probabilities) and per-frame scratch
   __shared__ int bnode[BEAM_MAXW], bpar[BEAM_MAXW], blab[BEAM_MAXW], bdep[BEAM_MAXW], merged[BEAM_MAXW];
   __shared__ float bpb[BEAM_MAXW], bpnb[BEAM_MAXW], bptot[BEAM_MAXW], lpl[BEAM_MAXW], spb[BEAM_MAXW], spnb[BEAM_MAXW];
@@ -272,15 +284,30 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
   __shared__ int s_nc, s_nb, s_ntrie;
 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int Tb = min(max(logit_len[b], 0), Tm);
+  int Tb = logit_len ? min(max(logit_len[b], 0), Tm) : 0;
+  if ((mode & BEAM_LOAD) && !(mode & BEAM_OUTPUT) && Tb == 0) return;  // an idle stream keeps every byte of its beam
   const Trie tr{trie_parent + (long)b * nmax, trie_label + (long)b * nmax, trie_depth + (long)b * nmax};
   unsigned long long* hk = hkeys + (long)b * hcap;
   int* hv = hvals + (long)b * hcap;
-  for (unsigned i = tid; i < hcap; i += BEAM_THREADS) hk[i] = beam_trie::EMPTY;
-  if (tid == 0) {
-    tr.parent[0] = -1; tr.label[0] = -1; tr.depth[0] = 0;
-    bnode[0] = 0; bpar[0] = -1; blab[0] = -1; bdep[0] = 0; bpb[0] = 0.f; bpnb[0] = -INFINITY;
-    s_nb = 1; s_ntrie = 1;
+  int frames0 = 0;
+  if (mode & BEAM_LOAD) {
+    const int* cnt = cy.cnt + b * CC_N;
+    const int nb0 = min(max(cnt[CC_LIVE], 0), W);
+    const long c0 = (long)b * W;
+    if (tid < nb0) {
+      bnode[tid] = cy.node[c0 + tid]; bpar[tid] = cy.par[c0 + tid]; blab[tid] = cy.lab[c0 + tid]; bdep[tid] = cy.dep[c0 + tid];
+      bpb[tid] = cy.pb[c0 + tid]; bpnb[tid] = cy.pnb[c0 + tid];
+    }
+    if (tid == 0) { s_nb = nb0; s_ntrie = cnt[CC_NODES]; }
+    frames0 = cnt[CC_FRAMES];
+    Tb = min(Tb, max(Tcap - frames0, 0));
+  } else {
+    for (unsigned i = tid; i < hcap; i += BEAM_THREADS) hk[i] = beam_trie::EMPTY;
+    if (tid == 0) {
+      tr.parent[0] = -1; tr.label[0] = -1; tr.depth[0] = 0;
+      bnode[0] = 0; bpar[0] = -1; blab[0] = -1; bdep[0] = 0; bpb[0] = 0.f; bpnb[0] = -INFINITY;
+      s_nb = 1; s_ntrie = 1;
+    }
   }
   if (tid < BEAM_MAXW) win[tid] = 0;
   __syncthreads();
@@ -430,8 +457,20 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
     __syncthreads();
   }
 
-  // final beam, best first (ties: smaller label sequence); top P paths, dense and 0 padded
   const int nb = s_nb;
+  if (mode & BEAM_STORE) {
+    const long c0 = (long)b * W;
+    if (tid < nb) {
+      cy.node[c0 + tid] = bnode[tid]; cy.par[c0 + tid] = bpar[tid]; cy.lab[c0 + tid] = blab[tid]; cy.dep[c0 + tid] = bdep[tid];
+      cy.pb[c0 + tid] = bpb[tid]; cy.pnb[c0 + tid] = bpnb[tid];
+    }
+    if (tid == 0) {
+      int* cnt = cy.cnt + b * CC_N;
+      cnt[CC_LIVE] = nb; cnt[CC_NODES] = s_ntrie; cnt[CC_FRAMES] = frames0 + Tb;
+    }
+  }
+  if (!(mode & BEAM_OUTPUT)) return;
+  // final beam, best first (ties: smaller label sequence); top P paths, dense and 0 padded
   if (tid < nb) {
     const float tq = dlse2(bpb[tid], bpnb[tid]);
     int rank = 0;
@@ -450,14 +489,59 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
     tokens_len[obase + p] = p < nb ? bdep[win[p]] : 0;
     log_prob[obase + p] = p < nb ? npb[p] : -INFINITY;
   }
-  for (long e = tid; e < (long)P * Tm; e += BEAM_THREADS) {
-    const int p = (int)(e / Tm), pos = (int)(e % Tm);
-    if (p >= nb || pos >= bdep[win[p]]) tokens[obase * Tm + e] = 0;
+  for (long e = tid; e < (long)P * OW; e += BEAM_THREADS) {
+    const int p = (int)(e / OW), pos = (int)(e % OW);
+    if (p >= nb || pos >= bdep[win[p]]) tokens[obase * OW + e] = 0;
   }
   if (tid < min(nb, P)) {
-    int32_t* out = tokens + (obase + tid) * Tm;
-    for (int n = bnode[win[tid]], d = bdep[win[tid]]; n > 0; n = tr.parent[n]) out[--d] = tr.label[n];
+    int32_t* out = tokens + (obase + tid) * OW;
+    for (int n = bnode[win[tid]], d = bdep[win[tid]]; n > 0; n = tr.parent[n])
+      if (--d < OW) out[d] = tr.label[n];  // (a row as wide as the frames searched holds every label)
   }
+}
+
+// ---- tfasr_ctc_beam_reset: the streams named by `mask` (NULL: all) hold the empty prefix alone ----
+__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_reset_kernel(const int32_t* __restrict__ mask, int* trie_parent, int* trie_label,
+                                                                      int* trie_depth, unsigned long long* hkeys, CtcCarry cy, int W, long nmax,
+                                                                      unsigned hcap) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (mask && !mask[b]) return;
+  unsigned long long* hk = hkeys + (long)b * hcap;
+  for (unsigned i = tid; i < hcap; i += BEAM_THREADS) hk[i] = beam_trie::EMPTY;
+  if (tid == 0) {
+    const long n0 = (long)b * nmax, c0 = (long)b * W;
+    trie_parent[n0] = -1; trie_label[n0] = -1; trie_depth[n0] = 0;
+    cy.node[c0] = 0; cy.par[c0] = -1; cy.lab[c0] = -1; cy.dep[c0] = 0; cy.pb[c0] = 0.f; cy.pnb[c0] = -INFINITY;
+    int* cnt = cy.cnt + b * CC_N;
+    cnt[CC_LIVE] = 1; cnt[CC_NODES] = 1; cnt[CC_FRAMES] = 0;
+  }
+}
+
+// ---- tfasr_ctc_beam_commit: one wave per stream, a lane per live row; `fin` streams commit their best row (the n-best order) ----
+__global__ __launch_bounds__(64) void ctc_beam_commit_kernel(int* trie_parent, int* trie_label, int* trie_depth, CtcCarry cy,
+                                                            const int32_t* __restrict__ fin, int32_t* __restrict__ committed,
+                                                            int32_t* __restrict__ tokens, int32_t* __restrict__ ntokens, int W, int width,
+                                                            long nmax) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int nb = min(max(cy.cnt[b * CC_N + CC_LIVE], 0), W);
+  const Trie tr{trie_parent + (long)b * nmax, trie_label + (long)b * nmax, trie_depth + (long)b * nmax};
+  const bool live = lane < nb;
+  const long c0 = (long)b * W;
+  const int node = live ? cy.node[c0 + lane] : 0;
+  int target = 0;
+  if (nb > 0 && fin && fin[b]) {
+    const float tq = live ? dlse2(cy.pb[c0 + lane], cy.pnb[c0 + lane]) : -INFINITY;
+    bool best = live;
+    for (int p = 0; p < nb && best; ++p) {
+      const float tp = dlse2(cy.pb[c0 + p], cy.pnb[c0 + p]);
+      if (tp > tq || (tp == tq && p != lane && seq_less(tr, Seq{cy.node[c0 + p], -1}, Seq{node, -1}))) best = false;
+    }
+    const unsigned long long m = __ballot(best);
+    target = m ? __shfl(node, __ffsll((long long)m) - 1, 64) : __shfl(node, 0, 64);
+  } else if (nb > 0) {
+    target = beam_trie::common_ancestor(tr, node, live);
+  }
+  beam_trie::commit_labels(tr, target, lane, committed + b, tokens + (long)b * width, ntokens + b, width, 0);
 }
 
 inline size_t beam_align(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -466,15 +550,16 @@ struct BeamLayout {
   int K;
   long nmax;
   unsigned hcap;
-  size_t off_lse, off_lpb, off_tc, off_tlp, off_par, off_lab, off_dep, off_hk, off_hv, total;
+  size_t off_lse, off_lpb, off_tc, off_tlp, off_par, off_lab, off_dep, off_hk, off_hv, off_carry, total;
 };
 
-inline BeamLayout beam_layout(int B, int T, int V, int W) {
+// C = frames per launch (the per-frame scratch), Tcap = frames per beam (the trie); the one-shot search has C = Tcap = T
+inline BeamLayout beam_layout(int B, int C, int Tcap, int V, int W) {
   BeamLayout L;
   L.K = std::min(2 * W, V - 1);
-  L.nmax = 1 + (long)W * T;  // at most W new nodes per frame
+  L.nmax = 1 + (long)W * Tcap;  // at most W new nodes per frame
   L.hcap = beam_trie::table_cap(L.nmax);
-  const size_t rows = (size_t)B * T;
+  const size_t rows = (size_t)B * C;
   size_t o = 0;
   L.off_lse = o; o += beam_align(rows * 4);
   L.off_lpb = o; o += beam_align(rows * 4);
@@ -485,8 +570,38 @@ inline BeamLayout beam_layout(int B, int T, int V, int W) {
   L.off_dep = o; o += beam_align((size_t)B * L.nmax * 4);
   L.off_hk = o; o += beam_align((size_t)B * L.hcap * 8);
   L.off_hv = o; o += beam_align((size_t)B * L.hcap * 4);
+  L.off_carry = o; o += 6 * beam_align((size_t)B * W * 4) + beam_align((size_t)B * CC_N * 4);
   L.total = o;
   return L;
+}
+
+struct BeamWs { float *lse, *lpb, *tlp; int32_t* tc; int *par, *lab, *dep, *hv; unsigned long long* hk; CtcCarry cy; };
+
+inline BeamWs beam_carve(const BeamLayout& L, void* workspace, int B, int W) {
+  char* ws = (char*)workspace;
+  BeamWs w;
+  w.lse = (float*)(ws + L.off_lse); w.lpb = (float*)(ws + L.off_lpb); w.tc = (int32_t*)(ws + L.off_tc); w.tlp = (float*)(ws + L.off_tlp);
+  w.par = (int*)(ws + L.off_par); w.lab = (int*)(ws + L.off_lab); w.dep = (int*)(ws + L.off_dep);
+  w.hk = (unsigned long long*)(ws + L.off_hk); w.hv = (int*)(ws + L.off_hv);
+  const size_t a = beam_align((size_t)B * W * 4);
+  char* c = ws + L.off_carry;
+  w.cy = CtcCarry{(int*)c, (int*)(c + a), (int*)(c + 2 * a), (int*)(c + 3 * a), (float*)(c + 4 * a), (float*)(c + 5 * a), (int*)(c + 6 * a)};
+  return w;
+}
+
+// the frame kernel over logits [B, C, V], then the search kernel: both searches, whole and in pieces
+template <typename T>
+int beam_launch(const BeamLayout& L, const BeamWs& w, const void* logits, const int32_t* logit_len, int B, int C, int Tcap, int V, int W, int P,
+                int blank, int mode, int OW, int32_t* tokens, int32_t* tokens_len, float* log_prob, hipStream_t s) {
+  if (logit_len) {
+    const long rows = (long)B * C;
+    const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
+    TFASR_KLAUNCH(ctc_beam_frame_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)logits, logit_len, w.lse, w.lpb, w.tc, w.tlp, B, C, V, L.K, blank);
+  }
+  TFASR_KLAUNCH(ctc_beam_search_kernel<T>, dim3(B), dim3(BEAM_THREADS), 0, s, (const T*)logits, logit_len, w.lse, w.lpb, w.tc, w.tlp, w.par, w.lab,
+                w.dep, w.hk, w.hv, C, V, W, L.K, P, L.nmax, L.hcap, tokens, tokens_len, log_prob, w.cy, mode, Tcap, OW);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
 }
 
 inline bool beam_shape_ok(int B, int T, int V, int W) {
@@ -498,7 +613,7 @@ inline bool beam_shape_ok(int B, int T, int V, int W) {
 
 extern "C" int tfasr_ctc_beam_search_workspace_size(int B, int T, int V, int beam_width, size_t* bytes) {
   if (!bytes || !beam_shape_ok(B, T, V, beam_width)) return TFASR_STATUS_INVALID_VALUE;
-  *bytes = beam_layout(B, T, V, beam_width).total;
+  *bytes = beam_layout(B, T, T, V, beam_width).total;
   return TFASR_STATUS_SUCCESS;
 }
 
@@ -509,30 +624,80 @@ extern "C" int tfasr_ctc_beam_search(const void* logits, const int32_t* logit_le
   if (!beam_shape_ok(B, T, V, beam_width) || top_paths < 1 || top_paths > beam_width || blank_index < 0 || blank_index >= V)
     return TFASR_STATUS_INVALID_VALUE;
   if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
-  const BeamLayout L = beam_layout(B, T, V, beam_width);
+  const BeamLayout L = beam_layout(B, T, T, V, beam_width);
   if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  const BeamWs w = beam_carve(L, workspace, B, beam_width);
   hipStream_t s = (hipStream_t)stream_;
-  char* ws = (char*)workspace;
-  float* lse = (float*)(ws + L.off_lse);
-  float* lpb = (float*)(ws + L.off_lpb);
-  int32_t* tc = (int32_t*)(ws + L.off_tc);
-  float* tlp = (float*)(ws + L.off_tlp);
-  int* par = (int*)(ws + L.off_par);
-  int* lab = (int*)(ws + L.off_lab);
-  int* dep = (int*)(ws + L.off_dep);
-  unsigned long long* hk = (unsigned long long*)(ws + L.off_hk);
-  int* hv = (int*)(ws + L.off_hv);
-  const long rows = (long)B * T;
-  const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
-  if (dtype == TFASR_F32) {
-    TFASR_KLAUNCH(ctc_beam_frame_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)logits, logit_len, lse, lpb, tc, tlp, B, T, V, L.K, blank_index);
-    TFASR_KLAUNCH(ctc_beam_search_kernel<float>, dim3(B), dim3(BEAM_THREADS), 0, s, (const float*)logits, logit_len, lse, lpb, tc, tlp, par, lab, dep,
-                  hk, hv, T, V, beam_width, L.K, top_paths, L.nmax, L.hcap, tokens, tokens_len, log_prob);
-  } else {
-    TFASR_KLAUNCH(ctc_beam_frame_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)logits, logit_len, lse, lpb, tc, tlp, B, T, V, L.K, blank_index);
-    TFASR_KLAUNCH(ctc_beam_search_kernel<bf16_t>, dim3(B), dim3(BEAM_THREADS), 0, s, (const bf16_t*)logits, logit_len, lse, lpb, tc, tlp, par, lab,
-                  dep, hk, hv, T, V, beam_width, L.K, top_paths, L.nmax, L.hcap, tokens, tokens_len, log_prob);
-  }
+  // begin + all T frames + n-best in one launch of the kernel the chunked entries run
+  if (dtype == TFASR_F32)
+    return beam_launch<float>(L, w, logits, logit_len, B, T, T, V, beam_width, top_paths, blank_index, BEAM_OUTPUT, T, tokens, tokens_len, log_prob, s);
+  return beam_launch<bf16_t>(L, w, logits, logit_len, B, T, T, V, beam_width, top_paths, blank_index, BEAM_OUTPUT, T, tokens, tokens_len, log_prob, s);
+}
+
+// ---- the search in pieces (streaming sessions).  The workspace (tfasr_ctc_beam_stream_workspace_size) IS the carried state of B
+// streams: per-frame scratch for chunks of at most C frames, a trie for Tcap frames per stream, and the beam rows ----
+namespace {
+inline bool stream_shape_ok(int B, int C, int Tcap, int V, int W) { return beam_shape_ok(B, Tcap, V, W) && C >= 1 && C <= Tcap; }
+}  // namespace
+
+extern "C" int tfasr_ctc_beam_stream_workspace_size(int B, int C, int Tcap, int V, int beam_width, size_t* bytes) {
+  if (!bytes || !stream_shape_ok(B, C, Tcap, V, beam_width)) return TFASR_STATUS_INVALID_VALUE;
+  *bytes = beam_layout(B, C, Tcap, V, beam_width).total;
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_reset(const int32_t* mask, int B, int C, int Tcap, int V, int beam_width, void* workspace, size_t workspace_bytes,
+                                    void* stream_) {
+  if (!workspace || !stream_shape_ok(B, C, Tcap, V, beam_width)) return TFASR_STATUS_INVALID_VALUE;
+  const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  const BeamWs w = beam_carve(L, workspace, B, beam_width);
+  TFASR_KLAUNCH(ctc_beam_reset_kernel, dim3(B), dim3(BEAM_THREADS), 0, (hipStream_t)stream_, mask, w.par, w.lab, w.dep, w.hk, w.cy, beam_width,
+                L.nmax, L.hcap);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_advance(const void* logits, const int32_t* nvalid, int B, int C, int Cn, int Tcap, int V, int beam_width,
+                                      int blank_index, int dtype, int frames_max_after, void* workspace, size_t workspace_bytes,
+                                      void* stream_) {
+  // logits [B, Cn, V], Cn <= C (the chunk capacity the workspace was sized with)
+  if (!logits || !nvalid || !workspace || !stream_shape_ok(B, C, Tcap, V, beam_width) || Cn < 1 || Cn > C || blank_index < 0 ||
+      blank_index >= V || frames_max_after < 0 || frames_max_after > Tcap)
+    return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
+  const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  const BeamWs w = beam_carve(L, workspace, B, beam_width);
+  hipStream_t s = (hipStream_t)stream_;
+  const int mode = BEAM_LOAD | BEAM_STORE;
+  if (dtype == TFASR_F32)
+    return beam_launch<float>(L, w, logits, nvalid, B, Cn, Tcap, V, beam_width, 1, blank_index, mode, 1, nullptr, nullptr, nullptr, s);
+  return beam_launch<bf16_t>(L, w, logits, nvalid, B, Cn, Tcap, V, beam_width, 1, blank_index, mode, 1, nullptr, nullptr, nullptr, s);
+}
+
+extern "C" int tfasr_ctc_beam_commit(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens, int B, int C, int Tcap,
+                                     int V, int beam_width, int width, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!committed || !tokens || !ntokens || !workspace || !stream_shape_ok(B, C, Tcap, V, beam_width) || width < 1)
+    return TFASR_STATUS_INVALID_VALUE;
+  const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  const BeamWs w = beam_carve(L, workspace, B, beam_width);
+  TFASR_KLAUNCH(ctc_beam_commit_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream_, w.par, w.lab, w.dep, w.cy, final_mask, committed, tokens,
+                ntokens, beam_width, width, L.nmax);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_nbest(int B, int C, int Tcap, int V, int beam_width, int top_paths, int width, int32_t* tokens,
+                                    int32_t* tokens_len, float* log_prob, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!tokens || !tokens_len || !log_prob || !workspace || !stream_shape_ok(B, C, Tcap, V, beam_width) || top_paths < 1 ||
+      top_paths > beam_width || width < 1 || width > Tcap)
+    return TFASR_STATUS_INVALID_VALUE;
+  const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  const BeamWs w = beam_carve(L, workspace, B, beam_width);
+  // the search kernel over zero frames: load the beam, rank it, write the paths
+  return beam_launch<float>(L, w, nullptr, nullptr, B, C, Tcap, V, beam_width, top_paths, 0, BEAM_LOAD | BEAM_OUTPUT, width, tokens, tokens_len,
+                            log_prob, (hipStream_t)stream_);
 }

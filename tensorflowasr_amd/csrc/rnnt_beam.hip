@@ -18,6 +18,10 @@
 // special classes - they are scored explicitly from logits - lse, every other class adds the same row total to lp.
 // The prediction step runs for every row; a stay row recomputes its post-state and projection from unchanged inputs, and the f32
 // GEMM's k order per element does not depend on the row's position (split_k 1): the same bits as the cached values.
+// The search in pieces (tfasr_rnnt_beam_reset / _advance / _commit / _nbest_states, streaming sessions): the workspace sized with
+// T = Tcap is the carried state of B streams, rb_frames is the one frame loop (the one-shot search = begin + rb_frames over all T
+// frames + n-best).  Between two advances a beam is what the select leaves - node, total, token, gathered pre-state - and the
+// advance starts with the prediction step, which rebuilds the rest with the same bits.
 // Arithmetic: products f32 on the f32 master weights; totals, merges (max + log1p(exp(-|a-b|))) and comparisons f64; scores f32.
 #include "beam_trie.h"
 #include "common.h"
@@ -96,11 +100,13 @@ inline bool rb_shape_ok(int B, int T, int U, int J, int V, int W) {
 }
 
 // ---- one empty hypothesis per utterance: row b*W = (empty sequence, total 0, initial token), the other rows dead; the initial
-// state goes to every row's gather slot (hnx / cnx) when the caller runs the prediction network ----
+// state goes to every row's gather slot (hnx / cnx) when the caller runs the prediction network.  `mask` [B] (optional) names the
+// utterances to begin: the others are not touched ----
 __global__ __launch_bounds__(RB_THREADS) void rb_begin_kernel(const int32_t* __restrict__ init_tok, const float* __restrict__ init_h,
-                                                             const float* __restrict__ init_c, Ws s, int W, int U, int blank, long nmax,
-                                                             unsigned hcap, bool state) {
+                                                             const float* __restrict__ init_c, const int32_t* __restrict__ mask, Ws s,
+                                                             int W, int U, int blank, long nmax, unsigned hcap, bool state) {
   const int b = blockIdx.x, tid = threadIdx.x;
+  if (mask && !mask[b]) return;  // (tfasr_rnnt_beam_reset: the other streams keep their beams)
   for (int i = tid; i < W; i += RB_THREADS) {
     const long r = (long)b * W + i;
     s.node[r] = 0;
@@ -167,15 +173,16 @@ __global__ __launch_bounds__(RB_THREADS) void rb_cell_kernel(const float* __rest
   for (int u = tid; u < U; u += RB_THREADS) s.y[r * U + u] = (s.hpost[r * U + u] - mu) * rs * ln_g[u] + ln_b[u];
 }
 
-// ---- z = tanh(encj[b, t] + pred[row]) for the rows of utterances that still have frame t (TransducerJointMerge add + tanh) ----
-__global__ __launch_bounds__(256) void rb_join_kernel(const float* __restrict__ encj, const int32_t* __restrict__ nframes, Ws s, int B, int T,
+// ---- z = tanh(encj[b, t] + pred[row]) for the rows of utterances that still have frame t (TransducerJointMerge add + tanh); C = the
+// frames per utterance of encj (the whole utterance, or one chunk of it) ----
+__global__ __launch_bounds__(256) void rb_join_kernel(const float* __restrict__ encj, const int32_t* __restrict__ nframes, Ws s, int B, int C,
                                                      int J, int W, int t) {
   const long n = (long)B * W * J;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
     const long r = e / J;
     const int j = (int)(e % J), b = (int)(r / W);
     if (t >= nframes[b]) continue;
-    s.z[e] = tanhf(encj[((long)b * T + t) * J + j] + s.pred[e]);
+    s.z[e] = tanhf(encj[((long)b * C + t) * J + j] + s.pred[e]);
   }
 }
 
@@ -411,8 +418,23 @@ __global__ __launch_bounds__(RB_THREADS) void rb_nbest_kernel(Ws s, int T, int U
     }
   if (tid < min(nb, P)) {
     int32_t* out = tokens + (o0 + tid) * T;
-    for (int n = s.node[r0 + tid], d = dep[n]; n > 0; n = par[n]) out[--d] = lab[n];
+    for (int n = s.node[r0 + tid], d = dep[n]; n > 0; n = par[n])
+      if (--d < T) out[d] = lab[n];  // (a row as wide as the frames searched holds every label)
   }
+}
+
+// ---- tfasr_rnnt_beam_commit: one wave per stream, a lane per live row ----
+__global__ __launch_bounds__(64) void rb_commit_kernel(Ws s, const int32_t* __restrict__ fin, int32_t* __restrict__ committed,
+                                                      int32_t* __restrict__ tokens, int32_t* __restrict__ ntokens, int W, int width, int blank,
+                                                      long nmax) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int nb = min(s.cnt[b * CNT_N + CNT_LIVE], W);
+  const Trie tr{s.par + (long)b * nmax, s.lab + (long)b * nmax, s.dep + (long)b * nmax};
+  const bool live = lane < nb;
+  const int node = live ? s.node[(long)b * W + lane] : 0;
+  int target = 0;
+  if (nb > 0) target = (fin && fin[b]) ? __shfl(node, 0, 64) : beam_trie::common_ancestor(tr, node, live);
+  beam_trie::commit_labels(tr, target, lane, committed + b, tokens + (long)b * width, ntokens + b, width, blank);
 }
 
 int rb_gemm(const float* A, const float* Bm, const float* bias, float* D, int M, int N, int Kd, hipStream_t st) {
@@ -425,9 +447,9 @@ int rb_gemm(const float* A, const float* Bm, const float* bias, float* D, int M,
 
 #define RB_TRY(x) do { const int st_ = (x); if (st_ != TFASR_STATUS_SUCCESS) return st_; } while (0)
 
-int rb_begin(const RbLayout& L, const Ws& s, const int32_t* init_tok, const float* init_h, const float* init_c, int B, int U, int W, int blank,
-             bool state, hipStream_t st) {
-  TFASR_KLAUNCH(rb_begin_kernel, dim3(B), dim3(RB_THREADS), 0, st, init_tok, init_h, init_c, s, W, U, blank, L.nmax, L.hcap, state);
+int rb_begin(const RbLayout& L, const Ws& s, const int32_t* init_tok, const float* init_h, const float* init_c, const int32_t* mask, int B, int U,
+             int W, int blank, bool state, hipStream_t st) {
+  TFASR_KLAUNCH(rb_begin_kernel, dim3(B), dim3(RB_THREADS), 0, st, init_tok, init_h, init_c, mask, s, W, U, blank, L.nmax, L.hcap, state);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
@@ -461,6 +483,36 @@ int rb_predict(const Ws& s, const PredW& pw, int R, int U, int J, int V, float l
   return rb_gemm(s.y, pw.wjp, pw.bjp, s.pred, R, J, U, st);
 }
 
+// THE frame loop (the one-shot search and tfasr_rnnt_beam_advance): C frames of encj [B, C, J] from the beams the workspace holds, for
+// the utterances with t < nframes[b] and fewer than Tcap frames behind them.  The prediction step comes first: it rebuilds hpre / cpre /
+// hpost / cpost / y / pred from the gathered pre-states (hnx / cnx, tok), which are all of a beam's prediction state between calls.
+int rb_frames(const RbLayout& L, const Ws& s, const PredW& pw, const float* vocab_w, const float* vocab_b, const float* encj,
+              const int32_t* nframes, int B, int C, int Tcap, int U, int J, int V, int W, int blank, float ln_eps, hipStream_t st) {
+  const int R = B * W;
+  RB_TRY(rb_predict(s, pw, R, U, J, V, ln_eps, st));
+  const long nz = (long)R * J;
+  const int jgrid = (int)std::max<long>(1, std::min<long>((nz + 255) / 256, 4096));
+  for (int t = 0; t < C; ++t) {
+    TFASR_KLAUNCH(rb_join_kernel, dim3(jgrid), dim3(256), 0, st, encj, nframes, s, B, C, J, W, t);
+    TFASR_CHECK_LAUNCH();
+    RB_TRY(rb_gemm(s.z, vocab_w, vocab_b, s.logits, R, V, J, st));
+    RB_TRY(rb_select(L, s, s.logits, nframes, t, B, Tcap, U, V, W, blank, true, st));
+    if (t + 1 < C) RB_TRY(rb_predict(s, pw, R, U, J, V, ln_eps, st));
+  }
+  return TFASR_STATUS_SUCCESS;
+}
+
+// G = emb @ lstm_k, the input half of every token's pre-activation: `packed`'s G section (decode_pack's layout: after the recurrent,
+// joint and vocabulary tiles), or computed into the workspace
+int rb_weights(const Ws& s, PredW& pw, const float* emb, const float* lstm_k, const float* packed, int E, int U, int J, int V, hipStream_t st) {
+  if (packed) {
+    pw.G = packed + (long)(U / 4) * U * 16 + (long)((J + 15) / 16) * U * 16 + (long)((V + 15) / 16) * J * 16;
+    pw.g_packed = 1;
+    return TFASR_STATUS_SUCCESS;
+  }
+  return rb_gemm(emb, lstm_k, nullptr, s.G, V, 4 * U, E, st);
+}
+
 }  // namespace
 
 extern "C" int tfasr_rnnt_beam_workspace_size(int B, int T, int U, int J, int V, int beam_width, size_t* bytes) {
@@ -474,7 +526,7 @@ extern "C" int tfasr_rnnt_beam_begin(const int32_t* init_tok, int B, int T, int 
   if (!workspace || !rb_shape_ok(B, T, U, J, V, beam_width) || blank < 0 || blank >= V) return TFASR_STATUS_INVALID_VALUE;
   const RbLayout L = rb_layout(B, T, U, J, V, beam_width);
   if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
-  return rb_begin(L, rb_carve(L, workspace, B), init_tok, nullptr, nullptr, B, U, beam_width, blank, false, (hipStream_t)stream);
+  return rb_begin(L, rb_carve(L, workspace, B), init_tok, nullptr, nullptr, nullptr, B, U, beam_width, blank, false, (hipStream_t)stream);
 }
 
 extern "C" int tfasr_rnnt_beam_select(const float* logits, const int32_t* nframes, int t, int B, int T, int U, int J, int V, int beam_width,
@@ -515,24 +567,66 @@ extern "C" int tfasr_rnnt_beam_search(const float* emb, const float* lstm_k, con
   if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
   hipStream_t st = (hipStream_t)stream;
   const Ws s = rb_carve(L, workspace, B);
-  const int W = beam_width, R = B * W;
+  const int W = beam_width;
   PredW pw{s.G, lstm_rk, lstm_b, ln_g, ln_b, joint_pred_w, joint_pred_b, 0};
-  if (packed) {  // G section of decode_pack's layout: after the recurrent, joint and vocabulary tiles
-    pw.G = packed + (long)(U / 4) * U * 16 + (long)((J + 15) / 16) * U * 16 + (long)((V + 15) / 16) * J * 16;
-    pw.g_packed = 1;
-  } else {
-    RB_TRY(rb_gemm(emb, lstm_k, nullptr, s.G, V, 4 * U, E, st));  // G = emb @ lstm_k: the input half of every token's pre-activation
-  }
-  RB_TRY(rb_begin(L, s, init_tok, init_h, init_c, B, U, W, blank, true, st));
-  RB_TRY(rb_predict(s, pw, R, U, J, V, ln_eps, st));
-  const long nz = (long)R * J;
-  const int jgrid = (int)std::max<long>(1, std::min<long>((nz + 255) / 256, 4096));
-  for (int t = 0; t < T; ++t) {
-    TFASR_KLAUNCH(rb_join_kernel, dim3(jgrid), dim3(256), 0, st, encj, nframes, s, B, T, J, W, t);
-    TFASR_CHECK_LAUNCH();
-    RB_TRY(rb_gemm(s.z, vocab_w, vocab_b, s.logits, R, V, J, st));
-    RB_TRY(rb_select(L, s, s.logits, nframes, t, B, T, U, V, W, blank, true, st));
-    if (t + 1 < T) RB_TRY(rb_predict(s, pw, R, U, J, V, ln_eps, st));
-  }
+  // the one-shot search = begin + one advance over all T frames + n-best
+  RB_TRY(rb_weights(s, pw, emb, lstm_k, packed, E, U, J, V, st));
+  RB_TRY(rb_begin(L, s, init_tok, init_h, init_c, nullptr, B, U, W, blank, true, st));
+  RB_TRY(rb_frames(L, s, pw, vocab_w, vocab_b, encj, nframes, B, T, T, U, J, V, W, blank, ln_eps, st));
   return rb_nbest(L, s, B, T, U, W, top_paths, blank, tokens, tokens_len, score, next_tok, next_h, next_c, st);
+}
+
+// ---- the search in pieces (streaming sessions): the workspace, sized with T = Tcap, IS the carried beam state of B streams ----
+extern "C" int tfasr_rnnt_beam_reset(const int32_t* mask, int B, int Tcap, int U, int J, int V, int beam_width, int blank, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  if (!workspace || !rb_shape_ok(B, Tcap, U, J, V, beam_width) || blank < 0 || blank >= V) return TFASR_STATUS_INVALID_VALUE;
+  const RbLayout L = rb_layout(B, Tcap, U, J, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  return rb_begin(L, rb_carve(L, workspace, B), nullptr, nullptr, nullptr, mask, B, U, beam_width, blank, true, (hipStream_t)stream);
+}
+
+extern "C" int tfasr_rnnt_beam_advance(const float* emb, const float* lstm_k, const float* lstm_rk, const float* lstm_b, const float* ln_g,
+                                       const float* ln_b, const float* joint_pred_w, const float* joint_pred_b, const float* vocab_w,
+                                       const float* vocab_b, const float* packed, const float* encj, const int32_t* nvalid, int B, int C,
+                                       int Tcap, int E, int U, int J, int V, int beam_width, int blank, float ln_eps, int frames_max_after,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (!emb || !lstm_k || !lstm_rk || !lstm_b || !joint_pred_w || !joint_pred_b || !vocab_w || !vocab_b || !encj || !nvalid || !workspace)
+    return TFASR_STATUS_INVALID_VALUE;
+  if (!ln_g != !ln_b) return TFASR_STATUS_INVALID_VALUE;
+  if (!rb_shape_ok(B, Tcap, U, J, V, beam_width) || C < 1 || C > Tcap || E < 1 || blank < 0 || blank >= V) return TFASR_STATUS_INVALID_VALUE;
+  if (frames_max_after < 0 || frames_max_after > Tcap) return TFASR_STATUS_INVALID_VALUE;  // (the trie holds 1 + W * Tcap nodes)
+  if (packed && (U % 16 || J % 16)) return TFASR_STATUS_INVALID_VALUE;
+  const RbLayout L = rb_layout(B, Tcap, U, J, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t st = (hipStream_t)stream;
+  const Ws s = rb_carve(L, workspace, B);
+  PredW pw{s.G, lstm_rk, lstm_b, ln_g, ln_b, joint_pred_w, joint_pred_b, 0};
+  RB_TRY(rb_weights(s, pw, emb, lstm_k, packed, E, U, J, V, st));
+  return rb_frames(L, s, pw, vocab_w, vocab_b, encj, nvalid, B, C, Tcap, U, J, V, beam_width, blank, ln_eps, st);
+}
+
+extern "C" int tfasr_rnnt_beam_commit(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens, int B, int Tcap, int U,
+                                      int J, int V, int beam_width, int width, int blank, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  if (!committed || !tokens || !ntokens || !workspace || !rb_shape_ok(B, Tcap, U, J, V, beam_width) || width < 1 || blank < 0 || blank >= V)
+    return TFASR_STATUS_INVALID_VALUE;
+  const RbLayout L = rb_layout(B, Tcap, U, J, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t st = (hipStream_t)stream;
+  TFASR_KLAUNCH(rb_commit_kernel, dim3(B), dim3(64), 0, st, rb_carve(L, workspace, B), final_mask, committed, tokens, ntokens, beam_width, width,
+                blank, L.nmax);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_rnnt_beam_nbest_states(int B, int Tcap, int U, int J, int V, int beam_width, int top_paths, int blank, int width,
+                                            int32_t* tokens, int32_t* tokens_len, float* score, int32_t* next_tok, float* next_h,
+                                            float* next_c, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!tokens || !tokens_len || !score || !next_tok || !next_h || !next_c || !workspace || !rb_shape_ok(B, Tcap, U, J, V, beam_width) ||
+      top_paths < 1 || top_paths > beam_width || blank < 0 || blank >= V || width < 1 || width > Tcap)
+    return TFASR_STATUS_INVALID_VALUE;
+  const RbLayout L = rb_layout(B, Tcap, U, J, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  return rb_nbest(L, rb_carve(L, workspace, B), B, width, U, beam_width, top_paths, blank, tokens, tokens_len, score, next_tok, next_h, next_c,
+                  (hipStream_t)stream);
 }

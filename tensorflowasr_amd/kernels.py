@@ -1212,6 +1212,191 @@ def rnnt_beam_nbest(seam, top_paths=None):
     return seam.nbest(top_paths)
 
 
+def _row_mask(rows, B, dev):
+    """rows (None = all) -> [B] int32 device mask, or None"""
+    if rows is None:
+        return None
+    rows = [int(b) for b in rows]
+    if any(not 0 <= b < B for b in rows):
+        raise ValueError(f"stream rows {rows} outside [0, B = {B})")
+    m = torch.zeros(B, dtype=torch.int32)
+    if rows:
+        m[rows] = 1
+    return m.to(dev)
+
+
+class _BeamStream:
+    """What RnntBeamStream and CtcBeamStream share: the host's frame counts (the capacity check needs no device round trip), the
+    committed depths and the commit call."""
+
+    def _init_common(self, B, Tcap, V, beam_width, device):
+        self.B, self.Tcap, self.V = int(B), int(Tcap), int(V)
+        if self.B < 1 or self.Tcap < 1:
+            raise ValueError(f"{self.what}: B {self.B} and Tcap {self.Tcap} must be >= 1")
+        self.frames = [0] * self.B  # frames consumed per stream since its reset
+        self.committed = torch.zeros(self.B, dtype=torch.int32, device=device)
+
+    def _take(self, nvalid, C):
+        """check a chunk's nvalid (host values) against C and the capacity BEFORE anything is queued -> (list, frames_max_after)"""
+        nv = [int(v) for v in (nvalid.tolist() if hasattr(nvalid, "tolist") else nvalid)]
+        if len(nv) != self.B or any(not 0 <= v <= C for v in nv):
+            raise ValueError(f"{self.what}: nvalid {nv} must be [B = {self.B}] values in [0, C = {C}]")
+        after = [f + v for f, v in zip(self.frames, nv)]
+        for b, a in enumerate(after):
+            if a > self.Tcap:
+                raise RuntimeError(f"{self.what}: stream {b} would reach {a} frames, past its capacity of {self.Tcap}: reset it")
+        return nv, max(after)
+
+    def _reset_host(self, rows):
+        for b in (range(self.B) if rows is None else rows):
+            self.frames[int(b)] = 0
+        if rows is None:
+            self.committed.zero_()
+        elif len(rows):
+            self.committed[torch.as_tensor([int(b) for b in rows], dtype=torch.long, device=self.committed.device)] = 0
+
+    def _width(self):
+        return max(max(self.frames), 1)  # a hypothesis is never longer than the frames consumed
+
+
+class RnntBeamStream(_BeamStream):
+    """The transducer beam search in pieces (tfasr_rnnt_beam_reset / _advance / _commit / _nbest_states): B streams, each carrying its
+    whole beam from chunk to chunk in a workspace this object owns (never the cached workspace() of the one-shot search).  weights =
+    (emb, lstm_k, lstm_rk, lstm_b, ln_g, ln_b, wjp, bjp, wv, bv) f32, as rnnt_beam_search takes them.  Tcap = the most frames a stream
+    consumes between resets."""
+    what = "tfasr_rnnt_beam_advance"
+
+    def __init__(self, weights, B, Tcap, beam_width, blank=0, ln_eps=1e-3, packed=None):
+        emb, lstm_k, lstm_rk, lstm_b, ln_g, ln_b, wjp, bjp, wv, bv = weights
+        self.weights, self.packed, self.ln_eps = tuple(weights), packed, float(ln_eps)
+        V, self.E = emb.shape
+        self.U, self.J = lstm_rk.shape[0], wjp.shape[1]
+        self.beam_width, _, self.blank = _rnnt_beam_args(V, beam_width, 1, blank)
+        self._init_common(B, Tcap, V, beam_width, emb.device)
+        self.ws = torch.empty(rnnt_beam_workspace_size(self.B, self.Tcap, self.U, self.J, self.V, self.beam_width), dtype=torch.uint8,
+                              device=emb.device)
+        self.reset()
+
+    def _dims(self):
+        return self.B, self.Tcap, self.U, self.J, self.V, self.beam_width
+
+    def reset(self, rows=None):
+        """one empty hypothesis for the given streams (default: all); the others keep every bit"""
+        rows = None if rows is None else list(rows)
+        mask = _row_mask(rows, self.B, self.ws.device)
+        check(_L().tfasr_rnnt_beam_reset(_p(mask), *self._dims(), self.blank, _p(self.ws), self.ws.numel(), _stream()), "rnnt_beam_reset")
+        self._reset_host(rows)
+
+    def advance(self, encj, nvalid):
+        """encj [B, C, J] f32 (device), nvalid [B] host values in [0, C]: frame t is searched for the streams with t < nvalid[b]"""
+        if encj.dim() != 3 or encj.shape[0] != self.B or encj.shape[2] != self.J or encj.dtype != torch.float32:
+            raise ValueError(f"rnnt_beam_advance: encj {tuple(encj.shape)} {encj.dtype}, expected [{self.B}, C, {self.J}] float32")
+        C = int(encj.shape[1])
+        nv, after = self._take(nvalid, C)
+        encj = encj.contiguous()
+        w = self.weights
+        check(_L().tfasr_rnnt_beam_advance(*[_p(x) for x in w], _p(self.packed), _p(encj), _p(_i32(nv, self.ws.device)), self.B, C,
+                                           self.Tcap, self.E, self.U, self.J, self.V, self.beam_width, self.blank, self.ln_eps, after,
+                                           _p(self.ws), self.ws.numel(), _stream()), "rnnt_beam_advance")
+        self.frames = [f + v for f, v in zip(self.frames, nv)]
+
+    def commit(self, final_rows=()):
+        """-> (tokens [B, width] blank padded, ntokens [B]) device tensors: the labels new in the streams' stable prefixes (the part
+        every live hypothesis shares); the streams in final_rows commit their whole best hypothesis"""
+        dev, width = self.ws.device, self._width()
+        final_rows = list(final_rows)
+        fin = _row_mask(final_rows, self.B, dev) if final_rows else None
+        tokens = torch.empty(self.B, width, dtype=torch.int32, device=dev)
+        n = torch.empty(self.B, dtype=torch.int32, device=dev)
+        check(_L().tfasr_rnnt_beam_commit(_p(fin), _p(self.committed), _p(tokens), _p(n), *self._dims(), width, self.blank, _p(self.ws),
+                                          self.ws.numel(), _stream()), "rnnt_beam_commit")
+        return tokens, n
+
+    def nbest(self, top_paths=None):
+        """the current beams as rnnt_beam_search returns them: (tokens [B, NP, L], lengths, scores, next_tok, next_h, next_c), L = the
+        most frames a stream has consumed (at least 1)"""
+        _, top_paths, _ = _rnnt_beam_args(self.V, self.beam_width, top_paths or self.beam_width, self.blank)
+        dev, width, B, U = self.ws.device, self._width(), self.B, self.U
+        tokens = torch.empty(B, top_paths, width, dtype=torch.int32, device=dev)
+        lengths = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, top_paths, dtype=torch.float32, device=dev)
+        next_tok = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
+        next_h = torch.empty(B, top_paths, U, dtype=torch.float32, device=dev)
+        next_c = torch.empty(B, top_paths, U, dtype=torch.float32, device=dev)
+        check(_L().tfasr_rnnt_beam_nbest_states(*self._dims(), top_paths, self.blank, width, _p(tokens), _p(lengths), _p(scores),
+                                                _p(next_tok), _p(next_h), _p(next_c), _p(self.ws), self.ws.numel(), _stream()),
+              "rnnt_beam_nbest_states")
+        return tokens, lengths, scores, next_tok, next_h, next_c
+
+
+class CtcBeamStream(_BeamStream):
+    """The CTC prefix beam search in pieces (tfasr_ctc_beam_reset / _advance / _commit / _nbest): B streams, chunks of at most C
+    frames, at most Tcap frames per stream between resets; the workspace (this object's own) carries the beams.  blank_index=None: class
+    V-1, as ctc_beam_search_device."""
+    what = "tfasr_ctc_beam_advance"
+
+    def __init__(self, B, C, Tcap, V, beam_width, blank_index=None, device="cuda"):
+        self.C, self.beam_width = int(C), int(beam_width)
+        bi = int(V) - 1 if blank_index is None else int(blank_index)
+        if not 1 <= self.beam_width <= 64:
+            raise ValueError(f"tfasr_ctc_beam_advance: beam_width {self.beam_width} outside [1, 64] (the beam lives in one workgroup's LDS)")
+        if V < 2 or not 0 <= bi < V:
+            raise ValueError(f"tfasr_ctc_beam_advance: blank_index {bi} outside [0, V = {V}) or V < 2")
+        if not 1 <= self.C <= int(Tcap):
+            raise ValueError(f"tfasr_ctc_beam_advance: chunk capacity {self.C} outside [1, Tcap = {Tcap}]")
+        self.blank_index = bi
+        self._init_common(B, Tcap, V, beam_width, device)
+        n = ctypes.c_size_t(0)
+        check(_L().tfasr_ctc_beam_stream_workspace_size(*self._dims(), ctypes.byref(n)), "ctc_beam_stream_ws")
+        self.ws = torch.empty(n.value, dtype=torch.uint8, device=device)
+        self.reset()
+
+    def _dims(self):
+        return self.B, self.C, self.Tcap, self.V, self.beam_width
+
+    def reset(self, rows=None):
+        rows = None if rows is None else list(rows)
+        mask = _row_mask(rows, self.B, self.ws.device)
+        check(_L().tfasr_ctc_beam_reset(_p(mask), *self._dims(), _p(self.ws), self.ws.numel(), _stream()), "ctc_beam_reset")
+        self._reset_host(rows)
+
+    def advance(self, logits, nvalid):
+        """logits [B, Cn <= C, V] f32 / bf16 (device), nvalid [B] host values in [0, Cn]"""
+        if logits.dim() != 3 or logits.shape[0] != self.B or logits.shape[2] != self.V or not 1 <= logits.shape[1] <= self.C:
+            raise ValueError(f"ctc_beam_advance: logits {tuple(logits.shape)}, expected [{self.B}, <= {self.C}, {self.V}]")
+        Cn = int(logits.shape[1])
+        nv, after = self._take(nvalid, Cn)
+        logits = logits.contiguous()
+        B, C, Tcap, V, W = self._dims()
+        check(_L().tfasr_ctc_beam_advance(_p(logits), _p(_i32(nv, self.ws.device)), B, C, Cn, Tcap, V, W, self.blank_index, _dt(logits),
+                                          after, _p(self.ws), self.ws.numel(), _stream()), "ctc_beam_advance")
+        self.frames = [f + v for f, v in zip(self.frames, nv)]
+
+    def commit(self, final_rows=()):
+        """-> (tokens [B, width] 0 padded, ntokens [B]) device tensors, as RnntBeamStream.commit"""
+        dev, width = self.ws.device, self._width()
+        final_rows = list(final_rows)
+        fin = _row_mask(final_rows, self.B, dev) if final_rows else None
+        tokens = torch.empty(self.B, width, dtype=torch.int32, device=dev)
+        n = torch.empty(self.B, dtype=torch.int32, device=dev)
+        check(_L().tfasr_ctc_beam_commit(_p(fin), _p(self.committed), _p(tokens), _p(n), *self._dims(), width, _p(self.ws),
+                                         self.ws.numel(), _stream()), "ctc_beam_commit")
+        return tokens, n
+
+    def nbest(self, top_paths=None):
+        """the current beams as ctc_beam_search_device returns them: (tokens [B, P, L] 0 padded, lengths [B, P], log_prob [B, P])"""
+        top_paths = int(top_paths or self.beam_width)
+        if not 1 <= top_paths <= self.beam_width:
+            raise ValueError(f"tfasr_ctc_beam_nbest: top_paths {top_paths} outside [1, beam_width = {self.beam_width}]")
+        dev, width, B = self.ws.device, self._width(), self.B
+        tokens = torch.empty(B, top_paths, width, dtype=torch.int32, device=dev)
+        lengths = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
+        log_prob = torch.empty(B, top_paths, dtype=torch.float32, device=dev)
+        check(_L().tfasr_ctc_beam_nbest(*self._dims(), top_paths, width, _p(tokens), _p(lengths), _p(log_prob), _p(self.ws),
+                                        self.ws.numel(), _stream()), "ctc_beam_nbest")
+        return tokens, lengths, log_prob
+
+
 def ctc_greedy_decode(logits, logit_len, blank=0):
     B, T, V = logits.shape
     am = torch.empty(B * T, dtype=torch.int32, device=logits.device)

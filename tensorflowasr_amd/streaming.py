@@ -1,5 +1,5 @@
 """Incremental recognition with the streaming Conformer (chunked attention mask, causal convolutions): chunk-by-chunk encoder with
-state carried on the device, and the greedy searches continued across chunks.
+state carried on the device, and the searches (greedy, or a beam carried whole) continued across chunks.
 
 The contract ("Streaming"): stream b of a session produces the encoder frames and the tokens that `model.encode` /
 `model.recognize` produce for that utterance run ALONE (batch size 1), however the samples arrive and whatever the other streams of the
@@ -8,6 +8,8 @@ session do.  State carried per stream:
     subsampling   the last 2 feature frames and the last 2 frames of the first convolution's activation (zeros = the causal padding)
     each block    K and V of the last `history_size` frames (rings), the last kernel_size - 1 GLU outputs of the conv module
     search        last token, LSTM h / c (transducer); the class of the last frame (CTC)
+    beam search   (beam_width >= 1) the whole beam: rows, f64 totals, label trie + table, prediction states (K.RnntBeamStream); the
+                  CTC search's rows and trie (K.CtcBeamStream); the depth committed so far
 The kernels that touch carried state are csrc/stream.hip; the dense pieces are the forward kernels of training with T = chunk_size.
 """
 import math
@@ -156,10 +158,41 @@ def encode_chunk(state, feats, nframes):
     return x.view(B, C, d), nvalid
 
 
-class StreamingRecognizer:
-    """model.stream(): accept() PCM as it arrives, get the new tokens back; finish() flushes a stream's tail."""
+def check_stream_args(batch_size=1, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
+    """The session arguments that need no device to judge -> them as ints.  beam_width 0 = the greedy session; 1 .. 64 = a beam of that
+    many hypotheses per stream (the device searches keep a beam in one workgroup's LDS: 64 rows at most)."""
+    batch_size, max_tokens_per_frame, beam_width, max_frames = int(batch_size), int(max_tokens_per_frame), int(beam_width), int(max_frames)
+    if batch_size < 1:
+        raise ValueError(f"stream: batch_size {batch_size} must be >= 1")
+    if max_tokens_per_frame < 1:
+        raise ValueError(f"stream: max_tokens_per_frame {max_tokens_per_frame} must be >= 1")
+    if not 0 <= beam_width <= 64:
+        raise ValueError(f"stream: beam_width {beam_width} outside [0, 64] (0 = greedy; a beam lives in one workgroup's LDS)")
+    if max_frames < 1:
+        raise ValueError(f"stream: max_frames {max_frames} must be >= 1 (the encoder frames one stream may consume between resets)")
+    return batch_size, max_tokens_per_frame, beam_width, max_frames
 
-    def __init__(self, model, batch_size=1, precision=None, max_tokens_per_frame=3):
+
+class StreamingRecognizer:
+    """model.stream(): accept() PCM as it arrives, get the new tokens back; finish() flushes a stream's tail.
+
+    beam_width = 0: the greedy search (recognize_single's rule, up to max_tokens_per_frame symbols per frame).
+    beam_width >= 1: the device beam search (at most ONE symbol per frame) with the whole beam carried from chunk to chunk: after any
+    sequence of accept calls stream b holds exactly the beam recognize_beam_encoded / recognize_nbest hold after the same encoder frames
+    (f32 on the f32 master weights whatever the encoder's type).  StreamOutput.tokens are then the tokens COMMITTED by the call: the
+    labels new in the prefix that every live hypothesis shares, which can no longer change; finish() commits the rest of the best
+    hypothesis, so the concatenation of a stream's outputs is its best path.  hypotheses() gives the current n-best in full.  Because the
+    beam emits one symbol per frame at most, a beam_width=1 session equals the greedy session made with max_tokens_per_frame=1, not the
+    default greedy session.  The CTC head's beam session treats class V-1 as blank, as recognize_beam does.
+    max_frames bounds the encoder frames of one stream between resets (a chunk past it raises RuntimeError; reset() frees the slot).
+    Beam memory per stream, with W = beam_width, N = 1 + W * max_frames trie nodes and H = the power of two >= 2 N table slots:
+        transducer  12 N + 12 H + W * (4 V + 44 U + 8 J + 12 min(2 W, V - 1) + 28) bytes   (U = rnn_units, J = joint_dim)
+        CTC         12 N + 12 H + 24 W + 8 chunk_size * (1 + min(2 W, V - 1)) bytes
+    (W = 10, max_frames = 3000, V = 1000, U = J = 320: about 1.4 MB per stream.)"""
+
+    def __init__(self, model, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
+        batch_size, max_tokens_per_frame, self.beam_width, self.max_frames = check_stream_args(batch_size, max_tokens_per_frame, beam_width,
+                                                                                             max_frames)
         self.model = model
         self.enc_model = _twin(model, precision)
         self.state = StreamState(self.enc_model, batch_size)
@@ -186,7 +219,10 @@ class StreamingRecognizer:
             self.emitted = [0] * B  # feature frames consumed
             self.frames = [0] * B  # encoder frames emitted
             self.finished = [False] * B
-            if self.ctc:
+            self.beam = None
+            if self.beam_width:
+                self.beam = self._new_beam()
+            elif self.ctc:
                 self.last_class = torch.full((B,), -1, dtype=torch.int32, device=dev)
             else:
                 P = m.cfg.rnn_units
@@ -202,7 +238,9 @@ class StreamingRecognizer:
             self.total[b] = self.emitted[b] = self.frames[b] = 0
             self.finished[b] = False
         r = torch.as_tensor(rows, dtype=torch.long, device=dev)
-        if self.ctc:
+        if self.beam is not None:
+            self.beam.reset(rows)
+        elif self.ctc:
             self.last_class[r] = -1
         else:
             self.prev_tok[r] = m.blank
@@ -265,16 +303,72 @@ class StreamingRecognizer:
             if self.encoded_log is not None:
                 self.encoded_log.append((enc, nv))
             self.chunks_run += 1
-            toks = self._search_ctc(enc, nvalid) if self.ctc else self._search(enc, nvalid, nv)
+            if self.beam is not None:
+                self._advance_beam(enc, nv)
+            else:
+                toks = self._search_ctc(enc, nvalid) if self.ctc else self._search(enc, nvalid, nv)
             for b in range(B):
                 self.frames[b] += nv[b]
-                new[b].extend(toks[b])
+                if self.beam is None:
+                    new[b].extend(toks[b])
+        if self.beam is not None:  # one commit per call: the labels that became stable, and the rest of the best row for flushed streams
+            ct, cn = self.beam.commit(final_rows=sorted(flush_rows))
+            th, tl = ct.cpu(), cn.cpu()
+            new = [th[b, :int(tl[b])].tolist() for b in range(B)]
         W = max(max(len(t) for t in new), 1)
         out = torch.full((B, W), m.blank, dtype=torch.int32)
         for b in range(B):
             if new[b]:
                 out[b, :len(new[b])] = torch.tensor(new[b], dtype=torch.int32)
         return StreamOutput(out, torch.tensor([len(t) for t in new], dtype=torch.int32), torch.tensor(self.frames, dtype=torch.int32))
+
+    # ------------------------------------------------------------------------------------------- beam sessions
+    def _new_beam(self):
+        m = self.model
+        ps, c = m.ps, m.cfg
+        if self.ctc:
+            return K.CtcBeamStream(self.B, self.C, self.max_frames, c.vocab_size, self.beam_width, blank_index=None, device=m.device)
+        lng, lnb = (ps.p("pred/ln/g"), ps.p("pred/ln/b")) if c.prediction_layer_norm else (None, None)
+        weights = (ps.p("pred/emb"), ps.p2d("pred/lstm/k"), ps.p2d("pred/lstm/rk"), ps.p("pred/lstm/b"), lng, lnb, ps.p2d("joint/pred/w"),
+                   ps.p("joint/pred/b"), ps.p2d("joint/vocab/w"), ps.p("joint/vocab/b"))
+        return K.RnntBeamStream(weights, self.B, self.max_frames, self.beam_width, blank=m.blank)
+
+    def _check_capacity(self, flush_rows=(), more=None):
+        """refuse a call (more[b] further samples, or the flush of some streams) whose chunks would take a stream past max_frames, before
+        anything of it is buffered or queued: the session stays as it was"""
+        if self.beam is None:
+            return
+        for b in range(self.B):
+            n, emitted, frames = len(self.buf[b]) + (more[b] if more else 0), self.emitted[b], self.frames[b]
+            total = self.total[b] + (more[b] if more else 0)
+            flush = b in flush_rows and not self.finished[b]
+            while True:  # the chunks _run will take from this stream (_ready's rule)
+                take = self.chunk_frames if n >= self.chunk_samples else (min(-(-total // self.step) - emitted, self.chunk_frames) if flush else 0)
+                if take <= 0:
+                    break
+                n, emitted, frames = max(n - take * self.step, 0), emitted + take, frames + -(-(-(-take // 2)) // 2)
+            if frames > self.max_frames:
+                raise RuntimeError(f"stream {b} would pass max_frames = {self.max_frames} encoder frames ({self.frames[b]} so far, {frames} after "
+                                   "this call): reset it, or open the session with a larger max_frames")
+
+    def _advance_beam(self, enc, nv):
+        m = self.model
+        ps = m.ps
+        B, C, _ = enc.shape
+        if self.ctc:
+            logits = K.matmul(self._enc32(enc), ps.p2d("dec/logits/w"), bias=ps.p("dec/logits/b")).view(B, C, m.cfg.vocab_size)
+            self.beam.advance(logits, nv)
+        else:
+            encj = K.matmul(self._enc32(enc), ps.p2d("joint/enc/w"), bias=ps.p("joint/enc/b")).view(B, C, m.cfg.joint_dim)
+            self.beam.advance(encj, nv)
+
+    def hypotheses(self, top_paths=None):
+        """The current n-best of every stream in full, committed part included: (tokens [B, P, L] blank padded (CTC: 0 padded), lengths
+        [B, P], scores [B, P]) device tensors, best first; P = top_paths (default: beam_width).  Valid after every accept and after
+        finish, until reset."""
+        if self.beam is None:
+            raise ValueError("hypotheses() needs a beam session: open it with model.stream(beam_width >= 1)")
+        return tuple(self.beam.nbest(top_paths)[:3])
 
     def _enc32(self, enc):
         B, C, d = enc.shape
@@ -359,6 +453,7 @@ class StreamingRecognizer:
         for b in range(self.B):
             if lens[b] > 0 and self.finished[b]:
                 raise RuntimeError(f"stream {b} is finished: reset it before it takes another utterance")
+        self._check_capacity(more=[max(n, 0) for n in lens])
         for b in range(self.B):
             if lens[b] > 0:
                 self.buf[b] = np.concatenate([self.buf[b], x[b, :lens[b]]])
@@ -369,6 +464,7 @@ class StreamingRecognizer:
         """Pad the tail of the given streams (default: all) as pad_end=True does, run their last (partial) chunk -> StreamOutput; those
         streams then refuse accept until reset."""
         rows = [b for b in (range(self.B) if rows is None else rows) if not self.finished[b]]
+        self._check_capacity(flush_rows=set(rows))
         out = self._run(flush_rows=set(rows))
         for b in rows:
             self.finished[b] = True
