@@ -939,6 +939,30 @@ int tfasr_edit_distance_workspace_size(int P, int N, int M, size_t* bytes);
 int tfasr_edit_distance(const int32_t* hyp, const int32_t* hyp_len, const int32_t* ref, const int32_t* ref_len, int P, int N, int M,
                         int skip_id, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Causal dense Conv1D, channels-last (csrc/conv1d.hip; declarations added under ABI 44, nothing existing changes): the Jasper encoder's
+ * layer, keras.layers.Conv1D(padding="causal") with the inference BatchNorm, the residual sum and the ReLU in its epilogue.
+ *   x [B, lead + T, Cin]: `lead` rows of real left context (a stream's carried tail; 0 offline) followed by the T rows to convolve;
+ *   y [B, ceil(T / stride), Cout];  y[b,t,:] = sum_k sum_c x[b, lead + t*stride + (k - (K-1))*dilation, c] * w[k,c,:], rows in front of
+ *   the buffer (the causal padding) and past it read as zeros;  v = (acc + bias[n]) * scale[n] + shift[n] (each of the three f32 [Cout]
+ *   vectors may be NULL), v += addend[b,t,n] (activation type, y's shape, may be NULL), ReLU when relu != 0 - all in f32 before the store.
+ *   w: TFASR_F32 -> the Keras kernel [K, Cin, Cout] f32;  TFASR_BF16 -> the packed bf16 copy tfasr_conv1d_pack_weight writes
+ *   (tfasr_conv1d_packed_weight_elems bf16 elements; pack once per weight load).
+ * 1 <= K <= 32, stride 1 or 2, dilation >= 1 with (K-1)*dilation <= 256, Cin and Cout multiples of 16, any B and T: anything else is
+ * UNSUPPORTED (INVALID_VALUE for null / non-positive / misaligned arguments), decided on the host before any launch.  An output element's
+ * value does not depend on B, T, lead or its row's place in a tile (one tile shape per type, no split reduction).  No workspace is
+ * needed today (the size query answers 0 and needs no device); the arguments exist so that may change without an ABI break.
+ * tfasr_conv1d_tail_update: tail [B, tail_rows, C] = rows nvalid[b] .. nvalid[b] + tail_rows - 1 of window [B, rows, C] (= old tail ++
+ * new rows; nvalid clamped to [0, rows - tail_rows]): a stream's next left context; nvalid == 0 leaves the tail bit-equal. */
+int tfasr_conv1d_packed_weight_elems(int K, int Cin, int Cout, size_t* elems);
+int tfasr_conv1d_pack_weight(const float* w, void* packed, int K, int Cin, int Cout, void* stream);
+int tfasr_conv1d_workspace_size(int B, int T, int Cin, int Cout, int K, int stride, int dilation, int dtype, size_t* bytes);
+int tfasr_conv1d_fwd(const void* x, const void* w, const float* bias, const float* scale, const float* shift, const void* addend, void* y,
+                     int B, int T, int lead, int Cin, int Cout, int K, int stride, int dilation, int relu, int dtype, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int tfasr_conv1d_tail_update(const void* window, const int32_t* nvalid, void* tail, int B, int rows, int tail_rows, int C, int dtype,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

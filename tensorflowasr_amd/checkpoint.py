@@ -82,6 +82,27 @@ def keras_path(name, dw_norm="batch", sub_norm="batch"):
     raise KeyError(f"no Keras path is known for {name!r}")
 
 
+_JASPER_LEAF = {"conv1d/w": "conv1d/kernel", "conv1d/b": "conv1d/bias", "pointwise_conv1d/w": "pointwise_conv1d/kernel",
+                "pointwise_conv1d/b": "pointwise_conv1d/bias", "bn/g": "bn/gamma", "bn/b": "bn/beta", "bn/mm": "bn/moving_mean",
+                "bn/mv": "bn/moving_variance", "logits/w": "logits/kernel", "logits/b": "logits/bias"}
+
+
+def jasper_keras_path(name, *_):
+    """Keras variable path of a Jasper tensor (models/ctc/jasper.py:96-122: JasperEncoder "encoder", JasperDecoder "decoder"; layer names
+    of encoders/jasper.py): enc/block_1/subordinate_2/residual_0/bn/mm -> encoder/block_1/subordinate_2/residual_0/bn/moving_mean."""
+    top, _, rest = name.partition("/")
+    head, _, leaf = rest.rpartition("/")
+    layer = head.rpartition("/")[2]
+    key = f"{layer}/{leaf}"
+    if top not in ("enc", "dec") or key not in _JASPER_LEAF:
+        raise KeyError(f"no Keras path is known for {name!r}")
+    return {"enc": "encoder/", "dec": "decoder/"}[top] + head[:len(head) - len(layer)] + _JASPER_LEAF[key]
+
+
+def _path_fn(model):
+    return jasper_keras_path if getattr(model.cfg, "encoder", "conformer") == "jasper" else keras_path
+
+
 def _to_keras_layout(name, a):
     if name.endswith("conv/pw1/w") or name.endswith("conv/pw2/w"):
         return a.reshape(1, *a.shape)            # Conv1D kernel [1, cin, cout]
@@ -97,22 +118,24 @@ def _from_keras_layout(name, a, shape, path=None):
     return a.reshape(shape)
 
 
-def to_keras(exported, dw_norm="batch", sub_norm="batch"):
+def to_keras(exported, dw_norm="batch", sub_norm="batch", path_fn=keras_path):
     """ParamStore.export_keras() dict (name -> tensor) -> {Keras path: float32 ndarray in the Keras layout}."""
     out = {}
     for name, t in exported.items():
         a = np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32)
-        out[keras_path(name, dw_norm, sub_norm)] = _to_keras_layout(name, a)
+        if path_fn is jasper_keras_path and name == "dec/logits/w":
+            a = a.reshape(1, *a.shape)           # JasperDecoder's "logits" is a Conv1D with one tap: kernel [1, C, V]
+        out[path_fn(name, dw_norm, sub_norm)] = _to_keras_layout(name, a)
     return out
 
 
-def from_keras(arrays, template, strict=True, dw_norm="batch", sub_norm="batch"):
+def from_keras(arrays, template, strict=True, dw_norm="batch", sub_norm="batch", path_fn=keras_path):
     """{Keras path: array} -> dict in the layout of `template` (= ParamStore.export_keras(), which fixes names and shapes).
     strict: every variable of the model must be present and no unknown array may remain."""
     arrays = dict(arrays)
     out, missing = {}, []
     for name, t in template.items():
-        path = keras_path(name, dw_norm, sub_norm)
+        path = path_fn(name, dw_norm, sub_norm)
         if path not in arrays:
             missing.append(path)
             continue
@@ -125,7 +148,8 @@ def from_keras(arrays, template, strict=True, dw_norm="batch", sub_norm="batch")
 
 def save_weights(model, filepath):
     """BaseModel.save_weights (base_model.py:55-57): every trainable variable + BatchNorm moving statistics -> `.npz`."""
-    arrays = to_keras(model.ps.export_keras(), getattr(model.cfg, "convm_dw_norm", "batch"), getattr(model.cfg, "sub_norm", "batch"))
+    arrays = to_keras(model.ps.export_keras(), getattr(model.cfg, "convm_dw_norm", "batch"), getattr(model.cfg, "sub_norm", "batch"),
+                      _path_fn(model))
     with open(filepath, "wb") as f:  # (np.savez would append ".npz" to a bare name)
         np.savez(f, **{k.replace("/", "|"): v for k, v in arrays.items()})
     return sorted(arrays)
@@ -138,7 +162,8 @@ def load_weights(model, filepath, strict=True):
     with np.load(filepath) as z:
         arrays = {k.replace("|", "/"): z[k] for k in z.files}
     template = model.ps.export_keras()
-    got = from_keras(arrays, template, strict=strict, dw_norm=getattr(model.cfg, "convm_dw_norm", "batch"), sub_norm=getattr(model.cfg, "sub_norm", "batch"))
+    got = from_keras(arrays, template, strict=strict, dw_norm=getattr(model.cfg, "convm_dw_norm", "batch"), sub_norm=getattr(model.cfg, "sub_norm", "batch"),
+                     path_fn=_path_fn(model))
     merged = {k: (torch.from_numpy(np.ascontiguousarray(got[k])) if k in got else v) for k, v in template.items()}
     model.ps.import_keras(merged)
     return sorted(got)

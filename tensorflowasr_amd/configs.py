@@ -10,12 +10,13 @@ import math
 from dataclasses import dataclass, field
 
 
-def speech_kwargs(sc):
+def speech_kwargs(sc, log_bases=("e",)):
     """`speech_config` of the reference's YAML (FeatureExtraction.__init__, models/layers/feature_extraction.py:32-130) -> the front-end
     fields of ConformerConfig.  Options the MI355X front end does not implement fail loudly instead of being ignored; the epsilon range
-    check is the reference's (feature_extraction.py:113)."""
+    check is the reference's (feature_extraction.py:113).  log_bases: the values of `log_base` the caller's model handles (the result
+    does not carry the base: a model that accepts "10" reads it from the mapping itself)."""
     sc = dict(sc or {})
-    only = {"feature_type": ("log_mel_spectrogram",), "pad_end": (True,), "use_librosa_like_stft": (False,), "log_base": ("e",),
+    only = {"feature_type": ("log_mel_spectrogram",), "pad_end": (True,), "use_librosa_like_stft": (False,), "log_base": tuple(log_bases),
             "normalize_signal": (False,), "normalize_zscore": (False,), "normalize_min_max": (False,), "padding": (0,)}
     for k, ok in only.items():
         if k in sc and sc[k] not in ok:
@@ -255,6 +256,151 @@ def conformer_tiny(vocab_size=29, **over):
               kernel_size=7, vocab_size=vocab_size)
     kw.update(over)
     return ConformerConfig(**kw)
+
+
+# ------------------------------------------------------------------------------------------------------------------ Jasper (CTC)
+@dataclass
+class JasperConfig:
+    """The keyword surface of tensorflow_asr.models.ctc.jasper.Jasper (models/ctc/jasper.py:61-92) with `speech_config` flattened as in
+    ConformerConfig.  Inference only: the dropout rates are kept for the record and never applied."""
+    # speech_config
+    sample_rate: int = 16000
+    frame_ms: int = 25
+    stride_ms: int = 10
+    nfft: int = 512
+    num_feature_bins: int = 80
+    preemphasis: float = 0.97
+    epsilon: float = 1e-6
+    lower_edge_hertz: float = 0.0
+    upper_edge_hertz: float = 8000.0
+    log_base: str = "10"
+    # encoder (models/encoders/jasper.py:231-256; values: examples/models/ctc/jasper/base.yml.j2:13-32)
+    dense: bool = True
+    padding: str = "causal"
+    first_additional_block_channels: int = 256
+    first_additional_block_kernels: int = 11
+    first_additional_block_strides: int = 2
+    first_additional_block_dilation: int = 1
+    first_additional_block_dropout: float = 0.2
+    nsubblocks: int = 3
+    block_channels: list = field(default_factory=lambda: [256, 384, 512, 640, 768])
+    block_kernels: list = field(default_factory=lambda: [11, 13, 17, 21, 25])
+    block_dropout: list = field(default_factory=lambda: [0.2, 0.2, 0.2, 0.3, 0.3])
+    second_additional_block_channels: int = 896
+    second_additional_block_kernels: int = 1
+    second_additional_block_strides: int = 1
+    second_additional_block_dilation: int = 2
+    second_additional_block_dropout: float = 0.4
+    third_additional_block_channels: int = 1024
+    third_additional_block_kernels: int = 1
+    third_additional_block_strides: int = 1
+    third_additional_block_dilation: int = 1
+    third_additional_block_dropout: float = 0.4
+    vocab_size: int = 1000
+    blank: int = 0
+    l2: float = 1e-6
+    # what the shared model code reads from every config
+    encoder: str = "jasper"
+    head: str = "ctc"
+    dropout: float = 0.0
+    chunk_size: int = None
+    history_size: int = None
+    time_masking: dict = None
+    freq_masking: dict = None
+    head_size: int = 64   # (no attention: the values only keep ParamStore's head / filter padding off)
+    num_heads: int = 1
+    filters: int = 64
+
+    def __post_init__(self):
+        self.block_channels, self.block_kernels = [int(v) for v in self.block_channels], [int(v) for v in self.block_kernels]
+        self.block_dropout = [float(v) for v in self.block_dropout]
+        if not len(self.block_channels) == len(self.block_kernels) == len(self.block_dropout):  # encoders/jasper.py:260
+            raise ValueError("block_channels, block_kernels and block_dropout must have one entry per block")
+        if str(self.padding) != "causal":
+            raise NotImplementedError(f"padding={self.padding!r}: only causal convolutions are on the MI355X hot path")
+        if self.log_base not in ("e", "10"):
+            raise NotImplementedError(f"log_base={self.log_base!r}: 'e' or '10'")
+        if int(self.nsubblocks) < 1:
+            raise ValueError("nsubblocks must be >= 1")
+        s1 = int(self.first_additional_block_strides)
+        if s1 not in (1, 2):
+            raise NotImplementedError(f"first_additional_block_strides={s1}: the Conv1D kernel strides by 1 or 2")
+        for which in ("second", "third"):
+            if int(getattr(self, which + "_additional_block_strides")) != 1:
+                raise NotImplementedError(f"{which}_additional_block_strides != 1: only the first block may stride (base.yml.j2:16,25,30)")
+        chans = [self.num_feature_bins, self.first_additional_block_channels, *self.block_channels, self.second_additional_block_channels,
+                 self.third_additional_block_channels]
+        if any(int(c) <= 0 or int(c) % 16 for c in chans):
+            raise NotImplementedError(f"channel counts {chans} (feature bins included): the Conv1D kernel takes multiples of 16")
+        for k, d in [(self.first_additional_block_kernels, self.first_additional_block_dilation), *((k, 1) for k in self.block_kernels),
+                     (self.second_additional_block_kernels, self.second_additional_block_dilation),
+                     (self.third_additional_block_kernels, self.third_additional_block_dilation)]:
+            if not 1 <= int(k) <= 32 or int(d) < 1 or (int(k) - 1) * int(d) > 256:
+                raise NotImplementedError(f"kernel {k} / dilation {d}: the Conv1D kernel takes 1..32 taps spanning at most 256 rows")
+
+    @property
+    def dmodel(self):
+        return int(self.third_additional_block_channels)
+
+    @property
+    def frame_length(self):
+        return int(round(self.sample_rate * self.frame_ms / 1000.0))
+
+    @property
+    def frame_step(self):
+        return int(round(self.sample_rate * self.stride_ms / 1000.0))
+
+    @property
+    def time_reduction_factor(self):
+        """encoders/jasper.py:318-320: the product of the three additional blocks' strides"""
+        return (int(self.first_additional_block_strides) * int(self.second_additional_block_strides)
+                * int(self.third_additional_block_strides))
+
+    def encoder_length(self, n):
+        """math_util.get_reduced_length: ceil(n / time_reduction_factor)"""
+        return -(-int(n) // self.time_reduction_factor)
+
+
+def jasper(vocab_size=1000, layout="base", **over):
+    """examples/models/ctc/jasper/base.yml.j2 (5 blocks of 3 sub-blocks, dense residuals); layout="10x5": the 10-block, 5-sub-block
+    network of arXiv:1904.03288 Table 1 that BASELINE.json names, through the same keys."""
+    kw = dict(vocab_size=vocab_size)
+    if layout == "10x5":
+        kw.update(nsubblocks=5, block_channels=[256, 256, 384, 384, 512, 512, 640, 640, 768, 768],
+                  block_kernels=[11, 11, 13, 13, 17, 17, 21, 21, 25, 25], block_dropout=[0.2, 0.2, 0.2, 0.2, 0.2, 0.2, 0.3, 0.3, 0.3, 0.3])
+    elif layout != "base":
+        raise ValueError(f"layout {layout!r}: 'base' or '10x5'")
+    kw.update(over)
+    return JasperConfig(**kw)
+
+
+def jasper_tiny(vocab_size=29, **over):
+    kw = dict(vocab_size=vocab_size, nsubblocks=3, block_channels=[64, 96], block_kernels=[11, 13], block_dropout=[0.0, 0.0],
+              first_additional_block_channels=48, first_additional_block_kernels=11, second_additional_block_channels=128,
+              third_additional_block_channels=160)
+    kw.update(over)
+    return JasperConfig(**kw)
+
+
+def jasper_from_reference(config: dict):
+    """The YAML's `model_config.config` of tensorflow_asr.models.ctc.jasper>Jasper (base.yml.j2:3-38) -> JasperConfig.  Options that are
+    not built raise (JasperConfig.__post_init__ and speech_kwargs); a regulariser other than l2 on the kernels, too."""
+    c = dict(config)
+    sc = dict(c.get("speech_config", {}))
+    for k in ("bias_regularizer", "activity_regularizer"):
+        if c.get(k) is not None:
+            raise NotImplementedError(f"{k}={c[k]!r}: not built")
+    reg = c.get("kernel_regularizer") or {}
+    kw = dict(**speech_kwargs(sc, log_bases=("e", "10")), log_base=str(sc.get("log_base", "e")),
+              l2=float((reg.get("config") or {}).get("l2", 1e-6)) if isinstance(reg, dict) else 1e-6)
+    fields = {f for f in JasperConfig.__dataclass_fields__}
+    for k, v in c.items():
+        if k in ("speech_config", "kernel_regularizer", "bias_regularizer", "activity_regularizer", "name"):
+            continue
+        if k not in fields or k in ("encoder", "head", "head_size", "num_heads", "filters", "chunk_size", "history_size"):
+            raise NotImplementedError(f"{k}={v!r}: not a keyword of models/ctc/jasper.py:61-92 that is built here")
+        kw[k] = v
+    return JasperConfig(**kw)
 
 
 def transformer_schedule(step, dmodel, warmup_steps=10000, scale=2.0, max_lr=None, min_lr=None):

@@ -1591,3 +1591,63 @@ def ctc_greedy_decode_carry(logits, logit_len, last_class, blank=0):
     check(_L().tfasr_ctc_greedy_decode_carry(_p(logits), _p(logit_len), _p(last_class), _p(ws), _p(tokens), _p(tlen), B, T, V, blank,
                                              _dt(logits), _stream()), "ctc_greedy_decode_carry")
     return tokens, tlen
+
+
+# ------------------------------------------------------------------------------------------- causal dense Conv1D (csrc/conv1d.hip)
+def _conv1d_check(st, what):
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported(f"{what}: outside 1 <= K <= 32, stride 1 | 2, (K - 1) * dilation <= 256, Cin % 16 == Cout % 16 == 0 "
+                                    "(see include/tfasr_hip.h)")
+    check(st, what)
+
+
+def conv1d_workspace_size(B, T, Cin, Cout, K, stride=1, dilation=1, dtype=TFASR_F32):
+    """Bytes of caller-owned workspace tfasr_conv1d_fwd needs for this shape (answers without a device)."""
+    n = ctypes.c_size_t(0)
+    _conv1d_check(_L().tfasr_conv1d_workspace_size(B, T, Cin, Cout, K, stride, dilation, dtype, ctypes.byref(n)), "conv1d_workspace_size")
+    return n.value
+
+
+def conv1d_pack_weight(w):
+    """Keras Conv1D kernel [K, Cin, Cout] f32 (device) -> the packed bf16 copy the MFMA kernel's B operand reads (once per weight load)."""
+    K, Cin, Cout = w.shape
+    n = ctypes.c_size_t(0)
+    _conv1d_check(_L().tfasr_conv1d_packed_weight_elems(K, Cin, Cout, ctypes.byref(n)), "conv1d_packed_weight_elems")
+    out = torch.empty(n.value, dtype=torch.bfloat16, device=w.device)
+    assert w.dtype == torch.float32
+    _conv1d_check(_L().tfasr_conv1d_pack_weight(_p(w), _p(out), K, Cin, Cout, _stream()), "conv1d_pack_weight")
+    return out
+
+
+def conv1d_fwd(x, w, shape, bias=None, scale=None, shift=None, addend=None, relu=False, stride=1, dilation=1, lead=0, out=None):
+    """Causal Conv1D: x [B, lead + T, Cin] (f32 | bf16) -> [B, ceil(T / stride), Cout]; shape = (K, Cin, Cout).  w: the Keras kernel
+    (f32 activations) or conv1d_pack_weight's copy (bf16 activations).  Epilogue (acc + bias) * scale + shift [+ addend] [ReLU] in f32."""
+    K, Cin, Cout = (int(v) for v in shape)
+    B, rows = x.shape[0], x.shape[1]
+    T = rows - int(lead)
+    assert x.dim() == 3 and x.shape[2] == Cin and T >= 0
+    Tout = -(-T // stride) if stride > 0 else 0
+    if out is None:
+        out = torch.empty(B, Tout, Cout, dtype=x.dtype, device=x.device)
+    assert w.dtype == x.dtype and (addend is None or (addend.shape == out.shape and addend.dtype == x.dtype))
+    assert out.shape == (B, Tout, Cout) and out.dtype == x.dtype
+    want = ctypes.c_size_t(K * Cin * Cout)
+    if x.dtype != torch.float32:
+        _conv1d_check(_L().tfasr_conv1d_packed_weight_elems(K, Cin, Cout, ctypes.byref(want)), "conv1d_packed_weight_elems")
+    if w.numel() != want.value:
+        raise _lib.TfasrError(f"conv1d_fwd: the kernel holds {w.numel()} elements, {want.value} expected for {(K, Cin, Cout)} in {x.dtype}")
+    for v in (bias, scale, shift):
+        assert v is None or (v.dtype == torch.float32 and v.numel() == Cout)
+    nbytes = conv1d_workspace_size(B, T, Cin, Cout, K, stride, dilation, _dt(x))
+    ws = workspace(nbytes, x.device, "conv1d") if nbytes else None
+    _conv1d_check(_L().tfasr_conv1d_fwd(_p(x), _p(w), _p(bias), _p(scale), _p(shift), _p(addend), _p(out), B, T, int(lead), Cin, Cout, K, stride,
+                                        dilation, 1 if relu else 0, _dt(x), _p(ws), nbytes, _stream()), "conv1d_fwd")
+    return out
+
+
+def conv1d_tail_update(window, nvalid, tail):
+    """tail [B, n, C] <- rows nvalid[b] .. nvalid[b] + n - 1 of window [B, rows, C] (old tail ++ new rows); nvalid [B] int32 device."""
+    B, rows, C = window.shape
+    assert tail.shape[0] == B and tail.shape[2] == C and tail.dtype == window.dtype and nvalid.dtype == torch.int32
+    check(_L().tfasr_conv1d_tail_update(_p(window), _p(nvalid), _p(tail), B, rows, tail.shape[1], C, _dt(window), _stream()), "conv1d_tail_update")
+    return tail

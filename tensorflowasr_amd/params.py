@@ -43,15 +43,19 @@ def param_specs(cfg, head_phys=None, filt_phys=None):
     """[(name, shape, regularized, init)] in forward order. init in {glorot, zeros, ones, embed, orth, lstm_bias}.
     head_phys: physical (stored) head dimension of the attention variables, >= cfg.head_size (ParamStore: zero padding);
     filt_phys: physical channel count of the convolutional subsampling, >= cfg.filters (glorot fans stay the reference's)."""
+    s = []
+
+    def add(name, shape, reg, init, fans=None):
+        s.append((name, tuple(shape), reg, init, fans))
+
+    if getattr(cfg, "encoder", "conformer") == "jasper":
+        jasper_specs(cfg, add)
+        return _tail_specs(cfg, add, s)
     d, H, dh, Cl = cfg.dmodel, cfg.num_heads, cfg.head_size, cfg.filters
     C = filt_phys or Cl
     Kk, V, E, P, J = cfg.kernel_size, cfg.vocab_size, cfg.embed_dim, cfg.rnn_units, cfg.joint_dim
     F2 = -(-(-(-cfg.num_feature_bins // 2)) // 2)
     HD = H * (head_phys or dh)
-    s = []
-
-    def add(name, shape, reg, init, fans=None):
-        s.append((name, tuple(shape), reg, init, fans))
 
     if getattr(cfg, "encoder", "conformer") == "contextnet":
         contextnet_specs(cfg, add)
@@ -96,10 +100,11 @@ def param_specs(cfg, head_phys=None, filt_phys=None):
 
 def _tail_specs(cfg, add, s):
     """prediction + joint networks (shared by every encoder family)"""
-    d, V, E, P, J = cfg.dmodel, cfg.vocab_size, cfg.embed_dim, cfg.rnn_units, cfg.joint_dim
+    d, V = cfg.dmodel, cfg.vocab_size
     if getattr(cfg, "head", "transducer") == "ctc":  # ConformerDecoder (models/ctc/conformer.py:21-47): Dense(vocab_size) "logits"
         add("dec/logits/w", (d, V), True, "glorot"); add("dec/logits/b", (V,), False, "zeros")
         return s
+    E, P, J = cfg.embed_dim, cfg.rnn_units, cfg.joint_dim
     add("pred/emb", (V, E), True, "embed")
     add("pred/lstm/k", (E, 4 * P), True, "glorot")
     add("pred/lstm/rk", (P, 4 * P), False, "orth")
@@ -146,7 +151,59 @@ def contextnet_specs(cfg, add):
         add(p + "fc2/w", (C // 8, C), True, "glorot"); add(p + "fc2/b", (C,), False, "zeros")
 
 
+def jasper_modules(cfg):
+    """Every Conv1D + BatchNormalization pair of JasperEncoder (encoders/jasper.py:264-317) in forward order, under the reference's layer
+    names: [dict(name, cin, cout, K, stride, dilation, residuals)].  `residuals` is None for a plain JasperSubBlock and, for the last
+    sub-block of a block (JasperSubBlockResidual, :112-161), the list of (name, cin, source): its JasperResidual layers (pointwise conv +
+    BatchNorm), `source` = index into the encoder's running residual list (dense: the inputs of blocks 0 .. i; else the block's own)."""
+    mods = []
+    c = int(cfg.num_feature_bins)
+
+    def sub(name, cout, K, stride=1, dilation=1, residuals=None):
+        nonlocal c
+        mods.append(dict(name=name, cin=c, cout=int(cout), K=int(K), stride=int(stride), dilation=int(dilation), residuals=residuals))
+        c = int(cout)
+
+    sub("enc/first_block", cfg.first_additional_block_channels, cfg.first_additional_block_kernels, cfg.first_additional_block_strides,
+        cfg.first_additional_block_dilation)
+    inputs = []  # channel counts of the block inputs so far
+    n = int(cfg.nsubblocks)
+    for i, (ch, K) in enumerate(zip(cfg.block_channels, cfg.block_kernels)):
+        p = f"enc/block_{i}/"
+        inputs.append(c)
+        for j in range(n - 1):
+            sub(p + f"subordinate_{j}", ch, K)
+        srcs = list(range(i + 1)) if cfg.dense else [i]
+        last = p + f"subordinate_{n - 1}"
+        sub(last, ch, K, residuals=[(f"{last}/residual_{r}", inputs[src], src) for r, src in enumerate(srcs)])
+    sub("enc/second_block", cfg.second_additional_block_channels, cfg.second_additional_block_kernels, cfg.second_additional_block_strides,
+        cfg.second_additional_block_dilation)
+    sub("enc/third_block", cfg.third_additional_block_channels, cfg.third_additional_block_kernels, cfg.third_additional_block_strides,
+        cfg.third_additional_block_dilation)
+    return mods
+
+
+def jasper_specs(cfg, add):
+    """keras Conv1D: glorot-uniform kernel [K, Cin, Cout] (fans K Cin, K Cout), zero bias; the l2 regulariser covers the kernels and the
+    BatchNorm gamma / beta (encoders/jasper.py:45-53)."""
+    def pair(conv, bn, K, ci, co):
+        add(conv + "/w", (K, ci, co), True, "glorot", (K * ci, K * co))
+        add(conv + "/b", (co,), False, "zeros")
+        add(bn + "/b", (co,), True, "zeros")
+        add(bn + "/g", (co,), True, "ones")
+
+    for m in jasper_modules(cfg):
+        pair(m["name"] + "/conv1d", m["name"] + "/bn", m["K"], m["cin"], m["cout"])
+        for rname, rcin, _src in m["residuals"] or []:
+            pair(rname + "/pointwise_conv1d", rname + "/bn", 1, rcin, m["cout"])
+
+
 def bn_names(cfg):
+    if getattr(cfg, "encoder", "conformer") == "jasper":
+        out = []
+        for m in jasper_modules(cfg):
+            out += [m["name"] + "/bn"] + [r[0] + "/bn" for r in m["residuals"] or []]
+        return out
     if getattr(cfg, "encoder", "conformer") == "contextnet":
         out = []
         for blk in contextnet_modules(cfg):
@@ -221,6 +278,7 @@ class ParamStore:
         self.n = off
         self.names = [x[0] for x in ordered]
         self._views = {}
+        self.epoch = [0]  # bumped whenever the weights change (shared with alias()): caches derived from them compare it
         self.flat = torch.zeros(self.n, dtype=torch.float32, device=device)
         self.grad = torch.zeros(self.n, dtype=torch.float32, device=device)
         self.adam_m = torch.zeros(self.n, dtype=torch.float32, device=device)
@@ -389,6 +447,7 @@ class ParamStore:
                     v.narrow(ax, Cl, Cp - Cl).zero_()
 
     def refresh_shadow(self):
+        self.epoch[0] += 1
         if self.shadow is not self.flat:
             K.cast(self.flat, self.shadow)
 

@@ -78,6 +78,8 @@ class StreamState:
 
 def check_streamable(model):
     c = model.cfg
+    if getattr(c, "encoder", "conformer") == "jasper":
+        return  # causal convolutions only: streams exactly (JasperStreamState)
     if getattr(c, "encoder", "conformer") != "conformer":
         raise ValueError("streaming needs a Conformer encoder: ContextNet's squeeze-and-excite is a mean over the whole utterance")
     if c.chunk_size is None:
@@ -158,6 +160,49 @@ def encode_chunk(state, feats, nframes):
     return x.view(B, C, d), nvalid
 
 
+class JasperStreamState:
+    """Encoder state of `batch_size` Jasper streams: per Conv1D layer with more than one tap, the last (K - 1) * dilation rows of its
+    input, [B, (K - 1) * dilation, Cin] in the compute type (zeros = the causal padding of a stream's start)."""
+
+    def __init__(self, model, batch_size):
+        check_streamable(model)
+        self.model, self.B = model, int(batch_size)
+        self.tails = [torch.zeros(self.B, (m["K"] - 1) * m["dilation"], m["cin"], dtype=model.dtype, device=model.device) if m["K"] > 1 else None
+                      for m in model.layers]
+
+    def _tensors(self):
+        return [t for t in self.tails if t is not None]
+
+    reset, export, load = StreamState.reset, StreamState.export, StreamState.load
+
+
+@torch.no_grad()
+def jasper_encode_chunk(state, feats, nframes):
+    """One encoder step: feats [B, n, F] (compute type, device), nframes [B] feature frames that are real per stream (0 = idle; n; fewer
+    for a stream's last step; even everywhere else when the first block strides by 2) -> (enc [B, ceil(n / factor), dmodel], nvalid [B]
+    int32 device); advances state.  Each layer convolves [tail | rows] with the tail as real left context (tfasr_conv1d_fwd's `lead`),
+    then the tail moves to the last rows that are valid for the stream (tfasr_conv1d_tail_update)."""
+    m = state.model
+    nf = nframes.to(m.device).to(torch.int32) if isinstance(nframes, torch.Tensor) else m._h2d(list(nframes))
+    nf = nf.contiguous()
+    if feats.shape[0] != state.B:
+        raise ValueError(f"encode_chunk takes [B = {state.B}, n, F] feature frames")
+    x, residuals, starts, nv = feats.contiguous(), [], m._block_starts(), nf
+    for li, mod in enumerate(m.layers):
+        if li in starts:
+            residuals.append(x)
+        tail = state.tails[li]
+        if tail is None:
+            x = m._layer_fwd(x, mod, residuals)
+        else:
+            win = torch.cat([tail, x], 1)
+            x = m._layer_fwd(win, mod, residuals, lead=tail.shape[1])
+            K.conv1d_tail_update(win, nv, tail)
+        if mod["stride"] > 1:
+            nv = ((nv + (mod["stride"] - 1)) // mod["stride"]).to(torch.int32).contiguous()
+    return x, nv
+
+
 def check_stream_args(batch_size=1, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
     """The session arguments that need no device to judge -> them as ints.  beam_width 0 = the greedy session; 1 .. 64 = a beam of that
     many hypotheses per stream (the device searches keep a beam in one workgroup's LDS: 64 rows at most)."""
@@ -188,20 +233,39 @@ class StreamingRecognizer:
     Beam memory per stream, with W = beam_width, N = 1 + W * max_frames trie nodes and H = the power of two >= 2 N table slots:
         transducer  12 N + 12 H + W * (4 V + 44 U + 8 J + 12 min(2 W, V - 1) + 28) bytes   (U = rnn_units, J = joint_dim)
         CTC         12 N + 12 H + 24 W + 8 chunk_size * (1 + min(2 W, V - 1)) bytes
-    (W = 10, max_frames = 3000, V = 1000, U = J = 320: about 1.4 MB per stream.)"""
+    (W = 10, max_frames = 3000, V = 1000, U = J = 320: about 1.4 MB per stream.)
 
-    def __init__(self, model, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
+    A Jasper model (causal convolutions only) opens the same session through JasperCTC.stream(batch_size, chunk_frames=...): a step is
+    chunk_frames feature frames instead of 4 * chunk_size, its encoder state is JasperStreamState (per layer with K > 1 taps the last
+    (K - 1) * dilation input rows, sum over layers of B * (K - 1) * dilation * Cin elements), and in the CTC beam formula above chunk_size
+    reads chunk_frames / time_reduction_factor."""
+
+    def __init__(self, model, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000, chunk_frames=None):
         batch_size, max_tokens_per_frame, self.beam_width, self.max_frames = check_stream_args(batch_size, max_tokens_per_frame, beam_width,
                                                                                              max_frames)
         self.model = model
         self.enc_model = _twin(model, precision)
-        self.state = StreamState(self.enc_model, batch_size)
         self.B = int(batch_size)
         self.max_tokens_per_frame = int(max_tokens_per_frame)
         c = model.cfg
-        self.C = int(c.chunk_size)
+        self.jasper = getattr(c, "encoder", "conformer") == "jasper"
+        if self.jasper:
+            # a step is `chunk_frames` feature frames -> chunk_frames / factor encoder frames (a stream's last step: ceil of what is left)
+            factor = int(c.time_reduction_factor)
+            self.chunk_frames = int(chunk_frames if chunk_frames is not None else 32)
+            if self.chunk_frames < factor or self.chunk_frames % factor:
+                raise ValueError(f"stream: chunk_frames {self.chunk_frames} must be a positive multiple of the time reduction factor {factor}")
+            self.state = JasperStreamState(self.enc_model, batch_size)
+            self.C = self.chunk_frames // factor
+            self._reduce = lambda t: -(-t // factor)
+        else:
+            if chunk_frames is not None:
+                raise ValueError("stream: chunk_frames belongs to the Jasper session; a Conformer's step is 4 * chunk_size feature frames")
+            self.state = StreamState(self.enc_model, batch_size)
+            self.C = int(c.chunk_size)
+            self.chunk_frames = 4 * self.C
+            self._reduce = lambda t: -(-(-(-t // 2)) // 2)
         self.step, self.flen = int(c.frame_step), int(c.frame_length)
-        self.chunk_frames = 4 * self.C
         self.chunk_samples = self.step * (self.chunk_frames - 1) + self.flen  # samples a full chunk's feature frames cover
         self.ctc = c.head == "ctc"
         self.encoded_log = None  # a list here receives (enc [B, C, d], nvalid host list) of every chunk (callers that want the frames)
@@ -290,7 +354,9 @@ class StreamingRecognizer:
                     nlen[b] = len(seg)
             feats = K.logmel_stream(em._h2d(torch.from_numpy(sig), torch.float32), em._h2d(nlen), em._h2d(torch.from_numpy(self.prev.copy()), torch.float32),
                                     em._h2d(self.has_prev.copy()), self.chunk_frames, window, melw, band, c.frame_step, c.nfft, c.preemphasis,
-                                    c.epsilon, em.dtype)
+                                    c.epsilon, torch.float32 if self.jasper else em.dtype)
+            if self.jasper:
+                feats = em._scale_feats(feats)
             for b in range(B):
                 if take[b]:
                     used = take[b] * self.step
@@ -298,8 +364,8 @@ class StreamingRecognizer:
                         self.prev[b], self.has_prev[b] = self.buf[b][used - 1], 1
                     self.buf[b] = self.buf[b][used:]
                     self.emitted[b] += take[b]
-            enc, nvalid = encode_chunk(self.state, feats, take)
-            nv = [-(-(-(-t // 2)) // 2) for t in take]
+            enc, nvalid = (jasper_encode_chunk if self.jasper else encode_chunk)(self.state, feats, take)
+            nv = [self._reduce(t) for t in take]
             if self.encoded_log is not None:
                 self.encoded_log.append((enc, nv))
             self.chunks_run += 1
@@ -346,7 +412,7 @@ class StreamingRecognizer:
                 take = self.chunk_frames if n >= self.chunk_samples else (min(-(-total // self.step) - emitted, self.chunk_frames) if flush else 0)
                 if take <= 0:
                     break
-                n, emitted, frames = max(n - take * self.step, 0), emitted + take, frames + -(-(-(-take // 2)) // 2)
+                n, emitted, frames = max(n - take * self.step, 0), emitted + take, frames + self._reduce(take)
             if frames > self.max_frames:
                 raise RuntimeError(f"stream {b} would pass max_frames = {self.max_frames} encoder frames ({self.frames[b]} so far, {frames} after "
                                    "this call): reset it, or open the session with a larger max_frames")
