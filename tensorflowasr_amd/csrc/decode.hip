@@ -153,9 +153,10 @@ __global__ __launch_bounds__(256) void decode_update_regs_kernel(
   const int ti = tok_idx[b], fi = frame_idx[b], nfr = nframes[b], ptok = prev_tok[b];
   const int act = active[0];
   int nf = 0;
-  if (mode == 1) nf = per_frame[fi];  // (second round trip, single-utterance variant only)
-  else if (mode == 2) nf = per_frame[b];
+  if (mode == 2) nf = per_frame[b];
   if (!act) return;
+  // (second round trip, single-utterance variant only; behind the test: after the search has ended fi == nframes, one past per_frame)
+  if (mode == 1) nf = per_frame[fi];
   float m = -INFINITY;
 #pragma unroll
   for (int t = 0; t < NV; ++t) m = fmaxf(m, x[t]);
