@@ -963,6 +963,49 @@ int tfasr_conv1d_fwd(const void* x, const void* w, const float* bias, const floa
 int tfasr_conv1d_tail_update(const void* window, const int32_t* nvalid, void* tail, int B, int rows, int tail_rows, int C, int dtype,
                              void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * General strided Conv2D forward, channels-last (csrc/conv2d_gen.hip; declarations added under ABI 44, nothing existing changes): the
+ * DeepSpeech2 encoder's ConvBlock, keras.layers.Conv2D with the inference BatchNorm and the ReLU in its epilogue.
+ *   x [B, T, F, Cin], y [B, To, Fo, Cout];  y[b,t,f,n] = sum_{i,j,c} x[b, t*st + i - pad_t, f*sf + j - pad_f, c] * w[i,j,c,n], reads
+ *   outside the buffer are zeros;  v = (acc + bias[n]) * scale[n] + shift[n] (each of the three f32 [Cout] vectors may be NULL), ReLU when
+ *   relu != 0 - all in f32 before the store.  pad_t, pad_f, To, Fo are the caller's: the padding rule ("same", the reference's "causal")
+ *   is applied on the host (tensorflowasr_amd/kernels.py conv_pad_out).
+ *   w: TFASR_F32 -> the Keras kernel [kh, kw, Cin, Cout] f32;  TFASR_BF16 -> the packed bf16 copy tfasr_conv2d_pack_weight writes
+ *   (tfasr_conv2d_packed_weight_elems bf16 elements; pack once per weight load).
+ * 1 <= kh <= 16, 1 <= kw <= 48, st in {1,2,3}, sf in {1,2}, Cin = 1 or a multiple of 16 up to 128, Cout a multiple of 16 up to 128, To <=
+ * 65535: anything else is UNSUPPORTED (INVALID_VALUE for null / non-positive / misaligned arguments), decided on the host before any
+ * launch.  An output element's value does not depend on B, T or its place in a tile (one tile shape per type, no split reduction).  The
+ * bf16 kernel multiplies the up to 31 elements behind a tap row's window by zero weights: exact for finite inputs.  No workspace is needed
+ * today (the size query answers 0 and needs no device).
+ * tfasr_channel_affine_fwd: y[r,c] = x[r,c] * scale[c] + shift[c], ReLU when relu != 0 (scale / shift f32 [C], may be NULL): an
+ * inference BatchNorm + activation behind a layer that has no epilogue (RowConv1D). */
+int tfasr_conv2d_packed_weight_elems(int kh, int kw, int Cin, int Cout, size_t* elems);
+int tfasr_conv2d_pack_weight(const float* w, void* packed, int kh, int kw, int Cin, int Cout, void* stream);
+int tfasr_conv2d_workspace_size(int B, int T, int F, int To, int Fo, int Cin, int Cout, int kh, int kw, int st, int sf, int pad_t, int pad_f,
+                                int dtype, size_t* bytes);
+int tfasr_conv2d_fwd(const void* x, const void* w, const float* bias, const float* scale, const float* shift, void* y, int B, int T, int F,
+                     int To, int Fo, int Cin, int Cout, int kh, int kw, int st, int sf, int pad_t, int pad_f, int relu, int dtype,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_channel_affine_fwd(const void* x, const float* scale, const float* shift, void* y, long rows, int C, int relu, int dtype,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Inference LSTM recurrence over one or two directions (csrc/lstm_infer.hip; added under ABI 44): keras.layers.LSTM(return_sequences,
+ * zero_output_for_mask=True), alone (ndir 1) or as keras.layers.Bidirectional(merge "concat") (ndir 2).
+ *   xg [B, T, ndir*4P], row stride ld_xg elements: x @ W_d + b_d of every direction side by side;  rk [ndir, P, 4P];  gates i, f, c, o;
+ *   y [B, T, ndir*P], row stride ld_y: direction d writes columns [d*P, (d+1)*P).  Zero initial state.  Direction 0 walks t = 0 .. T-1,
+ *   direction 1 walks t = T-1 .. 0; a step with t >= lengths[b] (NULL: T) carries h and c and emits zeros.  h_last / c_last
+ *   [ndir, B, P] f32 (may be NULL): the state after the last step walked.  Activations and rk in `dtype`.
+ * TFASR_BF16 with B <= 64, P % 32 == 0, P <= 1024 and the grid resident: ONE persistent launch of ndir * P/16 workgroups, each direction
+ * with its own arrival counter and abort word.  Anything else, and every call under tfasr_lstm_set_persist(0) / TFASR_LSTM_PERSIST=0:
+ * the per-step kernels (tfasr_gemm + tfasr_lstm_step_fwd), direction 0 then direction 1.  Never UNSUPPORTED for a legal shape.
+ * workspace: tfasr_lstm_infer_workspace_size bytes (answers without a device), 16-byte aligned.  Its first ndir 64-byte records are the
+ * directions' synchronisation records {count, abort, ...}: after a stream synchronisation abort != 0 means a spin of the persistent
+ * launch timed out (1 s) and the remaining steps of y were overwritten with NaN. */
+int tfasr_lstm_infer_workspace_size(int B, int T, int P, int ndir, int dtype, size_t* bytes);
+int tfasr_lstm_infer_fwd(const void* xg, long ld_xg, const void* rk, const int32_t* lengths, void* y, long ld_y, float* h_last,
+                         float* c_last, int B, int T, int P, int ndir, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

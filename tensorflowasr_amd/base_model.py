@@ -408,4 +408,8 @@ def model_from_config(model_config, device=None, dtype=torch.bfloat16, seed=0, d
         if not hasattr(configs, "contextnet_from_reference"):
             raise NotImplementedError("ContextNet from a reference mapping: use configs.contextnet(alpha=...)")
         return ContextNetTransducer(configs.contextnet_from_reference(conf), device, dtype=dtype, seed=seed, dp=dp)
+    if key == "ctc.deepspeech2.DeepSpeech2":
+        from .deepspeech2 import DeepSpeech2CTC
+
+        return DeepSpeech2CTC(configs.deepspeech2_from_reference(conf), device, dtype=dtype, seed=seed, dp=dp)
     raise NotImplementedError(f"{name}: not on the MI355X hot path (SURVEY.md section 8: Conformer transducer / CTC, ContextNet)")

@@ -99,14 +99,30 @@ def jasper_keras_path(name, *_):
     return {"enc": "encoder/", "dec": "decoder/"}[top] + head[:len(head) - len(layer)] + _JASPER_LEAF[key]
 
 
+_DS2_LEAF = {"w": "kernel", "k": "kernel", "rk": "recurrent_kernel", "g": "gamma", "mm": "moving_mean", "mv": "moving_variance"}
+
+
+def deepspeech2_keras_path(name, *_):
+    """Keras variable path of a DeepSpeech2 tensor (models/ctc/deepspeech2.py:93-120: DeepSpeech2Encoder "encoder", DeepSpeech2Decoder
+    "decoder"; layer names of encoders/deepspeech2.py): enc/rnn_module/block_1/blstm/forward_lstm/rk ->
+    encoder/rnn_module/block_1/blstm/forward_lstm/recurrent_kernel; a `b` is a BatchNormalization's beta or a layer's bias."""
+    top, _, rest = name.partition("/")
+    head, _, leaf = rest.rpartition("/")
+    if top not in ("enc", "dec") or not head or leaf not in ("w", "k", "rk", "b", "g", "mm", "mv"):
+        raise KeyError(f"no Keras path is known for {name!r}")
+    kleaf = ("beta" if head.endswith("/bn") else "bias") if leaf == "b" else _DS2_LEAF[leaf]
+    return {"enc": "encoder/", "dec": "decoder/"}[top] + head + "/" + kleaf
+
+
 def _path_fn(model):
-    return jasper_keras_path if getattr(model.cfg, "encoder", "conformer") == "jasper" else keras_path
+    enc = getattr(model.cfg, "encoder", "conformer")
+    return jasper_keras_path if enc == "jasper" else deepspeech2_keras_path if enc == "deepspeech2" else keras_path
 
 
 def _to_keras_layout(name, a):
     if name.endswith("conv/pw1/w") or name.endswith("conv/pw2/w"):
         return a.reshape(1, *a.shape)            # Conv1D kernel [1, cin, cout]
-    if name.endswith("conv/dw/w"):
+    if name.endswith("conv/dw/w") or name.endswith("rowconv/conv/w"):
         return a.reshape(*a.shape, 1)            # DepthwiseConv1D kernel [K, C, 1]
     return a
 

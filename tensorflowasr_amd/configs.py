@@ -10,13 +10,14 @@ import math
 from dataclasses import dataclass, field
 
 
-def speech_kwargs(sc, log_bases=("e",)):
+def speech_kwargs(sc, log_bases=("e",), feature_types=("log_mel_spectrogram",)):
     """`speech_config` of the reference's YAML (FeatureExtraction.__init__, models/layers/feature_extraction.py:32-130) -> the front-end
     fields of ConformerConfig.  Options the MI355X front end does not implement fail loudly instead of being ignored; the epsilon range
     check is the reference's (feature_extraction.py:113).  log_bases: the values of `log_base` the caller's model handles (the result
-    does not carry the base: a model that accepts "10" reads it from the mapping itself)."""
+    does not carry the base: a model that accepts "10" reads it from the mapping itself).  feature_types: the values of `feature_type` the
+    caller's model handles (likewise not carried)."""
     sc = dict(sc or {})
-    only = {"feature_type": ("log_mel_spectrogram",), "pad_end": (True,), "use_librosa_like_stft": (False,), "log_base": tuple(log_bases),
+    only = {"feature_type": tuple(feature_types), "pad_end": (True,), "use_librosa_like_stft": (False,), "log_base": tuple(log_bases),
             "normalize_signal": (False,), "normalize_zscore": (False,), "normalize_min_max": (False,), "padding": (0,)}
     for k, ok in only.items():
         if k in sc and sc[k] not in ok:
@@ -401,6 +402,214 @@ def jasper_from_reference(config: dict):
             raise NotImplementedError(f"{k}={v!r}: not a keyword of models/ctc/jasper.py:61-92 that is built here")
         kw[k] = v
     return JasperConfig(**kw)
+
+
+# ------------------------------------------------------------------------------------------------------------------ DeepSpeech2 (CTC)
+@dataclass
+class DeepSpeech2Config:
+    """The keyword surface of tensorflow_asr.models.ctc.deepspeech2.DeepSpeech2 (models/ctc/deepspeech2.py:58-89) with `speech_config`
+    flattened as in ConformerConfig.  The defaults are the CLASS's defaults (:63-83); deepspeech2() holds the shipped YAML's values.
+    Inference only: the dropout rates and regularisers are kept for the record and never applied."""
+    # speech_config
+    sample_rate: int = 16000
+    frame_ms: int = 25
+    stride_ms: int = 10
+    nfft: int = 512
+    num_feature_bins: int = 80
+    preemphasis: float = 0.97
+    epsilon: float = 1e-6
+    lower_edge_hertz: float = 0.0
+    upper_edge_hertz: float = 8000.0
+    feature_type: str = "log_mel_spectrogram"
+    # encoder (models/encoders/deepspeech2.py:417-443)
+    conv_type: str = "conv2d"
+    conv_kernels: list = field(default_factory=lambda: [[11, 41], [11, 21], [11, 21]])
+    conv_strides: list = field(default_factory=lambda: [[3, 2], [1, 2], [1, 2]])
+    conv_filters: list = field(default_factory=lambda: [32, 32, 96])
+    conv_padding: str = "same"
+    conv_activation: str = "relu"
+    conv_initializer: str = None
+    rnn_nlayers: int = 5
+    rnn_type: str = "lstm"
+    rnn_units: int = 1024
+    rnn_bidirectional: bool = True
+    rnn_unroll: bool = False
+    rnn_rowconv: int = 0
+    rnn_rowconv_activation: str = "relu"
+    rnn_dropout: float = 0.1
+    rnn_initializer: str = None
+    fc_nlayers: int = 0
+    fc_units: int = 1024
+    fc_activation: str = "relu"
+    fc_dropout: float = 0.1
+    fc_initializer: str = None
+    initializer: str = "glorot_uniform"
+    vocab_size: int = 1000
+    blank: int = 0
+    l2: float = 0.0
+    bias_l2: float = 0.0
+    # what the shared model code reads from every config
+    encoder: str = "deepspeech2"
+    head: str = "ctc"
+    dropout: float = 0.0
+    chunk_size: int = None
+    history_size: int = None
+    time_masking: dict = None
+    freq_masking: dict = None
+    head_size: int = 64   # (no attention: the values only keep ParamStore's head / filter padding off)
+    num_heads: int = 1
+    filters: int = 64
+
+    def __post_init__(self):
+        self.conv_kernels = [[int(v) for v in k] for k in self.conv_kernels]
+        self.conv_strides = [[int(v) for v in k] for k in self.conv_strides]
+        self.conv_filters = [int(v) for v in self.conv_filters]
+        if not len(self.conv_kernels) == len(self.conv_strides) == len(self.conv_filters) >= 1:  # encoders/deepspeech2.py:160
+            raise ValueError("conv_kernels, conv_strides and conv_filters must have one entry per block")
+        if self.conv_type != "conv2d":
+            raise NotImplementedError(f"conv_type={self.conv_type!r}: only conv2d is built")
+        if self.rnn_type != "lstm":
+            raise NotImplementedError(f"rnn_type={self.rnn_type!r}: only lstm is built (no GRU / SimpleRNN recurrence)")
+        for k in ("conv_activation", "fc_activation") + (("rnn_rowconv_activation",) if self.has_rowconv else ()):
+            if str(getattr(self, k)) != "relu":
+                raise NotImplementedError(f"{k}={getattr(self, k)!r}: only relu is built")
+        if self.conv_padding not in ("same", "causal"):
+            raise NotImplementedError(f"conv_padding={self.conv_padding!r}: 'same' or 'causal'")
+        if self.feature_type not in ("log_mel_spectrogram", "spectrogram"):
+            raise NotImplementedError(f"feature_type={self.feature_type!r}: 'log_mel_spectrogram' or 'spectrogram'")
+        if self.feature_type == "spectrogram" and not 1 <= int(self.num_feature_bins) <= self.nfft // 2 + 1:
+            raise NotImplementedError(f"num_feature_bins={self.num_feature_bins}: a spectrogram has at most nfft / 2 + 1 bins")
+        cin = 1
+        for (kh, kw), (st, sf), co in zip(self.conv_kernels, self.conv_strides, self.conv_filters):
+            if not (1 <= kh <= 16 and 1 <= kw <= 48 and st in (1, 2, 3) and sf in (1, 2) and (cin == 1 or (cin % 16 == 0 and cin <= 128))
+                    and co % 16 == 0 and 16 <= co <= 128):
+                raise NotImplementedError(f"conv block kernel {[kh, kw]} strides {[st, sf]} channels {cin}->{co}: the Conv2D kernel takes up to "
+                                          "16 x 48 taps, strides (1..3, 1..2), 1 or a multiple of 16 (<= 128) input channels and a multiple "
+                                          "of 16 (<= 128) filters")
+            cin = co
+        if int(self.rnn_nlayers) < 1 or int(self.rnn_units) < 1 or int(self.rnn_units) % 16:
+            raise NotImplementedError(f"rnn_nlayers={self.rnn_nlayers} rnn_units={self.rnn_units}: at least one layer, units a multiple of 16")
+        if self.has_rowconv and 2 * int(self.rnn_rowconv) + 1 > 32:
+            raise NotImplementedError(f"rnn_rowconv={self.rnn_rowconv}: the depthwise kernel takes up to 32 taps")
+        if int(self.fc_nlayers) > 0 and int(self.fc_units) % 16:
+            raise NotImplementedError(f"fc_units={self.fc_units}: a multiple of 16")
+
+    @property
+    def has_rowconv(self):
+        """encoders/deepspeech2.py:231: RowConv1D only behind a unidirectional recurrence (rnn_rowconv is ignored otherwise)"""
+        return (not self.rnn_bidirectional) and int(self.rnn_rowconv) > 0
+
+    @property
+    def ndir(self):
+        return 2 if self.rnn_bidirectional else 1
+
+    @property
+    def rnn_out(self):
+        return self.ndir * int(self.rnn_units)
+
+    @property
+    def dmodel(self):
+        return int(self.fc_units) if int(self.fc_nlayers) > 0 else self.rnn_out
+
+    @property
+    def frame_length(self):
+        return int(round(self.sample_rate * self.frame_ms / 1000.0))
+
+    @property
+    def frame_step(self):
+        return int(round(self.sample_rate * self.stride_ms / 1000.0))
+
+    @property
+    def time_reduction_factor(self):
+        """encoders/deepspeech2.py:165-181: the product of the blocks' time strides"""
+        f = 1
+        for st, _ in self.conv_strides:
+            f *= st
+        return f
+
+    def conv_shapes(self):
+        """[(kh, kw, cin, cout, st, sf, F_in, F_out)] of the conv blocks, F_out = ceil(F_in / sf) under both padding rules"""
+        out, cin, F = [], 1, int(self.num_feature_bins)
+        for (kh, kw), (st, sf), co in zip(self.conv_kernels, self.conv_strides, self.conv_filters):
+            out.append((kh, kw, cin, co, st, sf, F, -(-F // sf)))
+            cin, F = co, -(-F // sf)
+        return out
+
+    @property
+    def rnn_in(self):
+        """width of the Reshape behind the conv module (merge_two_last_dims: F' * C)"""
+        s = self.conv_shapes()[-1]
+        return s[7] * s[3]
+
+    def encoder_length(self, n):
+        """ConvBlock.call (:110-116): math_util.conv_output_length per block over the TIME stride - ceil(n / st) under both padding rules"""
+        n = int(n)
+        for st, _ in self.conv_strides:
+            n = -(-n // st)
+        return n
+
+
+_DS2_YAML = dict(num_feature_bins=160, feature_type="spectrogram", conv_kernels=[[11, 41], [11, 21]], conv_strides=[[2, 2], [1, 2]],
+                 conv_filters=[32, 32], conv_initializer="he_uniform", rnn_nlayers=5, rnn_units=512, fc_nlayers=1, fc_units=1024,
+                 fc_initializer="he_uniform", l2=0.0005, bias_l2=0.0005,
+                 time_masking=dict(prob=1.0, num_masks=5, mask_factor=-1, p_upperbound=0.05, mask_value=0),
+                 freq_masking=dict(prob=1.0, num_masks=1, mask_factor=27, mask_value=0))
+
+
+def deepspeech2(vocab_size=1000, variant="base", **over):
+    """examples/models/ctc/deepspeech2/base.yml.j2 (2 conv blocks "same", 5 x BiLSTM(512), FC 1024); variant="uni": uni.yml.j2 (causal
+    convolutions, 5 x LSTM(512) each followed by RowConv1D(3))."""
+    kw = dict(_DS2_YAML, vocab_size=vocab_size)
+    if variant == "base":
+        kw.update(conv_padding="same", rnn_bidirectional=True, rnn_rowconv=0, rnn_dropout=0.5, fc_dropout=0.5)
+    elif variant == "uni":
+        kw.update(conv_padding="causal", rnn_bidirectional=False, rnn_rowconv=3, rnn_dropout=0.1, fc_dropout=0.1)
+    else:
+        raise ValueError(f"variant {variant!r}: 'base' or 'uni'")
+    kw.update(over)
+    return DeepSpeech2Config(**kw)
+
+
+def deepspeech2_tiny(vocab_size=29, **over):
+    kw = dict(vocab_size=vocab_size, num_feature_bins=16, feature_type="spectrogram", conv_kernels=[[5, 7], [3, 5]], conv_strides=[[2, 2], [1, 2]],
+              conv_filters=[16, 16], conv_padding="same", rnn_nlayers=2, rnn_units=32, rnn_bidirectional=True, rnn_rowconv=0, fc_nlayers=1,
+              fc_units=64, rnn_dropout=0.0, fc_dropout=0.0)
+    kw.update(over)
+    return DeepSpeech2Config(**kw)
+
+
+def deepspeech2_from_reference(config: dict):
+    """The YAML's `model_config.config` of tensorflow_asr.models.ctc.deepspeech2>DeepSpeech2 (base.yml.j2:3-54) -> DeepSpeech2Config.
+    Options that are not built raise with the option named (DeepSpeech2Config.__post_init__, speech_kwargs); rnn_unroll changes nothing
+    in the reference's arithmetic and is accepted either way."""
+    c = dict(config)
+    sc = dict(c.get("speech_config", {}))
+    aug = (sc.get("augmentation_config") or {}).get("feature_augment", {}) or {}
+
+    def _l2(reg, key):
+        if reg is None:
+            return 0.0
+        if not isinstance(reg, dict) or str(reg.get("class_name", "l2")).lower() != "l2":
+            raise NotImplementedError(f"{key}={reg!r}: only an l2 regulariser is known")
+        return float((reg.get("config") or {}).get("l2", 0.0))
+
+    kw = dict(**speech_kwargs(sc, feature_types=("log_mel_spectrogram", "spectrogram")), feature_type=str(sc.get("feature_type", "log_mel_spectrogram")),
+              l2=_l2(c.get("kernel_regularizer"), "kernel_regularizer"), bias_l2=_l2(c.get("bias_regularizer"), "bias_regularizer"))
+    if c.get("activity_regularizer") is not None:
+        raise NotImplementedError(f"activity_regularizer={c['activity_regularizer']!r}: not built")
+    fields = {f for f in DeepSpeech2Config.__dataclass_fields__}
+    for k, v in c.items():
+        if k in ("speech_config", "kernel_regularizer", "bias_regularizer", "activity_regularizer", "name"):
+            continue
+        if k not in fields or k in ("encoder", "head", "head_size", "num_heads", "filters", "chunk_size", "history_size", "dropout", "l2", "bias_l2",
+                                     "feature_type", "time_masking", "freq_masking"):
+            raise NotImplementedError(f"{k}={v!r}: not a keyword of models/ctc/deepspeech2.py:58-89 that is built here")
+        kw[k] = v
+    if "time_masking" in aug:
+        kw["time_masking"] = dict(aug["time_masking"])
+    if "freq_masking" in aug:
+        kw["freq_masking"] = dict(aug["freq_masking"])
+    return DeepSpeech2Config(**kw)
 
 
 def transformer_schedule(step, dmodel, warmup_steps=10000, scale=2.0, max_lr=None, min_lr=None):

@@ -162,6 +162,7 @@ extern "C" int tfasr_lstm_set_persist(int mode) {
   g_persist_override = mode < 0 ? -1 : (mode ? 1 : 0);
   return prev;
 }
+bool tfasr_lstm_persist_on() { return persist_enabled(); }  // the same switch for the inference recurrence (lstm_infer.hip)
 
 // steps [t0, t1) of the forward recurrence with the per-step kernels (never the persistent launch): what a caller uses to queue the chain
 // in SLICES between other work - the host blocks in hipLaunchKernel once a stream's launch queue holds ~1 ms of work, and while it is

@@ -1651,3 +1651,108 @@ def conv1d_tail_update(window, nvalid, tail):
     assert tail.shape[0] == B and tail.shape[2] == C and tail.dtype == window.dtype and nvalid.dtype == torch.int32
     check(_L().tfasr_conv1d_tail_update(_p(window), _p(nvalid), _p(tail), B, rows, tail.shape[1], C, _dt(window), _stream()), "conv1d_tail_update")
     return tail
+
+
+# ------------------------------------------------------------------------------------------- general Conv2D (csrc/conv2d_gen.hip)
+def _conv2d_check(st, what):
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported(f"{what}: outside 1 <= kh <= 16, 1 <= kw <= 48, time stride 1..3, frequency stride 1 | 2, Cin = 1 or a "
+                                    "multiple of 16 up to 128, Cout a multiple of 16 up to 128 (see include/tfasr_hip.h)")
+    check(st, what)
+
+
+def conv_pad_out(L, k, s, padding):
+    """(left padding, output length) of one axis: "same" as keras (out = ceil(L / s), total = max((out - 1) s + k - L, 0), left = total // 2),
+    "causal" as the reference's Conv2D (layers/convolution.py:132-144: k - 1 zeros in front, then "valid": out = ceil(L / s))."""
+    L, k, s = int(L), int(k), int(s)
+    out = -(-L // s)
+    if padding == "same":
+        return max((out - 1) * s + k - L, 0) // 2, out
+    if padding == "causal":
+        return k - 1, out
+    raise ValueError(f"padding {padding!r}: 'same' or 'causal'")
+
+
+def conv2d_pack_weight(w):
+    """Keras Conv2D kernel [kh, kw, Cin, Cout] f32 (device) -> the packed bf16 copy the MFMA kernel reads (once per weight load)."""
+    kh, kw, Cin, Cout = w.shape
+    n = ctypes.c_size_t(0)
+    _conv2d_check(_L().tfasr_conv2d_packed_weight_elems(kh, kw, Cin, Cout, ctypes.byref(n)), "conv2d_packed_weight_elems")
+    out = torch.empty(n.value, dtype=torch.bfloat16, device=w.device)
+    assert w.dtype == torch.float32
+    _conv2d_check(_L().tfasr_conv2d_pack_weight(_p(w), _p(out), kh, kw, Cin, Cout, _stream()), "conv2d_pack_weight")
+    return out
+
+
+def conv2d_fwd(x, w, shape, bias=None, scale=None, shift=None, relu=False, strides=(1, 1), padding="same", out=None):
+    """Conv2D, channels-last: x [B, T, F, Cin] (f32 | bf16) -> [B, ceil(T / st), ceil(F / sf), Cout]; shape = (kh, kw, Cin, Cout); padding
+    "same" or "causal" on both axes (conv_pad_out).  w: the Keras kernel (f32 activations) or conv2d_pack_weight's copy (bf16
+    activations).  Epilogue (acc + bias) * scale + shift [ReLU] in f32."""
+    kh, kw, Cin, Cout = (int(v) for v in shape)
+    st, sf = (int(v) for v in strides)
+    assert x.dim() == 4 and x.shape[3] == Cin
+    B, T, F = x.shape[:3]
+    (pad_t, To), (pad_f, Fo) = conv_pad_out(T, kh, st, padding), conv_pad_out(F, kw, sf, padding)
+    if out is None:
+        out = torch.empty(B, To, Fo, Cout, dtype=x.dtype, device=x.device)
+    assert w.dtype == x.dtype and out.shape == (B, To, Fo, Cout) and out.dtype == x.dtype
+    want = ctypes.c_size_t(kh * kw * Cin * Cout)
+    if x.dtype != torch.float32:
+        _conv2d_check(_L().tfasr_conv2d_packed_weight_elems(kh, kw, Cin, Cout, ctypes.byref(want)), "conv2d_packed_weight_elems")
+    if w.numel() != want.value:
+        raise _lib.TfasrError(f"conv2d_fwd: the kernel holds {w.numel()} elements, {want.value} expected for {(kh, kw, Cin, Cout)} in {x.dtype}")
+    for v in (bias, scale, shift):
+        assert v is None or (v.dtype == torch.float32 and v.numel() == Cout)
+    if B == 0 or To == 0 or Fo == 0:
+        return out
+    n = ctypes.c_size_t(0)
+    _conv2d_check(_L().tfasr_conv2d_workspace_size(B, T, F, To, Fo, Cin, Cout, kh, kw, st, sf, pad_t, pad_f, _dt(x), ctypes.byref(n)),
+                  "conv2d_workspace_size")
+    ws = workspace(n.value, x.device, "conv2d") if n.value else None
+    _conv2d_check(_L().tfasr_conv2d_fwd(_p(x), _p(w), _p(bias), _p(scale), _p(shift), _p(out), B, T, F, To, Fo, Cin, Cout, kh, kw, st, sf, pad_t,
+                                        pad_f, 1 if relu else 0, _dt(x), _p(ws), n.value, _stream()), "conv2d_fwd")
+    return out
+
+
+def channel_affine_fwd(x, scale=None, shift=None, relu=False, y=None):
+    """y = x * scale[c] + shift[c] over the last axis, ReLU when asked (an inference BatchNorm + activation; f32 vectors)."""
+    rows, C = x.numel() // x.shape[-1], x.shape[-1]
+    if y is None:
+        y = torch.empty_like(x)
+    check(_L().tfasr_channel_affine_fwd(_p(x), _p(scale), _p(shift), _p(y), rows, C, 1 if relu else 0, _dt(x), _stream()), "channel_affine_fwd")
+    return y
+
+
+# ------------------------------------------------------------------------------------------- inference LSTM (csrc/lstm_infer.hip)
+def lstm_infer_workspace_size(B, T, P, ndir=1, dtype=TFASR_F32):
+    n = ctypes.c_size_t(0)
+    check(_L().tfasr_lstm_infer_workspace_size(B, T, P, ndir, dtype, ctypes.byref(n)), "lstm_infer_workspace_size")
+    return n.value
+
+
+def lstm_infer_fwd(xg, rk, lengths=None, ndir=1, y=None, want_state=False, ws=None):
+    """The inference recurrence of one (ndir 1) or two (ndir 2: keras Bidirectional, concat) LSTMs over xg [B, T, ndir * 4P] (input
+    projections of the directions side by side), rk [ndir, P, 4P], lengths [B] int32 (device) or None -> y [B, T, ndir * P]; with
+    want_state also (h_last, c_last) [ndir, B, P] f32.  One persistent launch where the shape allows it, else the per-step kernels
+    (tfasr_lstm_infer_fwd decides).  ws: a uint8 workspace to use (its first ndir * 16 int32 words are the directions' {count, abort}
+    records, read by tests); default: the shared grow-only one."""
+    B, T, G = xg.shape
+    P = G // (4 * ndir)
+    assert G == ndir * 4 * P and rk.numel() == ndir * P * 4 * P and rk.dtype == xg.dtype and xg.is_contiguous()
+    assert lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == B)
+    if y is None:
+        y = torch.empty(B, T, ndir * P, dtype=xg.dtype, device=xg.device)
+    assert y.shape == (B, T, ndir * P) and y.dtype == xg.dtype
+    h_last = c_last = None
+    if want_state:
+        h_last = torch.empty(ndir, B, P, dtype=torch.float32, device=xg.device)
+        c_last = torch.empty(ndir, B, P, dtype=torch.float32, device=xg.device)
+    if B == 0 or T == 0:
+        return (y, h_last, c_last) if want_state else y
+    nbytes = lstm_infer_workspace_size(B, T, P, ndir, _dt(xg))
+    if ws is None:
+        ws = workspace(nbytes, xg.device, "lstm_infer")
+    assert ws.numel() >= nbytes
+    check(_L().tfasr_lstm_infer_fwd(_p(xg), G, _p(rk), _p(lengths), _p(y), ndir * P, _p(h_last), _p(c_last), B, T, P, ndir, _dt(xg), _p(ws),
+                                    ws.numel(), _stream()), "lstm_infer_fwd")
+    return (y, h_last, c_last) if want_state else y

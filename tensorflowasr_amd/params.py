@@ -51,6 +51,9 @@ def param_specs(cfg, head_phys=None, filt_phys=None):
     if getattr(cfg, "encoder", "conformer") == "jasper":
         jasper_specs(cfg, add)
         return _tail_specs(cfg, add, s)
+    if getattr(cfg, "encoder", "conformer") == "deepspeech2":
+        deepspeech2_specs(cfg, add)
+        return _tail_specs(cfg, add, s)
     d, H, dh, Cl = cfg.dmodel, cfg.num_heads, cfg.head_size, cfg.filters
     C = filt_phys or Cl
     Kk, V, E, P, J = cfg.kernel_size, cfg.vocab_size, cfg.embed_dim, cfg.rnn_units, cfg.joint_dim
@@ -198,7 +201,55 @@ def jasper_specs(cfg, add):
             pair(rname + "/pointwise_conv1d", rname + "/bn", 1, rcin, m["cout"])
 
 
+def deepspeech2_modules(cfg):
+    """The layers of DeepSpeech2Encoder (encoders/deepspeech2.py:446-484) in forward order under the reference's layer names:
+    dict(convs=[dict(name, kh, kw, cin, cout, st, sf)], rnns=[dict(name, din, P, dirs=[prefix per direction], rowconv=prefix | None, K)],
+    fcs=[dict(name, din, dout)])."""
+    convs = [dict(name=f"enc/conv_module/block_{i}", kh=kh, kw=kw, cin=ci, cout=co, st=st, sf=sf)
+             for i, (kh, kw, ci, co, st, sf, _fi, _fo) in enumerate(cfg.conv_shapes())]
+    rnns, din, P = [], cfg.rnn_in, int(cfg.rnn_units)
+    for i in range(int(cfg.rnn_nlayers)):
+        p = f"enc/rnn_module/block_{i}/"
+        dirs = [p + "blstm/forward_lstm", p + "blstm/backward_lstm"] if cfg.rnn_bidirectional else [p + "lstm"]
+        rnns.append(dict(name=p[:-1], din=din, P=P, dirs=dirs, rowconv=p + "rowconv" if cfg.has_rowconv else None,
+                         K=2 * int(cfg.rnn_rowconv) + 1))
+        din = cfg.rnn_out
+    fcs = []
+    for i in range(int(cfg.fc_nlayers)):
+        fcs.append(dict(name=f"enc/fc_module/block_{i}", din=din, dout=int(cfg.fc_units)))
+        din = int(cfg.fc_units)
+    return dict(convs=convs, rnns=rnns, fcs=fcs)
+
+
+def deepspeech2_specs(cfg, add):
+    """keras Conv2D kernel [kh, kw, Cin, Cout]; LSTM kernel [Din, 4P], recurrent_kernel [P, 4P], bias [4P] (unit forget bias); DepthwiseConv1D
+    kernel [K, C] without bias; Dense kernels.  The regularisers cover kernels and BatchNorm gamma / beta (encoders/deepspeech2.py:84-101)."""
+    m = deepspeech2_modules(cfg)
+    for c in m["convs"]:
+        fan = c["kh"] * c["kw"]
+        add(c["name"] + "/conv2d/w", (c["kh"], c["kw"], c["cin"], c["cout"]), True, "glorot", (fan * c["cin"], fan * c["cout"]))
+        add(c["name"] + "/conv2d/b", (c["cout"],), False, "zeros")
+        add(c["name"] + "/bn/b", (c["cout"],), True, "zeros")
+        add(c["name"] + "/bn/g", (c["cout"],), True, "ones")
+    for r in m["rnns"]:
+        for d in r["dirs"]:
+            add(d + "/k", (r["din"], 4 * r["P"]), True, "glorot")
+            add(d + "/rk", (r["P"], 4 * r["P"]), False, "orth")
+            add(d + "/b", (4 * r["P"],), False, "lstm_bias")
+        if r["rowconv"]:
+            C = r["P"]
+            add(r["rowconv"] + "/conv/w", (r["K"], C), True, "glorot", (r["K"] * C, r["K"]))
+            add(r["rowconv"] + "/bn/b", (C,), True, "zeros")
+            add(r["rowconv"] + "/bn/g", (C,), True, "ones")
+    for f in m["fcs"]:
+        add(f["name"] + "/fc/w", (f["din"], f["dout"]), True, "glorot")
+        add(f["name"] + "/fc/b", (f["dout"],), False, "zeros")
+
+
 def bn_names(cfg):
+    if getattr(cfg, "encoder", "conformer") == "deepspeech2":
+        m = deepspeech2_modules(cfg)
+        return [c["name"] + "/bn" for c in m["convs"]] + [r["rowconv"] + "/bn" for r in m["rnns"] if r["rowconv"]]
     if getattr(cfg, "encoder", "conformer") == "jasper":
         out = []
         for m in jasper_modules(cfg):
