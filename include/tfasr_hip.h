@@ -1006,6 +1006,26 @@ int tfasr_lstm_infer_workspace_size(int B, int T, int P, int ndir, int dtype, si
 int tfasr_lstm_infer_fwd(const void* xg, long ld_xg, const void* rk, const int32_t* lengths, void* y, long ld_y, float* h_last,
                          float* c_last, int B, int T, int P, int ndir, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Plain (absolute-position) scaled dot-product attention, fused forward (csrc/attn_plain.hip; added under ABI 44): the attention of the
+ * Transformer encoder (multihead_attention.py:216-423, `encoder_mha_type: mha`).  qkv [B*T, 3*H*dh] (fused projection output, q|k|v
+ * column blocks, as tfasr_relattn_fused_fwd reads it), out [B*T, H*dh], lse [B,H,T] f32 or NULL; nothing of size T x T is written.
+ *   score = scale * q.k;  mask[b,i,j] = (i < lengths[b]) AND (causal: j <= i) AND (window, as tfasr_relattn_fused_fwd: query i sees keys
+ *   [max(0, c - hist), min(T, c + chunk)), c = floor(i / chunk) * chunk; chunk <= 0: off; hist < 0: unlimited history).
+ * Keys are never masked by length.  A masked score is REPLACED by -1e9 (general.py:25-41): a valid query row gives its masked keys exactly
+ * zero probability; a padded query row (use_mask and i >= lengths[b]) attends uniformly over ALL T keys whatever the causal / window
+ * mask says (lse = log T), and key blocks outside a query block's windows are skipped only where no row of the block is padded.
+ * bf16: MFMA kernel, dh = 64 | 128, 16-byte aligned pointers.  f32: FMA kernel, dh % 16 == 0 and dh <= 128.  Anything else:
+ * TFASR_STATUS_UNSUPPORTED, nothing launched.
+ *
+ * tfasr_add_pe (csrc/elementwise.hip): y[b,t,:] = x[b,t,:] + (t < lengths[b] ? pe[t,:] : 0), SinusoidalPositionalEncoding.call
+ * (positional_encoding.py:69-85); pe [T, d] f32, lengths may be NULL (every frame valid), d % 8 == 0, y may alias x.
+ * ---------------------------------------------------------------------------------------------- */
+int tfasr_attn_plain_fwd(const void* qkv, const int32_t* lengths, void* out, float* lse /* may be NULL */,
+                         int B, int H, int T, int dh, float scale, int use_mask, int causal, int chunk, int hist,
+                         int dtype, void* stream);
+int tfasr_add_pe(const void* x, const float* pe, const int32_t* lengths, void* y, int B, int T, int d, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

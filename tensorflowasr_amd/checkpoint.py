@@ -114,9 +114,32 @@ def deepspeech2_keras_path(name, *_):
     return {"enc": "encoder/", "dec": "decoder/"}[top] + head + "/" + kleaf
 
 
+_TRANSFORMER_LEAF = {"w": "kernel", "b": "bias", "g": "gamma", "mm": "moving_mean", "mv": "moving_variance"}
+_TRANSFORMER_MHSA = {"q": "query", "k": "key", "v": "value", "o": "attention_output"}
+
+
+def transformer_keras_path(name, *_):
+    """Keras variable path of a Transformer tensor of ParamStore.export_keras() (q / k / v already split; models/ctc/transformer.py:88-117:
+    TransformerEncoder "encoder", TransformerDecoder "decoder"; layer names of encoders/transformer.py and layers/subsampling.py):
+    enc/block_1/mhsa/q/w -> encoder/block_1/mhsa/query/kernel.  The prediction / joint variables of the transducer keep the Conformer
+    transducer's paths (base_transducer.py)."""
+    if name.startswith(("pred/", "joint/")):
+        return _TAIL[name]
+    top, _, rest = name.partition("/")
+    head, _, leaf = rest.rpartition("/")
+    if top not in ("enc", "dec") or not head or leaf not in _TRANSFORMER_LEAF:
+        raise KeyError(f"no Keras path is known for {name!r}")
+    parent, _, layer = head.rpartition("/")
+    if parent.endswith("/mhsa") and layer in _TRANSFORMER_MHSA:
+        head = parent + "/" + _TRANSFORMER_MHSA[layer]
+    norm = layer.startswith(("bn_", "ln_"))
+    kleaf = "beta" if (leaf == "b" and norm) else _TRANSFORMER_LEAF[leaf]
+    return {"enc": "encoder/", "dec": "decoder/"}[top] + head + "/" + kleaf
+
+
 def _path_fn(model):
     enc = getattr(model.cfg, "encoder", "conformer")
-    return jasper_keras_path if enc == "jasper" else deepspeech2_keras_path if enc == "deepspeech2" else keras_path
+    return {"jasper": jasper_keras_path, "deepspeech2": deepspeech2_keras_path, "transformer": transformer_keras_path}.get(enc, keras_path)
 
 
 def _to_keras_layout(name, a):

@@ -612,6 +612,210 @@ def deepspeech2_from_reference(config: dict):
     return DeepSpeech2Config(**kw)
 
 
+# ------------------------------------------------------------------------------------------------------------------ Transformer (CTC / transducer)
+@dataclass
+class TransformerConfig:
+    """The keyword surface of tensorflow_asr.models.ctc.transformer.Transformer (models/ctc/transformer.py:56-87) and
+    tensorflow_asr.models.transducer.transformer.Transformer (models/transducer/transformer.py:21-67) with `speech_config` flattened as in
+    ConformerConfig and the `encoder_` prefix dropped.  The defaults are the shipped examples/models/ctc/transformer/base.yml.j2 (which says
+    `mha`; the classes' own default `relmha` is not built).  Inference only: the dropout rate is kept for the record and never applied."""
+    # speech_config
+    sample_rate: int = 16000
+    frame_ms: int = 25
+    stride_ms: int = 10
+    nfft: int = 512
+    num_feature_bins: int = 80
+    preemphasis: float = 0.97
+    epsilon: float = 1e-6
+    lower_edge_hertz: float = 0.0
+    upper_edge_hertz: float = 8000.0
+    # encoder (models/encoders/transformer.py:196-222)
+    sub_filters: list = field(default_factory=lambda: [512, 512])   # encoder_subsampling.filters (conv2d, 3x3 stride-2 causal blocks, relu)
+    sub_norm: str = "batch"                                         # encoder_subsampling.norms: both "batch" or both "none"
+    dmodel: int = 512
+    dff: int = 1024
+    num_blocks: int = 6
+    head_size: int = 128
+    num_heads: int = 4
+    mha_type: str = "mha"
+    interleave_relpe: bool = True
+    use_attention_causal_mask: bool = False
+    use_attention_auto_mask: bool = True
+    residual_factor: float = 1.0
+    norm_position: str = "post"
+    pwffn_activation: str = "relu"
+    dropout: float = 0.1
+    chunk_size: int = None
+    history_size: int = None
+    # model head: "ctc" (TransformerDecoder: one Dense(vocab) "logits") or "transducer" (prediction + joint networks, base_transducer.py)
+    head: str = "ctc"
+    embed_dim: int = 512
+    rnn_units: int = 320
+    joint_dim: int = 1024
+    prediction_layer_norm: bool = True
+    vocab_size: int = 1000
+    blank: int = 0
+    l2: float = 1e-6
+    # what the shared model code reads from every config
+    encoder: str = "transformer"
+    time_masking: dict = None
+    freq_masking: dict = None
+
+    def __post_init__(self):
+        self.sub_filters = [int(v) for v in self.sub_filters]
+        if len(self.sub_filters) != 2 or any(c <= 0 or c % 8 for c in self.sub_filters):
+            raise NotImplementedError(f"encoder_subsampling.filters={self.sub_filters}: two 3x3 stride-2 blocks, filters a multiple of 8")
+        if self.sub_norm not in ("batch", "none"):
+            raise NotImplementedError(f"encoder_subsampling.norms={self.sub_norm!r}: 'batch' or 'none'")
+        if self.mha_type != "mha":
+            raise NotImplementedError(f"encoder_mha_type={self.mha_type!r}: only mha (plain attention over absolute positions) is built in this encoder")
+        if self.norm_position not in ("post", "pre"):
+            raise NotImplementedError(f"encoder_norm_position={self.norm_position!r}: 'post' or 'pre'")
+        if self.pwffn_activation != "relu":
+            raise NotImplementedError(f"encoder_pwffn_activation={self.pwffn_activation!r}: only relu is built")
+        if self.head not in ("ctc", "transducer"):
+            raise ValueError(f"head {self.head!r}: 'ctc' or 'transducer'")
+        if (self.chunk_size is None) != (self.history_size is None):  # multihead_attention.py:342 needs both
+            self.chunk_size = self.history_size = None
+        if self.chunk_size is not None and int(self.chunk_size) < 1:
+            raise ValueError("encoder_chunk_size must be positive")
+        d, dh, dff = int(self.dmodel), int(self.head_size), int(self.dff)
+        if dh % 16 or dh > 128 or dh < 16:
+            raise NotImplementedError(f"encoder_head_size={dh}: the plain-attention kernels take a multiple of 16 up to 128 (64 | 128 in bf16)")
+        if d % 16 or dff % 16 or d < 16:
+            raise NotImplementedError(f"encoder_dmodel={d} encoder_dff={dff}: multiples of 16")
+        if int(self.num_blocks) < 1 or int(self.num_heads) < 1:
+            raise ValueError("encoder_num_blocks and encoder_num_heads must be positive")
+
+    @property
+    def filters(self):  # (ParamStore's filter padding reads it; nothing is padded here)
+        return self.sub_filters[0]
+
+    @property
+    def sub_freq(self):
+        """frequency bins behind the two stride-2 blocks"""
+        return -(-(-(-int(self.num_feature_bins) // 2)) // 2)
+
+    @property
+    def frame_length(self):
+        return int(round(self.sample_rate * self.frame_ms / 1000.0))
+
+    @property
+    def frame_step(self):
+        return int(round(self.sample_rate * self.stride_ms / 1000.0))
+
+    @property
+    def time_reduction_factor(self):
+        return 4
+
+    def encoder_length(self, n):
+        """Conv2dSubsampling.call (subsampling.py:218-230): math_util.conv_output_length "causal" per block = ceil(n / 2) twice"""
+        return -(-(-(-int(n) // 2)) // 2)
+
+
+def transformer(vocab_size=1000, head="ctc", streaming=False, **over):
+    """examples/models/ctc/transformer/base.yml.j2 (d 512, 6 blocks, 4 heads of 128, dff 1024, post-norm, mha); streaming=True:
+    base-streaming.yml.j2 (chunk 16, history 64).  head="rnnt": the same encoder under the transducer class with its constructor's
+    prediction / joint defaults (models/transducer/transformer.py:45-60; the reference ships no YAML for it)."""
+    if head not in ("ctc", "rnnt", "transducer"):
+        raise ValueError(f"head {head!r}: 'ctc' or 'rnnt'")
+    kw = dict(vocab_size=vocab_size, head="ctc" if head == "ctc" else "transducer",
+              time_masking=dict(prob=1.0, num_masks=5, mask_factor=-1, p_upperbound=0.05), freq_masking=dict(prob=1.0, num_masks=2, mask_factor=27))
+    if streaming:
+        kw.update(chunk_size=16, history_size=64)
+    kw.update(over)
+    return TransformerConfig(**kw)
+
+
+def transformer_tiny(vocab_size=29, head="ctc", **over):
+    kw = dict(vocab_size=vocab_size, head="ctc" if head == "ctc" else "transducer", num_feature_bins=16, sub_filters=[16, 16], dmodel=64, dff=128,
+              num_blocks=2, head_size=64, num_heads=2, dropout=0.0, embed_dim=24, rnn_units=24, joint_dim=40)
+    kw.update(over)
+    return TransformerConfig(**kw)
+
+
+_TRANSFORMER_KEYS = {  # constructor keyword -> field, of both reference classes
+    "encoder_dmodel": "dmodel", "encoder_dff": "dff", "encoder_num_blocks": "num_blocks", "encoder_head_size": "head_size",
+    "encoder_num_heads": "num_heads", "encoder_mha_type": "mha_type", "encoder_interleave_relpe": "interleave_relpe",
+    "encoder_use_attention_causal_mask": "use_attention_causal_mask", "encoder_use_attention_auto_mask": "use_attention_auto_mask",
+    "encoder_residual_factor": "residual_factor", "encoder_norm_position": "norm_position", "encoder_pwffn_activation": "pwffn_activation",
+    "encoder_dropout": "dropout", "encoder_history_size": "history_size", "encoder_chunk_size": "chunk_size",
+    "prediction_embed_dim": "embed_dim", "prediction_rnn_units": "rnn_units", "prediction_layer_norm": "prediction_layer_norm",
+    "joint_dim": "joint_dim", "vocab_size": "vocab_size", "blank": "blank",
+}
+_TRANSFORMER_ONLY = {  # keywords that change the network and are built for one value only
+    "encoder_memory_length": (None,), "encoder_trainable": (True,), "decoder_trainable": (True,), "bias_regularizer": (None,),
+    "activity_regularizer": (None,), "prediction_label_encode_mode": ("embedding",), "prediction_num_rnns": (1,),
+    "prediction_rnn_type": ("lstm",), "prediction_projection_units": (0,), "prediction_trainable": (True,), "joint_activation": ("tanh",),
+    "prejoint_encoder_linear": (True,), "prejoint_prediction_linear": (True,), "postjoint_linear": (False,), "joint_mode": ("add",),
+    "joint_trainable": (True,),
+}
+_TRANSFORMER_IGNORED = ("name", "speech_config", "encoder_subsampling", "kernel_regularizer",
+                        # change nothing in the inference arithmetic of the mha encoder: relmha's own causal switch, the attention
+                        # implementation hint, keras' LSTM implementation / unroll switches
+                        "encoder_mha_causal", "encoder_flash_attention", "prediction_rnn_implementation", "prediction_rnn_unroll")
+
+
+def transformer_from_reference(config: dict, head="ctc", class_name: str = None):
+    """The YAML's `model_config.config` of tensorflow_asr.models.ctc.transformer>Transformer (base.yml.j2:3-50) or of the transducer class
+    -> TransformerConfig.  A keyword the mapping omits takes the CLASS's default (so an mha model must say `encoder_mha_type: mha`, as the
+    shipped files do).  Every keyword is mapped or raises NotImplementedError with its name."""
+    c = dict(config)
+    if class_name is not None:
+        head = "ctc" if ".ctc." in class_name else "rnnt"
+    if head not in ("ctc", "rnnt", "transducer"):
+        raise ValueError(f"head {head!r}: 'ctc' or 'rnnt'")
+    ctc = head == "ctc"
+    sc = dict(c.get("speech_config", {}))
+    aug = (sc.get("augmentation_config") or {}).get("feature_augment", {}) or {}
+    for k, ok in _TRANSFORMER_ONLY.items():
+        if k in c and c[k] not in ok:
+            raise NotImplementedError(f"{k}={c[k]!r}: only {ok} is built")
+    if not ctc and "prediction_layer_norm" in c and not c["prediction_layer_norm"]:
+        raise NotImplementedError("prediction_layer_norm=False: the transducer's prediction network ends in a LayerNorm here")
+    sub = dict(c.get("encoder_subsampling") or {})
+    stype = sub.pop("type", None)
+    if stype != "conv2d":
+        raise NotImplementedError(f"encoder_subsampling.type={stype!r}: only conv2d is built (not vgg / conv1d)")
+    if "filters" not in sub:
+        raise ValueError("encoder_subsampling.filters is required (subsampling.py:166)")
+
+    def _pairs(v):
+        return [list(x) if isinstance(x, (list, tuple)) else [x, x] for x in v]
+
+    # keys the mapping omits take Conv2dSubsampling's own defaults (subsampling.py:166-171)
+    kernels, strides = _pairs(sub.pop("kernels", [[3, 3], [3, 3]])), _pairs(sub.pop("strides", [[2, 1], [2, 1]]))
+    paddings, norms = [str(v) for v in sub.pop("paddings", ["causal", "causal"])], [str(v) for v in sub.pop("norms", ["none", "none"])]
+    acts = [str(v) for v in sub.pop("activations", ["relu", "relu"])]
+    filters = list(sub.pop("filters"))
+    if sub:
+        raise NotImplementedError(f"encoder_subsampling.{sorted(sub)[0]}: not a keyword of Conv2dSubsampling")
+    if kernels != [[3, 3], [3, 3]] or strides != [[2, 2], [2, 2]]:
+        raise NotImplementedError(f"encoder_subsampling kernels={kernels} strides={strides}: only two 3x3 stride-2 blocks are built")
+    if paddings != ["causal", "causal"]:
+        raise NotImplementedError(f"encoder_subsampling.paddings={paddings}: only causal")
+    if norms not in (["batch", "batch"], ["none", "none"]):
+        raise NotImplementedError(f"encoder_subsampling.norms={norms}: both 'batch' or both 'none'")
+    if acts != ["relu", "relu"]:
+        raise NotImplementedError(f"encoder_subsampling.activations={acts}: only relu")
+    reg = c.get("kernel_regularizer") or {}
+    if reg and (not isinstance(reg, dict) or str(reg.get("class_name", "l2")).lower() != "l2"):
+        raise NotImplementedError(f"kernel_regularizer={reg!r}: only an l2 regulariser is known")
+    kw = dict(**speech_kwargs(sc), sub_filters=filters, sub_norm=norms[0], head="ctc" if ctc else "transducer", mha_type="relmha",
+              l2=float((reg.get("config") or {}).get("l2", 0.0)) if reg else 0.0)
+    for k, v in c.items():
+        if k in _TRANSFORMER_IGNORED or k in _TRANSFORMER_ONLY:
+            continue
+        if k not in _TRANSFORMER_KEYS or (ctc and k.startswith(("prediction_", "joint_"))):
+            raise NotImplementedError(f"{k}={v!r}: not a keyword of the reference's Transformer class that is built here")
+        kw[_TRANSFORMER_KEYS[k]] = v
+    if "time_masking" in aug:
+        kw["time_masking"] = dict(aug["time_masking"])
+    if "freq_masking" in aug:
+        kw["freq_masking"] = dict(aug["freq_masking"])
+    return TransformerConfig(**kw)
+
+
 def transformer_schedule(step, dmodel, warmup_steps=10000, scale=2.0, max_lr=None, min_lr=None):
     """TransformerSchedule.__call__ (optimizers/schedules.py:28-37)."""
     step = float(step)

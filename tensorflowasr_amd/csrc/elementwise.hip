@@ -983,3 +983,40 @@ extern "C" int tfasr_specaugment(void* x, const int32_t* fmask, const int32_t* t
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
+
+// ---------------------------------------------------------------------------------------- absolute position encoding
+// SinusoidalPositionalEncoding.call (positional_encoding.py:69-85): y[b,t,:] = x[b,t,:] + (t < lengths[b] ? pe[t,:] : 0); pe [T, d] f32
+// (the host builds the table once per T), the sum in f32, rounded once to the storage type.  d % 8 == 0.
+namespace {
+template <typename T>
+__global__ __launch_bounds__(256) void add_pe_kernel(const T* __restrict__ x, const float* __restrict__ pe, const int32_t* __restrict__ lengths,
+                                                     T* __restrict__ y, int B, int Tn, int d) {
+  const int d8 = d / 8;
+  const long n8 = (long)B * Tn * d8;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % d8) * 8;
+    const long row = i / d8;
+    const int t = (int)(row % Tn), b = (int)(row / Tn);
+    float v[8];
+    ld8(x + row * d + c, v);
+    if (!lengths || t < lengths[b]) {
+      float p[8];
+      ld8(pe + (long)t * d + c, p);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] += p[e];
+    }
+    st8(y + row * d + c, v);
+  }
+}
+}  // namespace
+
+extern "C" int tfasr_add_pe(const void* x, const float* pe, const int32_t* lengths, void* y, int B, int T, int d, int dtype, void* stream_) {
+  if (!x || !pe || !y || B <= 0 || T <= 0 || d <= 0 || d % 8 != 0) return TFASR_STATUS_INVALID_VALUE;
+  if ((((uintptr_t)x | (uintptr_t)pe | (uintptr_t)y) & 15) != 0) return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t s = (hipStream_t)stream_;
+  const int grid = flat_grid((long)B * T * d / 8);
+  DISPATCH_T(dtype, TFASR_KLAUNCH(add_pe_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, pe, lengths, (float*)y, B, T, d),
+             TFASR_KLAUNCH(add_pe_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, pe, lengths, (bf16_t*)y, B, T, d));
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}

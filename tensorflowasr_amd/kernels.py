@@ -1756,3 +1756,33 @@ def lstm_infer_fwd(xg, rk, lengths=None, ndir=1, y=None, want_state=False, ws=No
     check(_L().tfasr_lstm_infer_fwd(_p(xg), G, _p(rk), _p(lengths), _p(y), ndir * P, _p(h_last), _p(c_last), B, T, P, ndir, _dt(xg), _p(ws),
                                     ws.numel(), _stream()), "lstm_infer_fwd")
     return (y, h_last, c_last) if want_state else y
+
+
+# ------------------------------------------------------------------------------------------- plain attention (csrc/attn_plain.hip)
+def attn_plain_fwd(qkv, lengths, B, H, T, dh, scale, use_mask=True, causal=False, chunk_size=None, history_size=None, want_lse=False, out=None):
+    """Fused scaled dot-product attention of the Transformer encoder: qkv [B*T, 3*H*dh] (q|k|v column blocks) -> out [B*T, H*dh]
+    (and lse [B, H, T] f32 when asked).  Padded query rows (use_mask, i >= lengths[b]) attend uniformly over all T keys; keys are never
+    masked by length; causal = the lower triangle; chunk_size / history_size = the streaming window of relattn_fused_fwd.
+    bf16: dh 64 | 128; f32: dh % 16 == 0, dh <= 128; anything else raises TfasrUnsupported and launches nothing."""
+    assert qkv.dim() == 2 and qkv.shape == (B * T, 3 * H * dh)
+    if out is None:
+        out = torch.empty(B * T, H * dh, dtype=qkv.dtype, device=qkv.device)
+    assert out.shape == (B * T, H * dh) and out.dtype == qkv.dtype
+    lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device) if want_lse else None
+    ck, hs = _window(chunk_size, history_size)
+    st = _L().tfasr_attn_plain_fwd(_p(qkv), _p(lengths), _p(out), _p(lse), B, H, T, dh, float(scale), 1 if use_mask else 0, 1 if causal else 0,
+                                   ck, hs, _dt(qkv), _stream())
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported(f"attn_plain_fwd: head size {dh} in {qkv.dtype}: bf16 takes 64 | 128, f32 a multiple of 16 up to 128")
+    check(st, "attn_plain_fwd")
+    return (out, lse) if want_lse else out
+
+
+def add_pe(x, pe, lengths=None, y=None):
+    """y[b, t, :] = x[b, t, :] + (t < lengths[b] ? pe[t, :] : 0): x [B, T, d] (f32 | bf16), pe [T, d] f32; y may be x."""
+    B, T, d = x.shape
+    assert pe.dtype == torch.float32 and pe.shape == (T, d)
+    if y is None:
+        y = torch.empty_like(x)
+    check(_L().tfasr_add_pe(_p(x), _p(pe), _p(lengths), _p(y), B, T, d, _dt(x), _stream()), "add_pe")
+    return y

@@ -54,6 +54,9 @@ def param_specs(cfg, head_phys=None, filt_phys=None):
     if getattr(cfg, "encoder", "conformer") == "deepspeech2":
         deepspeech2_specs(cfg, add)
         return _tail_specs(cfg, add, s)
+    if getattr(cfg, "encoder", "conformer") == "transformer":
+        transformer_specs(cfg, add)
+        return _tail_specs(cfg, add, s)
     d, H, dh, Cl = cfg.dmodel, cfg.num_heads, cfg.head_size, cfg.filters
     C = filt_phys or Cl
     Kk, V, E, P, J = cfg.kernel_size, cfg.vocab_size, cfg.embed_dim, cfg.rnn_units, cfg.joint_dim
@@ -246,7 +249,44 @@ def deepspeech2_specs(cfg, add):
         add(f["name"] + "/fc/b", (f["dout"],), False, "zeros")
 
 
+def transformer_modules(cfg):
+    """The layers of TransformerEncoder (encoders/transformer.py:196-311) in forward order under the reference's layer names:
+    dict(convs=[dict(name, bn=name | None, cin, cout)], linear=dict(name, din, dout), blocks=[prefix "enc/block_i"])."""
+    convs, cin = [], 1
+    for i, co in enumerate(cfg.sub_filters):
+        p = f"enc/subsampling/block_{i}/"
+        convs.append(dict(name=p + f"conv_{i}", bn=p + f"bn_{i}" if cfg.sub_norm == "batch" else None, cin=cin, cout=int(co)))
+        cin = int(co)
+    return dict(convs=convs, linear=dict(name="enc/linear", din=cfg.sub_freq * cin, dout=int(cfg.dmodel)),
+                blocks=[f"enc/block_{i}" for i in range(int(cfg.num_blocks))])
+
+
+def transformer_specs(cfg, add):
+    """keras Conv2D kernels [3, 3, Cin, Cout]; the MultiHeadAttention query / key / value kernels [d, H, dh] are stored fused as one
+    [d, 3 H dh] matrix (columns q|k|v) and the output kernel [H, dh, d] as [H dh, d]: what the GEMMs read (export_keras / import_keras
+    convert).  The regulariser covers kernels and the BatchNorm gamma / beta (subsampling.py:184-203, encoders/transformer.py:94-146)."""
+    m = transformer_modules(cfg)
+    d, H, dh, dff = int(cfg.dmodel), int(cfg.num_heads), int(cfg.head_size), int(cfg.dff)
+    for c in m["convs"]:
+        add(c["name"] + "/w", (3, 3, c["cin"], c["cout"]), True, "glorot", (9 * c["cin"], 9 * c["cout"]))
+        add(c["name"] + "/b", (c["cout"],), False, "zeros")
+        if c["bn"]:
+            add(c["bn"] + "/b", (c["cout"],), True, "zeros")
+            add(c["bn"] + "/g", (c["cout"],), True, "ones")
+    add("enc/linear/w", (m["linear"]["din"], d), True, "glorot")
+    add("enc/linear/b", (d,), False, "zeros")
+    for p in m["blocks"]:
+        add(p + "/mhsa/qkv/w", (d, 3 * H * dh), True, "glorot", (d, H * dh)); add(p + "/mhsa/qkv/b", (3 * H * dh,), False, "zeros")
+        add(p + "/mhsa/o/w", (H * dh, d), True, "glorot"); add(p + "/mhsa/o/b", (d,), False, "zeros")
+        add(p + "/ln_1/g", (d,), True, "ones"); add(p + "/ln_1/b", (d,), True, "zeros")
+        add(p + "/pwffn/ffn_1/w", (d, dff), True, "glorot"); add(p + "/pwffn/ffn_1/b", (dff,), False, "zeros")
+        add(p + "/pwffn/ffn_2/w", (dff, d), True, "glorot"); add(p + "/pwffn/ffn_2/b", (d,), False, "zeros")
+        add(p + "/ln_2/g", (d,), True, "ones"); add(p + "/ln_2/b", (d,), True, "zeros")
+
+
 def bn_names(cfg):
+    if getattr(cfg, "encoder", "conformer") == "transformer":
+        return [c["bn"] for c in transformer_modules(cfg)["convs"] if c["bn"]]
     if getattr(cfg, "encoder", "conformer") == "deepspeech2":
         m = deepspeech2_modules(cfg)
         return [c["name"] + "/bn" for c in m["convs"]] + [r["rowconv"] + "/bn" for r in m["rnns"] if r["rowconv"]]
