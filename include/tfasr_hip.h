@@ -117,7 +117,10 @@ int tfasr_rnnt_loss_packed(const void* logits, void* grads, const int32_t* label
  * CTC loss (CtcLoss.call -> tf.nn.ctc_loss(logits_time_major=False, blank_index=0), losses/ctc_loss.py:47-66) and
  * CTC greedy decoding (tf.nn.ctc_greedy_decoder(merge_repeated=True), models/ctc/base_ctc.py:102-124).
  * logits [B,T,V] raw activations, labels [B,U] dense, costs [B] = -log p(labels|x); grads (may alias logits) =
- * grad_scale[b] * dcost_b/dlogits, zero for t >= logit_len[b].  2U+1 <= 1024.
+ * grad_scale[b] * dcost_b/dlogits, zero for t >= logit_len[b].  2U+1 <= 1024, V <= 16384 when grads are asked for.
+ * label_len is read as clamped to [0, U] (a negative length is an empty one), logit_len to [0, T], a label to [0, V-1].
+ * A row without frames costs 0 without labels and +inf with them; a row whose labels do not fit its frames costs +inf;
+ * the gradient of both is zero.
  * greedy: tokens [B,T] (blank padded), tokens_len [B]; workspace_argmax [B*T] int32.
  * ---------------------------------------------------------------------------------------------- */
 int tfasr_ctc_loss_workspace_size(int B, int T, int U, int V, size_t* bytes);

@@ -51,7 +51,7 @@ __global__ void ctc_scan_kernel(const T* __restrict__ logits, const float* __res
                                 int V, int blank, float* __restrict__ alpha, float* __restrict__ beta, float* __restrict__ costs) {
   extern __shared__ float sh[];
   const int b = blockIdx.x, s = threadIdx.x, nthr = blockDim.x;
-  const int Tl = min(logit_len[b], Tm), Ul = min(label_len[b], U);
+  const int Tl = min(logit_len[b], Tm), Ul = max(min(label_len[b], U), 0);  // a negative length is an empty one, as in csrc/align.hip
   const int S = 2 * Ul + 1, Smax = 2 * U + 1;
   float* buf0 = sh;
   float* buf1 = sh + nthr;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const T* logits, T* grads
                                                        const float* __restrict__ costs, int Tm, int U, int V, int blank) {
   extern __shared__ float occ[];  // V floats
   const int b = blockIdx.x / Tm, t = blockIdx.x % Tm;
-  const int Tl = min(logit_len[b], Tm), Ul = min(label_len[b], U);
+  const int Tl = min(logit_len[b], Tm), Ul = max(min(label_len[b], U), 0);  // a negative length is an empty one, as in csrc/align.hip
   const T* row = logits + ((long)b * Tm + t) * V;
   T* out = grads + ((long)b * Tm + t) * V;
   if (t >= Tl) { for (int v = threadIdx.x; v < V; v += blockDim.x) Num<T>::st(out + v, 0.f); return; }

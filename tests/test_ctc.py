@@ -1,4 +1,7 @@
-"""CTC loss / greedy decode: oracle vs brute force (CPU) and HIP kernels vs oracle (GPU)."""
+"""CTC loss / greedy decode: oracle vs brute force (CPU) and HIP kernels vs oracle (GPU).
+
+The GPU case here is the quick check at one wave of lattice states (U <= 25); tests/test_ctc_loss_gpu.py takes the same kernels to
+several waves, production lengths, the grid-stride pass and the edges of V, blank and the lengths."""
 import numpy as np
 import pytest
 import torch
