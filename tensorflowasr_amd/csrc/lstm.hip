@@ -6,7 +6,7 @@
 // (t >= length) the state is carried and the emitted output is zero.
 // The two GEMMs (x@W+b for all steps at once, h_{t-1}@R per step) run on the MFMA GEMM family; these
 // kernels do the per-step gate math, one thread per (batch row, hidden unit).
-#include "common.h"
+#include "lstm_handoff.h"  // recurrent_gemm_args, tfasr_lstm_persist_on
 #include <stdlib.h>
 #include <string.h>
 
@@ -178,10 +178,7 @@ extern "C" int tfasr_lstm_seq_fwd_range(const void* xg, const void* rk, const vo
     const float* cprev = t > 0 ? cseq + (long)(t - 1) * P : c0;
     const long cps = t > 0 ? (long)U1 * P : c0_stride_b;
     if (hprev) {
-      tfasr_gemm_args a;
-      memset(&a, 0, sizeof(a));
-      a.A = hprev; a.B = rk; a.D = hr; a.M = B; a.N = 4 * P; a.K = P; a.lda = hps; a.ldb = 4 * P; a.ldd = 4 * P;
-      a.nb1 = a.nb2 = 1; a.alpha = 1.f; a.beta = 1.f; a.dtype = dtype; a.out_f32 = 1; a.split_k = 1;
+      const tfasr_gemm_args a = recurrent_gemm_args(hprev, hps, rk, hr, B, P, dtype);
       const int st = tfasr_gemm(&a, stream);
       if (st != TFASR_STATUS_SUCCESS) return st;
     }

@@ -12,74 +12,15 @@
 // lstm_persist.hip (workgroup = 16 hidden units, its slice of R in registers, h_{t-1} staged in LDS, z = h R on the matrix cores) with the
 // training buffers removed and each direction a group of its own: own arrival counter, own abort word (two Sync records at the front of
 // the workspace), own hand-off buffer for h_t ([ndir, B, T, P] bf16 behind the records: one slot per step, never reused inside a
-// launch).  The hand-off protocol is lstm_persist.hip's, unchanged (the helpers below are copies): write-through stores of h_t drained
-// by every storing wave, one agent-scope counter, one lane polling relaxed, one agent-scope acquire after the match, every spin bounded by
-// the wall clock, a timed-out workgroup poisons what it owns of the remaining steps with NaN, and the launch is refused unless the
-// whole grid can be resident.  The two directions never wait for each other.
+// launch).  The hand-off protocol is lstm_handoff.h's: write-through stores of h_t drained by every storing wave, one agent-scope
+// counter, one lane polling relaxed, one agent-scope acquire after the match, every spin bounded by the wall clock, a timed-out
+// workgroup poisons what it owns of the remaining steps with NaN, and the launch is refused unless the whole grid can be resident.
+// The two directions never wait for each other.
 // Any other shape or type, and every call while tfasr_lstm_set_persist(0) / TFASR_LSTM_PERSIST=0 is in force: the per-step kernels
 // (recurrent tfasr_gemm + tfasr_lstm_step_fwd), direction 0 queued ascending, then direction 1 descending.
-#include "common.h"
-#include <string.h>
-
-bool tfasr_lstm_persist_on();  // lstm.hip: tfasr_lstm_set_persist / TFASR_LSTM_PERSIST
+#include "lstm_handoff.h"
 
 namespace {
-
-typedef __attribute__((address_space(1))) unsigned int gu32;
-#define AGENT_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-constexpr int PW = 16;          // hidden units per workgroup
-constexpr int MAXKS = 32;       // k-steps of 32 per wave: P <= 1024
-constexpr long long SPIN_TICKS = 100000000LL;  // 1 s of the 100 MHz wall clock
-
-struct Sync { unsigned int count; unsigned int abort; unsigned int pad[14]; };
-
-// ---- copies of lstm_persist.hip's hand-off helpers (kept identical)
-// wait until *count >= target (one lane polls, relaxed); false on timeout / abort
-__device__ __forceinline__ bool wait_count(Sync* s, unsigned target) {
-  bool ok = true;
-  if (threadIdx.x == 0) {
-    const long long t0 = wall_clock64();
-    unsigned spins = 0;
-    gu32* cnt = (gu32*)&s->count;
-    gu32* abt = (gu32*)&s->abort;
-    while (__hip_atomic_load(cnt, AGENT_RLX) < target) {
-      __builtin_amdgcn_s_sleep(2);
-      if ((++spins & 255u) == 0) {
-        if (__hip_atomic_load(abt, AGENT_RLX) != 0u || wall_clock64() - t0 > SPIN_TICKS) {
-          __hip_atomic_store(abt, 1u, AGENT_RLX);
-          ok = false;
-          break;
-        }
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // ONE buffer_inv sc1 after the match: drops this CU's stale L1 lines
-  }
-  return __syncthreads_and(ok ? 1 : 0) != 0;
-}
-
-// every storing wave has drained its write-through stores -> one arrival
-__device__ __forceinline__ void arrive(Sync* s) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add((gu32*)&s->count, 1u, AGENT_RLX);
-}
-
-// write-through (sc1) store of two adjacent bf16 values: visible at device scope once the storing wave has drained its stores
-__device__ __forceinline__ void store_wt2(bf16_t* p, float lo, float hi) {
-  __hip_atomic_store((gu32*)p, pack2_bf16(lo, hi), AGENT_RLX);
-}
-__device__ __forceinline__ void ld2(const bf16_t* p, float& lo, float& hi) {
-  const unsigned v = *reinterpret_cast<const unsigned*>(p);
-  lo = __uint_as_float(v << 16);
-  hi = __uint_as_float(v & 0xffff0000u);
-}
-
-__device__ __forceinline__ void poison_rows(bf16_t* base, long row_stride, long step_stride, int t_lo, int t_hi, int B, int col0, int width) {
-  for (int t = t_lo; t < t_hi; ++t)
-    for (int i = threadIdx.x; i < B * width; i += blockDim.x)
-      base[(long)(i / width) * row_stride + (long)t * step_stride + col0 + i % width] = (bf16_t)0x7FC0;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 template <int MT>  // MT = ceil(B / 16) batch row tiles
@@ -231,28 +172,6 @@ __global__ __launch_bounds__(256) void state_out_kernel(const T* __restrict__ h,
   if (c_last) c_last[i] = c[i];
 }
 
-bool persist_ok(int B, int P, int dtype) { return dtype == TFASR_BF16 && B >= 1 && B <= 64 && P % 32 == 0 && P >= 32 && P <= 32 * MAXKS; }
-
-// copy of lstm_persist.hip's residency check: the workgroups of a launch wait for each other, so ALL of them must be resident at once
-template <typename KERNEL>
-bool grid_fits(KERNEL kernel, int grid, size_t smem) {
-  struct Entry { const void* fn; int dev; size_t smem; int grid; int ok; };
-  static thread_local Entry cache[16];
-  static thread_local int used = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  const void* fn = reinterpret_cast<const void*>(kernel);
-  for (int i = 0; i < used; ++i)
-    if (cache[i].fn == fn && cache[i].dev == dev && cache[i].smem == smem && cache[i].grid == grid) return cache[i].ok != 0;
-  int cus = 0, per_cu = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, smem) != hipSuccess) return false;
-  const int ok = (long)per_cu * cus >= grid ? 1 : 0;
-  Entry& e = cache[used < 16 ? used++ : (used = 1, 0)];
-  e.fn = fn; e.dev = dev; e.smem = smem; e.grid = grid; e.ok = ok;
-  return ok != 0;
-}
-
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // workspace layout: [ndir Sync records | persistent: h hand-off [ndir, B, T, P] bf16 | step route: per direction hr [B, 4P] f32,
@@ -304,18 +223,16 @@ extern "C" int tfasr_lstm_infer_fwd(const void* xg, long ld_xg, const void* rk, 
     const int MT = (B + 15) / 16, Bp = MT * 16;
     const size_t smem = (size_t)Bp * (P * 2 + 16) + (size_t)4 * Bp * PW * 4;
     const dim3 grid(ndir * (P / PW));
-    const bool fits = MT == 1 ? grid_fits(lstm_infer_kernel<1>, grid.x, smem) : MT == 2 ? grid_fits(lstm_infer_kernel<2>, grid.x, smem)
-                      : MT == 3 ? grid_fits(lstm_infer_kernel<3>, grid.x, smem) : grid_fits(lstm_infer_kernel<4>, grid.x, smem);
-    if (fits) {
+    const int st = with_mt(MT, [&](auto mt) -> int {
+      auto kernel = lstm_infer_kernel<decltype(mt)::value>;
+      if (!grid_fits(kernel, grid.x, smem)) { (void)hipGetLastError(); return TFASR_STATUS_UNSUPPORTED; }
       if (hipMemsetAsync(ws + l.sync, 0, (size_t)ndir * sizeof(Sync), s) != hipSuccess) return TFASR_STATUS_EXECUTION_FAILED;
-#define TFASR_LAUNCH(M) TFASR_KLAUNCH(lstm_infer_kernel<M>, grid, dim3(256), smem, s, (const bf16_t*)xg, ld_xg, (const bf16_t*)rk, lengths, \
-                                      (bf16_t*)y, ld_y, (bf16_t*)(ws + l.hbuf), h_last, c_last, B, T, P, (Sync*)(ws + l.sync))
-      switch (MT) { case 1: TFASR_LAUNCH(1); break; case 2: TFASR_LAUNCH(2); break; case 3: TFASR_LAUNCH(3); break; default: TFASR_LAUNCH(4); }
-#undef TFASR_LAUNCH
+      TFASR_KLAUNCH(kernel, grid, dim3(256), smem, s, (const bf16_t*)xg, ld_xg, (const bf16_t*)rk, lengths, (bf16_t*)y, ld_y, (bf16_t*)(ws + l.hbuf),
+                    h_last, c_last, B, T, P, (Sync*)(ws + l.sync));
       TFASR_CHECK_LAUNCH();
       return TFASR_STATUS_SUCCESS;
-    }
-    (void)hipGetLastError();
+    });
+    if (st != TFASR_STATUS_UNSUPPORTED) return st;  // (the grid does not fit: the per-step route)
   }
 
   // per-step route: recurrent GEMM (f32 out) + the cell kernel per step; the state ping-pongs between two [B, P] buffers
@@ -332,10 +249,7 @@ extern "C" int tfasr_lstm_infer_fwd(const void* xg, long ld_xg, const void* rk, 
       const int t = d ? T - 1 - step : step;
       const int cur = step & 1, prv = cur ^ 1;
       if (step > 0) {
-        tfasr_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A = hb[prv]; a.B = rkd; a.D = hr; a.M = B; a.N = 4 * P; a.K = P; a.lda = P; a.ldb = 4 * P; a.ldd = 4 * P;
-        a.nb1 = a.nb2 = 1; a.alpha = 1.f; a.beta = 1.f; a.dtype = dtype; a.out_f32 = 1; a.split_k = 1;
+        const tfasr_gemm_args a = recurrent_gemm_args(hb[prv], P, rkd, hr, B, P, dtype);
         const int st = tfasr_gemm(&a, stream_);
         if (st != TFASR_STATUS_SUCCESS) return st;
       }

@@ -13,73 +13,15 @@
 // Backward (BPTT).  Workgroup j owns the same 16 units: rows u of R (16 x 4P, k-contiguous) in registers (wave q = the k range of
 // gate q), dh / dc carries in registers.  Per step: gather dz_{t+1} [B, 4P] (published by all workgroups) straight into MFMA A
 // fragments, dhr = dz_{t+1} R^T for the owned units (4 partial k ranges summed through LDS), cell backward, publish dz_t.
-// Every spin is bounded by the wall clock; a timeout raises a flag (second word of the caller's 64-byte `sync` record) that makes every
-// workgroup leave - after overwriting what it owns of the remaining steps with NaN (no hang, and no silently wrong result: the step's loss /
-// gradients are NaN); the caller can also check the word after a stream synchronisation.  The launch itself is refused unless the whole
-// grid can be resident at once (`grid_fits`).
+// The hand-off protocol, its timeout / abort / NaN-poisoning rule and the residency check every launch must pass: lstm_handoff.h.
 // Measured (B = 32, U1 = 111, P = 640): 8.7 us per forward step, 13.4 us per backward step - the hand-off itself (drain of the
 // write-through stores, 40 arrivals on one counter, poll, acquire, re-load of the exchanged vector), not the loads' issue order:
 // batching every load of a step in front of its first use changed nothing.
-#include "common.h"
+// The step-range parameters of the two kernels (rk_t, t_begin, t_end) are dead, and stay: without them the MT = 1 instantiations ran 1.0 -
+// 1.6 % slower in three sessions, outside the parent's run-to-run spread (profiles/lstm_persist_refactor_timing.json).
+#include "lstm_handoff.h"
 
 namespace {
-
-typedef __attribute__((address_space(1))) unsigned int gu32;
-#define AGENT_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-constexpr int PW = 16;          // hidden units per workgroup
-constexpr int MAXKS = 32;       // k-steps of 32 per wave: P <= 1024
-constexpr long long SPIN_TICKS = 100000000LL;  // 1 s of the 100 MHz wall clock
-
-struct Sync { unsigned int count; unsigned int abort; unsigned int pad[14]; };
-
-// wait until *count >= target (one lane polls, relaxed); false on timeout / abort
-__device__ __forceinline__ bool wait_count(Sync* s, unsigned target) {
-  bool ok = true;
-  if (threadIdx.x == 0) {
-    const long long t0 = wall_clock64();
-    unsigned spins = 0;
-    gu32* cnt = (gu32*)&s->count;
-    gu32* abt = (gu32*)&s->abort;
-    while (__hip_atomic_load(cnt, AGENT_RLX) < target) {
-      __builtin_amdgcn_s_sleep(2);
-      if ((++spins & 255u) == 0) {
-        if (__hip_atomic_load(abt, AGENT_RLX) != 0u || wall_clock64() - t0 > SPIN_TICKS) {
-          __hip_atomic_store(abt, 1u, AGENT_RLX);
-          ok = false;
-          break;
-        }
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // ONE buffer_inv sc1 after the match: drops this CU's stale L1 lines
-  }
-  return __syncthreads_and(ok ? 1 : 0) != 0;
-}
-
-// every storing wave has drained its write-through stores -> one arrival
-__device__ __forceinline__ void arrive(Sync* s) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add((gu32*)&s->count, 1u, AGENT_RLX);
-}
-
-// write-through (sc1) store of two adjacent bf16 values: visible at device scope once the storing wave has drained its stores
-__device__ __forceinline__ void store_wt2(bf16_t* p, float lo, float hi) {
-  __hip_atomic_store((gu32*)p, pack2_bf16(lo, hi), AGENT_RLX);
-}
-__device__ __forceinline__ void ld2(const bf16_t* p, float& lo, float& hi) {
-  const unsigned v = *reinterpret_cast<const unsigned*>(p);
-  lo = __uint_as_float(v << 16);
-  hi = __uint_as_float(v & 0xffff0000u);
-}
-
-// A timed-out / aborted launch must not pass for a result: the leaving workgroup overwrites what it owns of the REMAINING
-// steps with NaN, so the loss / the gradients of that step are NaN (what the reference's TerminateOnNaN watches) - no host read needed.
-__device__ __forceinline__ void poison_rows(bf16_t* base, long row_stride, long step_stride, int t_lo, int t_hi, int B, int col0, int width) {
-  for (int t = t_lo; t < t_hi; ++t)
-    for (int i = threadIdx.x; i < B * width; i += blockDim.x)
-      base[(long)(i / width) * row_stride + (long)t * step_stride + col0 + i % width] = (bf16_t)0x7FC0;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 template <int MT>  // MT = ceil(B / 16) batch row tiles
@@ -379,35 +321,6 @@ __global__ __launch_bounds__(256) void lstm_persist_bwd_kernel(
   }
 }
 
-bool persist_ok(int B, int P, int dtype) { return dtype == TFASR_BF16 && B >= 1 && B <= 64 && P % 32 == 0 && P >= 32 && P <= 32 * MAXKS; }
-
-// The workgroups of a launch wait for each other, so ALL of them must be resident at once (an ordinary launch gives no such promise):
-// the launch is refused (UNSUPPORTED -> the caller's per-step kernels) unless resident-blocks-per-CU x CUs covers the grid.
-// NECESSARY, NOT SUFFICIENT: the occupancy query knows nothing about kernels of OTHER streams that hold CUs when the launch starts (the
-// encoder beside the prediction network); a workgroup that is not scheduled in time is caught by the kernels' wall-clock bound and abort
-// flag (results poisoned, `sync` word 1 set), never by a hang.
-// The answer depends on the kernel INSTANCE (the MT variants differ in registers, hence in blocks per CU), the device, the LDS size and the
-// grid: a small per-thread table keyed on all four (the function-pointer type is the same for every MT, so a function-local static would
-// be ONE entry shared by all instantiations - ADVICE r04).
-template <typename KERNEL>
-bool grid_fits(KERNEL kernel, int grid, size_t smem) {
-  struct Entry { const void* fn; int dev; size_t smem; int grid; int ok; };
-  static thread_local Entry cache[16];
-  static thread_local int used = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  const void* fn = reinterpret_cast<const void*>(kernel);
-  for (int i = 0; i < used; ++i)
-    if (cache[i].fn == fn && cache[i].dev == dev && cache[i].smem == smem && cache[i].grid == grid) return cache[i].ok != 0;
-  int cus = 0, per_cu = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, smem) != hipSuccess) return false;
-  const int ok = (long)per_cu * cus >= grid ? 1 : 0;
-  Entry& e = cache[used < 16 ? used++ : (used = 1, 0)];  // (full: start over - 16 distinct launch shapes per thread do not occur in one model)
-  e.fn = fn; e.dev = dev; e.smem = smem; e.grid = grid; e.ok = ok;
-  return ok != 0;
-}
-
 // R [P, 4P] -> R^T [4P, P] (bf16), 32 x 32 tiles through LDS: once per sequence, for the per-step forward launches
 
 }  // namespace
@@ -428,16 +341,15 @@ extern "C" int tfasr_lstm_persist_fwd(const void* xg, const void* rk, const void
   const int MT = (B + 15) / 16, Bp = MT * 16;
   const size_t smem = (size_t)Bp * (P * 2 + 16) + (size_t)4 * Bp * PW * 4;
   const dim3 grid(P / PW);
-#define TFASR_LAUNCH(M) TFASR_KLAUNCH(lstm_persist_fwd_kernel<M>, grid, dim3(256), smem, s, (const bf16_t*)xg, (const bf16_t*)rk, (const bf16_t*)h0, \
-                                           h0_stride_b, c0, c0_stride_b, lengths, (bf16_t*)gates, cseq, (bf16_t*)hseq, (bf16_t*)yseq, B, U1, P, (Sync*)sync)
-  const bool fits = MT == 1 ? grid_fits(lstm_persist_fwd_kernel<1>, grid.x, smem) : MT == 2 ? grid_fits(lstm_persist_fwd_kernel<2>, grid.x, smem)
-                    : MT == 3 ? grid_fits(lstm_persist_fwd_kernel<3>, grid.x, smem) : grid_fits(lstm_persist_fwd_kernel<4>, grid.x, smem);
-  if (!fits) { (void)hipGetLastError(); return TFASR_STATUS_UNSUPPORTED; }
-  if (hipMemsetAsync(sync, 0, sizeof(Sync), s) != hipSuccess) return TFASR_STATUS_EXECUTION_FAILED;
-  switch (MT) { case 1: TFASR_LAUNCH(1); break; case 2: TFASR_LAUNCH(2); break; case 3: TFASR_LAUNCH(3); break; default: TFASR_LAUNCH(4); }
-#undef TFASR_LAUNCH
-  TFASR_CHECK_LAUNCH();
-  return TFASR_STATUS_SUCCESS;
+  return with_mt(MT, [&](auto mt) -> int {
+    auto kernel = lstm_persist_fwd_kernel<decltype(mt)::value>;
+    if (!grid_fits(kernel, grid.x, smem)) { (void)hipGetLastError(); return TFASR_STATUS_UNSUPPORTED; }
+    if (hipMemsetAsync(sync, 0, sizeof(Sync), s) != hipSuccess) return TFASR_STATUS_EXECUTION_FAILED;
+    TFASR_KLAUNCH(kernel, grid, dim3(256), smem, s, (const bf16_t*)xg, (const bf16_t*)rk, (const bf16_t*)h0, h0_stride_b, c0, c0_stride_b, lengths,
+                  (bf16_t*)gates, cseq, (bf16_t*)hseq, (bf16_t*)yseq, B, U1, P, (Sync*)sync, (const bf16_t*)nullptr, 0, -1);
+    TFASR_CHECK_LAUNCH();
+    return TFASR_STATUS_SUCCESS;
+  });
 }
 
 extern "C" int tfasr_lstm_persist_bwd(const void* dy, const void* rk, const void* gates, const float* cseq, const int32_t* lengths, void* dz,
@@ -448,14 +360,13 @@ extern "C" int tfasr_lstm_persist_bwd(const void* dy, const void* rk, const void
   const int MT = (B + 15) / 16, Bp = MT * 16;
   const size_t smem = (size_t)4 * Bp * PW * 4;
   const dim3 grid(P / PW);
-#define TFASR_LAUNCH(M) TFASR_KLAUNCH(lstm_persist_bwd_kernel<M>, grid, dim3(256), smem, s, (const bf16_t*)dy, (const bf16_t*)rk, (const bf16_t*)gates, cseq, \
-                                           lengths, (bf16_t*)dz, dh_carry, dc_carry, B, U1, P, (Sync*)sync)
-  const bool fits = MT == 1 ? grid_fits(lstm_persist_bwd_kernel<1>, grid.x, smem) : MT == 2 ? grid_fits(lstm_persist_bwd_kernel<2>, grid.x, smem)
-                    : MT == 3 ? grid_fits(lstm_persist_bwd_kernel<3>, grid.x, smem) : grid_fits(lstm_persist_bwd_kernel<4>, grid.x, smem);
-  if (!fits) { (void)hipGetLastError(); return TFASR_STATUS_UNSUPPORTED; }
-  if (hipMemsetAsync(sync, 0, sizeof(Sync), s) != hipSuccess) return TFASR_STATUS_EXECUTION_FAILED;
-  switch (MT) { case 1: TFASR_LAUNCH(1); break; case 2: TFASR_LAUNCH(2); break; case 3: TFASR_LAUNCH(3); break; default: TFASR_LAUNCH(4); }
-#undef TFASR_LAUNCH
-  TFASR_CHECK_LAUNCH();
-  return TFASR_STATUS_SUCCESS;
+  return with_mt(MT, [&](auto mt) -> int {
+    auto kernel = lstm_persist_bwd_kernel<decltype(mt)::value>;
+    if (!grid_fits(kernel, grid.x, smem)) { (void)hipGetLastError(); return TFASR_STATUS_UNSUPPORTED; }
+    if (hipMemsetAsync(sync, 0, sizeof(Sync), s) != hipSuccess) return TFASR_STATUS_EXECUTION_FAILED;
+    TFASR_KLAUNCH(kernel, grid, dim3(256), smem, s, (const bf16_t*)dy, (const bf16_t*)rk, (const bf16_t*)gates, cseq, lengths, (bf16_t*)dz, dh_carry,
+                  dc_carry, B, U1, P, (Sync*)sync, 0, -1);
+    TFASR_CHECK_LAUNCH();
+    return TFASR_STATUS_SUCCESS;
+  });
 }

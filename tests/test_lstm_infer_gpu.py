@@ -95,6 +95,37 @@ def test_step_route(dev, B, T, P, ndir, dtype):
         K.lstm_set_persist(prev)
 
 
+@pytest.mark.parametrize("B,T,P", [(1, 2, 32),      # MT 1: two workgroups, one k-step, a single hand-off
+                                   (17, 9, 64),     # MT 2: one row into the second batch tile
+                                   (33, 7, 96),     # MT 3: an odd number of k-steps
+                                   (64, 5, 128)])   # MT 4: every row of the last tile live
+def test_persistent_launch_is_the_training_forward(dev, B, T, P):
+    """One direction, zero initial state: the inference kernel is the training forward (csrc/lstm_persist.hip) with the training buffers
+    removed - same fragment loads, staging, MFMA order, gate expressions and roundings - so y, the last carried h and the last c agree
+    bit for bit, and both launches count (P/16) * (T-1) arrivals on the hand-off of csrc/lstm_handoff.h."""
+    xg, rk, lens = (v.to(dev) for v in _case(B, T, P, 1, torch.bfloat16, seed=2000 * B + P))
+    bf = torch.bfloat16
+    gates = torch.empty(B, T, 4 * P, dtype=bf, device=dev)
+    cseq = torch.empty(B, T, P, dtype=torch.float32, device=dev)
+    hseq = torch.empty(B, T, P, dtype=bf, device=dev)
+    yseq = torch.empty(B, T, P, dtype=bf, device=dev)
+    sync = K.lstm_persist_sync(dev)
+    ws = torch.zeros(K.lstm_infer_workspace_size(B, T, P, 1, K._dt(xg)), dtype=torch.uint8, device=dev)
+    prev = K.lstm_set_persist(1)
+    try:
+        y, h_last, c_last = K.lstm_infer_fwd(xg, rk, lens, ndir=1, want_state=True, ws=ws)
+        K.lstm_persist_fwd(xg, rk[0], None, None, lens, gates, cseq, hseq, yseq, sync)
+        torch.cuda.synchronize()
+    finally:
+        K.lstm_set_persist(prev)
+    arrivals = (P // 16) * (T - 1)
+    assert ws[:64].view(torch.int32)[:2].tolist() == [arrivals, 0]  # {count, abort}: the persistent route ran, no wait timed out
+    assert sync[:2].tolist() == [arrivals, 0]
+    assert torch.equal(y, yseq)
+    assert torch.equal(h_last[0], hseq[:, -1].float())
+    assert torch.equal(c_last[0], cseq[:, -1])
+
+
 @pytest.mark.parametrize("ndir", [1, 2])
 def test_shape_outside_the_persistent_range(dev, ndir):
     """B = 65, P = 48: neither fits the persistent kernels; the entry point takes the per-step kernels by itself"""

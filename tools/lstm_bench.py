@@ -1,5 +1,6 @@
 """Time the prediction network's recurrence per direction: persistent kernels (csrc/lstm_persist.hip) vs the step-kernel path.
-    python tools/lstm_bench.py [B U1 P]"""
+    python tools/lstm_bench.py [B U1 P [OUT.jsonl]]     (OUT.jsonl: the persistent kernels' figures are appended as one JSON line)"""
+import json
 import os
 import sys
 import time
@@ -43,6 +44,9 @@ def t(fn, n=20):
 f = t(lambda: K.lstm_persist_fwd(xg, rk, None, None, lens, gates, cseq, hseq, yseq, sync))
 b = t(lambda: K.lstm_persist_bwd(dy, rk, gates, cseq, lens, dz, dhc, dcc, sync))
 print(f"persistent: B={B} U1={U1} P={P}: forward {f:.3f} ms ({f / U1 * 1e3:.2f} us/step), backward {b:.3f} ms ({b / U1 * 1e3:.2f} us/step), timeout flag {int(sync[1])}")
+if len(sys.argv) >= 5:
+    with open(sys.argv[4], "a") as out:
+        out.write(json.dumps({"B": B, "U1": U1, "P": P, "fwd_ms": round(f, 4), "bwd_ms": round(b, 4), "timeout": int(sync[1])}) + "\n")
 os.environ["TFASR_LSTM_PERSIST"] = os.environ.get("TFASR_LSTM_PERSIST", "1")
 print("seq API (TFASR_LSTM_PERSIST=%s): forward %.3f ms, backward %.3f ms" % (
     os.environ["TFASR_LSTM_PERSIST"], t(lambda: K.lstm_seq_fwd(xg, rk, None, None, lens, gates, cseq, hseq, yseq, hr)),
