@@ -206,8 +206,9 @@ __global__ __launch_bounds__(256) void rnnt_stats_finalize_kernel(const float2* 
 // in flight; the lattice threads exchange data through LDS alone (global alpha / beta cells are written, never re-read here).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// grid = (B, 2): y==0 -> alpha (forward), y==1 -> beta (backward). blockDim.x >= U1 (multiple of 64).
-__global__ void rnnt_lattice_kernel(const float* __restrict__ blank_lp, const float* __restrict__ truth_lp,
+// grid = (B, 2): y==0 -> alpha (forward), y==1 -> beta (backward). blockDim.x >= U1 (multiple of 64), up to 1024: the bound is
+// stated, not left to the compiler's default (128 VGPRs, 4 of the 64 ring registers spilled: 20 B of scratch per lane).
+__global__ __launch_bounds__(1024) void rnnt_lattice_kernel(const float* __restrict__ blank_lp, const float* __restrict__ truth_lp,
                                     const int32_t* __restrict__ label_len, const int32_t* __restrict__ logit_len,
                                     const long* __restrict__ cell_off, int Tm, int U1m, float* __restrict__ alpha,
                                     float* __restrict__ beta, float* __restrict__ costs) {
@@ -657,8 +658,8 @@ static int rnnt_impl(const void* logits, void* grads, const int32_t* labels, con
                        truth_lp, label_len, logit_len, cell_off, T, U1, alpha, beta, costs);
   TFASR_CHECK_LAUNCH();
   // gradient as coefficient pass + pure stream (rnnt_grad_apply_kernel) when the workspace has room for the coefficients (older callers
-  // sized it for 5 segments: they keep the one-launch kernel); TFASR_RNNT_GRAD_STREAM=0 forces the one-launch kernel
-  static const bool stream_off = false;
+  // sized it for 5 segments: they keep the one-launch kernel, as do V % 8 != 0 and V > 1024)
+  static const bool stream_off = false;  // A/B probe (compile time): the one-launch kernel
   const bool streamed = grads && !stream_off && (V % 8) == 0 && V <= 1024 && workspace_bytes >= 10 * seg && (dtype == TFASR_F32 || dtype == TFASR_BF16);
   float4* cbuf = coef ? (float4*)coef : (float4*)(ws + 5 * seg);
   int32_t* rlab = (int32_t*)(ws + 9 * seg);
