@@ -11,8 +11,8 @@
  *   - no allocation inside: every scratch buffer is caller-owned, sized by a `*_workspace_size` query;
  *   - every entry returns a tfasr_status_t; `tfasr_status_string` decodes it;
  *   - re-entrant per stream, no assumption about the process-wide current device beyond "the pointers and the stream belong
- *     to the device that is current on this thread".  State the library keeps: (i) the three switches of the table below that it reads itself
- *     (once, function-local statics); (ii) the block executor's internal second stream + events per device (tfasr_block_io.wgrad_slot), the
+ *     to the device that is current on this thread".  State the library keeps: (i) the four switches of the table below that it reads itself
+ *     (once, function-local statics; TFASR_ATTN_BWD_QK at every call, so that one process can compare both routes); (ii) the block executor's internal second stream + events per device (tfasr_block_io.wgrad_slot), the
  *     persistent-LSTM policy (tfasr_lstm_set_persist), and one flag set around a grouped launch that shares the chip with another stream;
  *     (iii) two measurement aids: a host-side launch counter (tfasr_launch_count) and the optional event record of tfasr_block_wgrad_probe -
  *     all of them assume what the rest of the design assumes anyway: ONE host thread queues the launches of a device.  Results never
@@ -23,6 +23,8 @@
  *       TFASR_FFN_FUSED=0        FFModule forward as LayerNorm + two products instead of tfasr_ffn_fused_fwd
  *       TFASR_LSTM_PERSIST=0|1   force the per-step / the persistent LSTM kernels (default: the caller's tfasr_lstm_set_persist policy)
  *       TFASR_DENSE_LN=0         (block executor) Dense data gradient and LayerNorm backward as two launches instead of tfasr_dense_ln_bwd
+ *       TFASR_ATTN_BWD_QK=0|1    (block executor) fused attention backward as tfasr_relattn_fused_bwd_q3 + _bwd_k (0) or as
+ *                                tfasr_relattn_bwd_prep + the one launch of both sides tfasr_relattn_fused_bwd_qk (1)
  *     Read by the Python host (tensorflowasr_amd/, bench.py):
  *       TFASR_LIB=<path>         load another build of this library (same-box A/B of two builds; probe builds)
  *       TFASR_HEAD_PAD=0, TFASR_FILTER_PAD=0   logical head size / subsampling filters instead of the 64-multiples
@@ -451,6 +453,21 @@ int tfasr_relattn_dpext(const void* ds, const void* qv, const int32_t* lengths, 
 int tfasr_relattn_fused_bwd_k(const void* qkv, const void* qu, const void* qv, const void* pext, const int32_t* lengths,
                               const void* dout, const float* lse, const float* dvec, void* dqkv, int B, int H, int T, int dh,
                               float scale, int use_mask, int chunk, int hist, int dtype, void* stream);
+
+/* Fused backward, both sides in ONE launch (csrc/attn_fused.hip relattn_fused_bwd_qk_kernel): tfasr_relattn_bwd_prep, then
+ * tfasr_relattn_fused_bwd_qk, give what tfasr_relattn_fused_bwd_q3 followed by tfasr_relattn_fused_bwd_k give - dq / dk / dv (all three
+ * column blocks of dqkv [B*T, 3*H*dh]), the unskewed ds [B,H,T,lds], qu / qv / dvec bitwise, du / dv / the bias row of dpext up to the order
+ * of their f32 atomics - with the key-side workgroups (longest samples first) filling the slots the query side leaves empty.
+ * _bwd_prep: one pass over q, o, dout that writes qu, qv [B*T, H*dh] (16-byte aligned), dvec [2,B,H,T] (the same rows _bwd_q3 writes: not
+ * those of wholly padded 64-query blocks) and order [B] int32 = the samples by min(lengths, T) descending, ties by index.
+ * _bwd_qk reads them (it writes none of them); tfasr_relattn_dpext follows as after _bwd_q3 / _bwd_k. */
+int tfasr_relattn_bwd_prep(const void* qkv, const float* ubias, const float* vbias, const void* pext, const int32_t* lengths,
+                           const void* o, const void* dout, void* qu, void* qv, float* dvec, int32_t* order, int B, int H, int T,
+                           int dh, int use_mask, int dtype, void* stream);
+int tfasr_relattn_fused_bwd_qk(const void* qkv, const float* ubias, const float* vbias, const void* pext, const int32_t* lengths,
+                               const void* dout, const float* lse, const void* qu, const void* qv, const float* dvec,
+                               const int32_t* order, void* dqkv, float* du, float* dv, void* ds, float* dpext, int B, int H, int T, int dh,
+                               int lds, float scale, int use_mask, int chunk, int hist, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * LSTM cell pointwise stages (keras LSTM, gates i,f,c,o; base_transducer.py:71-85,123-159)

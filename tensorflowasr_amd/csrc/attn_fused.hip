@@ -122,9 +122,11 @@ __device__ __forceinline__ short8_t q_frag(const bf16_t* qrow, const float* bias
 struct BlockId { int b, h, blk; bool ok; };
 // BLK_MAJOR = false (key-side backward: every workgroup of a sample runs equally long): the blocks of one (sample, head) are consecutive
 // in their XCD's order instead, so they are also resident at the same TIME and share the query-side tiles they all walk.
+// `lin`: the workgroup's id inside its role's range (the whole grid for the one-role kernels; the merged backward launch passes
+// blockIdx.x minus the start of the role's range, a multiple of 8: lin & 7 stays the XCD).
 template <bool BLK_MAJOR = true>
-__device__ __forceinline__ BlockId attn_block_id(int B, int H, int nblk) {
-  const int lin = blockIdx.x, xcd = lin & 7, slot = lin >> 3;
+__device__ __forceinline__ BlockId attn_block_id(int B, int H, int nblk, int lin) {
+  const int xcd = lin & 7, slot = lin >> 3;
   const int nbh = B * H, per = (nbh + 7) >> 3;
   const int blk = BLK_MAJOR ? slot / per : slot % nblk;
   const int bh = (BLK_MAJOR ? slot - blk * per : slot / nblk) * 8 + xcd;
@@ -133,6 +135,8 @@ __device__ __forceinline__ BlockId attn_block_id(int B, int H, int nblk) {
   id.b = bh / H; id.h = bh - id.b * H; id.blk = blk;
   return id;
 }
+template <bool BLK_MAJOR = true>
+__device__ __forceinline__ BlockId attn_block_id(int B, int H, int nblk) { return attn_block_id<BLK_MAJOR>(B, H, nblk, (int)blockIdx.x); }
 inline unsigned attn_grid_size(int B, int H, int nblk) { return (unsigned)(8 * ((B * H + 7) / 8) * nblk); }
 
 // streaming window of query i (compute_streaming_mask, multihead_attention.py:104-143): keys [lo, hi) are visible; outside it the
@@ -461,8 +465,42 @@ __device__ __forceinline__ short8_t row_frag(const bf16_t* row, int k0) {
 
 typedef float float2_t __attribute__((ext_vector_type(2)));
 
-template <bool STREAM, int MODE>
-__global__ __launch_bounds__(256, MODE == 2 ? 3 : 2) void relattn_fused_bwd_qT_kernel(
+// The prologue arithmetic of one query row, shared by the query-side body and relattn_bwd_prep_kernel so that both give the same bits:
+// the q + u / q + v / dO fragments of lane (r, g) (head dims kk*32 + g*8 .. +7) and its share of D_i = rowsum(dO * o) ...
+__device__ __forceinline__ float qrow_frags(const bf16_t* qrow, const float* ub, const float* vb, const bf16_t* dorow, const bf16_t* orow, int g,
+                                            short8_t (&bqu)[2], short8_t (&bqv)[2], short8_t (&bdo)[2]) {
+  float dpart = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    bqu[kk] = q_frag(qrow, ub, kk * 32 + g * 8);
+    bqv[kk] = q_frag(qrow, vb, kk * 32 + g * 8);
+    bdo[kk] = row_frag(dorow + kk * 32 + g * 8, 0);
+    float a[8], c[8];
+    ld8(dorow + kk * 32 + g * 8, a);
+    ld8(orow + kk * 32 + g * 8, c);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dpart += a[e] * c[e];
+  }
+  return dpart;
+}
+// ... and its share of the bias-row score (q_i + v) . pext[R] (`prow`: the bias row of this head); the caller sums both over the four g lanes
+__device__ __forceinline__ float qrow_bias_part(const short8_t (&bqv)[2], const bf16_t* prow, int g) {
+  float part = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    float pr[8];
+    ld8(prow + kk * 32 + g * 8, pr);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) part += bf16_to_f32((bf16_t)bqv[kk][t]) * pr[t];
+  }
+  return part;
+}
+
+// PRE (the merged launch, relattn_fused_bwd_qk_kernel): q + u, q + v and both planes of dvec were written by relattn_bwd_prep_kernel - the
+// body READS them (the same bits it would have formed) instead of forming and writing them.  `lin`: see attn_block_id.
+template <bool STREAM, int MODE, bool PRE>
+__device__ __forceinline__ void relattn_bwd_qT_body(
+    char* const smem, const int lin,
     const bf16_t* __restrict__ qkv, const float* __restrict__ ubias, const float* __restrict__ vbias,
     const bf16_t* __restrict__ pext, const int32_t* __restrict__ lengths, const bf16_t* __restrict__ o,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse, bf16_t* __restrict__ dq, bf16_t* __restrict__ dpos,
@@ -470,7 +508,7 @@ __global__ __launch_bounds__(256, MODE == 2 ? 3 : 2) void relattn_fused_bwd_qT_k
     long lddq, float* __restrict__ du, float* __restrict__ dv, int chunk, int hist, bf16_t* qu_out, bf16_t* qv_out) {
   constexpr bool QT_PIPE = MODE == 1, QT_LEAN = MODE == 2, QT_ALIAS = MODE != 0;
   constexpr int QT_TILE_BYTES = qt_tile_bytes(MODE);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  static_assert(!PRE || MODE == 1, "the reading mode exists for the pipelined build only");
   // K block [64 j][64 dh] row-major: rows = A operand of S^T, transposed = A operand of dq_u^T; V block: rows = A operand of dP^T;
   // window rows: rows = A operand of G^T, transposed = A operand of dq_v^T.  QT_PIPE: K and the window twice.
   char* const sK0 = smem;
@@ -484,7 +522,7 @@ __global__ __launch_bounds__(256, MODE == 2 ? 3 : 2) void relattn_fused_bwd_qT_k
   // whatever the key block, so it is cleared once: the cells outside that range stay zero, the ones inside are rewritten every block.
   char* sAg = QT_ALIAS ? reinterpret_cast<char*>(sG) : sStrips + 4 * SGTT_BYTES + w * QT_IMG_BYTES;
   const int r = lane & 15, g = lane >> 4;
-  const BlockId bid = attn_block_id(B, H, (T + BI - 1) / BI);
+  const BlockId bid = attn_block_id(B, H, (T + BI - 1) / BI, lin);
   if (!bid.ok) return;
   const int b = bid.b, h = bid.h, i0 = bid.blk * BI;
   const int HD = H * DH, LDQ = 3 * HD, R = 2 * T - 1, R1 = 2 * T;
@@ -509,28 +547,30 @@ __global__ __launch_bounds__(256, MODE == 2 ? 3 : 2) void relattn_fused_bwd_qT_k
   const int irow = min(i, T - 1);
   short8_t bqu[2], bqv[2], bdo[2];
   float dpart = 0.f;
+  if constexpr (PRE) {
 #pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-    bqu[kk] = q_frag(qb + (long)irow * LDQ, ubias + h * DH, kk * 32 + g * 8);
-    bqv[kk] = q_frag(qb + (long)irow * LDQ, vbias + h * DH, kk * 32 + g * 8);
-    const bf16_t* dorow = dout + ((long)b * T + irow) * HD + h * DH + kk * 32 + g * 8;
-    const bf16_t* orow = o + ((long)b * T + irow) * HD + h * DH + kk * 32 + g * 8;
-    bdo[kk] = row_frag(dorow, 0);
-    float a[8], c[8];
-    ld8(dorow, a);
-    ld8(orow, c);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) dpart += a[e] * c[e];
+    for (int kk = 0; kk < 2; ++kk) {
+      bqu[kk] = row_frag(qu_out + ((long)b * T + irow) * HD + h * DH, kk * 32 + g * 8);
+      bqv[kk] = row_frag(qv_out + ((long)b * T + irow) * HD + h * DH, kk * 32 + g * 8);
+      bdo[kk] = row_frag(dout + ((long)b * T + irow) * HD + h * DH, kk * 32 + g * 8);
+    }
+  } else {
+    dpart = qrow_frags(qb + (long)irow * LDQ, ubias + h * DH, vbias + h * DH, dout + ((long)b * T + irow) * HD + h * DH,
+                       o + ((long)b * T + irow) * HD + h * DH, g, bqu, bqv, bdo);
   }
-  if (qu_out && i < T) {  // q + u / q + v of this block's rows for the key-side and table-gradient kernels (the fragments ARE those rows)
+  if (!PRE && qu_out && i < T) {  // q + u / q + v of this block's rows for the key-side and table-gradient kernels (the fragments ARE those rows)
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       *reinterpret_cast<short8_t*>(qu_out + ((long)b * T + irow) * HD + h * DH + kk * 32 + g * 8) = bqu[kk];
       *reinterpret_cast<short8_t*>(qv_out + ((long)b * T + irow) * HD + h * DH + kk * 32 + g * 8) = bqv[kk];
     }
   }
-  dpart = xor32_sum(xor16_sum(dpart));  // D_i of this lane's query, in all four lanes of its column
-  if (g == 0 && i < T) dvec[((long)b * H + h) * T + i] = dpart;
+  if constexpr (PRE) {
+    dpart = dvec[((long)b * H + h) * T + irow];
+  } else {
+    dpart = xor32_sum(xor16_sum(dpart));  // D_i of this lane's query, in all four lanes of its column
+    if (g == 0 && i < T) dvec[((long)b * H + h) * T + i] = dpart;
+  }
   const float Di = dpart;
   const float scale2 = scale * 1.4426950408889634f;
   const float lse2 = lse[((long)b * H + h) * T + irow] * 1.4426950408889634f;
@@ -564,18 +604,11 @@ __global__ __launch_bounds__(256, MODE == 2 ? 3 : 2) void relattn_fused_bwd_qT_k
   const int njb = (T + BJ - 1) / BJ;
   // the bias-row score of this lane's query, (q_i + v) . pext[R]: the same for every key block, so it is formed once
   float gbias;
-  if constexpr (QT_PIPE || QT_LEAN) {
+  if constexpr (PRE) {
+    gbias = dvec[(long)B * H * T + ((long)b * H + h) * T + irow];
+  } else if constexpr (QT_PIPE || QT_LEAN) {
     // ... as a plain dot product from the fragments (head dims kk*32 + g*8 + t of this lane, the other three quarters in lanes r + 16 m)
-    float part = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      float pr[8];
-      ld8(pb + (long)R * HD + kk * 32 + g * 8, pr);
-#pragma unroll
-      for (int t = 0; t < 8; ++t) part += bf16_to_f32((bf16_t)bqv[kk][t]) * pr[t];
-    }
-    part = xor32_sum(xor16_sum(part));
-    gbias = part;
+    gbias = xor32_sum(xor16_sum(qrow_bias_part(bqv, pb + (long)R * HD, g)));
   } else {
     char* const sP = sP0;
     if (w == 0 && lane < 8) *reinterpret_cast<uint4*>(sP + 127 * 128 + lane * 16) = bias_row;  // window row 127 <- the bias row
@@ -596,7 +629,7 @@ __global__ __launch_bounds__(256, MODE == 2 ? 3 : 2) void relattn_fused_bwd_qT_k
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     gbias = sGb[r];
   }
-  if (g == 0 && i < T) dvec[(long)B * H * T + ((long)b * H + h) * T + i] = gbias;  // second plane of dvec: for the key-side kernel
+  if (!PRE && g == 0 && i < T) dvec[(long)B * H * T + ((long)b * H + h) * T + i] = gbias;  // second plane of dvec: for the key-side kernel
   const float Dis = Di * scale;
   // the bias row of the table (this lane's 16 head dims n*16 + g*4 + e) for the epilogue: requested here, so that the epilogue has no
   // global load of its own to wait for (every workgroup pays its prologue and epilogue latencies once, and a launch is two rounds of them)
@@ -615,6 +648,10 @@ __global__ __launch_bounds__(256, MODE == 2 ? 3 : 2) void relattn_fused_bwd_qT_k
     float l2 = lse2, gb = gbias, ds_ = Dis;
     asm volatile("" : "+v"(l2), "+v"(gb), "+v"(ds_));
     (void)l2; (void)gb; (void)ds_;
+    if constexpr (PRE) {  // (here the fragments are plain loads, first used inside the loop: the same holds for them)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) asm volatile("" : "+v"(bqu[kk]), "+v"(bqv[kk]), "+v"(bdo[kk]));
+    }
   }
 #ifdef TFASR_ATTN_TIMING
   long long ph[5] = {0, 0, 0, 0, 0};
@@ -863,6 +900,18 @@ __global__ __launch_bounds__(256, MODE == 2 ? 3 : 2) void relattn_fused_bwd_qT_k
 #endif
 }
 
+template <bool STREAM, int MODE>
+__global__ __launch_bounds__(256, MODE == 2 ? 3 : 2) void relattn_fused_bwd_qT_kernel(
+    const bf16_t* __restrict__ qkv, const float* __restrict__ ubias, const float* __restrict__ vbias,
+    const bf16_t* __restrict__ pext, const int32_t* __restrict__ lengths, const bf16_t* __restrict__ o,
+    const bf16_t* __restrict__ dout, const float* __restrict__ lse, bf16_t* __restrict__ dq, bf16_t* __restrict__ dpos,
+    float* __restrict__ dvec, int B, int H, int T, int ldp, float scale, int use_mask, float* __restrict__ dpext,
+    long lddq, float* __restrict__ du, float* __restrict__ dv, int chunk, int hist, bf16_t* qu_out, bf16_t* qv_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  relattn_bwd_qT_body<STREAM, MODE, false>(smem, (int)blockIdx.x, qkv, ubias, vbias, pext, lengths, o, dout, lse, dq, dpos, dvec, B, H, T, ldp, scale,
+                                           use_mask, dpext, lddq, du, dv, chunk, hist, qu_out, qv_out);
+}
+
 
 // Backward, part 3 (V2): the gradient of the projected position table,
 //   dpext[c, :] += sum_b sum_i dS_b[i, j(i,c)] * (q_i + v),     j(i,c) = (c - shift_b) - (T-1-i),   valid iff 0 <= c - shift_b < 2 len_b - 1
@@ -1038,13 +1087,16 @@ __device__ __forceinline__ short8_t img_frag(const char* s, int kbase, int r) {
   return v;
 }
 
+// `order` (the merged launch; nullptr: sample rank = sample index): the samples by length, longest first (relattn_bwd_prep_kernel) - a
+// workgroup runs as long as its sample is, and the hardware starts workgroups in id order.  dk / dv rows are owned by one workgroup each,
+// so the order changes no bit.  `lin`: see attn_block_id.
 template <bool STREAM>
-__global__ __launch_bounds__(256, 2) void relattn_fused_bwd_k_kernel(
+__device__ __forceinline__ void relattn_bwd_k_body(
+    char* const smem, const int lin, const int32_t* __restrict__ order,
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ qu, const bf16_t* __restrict__ qv,
     const bf16_t* __restrict__ pext, const int32_t* __restrict__ lengths, const bf16_t* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ dvec, bf16_t* __restrict__ dqkv, int B, int H, int T, float scale,
     int use_mask, int chunk, int hist) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const sQu0 = smem;                    // [2] qu blocks
   char* const sdO0 = sQu0 + 2 * SK_BYTES;     // [2] dO blocks
   char* const sQv = sdO0 + 2 * SK_BYTES;
@@ -1055,9 +1107,9 @@ __global__ __launch_bounds__(256, 2) void relattn_fused_bwd_k_kernel(
   char* const sAp = sW;
   char* const sAs = sW + 2048;
   const int r = lane & 15, g = lane >> 4;
-  const BlockId bid = attn_block_id<false>(B, H, (T + BJ - 1) / BJ);
+  const BlockId bid = attn_block_id<false>(B, H, (T + BJ - 1) / BJ, lin);
   if (!bid.ok) return;
-  const int b = bid.b, h = bid.h, j0 = bid.blk * BJ;
+  const int b = order ? order[bid.b] : bid.b, h = bid.h, j0 = bid.blk * BJ;
   const int HD = H * DH, LDQ = 3 * HD, R1 = 2 * T;
   const int len = lengths ? min(lengths[b], T) : T;
   const int shift = T - len;
@@ -1292,6 +1344,91 @@ __global__ __launch_bounds__(256, 2) void relattn_fused_bwd_k_kernel(
   }
 }
 
+template <bool STREAM>
+__global__ __launch_bounds__(256, 2) void relattn_fused_bwd_k_kernel(
+    const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ qu, const bf16_t* __restrict__ qv,
+    const bf16_t* __restrict__ pext, const int32_t* __restrict__ lengths, const bf16_t* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ dvec, bf16_t* __restrict__ dqkv, int B, int H, int T, float scale,
+    int use_mask, int chunk, int hist) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  relattn_bwd_k_body<STREAM>(smem, (int)blockIdx.x, nullptr, qkv, qu, qv, pext, lengths, dout, lse, dvec, dqkv, B, H, T, scale, use_mask, chunk, hist);
+}
+
+// ======================================================================================================================
+// Backward, both sides in ONE launch (tfasr_relattn_fused_bwd_qk).  As two launches each side leaves most of the chip empty for half of
+// its time: the live query-side workgroups are equally long and come to 1.1 - 1.4 rounds of the 512 resident slots, run as two; a key-side
+// workgroup is as long as its sample, and a long sample late in the batch starts when the rest is nearly done.  Here ids [0, nq) are the
+// query side in its block-major order (live blocks - the longest workgroups of the launch - first; a wholly padded block exits at once and
+// frees its slot) and ids [nq, nq + nk) the key side with the samples longest first (`order`), so the key side fills the slots the
+// query side's second round leaves empty.  For that the key side must not depend on the query side: what it used to read from it
+// (q + u, q + v, dvec) comes from relattn_bwd_prep_kernel, launched ahead, and the query side reads the same buffers (PRE).  No workgroup
+// waits for another one: no flag, no counter, no spin.  nq is a multiple of 8: both roles keep id & 7 = XCD (attn_block_id).
+// ======================================================================================================================
+constexpr int SMEM_BWD_QK = qt_smem(1) > SMEM_BWD_K ? qt_smem(1) : SMEM_BWD_K;
+static_assert((SMEM_BWD_QK + 1279) / 1280 * 2 <= 128, "two workgroups per CU");
+
+template <bool STREAM>
+__global__ __launch_bounds__(256, 2) void relattn_fused_bwd_qk_kernel(
+    const bf16_t* __restrict__ qkv, const float* __restrict__ ubias, const float* __restrict__ vbias, const bf16_t* __restrict__ pext,
+    const int32_t* __restrict__ lengths, const bf16_t* __restrict__ dout, const float* __restrict__ lse, const bf16_t* __restrict__ qu,
+    const bf16_t* __restrict__ qv, const float* __restrict__ dvec, const int32_t* __restrict__ order, bf16_t* __restrict__ dqkv,
+    bf16_t* __restrict__ dpos, float* __restrict__ dpext, float* __restrict__ du, float* __restrict__ dv, int B, int H, int T, int ldp,
+    float scale, int use_mask, int chunk, int hist, int nq) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lin = (int)blockIdx.x;
+  if (lin < nq) {
+    relattn_bwd_qT_body<STREAM, 1, true>(smem, lin, qkv, ubias, vbias, pext, lengths, nullptr, dout, lse, dqkv, dpos, const_cast<float*>(dvec), B, H, T,
+                                         ldp, scale, use_mask, dpext, 3L * H * DH, du, dv, chunk, hist, const_cast<bf16_t*>(qu), const_cast<bf16_t*>(qv));
+  } else {
+    relattn_bwd_k_body<STREAM>(smem, lin - nq, order, qkv, qu, qv, pext, lengths, dout, lse, dvec, dqkv, B, H, T, scale, use_mask, chunk, hist);
+  }
+}
+
+// Preparation of the merged launch: one pass over q, o and dO that writes q + u, q + v and both planes of dvec (D_i = rowsum(dO * o) and the
+// bias-row score (q_i + v) . pext[R]) with the arithmetic of the query-side body (qrow_frags / qrow_bias_part, the same lane layout and the
+// same reduction order: the same bits), for the rows the query-side kernel writes them for (every row of a 64-query block that is not wholly
+// padding).  Workgroup (0, 0, 0) also writes `order`: the samples by length, descending, ties by sample index - a permutation of 0 .. B-1.
+__global__ __launch_bounds__(256) void relattn_bwd_prep_kernel(
+    const bf16_t* __restrict__ qkv, const float* __restrict__ ubias, const float* __restrict__ vbias, const bf16_t* __restrict__ pext,
+    const int32_t* __restrict__ lengths, const bf16_t* __restrict__ o, const bf16_t* __restrict__ dout, bf16_t* __restrict__ qu_out,
+    bf16_t* __restrict__ qv_out, float* __restrict__ dvec, int32_t* __restrict__ order, int B, int H, int T, int use_mask) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
+    for (int s = threadIdx.x; s < B; s += 256) {
+      const int ls = lengths ? min(lengths[s], T) : T;
+      int rank = 0;
+      for (int t = 0; t < B; ++t) {
+        const int lt = lengths ? min(lengths[t], T) : T;
+        rank += (lt > ls || (lt == ls && t < s)) ? 1 : 0;
+      }
+      order[rank] = s;
+    }
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int b = blockIdx.z, h = blockIdx.y, i0 = blockIdx.x * BI;
+  const int HD = H * DH, LDQ = 3 * HD, R = 2 * T - 1;
+  const int len = lengths ? min(lengths[b], T) : T;
+  if (use_mask && i0 >= len) return;
+  const int i = i0 + w * 16 + r;
+  const int irow = min(i, T - 1);
+  const long orow = ((long)b * T + irow) * HD + h * DH;
+  short8_t bqu[2], bqv[2], bdo[2];
+  float dpart = qrow_frags(qkv + ((long)b * T + irow) * LDQ + h * DH, ubias + h * DH, vbias + h * DH, dout + orow, o + orow, g, bqu, bqv, bdo);
+  dpart = xor32_sum(xor16_sum(dpart));
+  const float gbias = xor32_sum(xor16_sum(qrow_bias_part(bqv, pext + (long)R * HD + h * DH, g)));
+  if (i < T) {
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      *reinterpret_cast<short8_t*>(qu_out + orow + kk * 32 + g * 8) = bqu[kk];
+      *reinterpret_cast<short8_t*>(qv_out + orow + kk * 32 + g * 8) = bqv[kk];
+    }
+    if (g == 0) {
+      dvec[((long)b * H + h) * T + i] = dpart;
+      dvec[(long)B * H * T + ((long)b * H + h) * T + i] = gbias;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int tfasr_relattn_fused_fwd(const void* qkv, const float* ubias, const float* vbias, const void* pext,
@@ -1367,6 +1504,44 @@ extern "C" int tfasr_relattn_fused_bwd_k(const void* qkv, const void* qu, const 
                 (const bf16_t*)pext, lengths, (const bf16_t*)dout, lse, dvec, (bf16_t*)dqkv, B, H, T, scale, use_mask, CH, HI)
   if (chunk > 0) TFASR_BK_LAUNCH(relattn_fused_bwd_k_kernel, SMEM_BWD_K, true, chunk, hist); else TFASR_BK_LAUNCH(relattn_fused_bwd_k_kernel, SMEM_BWD_K, false, 0, 0);
 #undef TFASR_BK_LAUNCH
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_relattn_bwd_prep(const void* qkv, const float* ubias, const float* vbias, const void* pext, const int32_t* lengths,
+                                      const void* o, const void* dout, void* qu, void* qv, float* dvec, int32_t* order, int B, int H, int T,
+                                      int dh, int use_mask, int dtype, void* stream_) {
+  if (!qkv || !ubias || !vbias || !pext || !o || !dout || !qu || !qv || !dvec || !order || B <= 0 || H <= 0 || T <= 0 || B > 65535 || H > 65535 ||
+      (((uintptr_t)qu | (uintptr_t)qv) & 15))
+    return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_BF16 || dh != DH) return TFASR_STATUS_UNSUPPORTED;
+  TFASR_KLAUNCH(relattn_bwd_prep_kernel, dim3((T + BI - 1) / BI, H, B), dim3(256), 0, (hipStream_t)stream_, (const bf16_t*)qkv, ubias, vbias,
+                (const bf16_t*)pext, lengths, (const bf16_t*)o, (const bf16_t*)dout, (bf16_t*)qu, (bf16_t*)qv, dvec, order, B, H, T, use_mask);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_relattn_fused_bwd_qk(const void* qkv, const float* ubias, const float* vbias, const void* pext, const int32_t* lengths,
+                                          const void* dout, const float* lse, const void* qu, const void* qv, const float* dvec,
+                                          const int32_t* order, void* dqkv, float* du, float* dv, void* ds, float* dpext, int B, int H, int T, int dh,
+                                          int lds, float scale, int use_mask, int chunk, int hist, int dtype, void* stream_) {
+  if (!qkv || !ubias || !vbias || !pext || !dout || !lse || !qu || !qv || !dvec || !order || !dqkv || !du || !dv || !ds || !dpext || B <= 0 || H <= 0 ||
+      T <= 0 || lds < T || (lds & 7) || (((uintptr_t)qu | (uintptr_t)qv) & 15))
+    return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_BF16 || dh != DH) return TFASR_STATUS_UNSUPPORTED;
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute((const void*)relattn_fused_bwd_qk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD_QK);
+    (void)hipFuncSetAttribute((const void*)relattn_fused_bwd_qk_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD_QK);
+    attr_done = true;
+  }
+  const unsigned nq = attn_grid_size(B, H, (T + BI - 1) / BI), nk = attn_grid_size(B, H, (T + BJ - 1) / BJ);
+#define TFASR_QK_LAUNCH(ST, CH, HI)                                                                                                          \
+  TFASR_KLAUNCH((relattn_fused_bwd_qk_kernel<ST>), dim3(nq + nk), dim3(256), SMEM_BWD_QK, (hipStream_t)stream_, (const bf16_t*)qkv, ubias, vbias, \
+                (const bf16_t*)pext, lengths, (const bf16_t*)dout, lse, (const bf16_t*)qu, (const bf16_t*)qv, dvec, order, (bf16_t*)dqkv,   \
+                (bf16_t*)ds, dpext, du, dv, B, H, T, lds, scale, use_mask, CH, HI, (int)nq)
+  if (chunk > 0) TFASR_QK_LAUNCH(true, chunk, hist); else TFASR_QK_LAUNCH(false, 0, 0);
+#undef TFASR_QK_LAUNCH
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }

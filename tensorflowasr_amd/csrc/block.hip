@@ -466,7 +466,20 @@ struct Ex {
       void* qu = act(scratch, rows * HD);
       void* qvb = act(scratch, rows * HD);
       if (dpext_deferred) qvb = io->qv_keep;
-      if (!dry) {
+      int32_t* order = (int32_t*)f32(scratch, B);  // the samples longest first, for the key side of the merged launch
+      // A/B switch of the merged launch (read at every call: one process can run both routes)
+      const char* qk_env = getenv("TFASR_ATTN_BWD_QK");
+      const bool merged = qk_env ? qk_env[0] != '0' : true;
+      if (!dry && merged) {
+        // preparation (qu / qvb = q + u / q + v, dvec, order), then the query and the key side in ONE launch, the key side's long samples first
+        chk(tfasr_relattn_bwd_prep(k->at_qkv, fp(TFASR_BP_AT_U), fp(TFASR_BP_AT_V), k->at_pext, io->lengths, k->at_att, datt, qu, qvb, dvec, order,
+                                   B, H, T, dh, c->use_mask, c->dtype, s));
+        chk(tfasr_relattn_fused_bwd_qk(k->at_qkv, fp(TFASR_BP_AT_U), fp(TFASR_BP_AT_V), k->at_pext, io->lengths, datt, k->at_lse, qu, qvb, dvec, order,
+                                       dqkv, gp(TFASR_BP_AT_U), gp(TFASR_BP_AT_V), dpos, dpext, B, H, T, dh, Tp, scale, c->use_mask,
+                                       c->chunk_size, c->history_size, c->dtype, s));
+        dq_done = true;
+        if (!dpext_deferred) chk(tfasr_relattn_dpext(dpos, qvb, io->lengths, dpext, B, H, T, dh, Tp, c->use_mask, c->dtype, s));
+      } else if (!dry) {
         // (also writes qu / qvb = q + u / q + v for the two kernels below: no tfasr_bias2_fwd launch)
         chk(tfasr_relattn_fused_bwd_q3(k->at_qkv, fp(TFASR_BP_AT_U), fp(TFASR_BP_AT_V), k->at_pext, io->lengths, k->at_att, datt, k->at_lse, dqkv,
                                        3L * HD, gp(TFASR_BP_AT_U), gp(TFASR_BP_AT_V), dpos, dvec, dpext, qu, qvb, B, H, T, dh, Tp, scale, c->use_mask,

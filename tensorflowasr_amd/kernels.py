@@ -799,6 +799,34 @@ def relattn_fused_bwd_k(qkv, qu, qv, pext, lengths, dout, lse, dvec, dqkv, B, H,
     return dqkv
 
 
+def relattn_bwd_prep(qkv, ubias, vbias, pext, lengths, o, dout, B, H, T, dh, use_mask=True, qu=None, qv=None, dvec=None):
+    """Preparation of the merged attention backward (tfasr_relattn_bwd_prep) -> (qu, qv [B*T, H*dh], dvec [2,B,H,T], order [B] int32:
+    the samples longest first).  qu / qv / dvec may be passed in (rows of wholly padded 64-query blocks are not written)."""
+    if qu is None:
+        qu = torch.empty(B * T, H * dh, dtype=qkv.dtype, device=qkv.device)
+    if qv is None:
+        qv = torch.empty(B * T, H * dh, dtype=qkv.dtype, device=qkv.device)
+    if dvec is None:
+        dvec = torch.empty(2, B, H, T, dtype=torch.float32, device=qkv.device)
+    order = torch.empty(B, dtype=torch.int32, device=qkv.device)
+    check(_L().tfasr_relattn_bwd_prep(_p(qkv), _p(ubias), _p(vbias), _p(pext), _p(lengths), _p(o), _p(dout), _p(qu), _p(qv), _p(dvec), _p(order),
+                                      B, H, T, dh, int(use_mask), _dt(qkv), _stream()), "relattn_bwd_prep")
+    return qu, qv, dvec, order
+
+
+def relattn_fused_bwd_qk(qkv, ubias, vbias, pext, lengths, dout, lse, qu, qv, dvec, order, dqkv, du, dv, dpext, B, H, T, dh, scale, use_mask=True,
+                         chunk_size=None, history_size=None, ds=None):
+    """Both sides of the fused attention backward in one launch (tfasr_relattn_fused_bwd_qk, after relattn_bwd_prep): writes dq, dk, dv
+    into dqkv [B*T, 3*H*dh], adds the u / v bias gradients into du / dv and the bias row's share into dpext -> ds [B,H,T,lds]."""
+    lds = -(-T // 8) * 8
+    if ds is None:
+        ds = torch.empty(B, H, T, lds, dtype=qkv.dtype, device=qkv.device)
+    check(_L().tfasr_relattn_fused_bwd_qk(_p(qkv), _p(ubias), _p(vbias), _p(pext), _p(lengths), _p(dout), _p(lse), _p(qu), _p(qv), _p(dvec),
+                                          _p(order), _p(dqkv), _p(du), _p(dv), _p(ds), _p(dpext), B, H, T, dh, lds, scale, int(use_mask),
+                                          *_window(chunk_size, history_size), _dt(qkv), _stream()), "relattn_fused_bwd_qk")
+    return ds
+
+
 # -------------------------------------------------------------------------------------- LSTM
 def lstm_step_fwd(xg_t, hr, h_prev, c_prev, lengths, t, gates_t, c_out, h_out, y_out, B, P):
     check(_L().tfasr_lstm_step_fwd(
