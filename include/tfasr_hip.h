@@ -931,6 +931,26 @@ int tfasr_stream_kv_append(const void* qkv, void* kcache, void* vcache, const in
                            int dh, int hist, int dtype, void* stream);
 int tfasr_stream_glu_dwconv_fwd(const void* glu_x, void* state, const float* w, const float* bias, const int32_t* nvalid, void* y, int B,
                                 int C, int d, int K, int dtype, void* stream);
+/* The streaming Transformer encoder's step (plain attention over absolute positions; declarations added under ABI 44, nothing existing
+ * changes).
+ * tfasr_stream_attn_plain_fwd: tfasr_stream_attn_fwd without the relative-position term and WITH the ring append, in one launch.
+ *   qkv [B*C, 3*H*dh], kcache / vcache [B, hist, H*dh] rings (NULL allowed with hist == 0), out [B*C, H*dh].  Stream b, nv = nvalid[b]
+ *   clamped to [0, C], nh = min(seen[b], hist): query row i < nv attends over the nh ring frames in time order followed by the chunk's
+ *   own rows 0 .. nv-1 (causal != 0: 0 .. i); score (q * scale) . k, max-subtracted softmax, times V, f32 accumulation; rows >= nv of
+ *   out are zero.  No length mask: a stream is an utterance alone, every row < nv is a valid query and there is no padded key.
+ *   Then the chunk's valid k / v rows go to slots (seen + r) % hist (only the last hist rows when nv > hist).  The grid is (H, B): a
+ *   workgroup is the only reader and the only writer of its head's column slice and writes it after its last ring read and a barrier;
+ *   an idle stream (nv == 0) writes none of its ring.  Keys and values are staged in LDS in blocks of 32 keys (54 KB static, no launch
+ *   attribute): each ring or chunk row is fetched from global memory once per workgroup; 16-byte loads when dh % 8 == 0 and the three
+ *   pointers are 16-byte aligned, a scalar path otherwise.  Limits and UNSUPPORTED / INVALID_VALUE answers as tfasr_stream_attn_fwd
+ *   (B <= 65535), decided on the host before any launch.
+ * tfasr_stream_add_pe: y[b,r,:] = x[b,r,:] + pe[seen[b] + r, :] for r < nvalid[b] (f32 add, one rounding to the storage type, as
+ *   tfasr_add_pe); rows >= nvalid[b] are copied; x, y [B, C, d], pe [Tcap, d] f32, y may alias x.  A valid row whose position lies outside
+ *   [0, Tcap) is written as NaN and pe is not read for it: a host that let the table run out hears of it instead of faulting. */
+int tfasr_stream_attn_plain_fwd(const void* qkv, void* kcache, void* vcache, const int32_t* seen, const int32_t* nvalid, void* out, int B,
+                                int C, int H, int dh, int hist, float scale, int causal, int dtype, void* stream);
+int tfasr_stream_add_pe(const void* x, const float* pe, const int32_t* seen, const int32_t* nvalid, void* y, int B, int C, int d, int Tcap,
+                        int dtype, void* stream);
 /* tfasr_logmel for a stream: signal [B, N] holds the unconsumed samples of every stream from column 0, nlen [B] how many of them are
  * real (the rest of a frame is zero padding: ask for frames past nlen only when flushing), prev [B] / has_prev [B] the last sample
  * consumed before column 0 (pre-emphasis of sample 0; has_prev == 0: start of the utterance).  out [B, T0, F]. */

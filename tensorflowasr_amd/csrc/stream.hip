@@ -7,6 +7,12 @@
 //   stream_kv_append_kernel  : the chunk's keys / values into the ring (its own launch AFTER the attention: every head of the attention
 //                              launch still reads the slots this overwrites - they lie inside the chunk's window)
 //   stream_glu_dwconv_kernel : GLU + causal depthwise conv whose left context is a carried [K-1, d] state, updated in place
+// and for the streaming Transformer encoder (plain attention over absolute positions, no convolution module):
+//   stream_attn_plain_kernel : the same chunk attention without the relative-position term, keys and values staged in LDS block by
+//                              block (every ring or chunk row leaves global memory once per workgroup), optional causal mask inside the
+//                              chunk, and the ring append in the SAME launch: a workgroup is the only reader and the only writer of its
+//                              head's column slice of the rings, and it writes them only after its last ring read and a barrier
+//   stream_add_pe_kernel     : x + pe[seen[b] + r] for the valid rows: the absolute position table at each stream's own offset
 // Streams of one batch stand at different offsets (seen[b]) and may be idle (nvalid[b] == 0): both are DEVICE vectors, nothing goes
 // through the host, and an idle stream's state is not written at all.
 // At these sizes (16 x 80 scores per head) every kernel is latency-bound: plain f32 FMAs (exact f32 products, as the search step
@@ -150,6 +156,200 @@ __global__ __launch_bounds__(256) void stream_glu_dwconv_kernel(const T* __restr
   for (int r = ph; r < K1; r += 4) Num<T>::st(state + ((long)b * K1 + r) * d + c, g[(nv + r) * 64 + cl]);
 }
 
+// ------------------------------------------------------------------------------------------- plain chunk attention + ring append
+constexpr int PKB = 32;           // keys per LDS block (>= MAXC: the chunk's own rows are one block, the LAST one)
+constexpr int PLDK = MAXDH + 4;   // widest key row in LDS: + one 16-byte access, so that lanes reading consecutive rows hit different banks
+constexpr int PROWS = 16;         // output rows per thread at most: 256 / dh >= 2 row groups, MAXC = 32 rows
+static_assert(PKB == 32 && MAXC <= PKB && MAXC <= 2 * PROWS, "stream_attn_plain_kernel's blocking: a half-wave of keys per block");
+
+template <bool VEC> __device__ __forceinline__ float dot_lds(const float* __restrict__ q, const float* __restrict__ k, int dh) {
+  float a = 0.f, b = 0.f, c = 0.f, d = 0.f;  // four chains: the products of one row are 128 dependent FMAs otherwise
+  if (VEC) {
+    for (int e = 0; e < dh; e += 8) {
+      const float4 q0 = *reinterpret_cast<const float4*>(q + e), q1 = *reinterpret_cast<const float4*>(q + e + 4);
+      const float4 k0 = *reinterpret_cast<const float4*>(k + e), k1 = *reinterpret_cast<const float4*>(k + e + 4);
+      a = fmaf(q0.x, k0.x, a); b = fmaf(q0.y, k0.y, b); c = fmaf(q0.z, k0.z, c); d = fmaf(q0.w, k0.w, d);
+      a = fmaf(q1.x, k1.x, a); b = fmaf(q1.y, k1.y, b); c = fmaf(q1.z, k1.z, c); d = fmaf(q1.w, k1.w, d);
+    }
+  } else {
+    for (int e = 0; e < dh; ++e) a = fmaf(q[e], k[e], a);
+  }
+  return (a + b) + (c + d);
+}
+
+// all-reduce over the 32 lanes of a half-wave in the vector unit alone (DPP row rotations, then one permlane16 swap for lane ^ 16):
+// wave_max / wave_sum go through ds_bpermute, an LDS round trip per step in a dependent chain
+__device__ __forceinline__ float half_max(float v) { return xor16_max(row16_max(v)); }
+__device__ __forceinline__ float half_sum(float v) { return xor16_sum(row16_sum(v)); }
+
+// grid (H, B), 256 threads.  Keys in time order: nh = min(seen, hist) ring frames (slot (seen - nh + jj) % hist), then the chunk's own
+// rows; they are walked in blocks of PKB with a running max / sum per query row (Ms / Ls) and the output rows in registers: thread t
+// owns column t % dh of rows t / dh + k * (256 / dh).  The own rows are the last block, so after the loop they still stand in LDS
+// (f32 copies of storage-type values: the conversion back is exact) and go from there into the ring.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void stream_attn_plain_kernel(const T* __restrict__ qkv, T* kc, T* vc, const int32_t* __restrict__ seen,
+                                                                const int32_t* __restrict__ nvalid, T* __restrict__ out, int C, int H, int dh,
+                                                                int hist, float scale, int causal) {
+  __shared__ __attribute__((aligned(16))) float Qs[MAXC * MAXDH];
+  __shared__ __attribute__((aligned(16))) float Ks[PKB * PLDK];
+  __shared__ __attribute__((aligned(16))) float Vs[PKB * MAXDH];
+  __shared__ __attribute__((aligned(16))) float Ps[MAXC * PKB];
+  __shared__ float Ms[MAXC], Ls[MAXC], As[MAXC];
+  const int h = blockIdx.x, b = blockIdx.y, HD = H * dh, t = threadIdx.x;
+  const int nv = min(max(nvalid[b], 0), C), sn = max(seen[b], 0);
+  T* ob = out + (long)b * C * HD + h * dh;
+  for (int i = nv * dh + t; i < C * dh; i += 256) Num<T>::st(ob + (long)(i / dh) * HD + i % dh, 0.f);
+  if (nv == 0) return;  // an idle stream: before any barrier, and nothing of its rings is written
+  const int nh = min(sn, hist), ldk = dh + (VEC ? 4 : 1);
+  const T* qb = qkv + (long)b * C * 3 * HD + h * dh;
+  T* kcb = kc + (long)b * hist * HD + h * dh;
+  T* vcb = vc + (long)b * hist * HD + h * dh;
+  const int G = 256 / dh, e = t % dh, g = t / dh, nkr = (nv + G - 1) / G;  // rows g + k G, k < nkr, of column e
+  const bool owner = g < G;
+  float acc[PROWS];
+#pragma unroll
+  for (int k = 0; k < PROWS; ++k) acc[k] = 0.f;
+  for (int i = t; i < nv * dh; i += 256) Qs[i] = Num<T>::ld(qb + (long)(i / dh) * 3 * HD + i % dh) * scale;
+  if (t < nv) { Ms[t] = -INFINITY; Ls[t] = 0.f; }
+  const int nring = (nh + PKB - 1) / PKB;
+  for (int blk = 0; blk <= nring; ++blk) {
+    const bool own = blk == nring;
+    const int j0 = blk * PKB, kbn = own ? nv : min(PKB, nh - j0), kb4 = (kbn + 3) & ~3;
+    if (blk) __syncthreads();  // the previous block's K / V / P are read no more
+    // ---- K and V rows of the block into LDS as f32; rows kbn .. kb4 - 1 zero (the P V loop walks keys four at a time)
+    if (VEC) {
+      const int c8 = dh >> 3;
+      for (int i = t; i < kb4 * c8; i += 256) {
+        const int row = i / c8, c = (i % c8) * 8;
+        float kk[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, vv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (row < kbn) {
+          if (own) {
+            ld8(qb + (long)row * 3 * HD + HD + c, kk);
+            ld8(qb + (long)row * 3 * HD + 2 * HD + c, vv);
+          } else {
+            const long slot = (sn - nh + j0 + row) % hist;
+            ld8(kcb + slot * HD + c, kk);
+            ld8(vcb + slot * HD + c, vv);
+          }
+        }
+        *reinterpret_cast<float4*>(Ks + row * ldk + c) = make_float4(kk[0], kk[1], kk[2], kk[3]);
+        *reinterpret_cast<float4*>(Ks + row * ldk + c + 4) = make_float4(kk[4], kk[5], kk[6], kk[7]);
+        *reinterpret_cast<float4*>(Vs + row * dh + c) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+        *reinterpret_cast<float4*>(Vs + row * dh + c + 4) = make_float4(vv[4], vv[5], vv[6], vv[7]);
+      }
+    } else {
+      for (int i = t; i < kb4 * dh; i += 256) {
+        const int row = i / dh, c = i % dh;
+        float kk = 0.f, vv = 0.f;
+        if (row < kbn) {
+          if (own) {
+            kk = Num<T>::ld(qb + (long)row * 3 * HD + HD + c);
+            vv = Num<T>::ld(qb + (long)row * 3 * HD + 2 * HD + c);
+          } else {
+            const long slot = (sn - nh + j0 + row) % hist;
+            kk = Num<T>::ld(kcb + slot * HD + c);
+            vv = Num<T>::ld(vcb + slot * HD + c);
+          }
+        }
+        Ks[row * ldk + c] = kk;
+        Vs[row * dh + c] = vv;
+      }
+    }
+    __syncthreads();
+    // ---- scores and the running max / sum: a half-wave per query row (8 rows per pass), one key per lane, the score never leaves its
+    // register.  With the causal flag own key j is hidden from the rows before it.  As = what the row's earlier blocks are scaled by
+    for (int r0 = 0; r0 < nv; r0 += 8) {
+      const int r = r0 + (t >> 5), j = t & 31;  // r <= 31 = MAXC - 1
+      const bool row = r < nv, live = row && j < kbn && !(own && causal && j > r);
+      const float s = live ? dot_lds<VEC>(Qs + r * dh, Ks + j * ldk, dh) : -INFINITY;
+      const float mo = row ? Ms[r] : 0.f;
+      const float mn = fmaxf(mo, half_max(s));  // finite from the first block on: a row sees every ring key and its own
+      const float p = live ? expf(s - mn) : 0.f;
+      const float sum = half_sum(p);
+      if (row) {
+        Ps[r * PKB + j] = p;  // (keys kbn .. 31: zero)
+        if (j == 0) {
+          const float a = expf(mo - mn);
+          As[r] = a;
+          Ls[r] = Ls[r] * a + sum;
+          Ms[r] = mn;
+        }
+      }
+    }
+    __syncthreads();
+    // ---- P V: one value read per key serves all rows of the thread
+    if (owner) {
+      int rc[PROWS];
+#pragma unroll
+      for (int k = 0; k < PROWS; ++k) {
+        rc[k] = min(g + k * G, nv - 1);  // (a row past nv computes row nv - 1 again and is dropped at the end)
+        if (k < nkr) acc[k] *= As[rc[k]];
+      }
+      for (int j = 0; j < kb4; j += 4) {
+        const float v0 = Vs[j * dh + e], v1 = Vs[(j + 1) * dh + e], v2 = Vs[(j + 2) * dh + e], v3 = Vs[(j + 3) * dh + e];
+#pragma unroll
+        for (int k = 0; k < PROWS; ++k) {
+          if (k < nkr) {
+            const float4 p = *reinterpret_cast<const float4*>(Ps + rc[k] * PKB + j);
+            acc[k] = fmaf(p.w, v3, fmaf(p.z, v2, fmaf(p.y, v1, fmaf(p.x, v0, acc[k]))));
+          }
+        }
+      }
+    }
+  }
+  if (owner) {
+#pragma unroll
+    for (int k = 0; k < PROWS; ++k) {
+      const int r = g + k * G;
+      if (k < nkr && r < nv) Num<T>::st(ob + (long)r * HD + e, acc[k] / Ls[r]);
+    }
+  }
+  // ---- ring append from LDS (the own block's K / V): every ring read of this workgroup lies before the barriers above.  With more valid
+  // rows than slots only the last `hist` rows go (no two rows share a slot)
+  for (int i = max(0, nv - hist) * dh + t; i < nv * dh && hist > 0; i += 256) {
+    const int r = i / dh, c = i % dh;
+    const long dst = (long)((sn + r) % hist) * HD + c;
+    Num<T>::st(kcb + dst, Ks[r * ldk + c]);
+    Num<T>::st(vcb + dst, Vs[r * dh + c]);
+  }
+}
+
+// grid flat over B * C * d (8 elements per thread when VEC): y = x + pe[seen[b] + r] for r < nvalid[b] in f32, one rounding; the other
+// rows are copied; a position outside [0, Tcap) is never read and gives NaN
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void stream_add_pe_kernel(const T* __restrict__ x, const float* __restrict__ pe, const int32_t* __restrict__ seen,
+                                                            const int32_t* __restrict__ nvalid, T* __restrict__ y, int B, int C, int d, int Tcap) {
+  constexpr int W = VEC ? 8 : 1;
+  const int dw = d / W;
+  const long n = (long)B * C * dw;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % dw) * W;
+    const long row = i / dw;
+    const int r = (int)(row % C), b = (int)(row / C);
+    const bool valid = r < nvalid[b];
+    const long pos = (long)seen[b] + r;
+    const bool inside = pos >= 0 && pos < Tcap;
+    if (VEC) {
+      float v[8];
+      ld8(x + row * d + c, v);
+      if (valid && inside) {
+        float p[8];
+        ld8(pe + pos * d + c, p);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] += p[k];
+      } else if (valid) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = NAN;
+      }
+      st8(y + row * d + c, v);
+    } else {
+      float v = Num<T>::ld(x + row * d + c);
+      if (valid) v = inside ? v + pe[pos * d + c] : NAN;
+      Num<T>::st(y + row * d + c, v);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int tfasr_stream_attn_fwd(const void* qkv, const float* ubias, const float* vbias, const void* pos, const void* kcache,
@@ -199,6 +399,39 @@ extern "C" int tfasr_stream_glu_dwconv_fwd(const void* glu_x, void* state, const
     TFASR_KLAUNCH(stream_glu_dwconv_kernel<float>, grid, dim3(256), 0, s, (const float*)glu_x, (float*)state, w, bias, nvalid, (float*)y, C, d, K);
   else
     TFASR_KLAUNCH(stream_glu_dwconv_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)glu_x, (bf16_t*)state, w, bias, nvalid, (bf16_t*)y, C, d, K);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_stream_attn_plain_fwd(const void* qkv, void* kcache, void* vcache, const int32_t* seen, const int32_t* nvalid, void* out,
+                                           int B, int C, int H, int dh, int hist, float scale, int causal, int dtype, void* stream_) {
+  if (!qkv || !seen || !nvalid || !out || B <= 0 || C <= 0 || H <= 0 || dh <= 0 || hist < 0) return TFASR_STATUS_INVALID_VALUE;
+  if (hist > 0 && (!kcache || !vcache)) return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
+  if (C > MAXC || (long)hist + C > MAXK || dh > MAXDH || B > 65535) return TFASR_STATUS_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream_;
+  const bool vec = (dh % 8 == 0) && ((((uintptr_t)qkv | (uintptr_t)kcache | (uintptr_t)vcache) & 15) == 0);
+#define TFASR_SP(TT, VV) TFASR_KLAUNCH((stream_attn_plain_kernel<TT, VV>), dim3(H, B), dim3(256), 0, s, (const TT*)qkv, (TT*)kcache, (TT*)vcache, \
+                                       seen, nvalid, (TT*)out, C, H, dh, hist, scale, causal != 0)
+  if (dtype == TFASR_F32) { if (vec) TFASR_SP(float, true); else TFASR_SP(float, false); }
+  else { if (vec) TFASR_SP(bf16_t, true); else TFASR_SP(bf16_t, false); }
+#undef TFASR_SP
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_stream_add_pe(const void* x, const float* pe, const int32_t* seen, const int32_t* nvalid, void* y, int B, int C, int d,
+                                   int Tcap, int dtype, void* stream_) {
+  if (!x || !pe || !seen || !nvalid || !y || B <= 0 || C <= 0 || d <= 0 || Tcap <= 0) return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t s = (hipStream_t)stream_;
+  const bool vec = (d % 8 == 0) && ((((uintptr_t)x | (uintptr_t)pe | (uintptr_t)y) & 15) == 0);
+  const long n = (long)B * C * (vec ? d / 8 : d);
+  const dim3 grid((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096));
+#define TFASR_PE(TT, VV) TFASR_KLAUNCH((stream_add_pe_kernel<TT, VV>), grid, dim3(256), 0, s, (const TT*)x, pe, seen, nvalid, (TT*)y, B, C, d, Tcap)
+  if (dtype == TFASR_F32) { if (vec) TFASR_PE(float, true); else TFASR_PE(float, false); }
+  else { if (vec) TFASR_PE(bf16_t, true); else TFASR_PE(bf16_t, false); }
+#undef TFASR_PE
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }

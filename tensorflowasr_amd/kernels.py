@@ -1588,6 +1588,34 @@ def stream_kv_append(qkv, kcache, vcache, seen, nvalid, B, C, H, dh, hist):
           "stream_kv_append")
 
 
+def stream_attn_plain_fwd(qkv, kcache, vcache, seen, nvalid, B, C, H, dh, hist, scale, causal=False, out=None):
+    """Plain chunk attention against the key / value rings AND the ring append, one launch: qkv [B*C, 3*H*dh] (a 2-D view whose rows are
+    contiguous with stride 3*H*dh may start anywhere), kcache / vcache [B, hist, H*dh] (None with hist == 0), seen / nvalid [B] int32 on
+    the device -> context [B*C, H*dh] (rows >= nvalid zero); the chunk's valid k / v rows are in the rings afterwards."""
+    if out is None:
+        out = torch.empty(B * C, H * dh, dtype=qkv.dtype, device=qkv.device)
+    if qkv.dim() != 2 or qkv.shape != (B * C, 3 * H * dh) or qkv.stride() != (3 * H * dh, 1):
+        raise _lib.TfasrError(f"stream_attn_plain_fwd: qkv {tuple(qkv.shape)} strides {qkv.stride()} is not [B*C, 3*H*dh] with contiguous rows")
+    st = _L().tfasr_stream_attn_plain_fwd(_pv(qkv), _p(kcache), _p(vcache), _p(seen), _p(nvalid), _p(out), B, C, H, dh, hist, scale,
+                                          1 if causal else 0, _dt(qkv), _stream())
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported(f"stream_attn_plain_fwd: chunk {C} / keys {hist + C} / head {dh} / batch {B} beyond the kernel's limits "
+                                    f"({STREAM_MAX_CHUNK}, {STREAM_MAX_KEYS}, {STREAM_MAX_HEAD}, 65535)")
+    check(st, "stream_attn_plain_fwd")
+    return out
+
+
+def stream_add_pe(x, pe, seen, nvalid, y=None):
+    """y[b, r, :] = x[b, r, :] + pe[seen[b] + r, :] for r < nvalid[b], other rows copied: x [B, C, d] (f32 | bf16), pe [Tcap, d] f32; y may
+    be x.  A valid row at or past Tcap becomes NaN (the table is never read past its end)."""
+    B, C, d = x.shape
+    assert pe.dtype == torch.float32 and pe.dim() == 2 and pe.shape[1] == d
+    if y is None:
+        y = torch.empty_like(x)
+    check(_L().tfasr_stream_add_pe(_p(x), _p(pe), _p(seen), _p(nvalid), _p(y), B, C, d, pe.shape[0], _dt(x), _stream()), "stream_add_pe")
+    return y
+
+
 def stream_glu_dwconv_fwd(glu_x, state, w, bias, nvalid, B, C, out=None):
     """GLU + causal depthwise conv over state [B, K-1, d] ++ the chunk's valid rows; glu_x [B*C, 2d] -> [B*C, d]; state updated in place."""
     d = glu_x.shape[-1] // 2

@@ -11,6 +11,9 @@ session do.  State carried per stream:
     beam search   (beam_width >= 1) the whole beam: rows, f64 totals, label trie + table, prediction states (K.RnntBeamStream); the
                   CTC search's rows and trie (K.CtcBeamStream); the depth committed so far
 The kernels that touch carried state are csrc/stream.hip; the dense pieces are the forward kernels of training with T = chunk_size.
+A Transformer with a chunked config streams under the same contract (TransformerStreamState, transformer_encode_chunk): its blocks carry
+the K / V rings only (there is no convolution module), the absolute position rows are taken at each stream's own offset, and the ring
+append is part of the attention launch.
 """
 import math
 import typing
@@ -76,10 +79,33 @@ class StreamState:
             a.copy_(b)
 
 
+def _check_transformer(model):
+    """A Transformer streams when its attention mask is the chunked one (use_attention_auto_mask, chunk_size, history_size >= 0) and the
+    sizes fit tfasr_stream_attn_plain_fwd; the causal flag is allowed (the kernel has it).  Everything else is refused in the words of the
+    model's other refusals ("inference only") followed by the reason."""
+    c = model.cfg
+    why = None
+    if c.chunk_size is None:
+        why = "chunk_size is None (full-context attention sees the whole utterance)"
+    elif not c.use_attention_auto_mask:
+        why = "use_attention_auto_mask is off (no mask is computed: every frame attends over the whole utterance)"
+    elif c.history_size is None or int(c.history_size) < 0:
+        why = "unlimited history would need an unbounded key / value cache"
+    else:
+        C, hist, dh = int(c.chunk_size), int(c.history_size), int(c.head_size)
+        if C < 1 or C > K.STREAM_MAX_CHUNK or hist + C > K.STREAM_MAX_KEYS or dh > K.STREAM_MAX_HEAD:
+            why = (f"chunk_size {C} / history_size {hist} / head {dh} beyond the streaming kernels' limits (chunk <= {K.STREAM_MAX_CHUNK}, "
+                   f"history + chunk <= {K.STREAM_MAX_KEYS}, head <= {K.STREAM_MAX_HEAD})")
+    if why is not None:
+        raise NotImplementedError(f"{type(model).__name__} is inference only, and this configuration cannot be streamed: {why}")
+
+
 def check_streamable(model):
     c = model.cfg
     if getattr(c, "encoder", "conformer") == "jasper":
         return  # causal convolutions only: streams exactly (JasperStreamState)
+    if getattr(c, "encoder", "conformer") == "transformer":
+        return _check_transformer(model)
     if getattr(c, "encoder", "conformer") != "conformer":
         raise ValueError("streaming needs a Conformer encoder: ContextNet's squeeze-and-excite is a mean over the whole utterance")
     if c.chunk_size is None:
@@ -157,6 +183,107 @@ def encode_chunk(state, feats, nframes):
         x = m._ffm_fwd(x, p + "ff2/", None, 0, False)
         x, _, _ = K.layernorm_fwd(x, ps.p(p + "ln/g"), ps.p(p + "ln/b"))
     state.seen += nvalid
+    return x.view(B, C, d), nvalid
+
+
+class TransformerStreamState:
+    """Encoder state of `batch_size` Transformer streams: seen, the last 2 feature frames, the last 2 rows of the first convolution
+    block's activation (after the folded BatchNorm and the ReLU), one K and one V ring [B, history_size, H * head_size] per block.  The
+    absolute position table [Tcap, dmodel] f32 is a constant, not state: its rows depend on the position only, so it is grown by doubling
+    (from the frame counters kept on the host) before a launch would pass its end, and it is not exported."""
+
+    def __init__(self, model, batch_size):
+        check_streamable(model)
+        c, dev, dt = model.cfg, model.device, model.dtype
+        self.model, self.B = model, int(batch_size)
+        B, hist, HD = self.B, int(c.history_size), int(c.num_heads) * int(c.head_size)
+        F1 = (c.num_feature_bins + 1) // 2
+        self.seen = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.feat_carry = torch.zeros(B, 2, c.num_feature_bins, dtype=dt, device=dev)
+        self.conv_carry = torch.zeros(B, 2, F1, int(c.sub_filters[0]), dtype=dt, device=dev)
+        nb = int(c.num_blocks)
+        ring = lambda: torch.zeros(B, hist, HD, dtype=dt, device=dev) if hist > 0 else None
+        self.kcache, self.vcache = [ring() for _ in range(nb)], [ring() for _ in range(nb)]
+        self.host_seen = [0] * B  # encoder frames per stream, as the device vector `seen` holds them
+        self.pe = None
+        self.reserve(4 * int(c.chunk_size))
+
+    def reserve(self, rows):
+        """the position table covers positions 0 .. rows - 1 at least"""
+        cap = 0 if self.pe is None else self.pe.shape[0]
+        if rows <= cap:
+            return
+        cap = max(cap, 256)
+        while cap < rows:
+            cap *= 2
+        from .transformer import sinusoid_table
+
+        c = self.model.cfg
+        self.pe = torch.from_numpy(sinusoid_table(cap, c.dmodel, bool(c.interleave_relpe))).to(self.model.device).contiguous()
+
+    def _tensors(self):
+        return [self.seen, self.feat_carry, self.conv_carry] + [t for t in self.kcache + self.vcache if t is not None]
+
+    def reset(self, rows=None):
+        StreamState.reset(self, rows)
+        for b in (range(self.B) if rows is None else rows):
+            self.host_seen[b] = 0
+
+    export = StreamState.export
+
+    def load(self, tensors):
+        StreamState.load(self, tensors)
+        self.host_seen = [int(v) for v in self.seen.tolist()]
+
+
+@torch.no_grad()
+def transformer_encode_chunk(state, feats, nframes):
+    """One step of the streaming Transformer encoder: feats [B, n <= 4C, F] (compute dtype, device), nframes [B] feature frames that are
+    real per stream (0 = idle, 4C = a full chunk, fewer for a stream's last chunk) -> (enc [B, C, dmodel], nvalid [B] int32 device);
+    advances state.  The subsampling is encode_chunk's on this model's layers, the position rows are those of each stream's own offset
+    (tfasr_stream_add_pe), and a block is TransformerEncoderMixin.block_fwd at T = C around tfasr_stream_attn_plain_fwd, which also
+    appends the chunk's keys and values to the rings."""
+    m = state.model
+    c, ps, dev = m.cfg, m.ps, m.device
+    B, C, hist = state.B, int(c.chunk_size), int(c.history_size)
+    H, dh, d = int(c.num_heads), int(c.head_size), int(c.dmodel)
+    n0 = 4 * C
+    host = [int(v) for v in (nframes.tolist() if isinstance(nframes, torch.Tensor) else nframes)]
+    if feats.shape[0] != B or feats.shape[1] > n0 or len(host) != B or min(host) < 0 or max(host) > feats.shape[1]:
+        raise ValueError(f"encode_chunk takes [B = {B}, <= {n0}, F] feature frames and B frame counts within them")
+    nf = m._h2d(host)
+    cat = torch.zeros(B, n0 + 2, c.num_feature_bins, dtype=m.dtype, device=dev)
+    cat[:, :2] = state.feat_carry
+    cat[:, 2:2 + feats.shape[1]] = feats
+    n1 = (nf + 1) // 2
+    nvalid = ((n1 + 1) // 2).to(torch.int32).contiguous()
+    two = torch.arange(2, device=dev)
+    # the carries move to the last two VALID rows (rows nf, nf + 1 of carry ++ new; nf == 0 picks the carry itself)
+    idx = (nf.long()[:, None] + two[None, :])
+    state.feat_carry.copy_(torch.gather(cat, 1, idx[:, :, None].expand(B, 2, cat.shape[2])))
+    # causal 3x3 stride-2 convs on carry(2) ++ new(n): output 0 belongs to the previous chunk, outputs 1.. are the originals
+    c0, c1 = m.modules["convs"]
+    a1 = K.conv1_fwd(cat, ps.p(c0["name"] + "/w"), ps.p(c0["name"] + "/b"))  # [B, 2C + 1, F1, C0]
+    a1 = K.channel_affine_fwd(a1, *m._affine(c0["bn"]), relu=True, y=a1)
+    F1, C0 = a1.shape[2], a1.shape[3]
+    cat1 = torch.cat([state.conv_carry, a1[:, 1:]], 1).contiguous()  # [B, 2C + 2, F1, C0]
+    idx1 = (n1.long()[:, None] + two[None, :])
+    state.conv_carry.copy_(torch.gather(cat1, 1, idx1[:, :, None, None].expand(B, 2, F1, C0)))
+    col = K.im2col_3x3s2(cat1)
+    T2, F2 = (cat1.shape[1] + 1) // 2, (F1 + 1) // 2  # C + 1
+    a2 = K.matmul(col, ps.w2d(c1["name"] + "/w"), bias=ps.p(c1["name"] + "/b"))
+    a2 = K.channel_affine_fwd(a2, *m._affine(c1["bn"]), relu=True, y=a2)
+    merged = a2.view(B, T2, F2 * c1["cout"])[:, 1:].reshape(B * C, F2 * c1["cout"])
+    x = K.matmul(merged, ps.w2d("enc/linear/w"), bias=ps.p("enc/linear/b"))  # [B*C, d]
+    nv_host = [-(-(-(-t // 2)) // 2) for t in host]
+    state.reserve(max(s + n for s, n in zip(state.host_seen, nv_host)))
+    x = K.stream_add_pe(x.view(B, C, d), state.pe, state.seen, nvalid).view(B * C, d)
+    scale, causal = 1.0 / math.sqrt(dh), bool(c.use_attention_causal_mask)
+    for i, p in enumerate(m.modules["blocks"]):
+        attend = lambda qkv, i=i: K.stream_attn_plain_fwd(qkv, state.kcache[i], state.vcache[i], state.seen, nvalid, B, C, H, dh, hist, scale, causal)
+        x = m.block_fwd(x, p, B, C, None, i, attend=attend)
+    state.seen += nvalid
+    state.host_seen = [s + n for s, n in zip(state.host_seen, nv_host)]
     return x.view(B, C, d), nvalid
 
 
@@ -238,7 +365,11 @@ class StreamingRecognizer:
     A Jasper model (causal convolutions only) opens the same session through JasperCTC.stream(batch_size, chunk_frames=...): a step is
     chunk_frames feature frames instead of 4 * chunk_size, its encoder state is JasperStreamState (per layer with K > 1 taps the last
     (K - 1) * dilation input rows, sum over layers of B * (K - 1) * dilation * Cin elements), and in the CTC beam formula above chunk_size
-    reads chunk_frames / time_reduction_factor."""
+    reads chunk_frames / time_reduction_factor.
+
+    A Transformer model with a chunked config (TransformerCTC.stream / TransformerTransducer.stream) takes the Conformer's step,
+    4 * chunk_size feature frames, and the Conformer's frame reduction; its encoder state is TransformerStreamState (per block two rings of
+    B * history_size * num_heads * head_size elements, plus the two subsampling carries)."""
 
     def __init__(self, model, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000, chunk_frames=None):
         batch_size, max_tokens_per_frame, self.beam_width, self.max_frames = check_stream_args(batch_size, max_tokens_per_frame, beam_width,
@@ -249,7 +380,9 @@ class StreamingRecognizer:
         self.max_tokens_per_frame = int(max_tokens_per_frame)
         c = model.cfg
         self.jasper = getattr(c, "encoder", "conformer") == "jasper"
+        self._encode = encode_chunk
         if self.jasper:
+            self._encode = jasper_encode_chunk
             # a step is `chunk_frames` feature frames -> chunk_frames / factor encoder frames (a stream's last step: ceil of what is left)
             factor = int(c.time_reduction_factor)
             self.chunk_frames = int(chunk_frames if chunk_frames is not None else 32)
@@ -261,7 +394,10 @@ class StreamingRecognizer:
         else:
             if chunk_frames is not None:
                 raise ValueError("stream: chunk_frames belongs to the Jasper session; a Conformer's step is 4 * chunk_size feature frames")
-            self.state = StreamState(self.enc_model, batch_size)
+            if getattr(c, "encoder", "conformer") == "transformer":  # the Conformer's step and frame reduction, its own encoder state
+                self.state, self._encode = TransformerStreamState(self.enc_model, batch_size), transformer_encode_chunk
+            else:
+                self.state = StreamState(self.enc_model, batch_size)
             self.C = int(c.chunk_size)
             self.chunk_frames = 4 * self.C
             self._reduce = lambda t: -(-(-(-t // 2)) // 2)
@@ -364,7 +500,7 @@ class StreamingRecognizer:
                         self.prev[b], self.has_prev[b] = self.buf[b][used - 1], 1
                     self.buf[b] = self.buf[b][used:]
                     self.emitted[b] += take[b]
-            enc, nvalid = (jasper_encode_chunk if self.jasper else encode_chunk)(self.state, feats, take)
+            enc, nvalid = self._encode(self.state, feats, take)
             nv = [self._reduce(t) for t in take]
             if self.encoded_log is not None:
                 self.encoded_log.append((enc, nv))

@@ -1,4 +1,4 @@
-"""Transformer CTC and transducer models on the HIP kernels and C ABI of the other models, inference only, offline.
+"""Transformer CTC and transducer models on the HIP kernels and C ABI of the other models, inference only, offline and streamed.
 
 Mirrors  tensorflow_asr.models.ctc.transformer.Transformer          (models/ctc/transformer.py:56-121: TransformerEncoder + TransformerDecoder)
          tensorflow_asr.models.transducer.transformer.Transformer   (models/transducer/transformer.py:21-120: the same encoder under Transducer)
@@ -33,8 +33,12 @@ the query is the LayerNorm's output and every block sees it.  The reference's ow
 with its mask; use_attention_auto_mask=False removes every mask, as in the reference (multihead_attention.py:375-384).
 
 Decoders, forced alignment, evaluate, the precision switch (f32 twin by default, bf16 opt-in) and the .npz checkpoints are inherited.
-Training, streaming sessions (they need a plain-attention counterpart of tfasr_stream_attn_fwd), relmha, the Memory cache and
-.weights.h5 import are not built: train_step / loss_and_backward / compile / stream / stream_state / encode_chunk raise.
+A chunked config (use_attention_auto_mask, chunk_size, history_size >= 0) also streams: stream / stream_state / encode_chunk open the
+sessions of tensorflowasr_amd/streaming.py (TransformerStreamState, transformer_encode_chunk: tfasr_stream_add_pe for the position rows
+at each stream's offset, tfasr_stream_attn_plain_fwd for the chunk against the carried K / V rings).  Stream b holds the frames of that
+utterance run ALONE: in a padded batch the padded frames of a shorter row's last chunk are visible keys (see Masking above).
+Training, relmha, the Memory cache, unlimited history, look-ahead and .weights.h5 import are not built: train_step / loss_and_backward /
+compile raise, and so do the three streaming entry points for a config that cannot be streamed.
 """
 import numpy as np
 import torch
@@ -80,9 +84,35 @@ class TransformerEncoderMixin:
     # ------------------------------------------------------------------------------------------- inference only
     def _inference_only(self, *a, **k):
         raise NotImplementedError(f"{type(self).__name__} is inference only: the plain-attention backward and BatchNorm in batch-statistics "
-                                  "mode are not built, and neither are streaming sessions (weights arrive through load_weights)")
+                                  "mode are not built (weights arrive through load_weights)")
 
-    train_step = loss_and_backward = compile = stream = stream_state = encode_chunk = _inference_only
+    train_step = loss_and_backward = compile = _inference_only
+
+    # ------------------------------------------------------------------------------------------- streaming (tensorflowasr_amd/streaming.py)
+    # A config that cannot be streamed (full context, no auto mask, unlimited history, sizes beyond the kernel) is refused by
+    # streaming.check_streamable before any argument is looked at: NotImplementedError, "... inference only ..." and the reason.
+    def stream(self, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
+        """Incremental recognition session (streaming.StreamingRecognizer) of a chunked config (base-streaming.yml.j2): a step is
+        4 * chunk_size feature frames; stream b gives the frames and tokens of that utterance run ALONE, however the samples arrive.
+        Sessions, beams and their memory as ConformerTransducer.stream / ConformerCTC.stream."""
+        from . import streaming
+
+        streaming.check_streamable(self)
+        return streaming.StreamingRecognizer(self, batch_size, precision, max_tokens_per_frame, beam_width, max_frames)
+
+    def stream_state(self, batch_size=1, precision=None):
+        """Encoder state of `batch_size` streams for encode_chunk (streaming.TransformerStreamState).  precision as encode."""
+        from . import streaming
+
+        streaming.check_streamable(self)
+        return streaming.TransformerStreamState(streaming._twin(self, precision), batch_size)
+
+    def encode_chunk(self, state, feats, nframes):
+        """One chunk of the streaming encoder: feats [B, n <= 4 chunk_size, F], nframes [B] -> (enc [B, chunk_size, dmodel], nvalid [B])."""
+        from . import streaming
+
+        streaming.check_streamable(self)
+        return streaming.transformer_encode_chunk(state, feats, nframes)
 
     def _encoder_length(self, t):
         return self.cfg.encoder_length(t)
@@ -171,13 +201,14 @@ class TransformerEncoderMixin:
             raise NotImplementedError("the unfused attention route has no causal mask")
         return unfused_attention(qkv, lens_dev, B, H, T, dh, scale, m["use_mask"], m["chunk_size"], m["history_size"])
 
-    def block_fwd(self, x, p, B, T, lens_dev, index=0):
-        """one TransformerBlock: x [B*T, d] -> [B*T, d]; index = its position in the encoder (which decides whether it sees the length mask)"""
+    def block_fwd(self, x, p, B, T, lens_dev, index=0, attend=None):
+        """one TransformerBlock: x [B*T, d] -> [B*T, d]; index = its position in the encoder (which decides whether it sees the length mask);
+        attend(qkv) -> context stands in for attention_fwd (the streaming step: the chunk against the rings, T = chunk_size)"""
         ps, c = self.ps, self.cfg
         f, pre = float(c.residual_factor), c.norm_position == "pre"
         h = K.layernorm_fwd(x, ps.p(p + "/ln_1/g"), ps.p(p + "/ln_1/b"), save_stats=False)[0] if pre else x
         qkv = K.matmul(h, ps.w2d(p + "/mhsa/qkv/w"), bias=ps.p(p + "/mhsa/qkv/b"))
-        ctxv = self.attention_fwd(qkv, B, T, lens_dev, index)
+        ctxv = attend(qkv) if attend is not None else self.attention_fwd(qkv, B, T, lens_dev, index)
         if pre:
             a = K.matmul(ctxv, ps.w2d(p + "/mhsa/o/w"), bias=ps.p(p + "/mhsa/o/b"), res=x, beta=f)
             h = K.layernorm_fwd(a, ps.p(p + "/ln_2/g"), ps.p(p + "/ln_2/b"), save_stats=False)[0]
