@@ -7,7 +7,7 @@
 // base's blank is 0 (base_ctc.py passes no blank index to the beam decoder) - so `blank_index` is a parameter and the Python
 // host passes V-1 to reproduce recognize_beam, 0 for a self-consistent decoder.
 #include "common.h"
-#include "beam_trie.h"
+#include "beam_select.h"
 #include <algorithm>
 #include <cmath>
 #include <unordered_map>
@@ -172,20 +172,13 @@ extern "C" int tfasr_ctc_beam_search_host(const float* logits, const int32_t* lo
 // Device prefix beam search (tfasr_ctc_beam_search): the same decoder as tfasr_ctc_beam_search_host above, stream ordered, with the
 // top `top_paths` paths of the final beam.  Two launches:
 //
-// 1. ctc_beam_frame_kernel, one wave per (b, t) row: the row's log-sum-exp (f32 max + f64 sum, the host routine's arithmetic, so
-//    lp = x - lse comes out as the host's value) and the row's top K = min(2W, V-1) NON-blank classes by (lp desc, class asc).
-//    Why 2W classes are enough: beam i extended by class c scores ptot_i + lp[c], monotone in lp[c], except for the classes that
-//    are "special" to row i: its own last label (a repeat adds pb_i, not ptot_i) and the merge targets (the labels of the beams
-//    whose parent is beam i: their "stay" mass joins the extension).  Row i has at most nb <= W specials, computed explicitly from
-//    logits - lse.  So at least W of the global top 2W classes are regular for row i, and they are row i's best W regular
-//    extensions; an extension outside them is beaten by W candidates of its own row and cannot enter a beam of width W.  The
-//    per-frame search is O(W^2) candidates instead of O(W*V).
-// 2. ctc_beam_search_kernel, one workgroup per utterance, all frames in one launch.  Per frame: stays (merged into their parent's
-//    extension when the parent is a beam, as in the host routine), specials, and each row's first W regular extensions from the
-//    top-K list become candidates in LDS (<= W^2 + 3W); each candidate counts the candidates better than it (early exit at W), the
-//    first W by (total desc, label sequence asc) are the next beam.  Label sequences live in a per-utterance trie in the workspace
-//    with an open-addressing (parent, label) -> node table: one node per label sequence for the whole utterance, so a prefix that
-//    leaves the beam and comes back keeps its mass.  The comparator walks the trie only on an exact tie of totals.
+// 1. ctc_beam_frame_kernel, one wave per (b, t) row: beam_select.h's frame pass in f32 (the host routine's arithmetic, so
+//    lp = x - lse comes out as the host's value).
+// 2. ctc_beam_search_kernel, one workgroup per utterance, all frames in one launch, the beam in LDS.  Per frame beam_select.h's
+//    selection over at most W^2 + 3W candidates, with what is CTC's own: a row carries the (blank-ending, label-ending) pair, a
+//    stay is merged into its parent's extension when the parent is a beam (as in the host routine), and the classes special to
+//    row i are its own last label (a repeat adds pb_i, not ptot_i) and its merge targets (the labels of the beams whose parent
+//    is beam i: their stay mass joins the extension).
 //
 // The search in pieces (tfasr_ctc_beam_reset / _advance / _commit / _nbest, streaming sessions) is the same two kernels: the search
 // kernel loads its LDS beam from the workspace's carry area instead of starting from the empty prefix, runs the chunk's frames and
@@ -193,20 +186,11 @@ extern "C" int tfasr_ctc_beam_search_host(const float* logits, const int32_t* lo
 // ================================================================================================================================
 namespace {
 
-constexpr int BEAM_MAXW = 64;
-constexpr int BEAM_MAXK = 2 * BEAM_MAXW;
-constexpr int BEAM_MAXC = BEAM_MAXW * BEAM_MAXW + 3 * BEAM_MAXW;  // stays + specials (<= 2 per beam) + W regulars per beam
-constexpr int BEAM_THREADS = 256;
+using namespace beam_select;
+using beam_trie::seq_less;
 
-__device__ __forceinline__ float dlse2(float a, float b) {  // lse2 above, same operation order
-  if (a == -INFINITY) return b;
-  if (b == -INFINITY) return a;
-  const float m = a > b ? a : b;
-  return m + log1pf(expf(-fabsf(a - b)));
-}
-
-// (lp, c) comes before (lq, d) in the frame's class order
-__device__ __forceinline__ bool cls_before(float lp, int c, float lq, int d) { return lp > lq || (lp == lq && c < d); }
+constexpr int BEAM_MAXK = 2 * MAXW;
+constexpr int BEAM_MAXC = MAXW * MAXW + 3 * MAXW;  // stays + specials (<= 2 per beam) + W regulars per beam
 
 template <typename T>
 __global__ __launch_bounds__(256) void ctc_beam_frame_kernel(const T* __restrict__ logits, const int32_t* __restrict__ logit_len,
@@ -254,17 +238,12 @@ __global__ __launch_bounds__(256) void ctc_beam_frame_kernel(const T* __restrict
   }
 }
 
-using beam_trie::Seq;
-using beam_trie::Trie;
-using beam_trie::seq_less;
-
-// the beam of every stream between two advances: what the search kernel holds in LDS, [B][W] each, and [B][CC_N] counters
+// the beam of every stream between two advances: what the search kernel holds in LDS, [B][W] each, and [B][CNT_N] counters
 struct CtcCarry { int *node, *par, *lab, *dep; float *pb, *pnb; int* cnt; };
-enum { CC_LIVE = 0, CC_NODES = 1, CC_FRAMES = 2, CC_N = 4 };
 enum { BEAM_LOAD = 1, BEAM_STORE = 2, BEAM_OUTPUT = 4 };  // one-shot search: BEAM_OUTPUT alone
 
 template <typename T>
-__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
+__global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
     const T* __restrict__ logits, const int32_t* __restrict__ logit_len, const float* __restrict__ lse_ws,
     const float* __restrict__ lpb_ws, const int32_t* __restrict__ top_c, const float* __restrict__ top_lp, int* trie_parent,
     int* trie_label, int* trie_depth, unsigned long long* hkeys, int* hvals, int Tm, int V, int W, int K, int P, long nmax,
@@ -273,43 +252,42 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
   // Tm = frames per utterance of `logits` (the whole utterance or one chunk), OW = the row width of `tokens`, Tcap = the most frames a
   // carried beam takes (its trie holds 1 + W * Tcap nodes)
   // beam state (node, its parent / last label / depth, probabilities) and per-frame scratch
-  __shared__ int bnode[BEAM_MAXW], bpar[BEAM_MAXW], blab[BEAM_MAXW], bdep[BEAM_MAXW], merged[BEAM_MAXW];
-  __shared__ float bpb[BEAM_MAXW], bpnb[BEAM_MAXW], bptot[BEAM_MAXW], lpl[BEAM_MAXW], spb[BEAM_MAXW], spnb[BEAM_MAXW];
-  __shared__ int nnode[BEAM_MAXW], npar[BEAM_MAXW], nlab[BEAM_MAXW], ndep[BEAM_MAXW], win[BEAM_MAXW];
-  __shared__ float npb[BEAM_MAXW], npnb[BEAM_MAXW];
+  __shared__ int bnode[MAXW], bpar[MAXW], blab[MAXW], bdep[MAXW], merged[MAXW];
+  __shared__ float bpb[MAXW], bpnb[MAXW], bptot[MAXW], lpl[MAXW], spb[MAXW], spnb[MAXW];
+  __shared__ int nnode[MAXW], npar[MAXW], nlab[MAXW], ndep[MAXW], win[MAXW];
+  __shared__ float npb[MAXW], npnb[MAXW];
   __shared__ int kc[BEAM_MAXK];
   __shared__ float klp[BEAM_MAXK];
   __shared__ float ctot[BEAM_MAXC];
-  __shared__ unsigned ccode[BEAM_MAXC];  // src | (label + 1) << 6; label -1 = the beam itself ("stay")
+  __shared__ unsigned ccode[BEAM_MAXC];
   __shared__ int s_nc, s_nb, s_ntrie;
 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   int Tb = logit_len ? min(max(logit_len[b], 0), Tm) : 0;
   if ((mode & BEAM_LOAD) && !(mode & BEAM_OUTPUT) && Tb == 0) return;  // an idle stream keeps every byte of its beam
-  const Trie tr{trie_parent + (long)b * nmax, trie_label + (long)b * nmax, trie_depth + (long)b * nmax};
+  const Trie tr = trie_at(trie_parent, trie_label, trie_depth, (long)b * nmax);
   unsigned long long* hk = hkeys + (long)b * hcap;
   int* hv = hvals + (long)b * hcap;
   int frames0 = 0;
   if (mode & BEAM_LOAD) {
-    const int* cnt = cy.cnt + b * CC_N;
-    const int nb0 = min(max(cnt[CC_LIVE], 0), W);
+    const int* cnt = cy.cnt + b * CNT_N;
+    const int nb0 = min(max(cnt[CNT_LIVE], 0), W);
     const long c0 = (long)b * W;
     if (tid < nb0) {
       bnode[tid] = cy.node[c0 + tid]; bpar[tid] = cy.par[c0 + tid]; blab[tid] = cy.lab[c0 + tid]; bdep[tid] = cy.dep[c0 + tid];
       bpb[tid] = cy.pb[c0 + tid]; bpnb[tid] = cy.pnb[c0 + tid];
     }
-    if (tid == 0) { s_nb = nb0; s_ntrie = cnt[CC_NODES]; }
-    frames0 = cnt[CC_FRAMES];
+    if (tid == 0) { s_nb = nb0; s_ntrie = cnt[CNT_NODES]; }
+    frames0 = cnt[CNT_FRAMES];
     Tb = min(Tb, max(Tcap - frames0, 0));
   } else {
-    for (unsigned i = tid; i < hcap; i += BEAM_THREADS) hk[i] = beam_trie::EMPTY;
+    clear_stream(tr, hk, hcap, tid);
     if (tid == 0) {
-      tr.parent[0] = -1; tr.label[0] = -1; tr.depth[0] = 0;
       bnode[0] = 0; bpar[0] = -1; blab[0] = -1; bdep[0] = 0; bpb[0] = 0.f; bpnb[0] = -INFINITY;
       s_nb = 1; s_ntrie = 1;
     }
   }
-  if (tid < BEAM_MAXW) win[tid] = 0;
+  if (tid < MAXW) win[tid] = 0;
   __syncthreads();
 
   for (int t = 0; t < Tb; ++t) {
@@ -319,10 +297,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
     const int nb = s_nb;
     if (tid < K) { kc[tid] = top_c[r * K + tid]; klp[tid] = top_lp[r * K + tid]; }
     if (tid < nb) {
-      bptot[tid] = dlse2(bpb[tid], bpnb[tid]);
+      bptot[tid] = lae(bpb[tid], bpnb[tid]);
       lpl[tid] = bpar[tid] >= 0 ? Num<T>::ld(row + blab[tid]) - lz : -INFINITY;
     }
-    if (tid < BEAM_MAXW) win[tid] = 0;
+    if (tid < MAXW) win[tid] = 0;
     if (tid == 0) s_nc = 0;
     __syncthreads();
     if (tid < nb) {
@@ -338,11 +316,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
     // --- candidates: stays not merged into a parent's extension
     if (tid < nb && merged[tid] < 0) {
       const int q = atomicAdd(&s_nc, 1);
-      ctot[q] = dlse2(spb[tid], spnb[tid]);
-      ccode[q] = (unsigned)tid;
+      ctot[q] = lae(spb[tid], spnb[tid]);
+      ccode[q] = cand_code(tid, -1);
     }
     // --- specials: pair (i, j): beam j's stay merged into (beam i, label of j); (i, i): beam i repeating its own last label
-    for (int pq = tid; pq < nb * nb; pq += BEAM_THREADS) {
+    for (int pq = tid; pq < nb * nb; pq += THREADS) {
       const int i = pq / nb, j = pq % nb;
       int c = -1, child = -1;
       if (j != i && merged[j] == i) { c = blab[j]; child = j; }
@@ -359,64 +337,30 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
       if (child < 0)
         for (int k = 0; k < nb; ++k)
           if (merged[k] == i && blab[k] == c) child = k;
-      if (child >= 0) { ext_pb = spb[child]; ext = dlse2(ext, spnb[child]); }
-      const float tot = dlse2(ext_pb, ext);
+      if (child >= 0) { ext_pb = spb[child]; ext = lae(ext, spnb[child]); }
+      const float tot = lae(ext_pb, ext);
       if (tot != -INFINITY) {
         const int q = atomicAdd(&s_nc, 1);
         ctot[q] = tot;
-        ccode[q] = (unsigned)i | ((unsigned)(c + 1) << 6);
+        ccode[q] = cand_code(i, c);
       }
     }
-    // --- regulars: wave per beam, lane per top-K class; the first W classes of the row that are not special to it
-    for (int i = wid; i < nb; i += BEAM_THREADS / 64) {
-      int seen = 0;
-      for (int k0 = 0; k0 < K; k0 += 64) {
-        const int k = k0 + lane;
-        bool reg = false;
-        int c = -1;
-        if (k < K) {
-          c = kc[k];
-          reg = !(bpar[i] >= 0 && c == blab[i]);
-          for (int j = 0; j < nb && reg; ++j)
-            if (merged[j] == i && blab[j] == c) reg = false;
-        }
-        const unsigned long long mask = __ballot(reg);
-        const int rank = seen + __popcll(mask & ((1ull << lane) - 1ull));
-        seen += __popcll(mask);
-        if (reg && rank < W && bptot[i] != -INFINITY) {
-          const float tot = bptot[i] + klp[k];
-          if (tot != -INFINITY) {
-            const int q = atomicAdd(&s_nc, 1);
-            ctot[q] = tot;
-            ccode[q] = (unsigned)i | ((unsigned)(c + 1) << 6);
-          }
-        }
-      }
-    }
+    // --- regulars: wave per beam; special to row i = its own last label and its merge targets
+    for (int i = wid; i < nb; i += THREADS / 64)
+      push_regulars(i, bptot[i], kc, klp, K, W, lane, [&](int c) {
+        bool special = bpar[i] >= 0 && c == blab[i];
+        for (int j = 0; j < nb && !special; ++j) special = merged[j] == i && blab[j] == c;
+        return special;
+      }, ctot, ccode, &s_nc);
     __syncthreads();
-    // --- the best `keep` candidates: rank = number of better candidates (exact order, so ranks are distinct)
     const int nc = s_nc, keep = min(W, nc);
-    for (int q = tid; q < nc; q += BEAM_THREADS) {
-      const float tq = ctot[q];
-      const unsigned cq = ccode[q];
-      const Seq sq{bnode[cq & 63], (int)(cq >> 6) - 1};
-      int rank = 0;
-      for (int p = 0; p < nc && rank < keep; ++p) {
-        const float tp = ctot[p];
-        if (tp > tq) ++rank;
-        else if (tp == tq && p != q) {
-          const unsigned cp = ccode[p];
-          if (seq_less(tr, Seq{bnode[cp & 63], (int)(cp >> 6) - 1}, sq)) ++rank;
-        }
-      }
-      if (rank < keep) win[rank] = q;
-    }
+    rank_candidates(ctot, ccode, nc, keep, bnode, tr, win, tid);
     __syncthreads();
     // --- the next beam: probabilities and (parent, label) of each winner; look the extended prefix up in the table
     bool fresh = false;
     if (tid < keep) {
       const unsigned code = ccode[win[tid]];
-      const int i = code & 63, c = (int)(code >> 6) - 1;
+      const int i = cand_row(code), c = cand_label(code);
       if (c < 0) {
         nnode[tid] = bnode[i]; npar[tid] = bpar[i]; nlab[tid] = blab[i]; ndep[tid] = bdep[i];
         npb[tid] = spb[i]; npnb[tid] = spnb[i];
@@ -425,7 +369,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
         const float add = rep ? bpb[i] : bptot[i];
         float ext = add != -INFINITY ? add + (Num<T>::ld(row + c) - lz) : -INFINITY, ext_pb = -INFINITY;
         for (int k = 0; k < nb; ++k)
-          if (merged[k] == i && blab[k] == c) { ext_pb = spb[k]; ext = dlse2(ext, spnb[k]); }
+          if (merged[k] == i && blab[k] == c) { ext_pb = spb[k]; ext = lae(ext, spnb[k]); }
         npb[tid] = ext_pb; npnb[tid] = ext;
         npar[tid] = bnode[i]; nlab[tid] = c; ndep[tid] = bdep[i] + 1;
         const int node = beam_trie::lookup(hk, hv, hcap, bnode[i], c);
@@ -433,18 +377,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
         fresh = node < 0;
       }
     }
-    // new nodes numbered in rank order (keep <= 64: wave 0 holds every winner)
-    int nfresh = 0;
-    if (wid == 0) {
-      const unsigned long long mask = __ballot(fresh);
-      nfresh = __popcll(mask);
-      if (fresh) {
-        const int node = s_ntrie + __popcll(mask & ((1ull << lane) - 1ull));
-        nnode[tid] = node;
-        tr.parent[node] = npar[tid]; tr.label[node] = nlab[tid]; tr.depth[node] = ndep[tid];
-        beam_trie::insert(hk, hv, hcap, npar[tid], nlab[tid], node);
-      }
-    }
+    const int nfresh = grow_trie(fresh, tid, &s_ntrie, tr, hk, hv, hcap, nnode, npar, nlab, ndep);
     __syncthreads();
     if (tid < keep) {
       bnode[tid] = nnode[tid]; bpar[tid] = npar[tid]; blab[tid] = nlab[tid]; bdep[tid] = ndep[tid];
@@ -465,17 +398,17 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
       cy.pb[c0 + tid] = bpb[tid]; cy.pnb[c0 + tid] = bpnb[tid];
     }
     if (tid == 0) {
-      int* cnt = cy.cnt + b * CC_N;
-      cnt[CC_LIVE] = nb; cnt[CC_NODES] = s_ntrie; cnt[CC_FRAMES] = frames0 + Tb;
+      int* cnt = cy.cnt + b * CNT_N;
+      cnt[CNT_LIVE] = nb; cnt[CNT_NODES] = s_ntrie; cnt[CNT_FRAMES] = frames0 + Tb;
     }
   }
   if (!(mode & BEAM_OUTPUT)) return;
   // final beam, best first (ties: smaller label sequence); top P paths, dense and 0 padded
   if (tid < nb) {
-    const float tq = dlse2(bpb[tid], bpnb[tid]);
+    const float tq = lae(bpb[tid], bpnb[tid]);
     int rank = 0;
     for (int p = 0; p < nb; ++p) {
-      const float tp = dlse2(bpb[p], bpnb[p]);
+      const float tp = lae(bpb[p], bpnb[p]);
       if (tp > tq || (tp == tq && p != tid && seq_less(tr, Seq{bnode[p], -1}, Seq{bnode[tid], -1}))) ++rank;
     }
     if (rank < P) {
@@ -485,35 +418,22 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_search_kernel(
   }
   __syncthreads();
   const long obase = (long)b * P;
-  for (int p = tid; p < P; p += BEAM_THREADS) {
-    tokens_len[obase + p] = p < nb ? bdep[win[p]] : 0;
-    log_prob[obase + p] = p < nb ? npb[p] : -INFINITY;
-  }
-  for (long e = tid; e < (long)P * OW; e += BEAM_THREADS) {
-    const int p = (int)(e / OW), pos = (int)(e % OW);
-    if (p >= nb || pos >= bdep[win[p]]) tokens[obase * OW + e] = 0;
-  }
-  if (tid < min(nb, P)) {
-    int32_t* out = tokens + (obase + tid) * OW;
-    for (int n = bnode[win[tid]], d = bdep[win[tid]]; n > 0; n = tr.parent[n])
-      if (--d < OW) out[d] = tr.label[n];  // (a row as wide as the frames searched holds every label)
-  }
+  for (int p = tid; p < P; p += THREADS) log_prob[obase + p] = p < nb ? npb[p] : -INFINITY;
+  write_paths(tr, nb, P, OW, 0, tid, [&](int p) { return bnode[win[p]]; }, tokens + obase * OW, tokens_len + obase);
 }
 
 // ---- tfasr_ctc_beam_reset: the streams named by `mask` (NULL: all) hold the empty prefix alone ----
-__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_reset_kernel(const int32_t* __restrict__ mask, int* trie_parent, int* trie_label,
-                                                                      int* trie_depth, unsigned long long* hkeys, CtcCarry cy, int W, long nmax,
-                                                                      unsigned hcap) {
+__global__ __launch_bounds__(THREADS) void ctc_beam_reset_kernel(const int32_t* __restrict__ mask, int* trie_parent, int* trie_label,
+                                                                 int* trie_depth, unsigned long long* hkeys, CtcCarry cy, int W, long nmax,
+                                                                 unsigned hcap) {
   const int b = blockIdx.x, tid = threadIdx.x;
   if (mask && !mask[b]) return;
-  unsigned long long* hk = hkeys + (long)b * hcap;
-  for (unsigned i = tid; i < hcap; i += BEAM_THREADS) hk[i] = beam_trie::EMPTY;
+  clear_stream(trie_at(trie_parent, trie_label, trie_depth, (long)b * nmax), hkeys + (long)b * hcap, hcap, tid);
   if (tid == 0) {
-    const long n0 = (long)b * nmax, c0 = (long)b * W;
-    trie_parent[n0] = -1; trie_label[n0] = -1; trie_depth[n0] = 0;
+    const long c0 = (long)b * W;
     cy.node[c0] = 0; cy.par[c0] = -1; cy.lab[c0] = -1; cy.dep[c0] = 0; cy.pb[c0] = 0.f; cy.pnb[c0] = -INFINITY;
-    int* cnt = cy.cnt + b * CC_N;
-    cnt[CC_LIVE] = 1; cnt[CC_NODES] = 1; cnt[CC_FRAMES] = 0;
+    int* cnt = cy.cnt + b * CNT_N;
+    cnt[CNT_LIVE] = 1; cnt[CNT_NODES] = 1; cnt[CNT_FRAMES] = 0;
   }
 }
 
@@ -523,54 +443,44 @@ __global__ __launch_bounds__(64) void ctc_beam_commit_kernel(int* trie_parent, i
                                                             int32_t* __restrict__ tokens, int32_t* __restrict__ ntokens, int W, int width,
                                                             long nmax) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int nb = min(max(cy.cnt[b * CC_N + CC_LIVE], 0), W);
-  const Trie tr{trie_parent + (long)b * nmax, trie_label + (long)b * nmax, trie_depth + (long)b * nmax};
+  const int nb = min(max(cy.cnt[b * CNT_N + CNT_LIVE], 0), W);
+  const Trie tr = trie_at(trie_parent, trie_label, trie_depth, (long)b * nmax);
   const bool live = lane < nb;
   const long c0 = (long)b * W;
   const int node = live ? cy.node[c0 + lane] : 0;
-  int target = 0;
+  int best_lane = -1;
   if (nb > 0 && fin && fin[b]) {
-    const float tq = live ? dlse2(cy.pb[c0 + lane], cy.pnb[c0 + lane]) : -INFINITY;
+    const float tq = live ? lae(cy.pb[c0 + lane], cy.pnb[c0 + lane]) : -INFINITY;
     bool best = live;
     for (int p = 0; p < nb && best; ++p) {
-      const float tp = dlse2(cy.pb[c0 + p], cy.pnb[c0 + p]);
+      const float tp = lae(cy.pb[c0 + p], cy.pnb[c0 + p]);
       if (tp > tq || (tp == tq && p != lane && seq_less(tr, Seq{cy.node[c0 + p], -1}, Seq{node, -1}))) best = false;
     }
     const unsigned long long m = __ballot(best);
-    target = m ? __shfl(node, __ffsll((long long)m) - 1, 64) : __shfl(node, 0, 64);
-  } else if (nb > 0) {
-    target = beam_trie::common_ancestor(tr, node, live);
+    best_lane = m ? __ffsll((long long)m) - 1 : 0;
   }
-  beam_trie::commit_labels(tr, target, lane, committed + b, tokens + (long)b * width, ntokens + b, width, 0);
+  commit_stream(tr, node, live, nb, best_lane, lane, committed + b, tokens + (long)b * width, ntokens + b, width, 0);
 }
 
-inline size_t beam_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct BeamLayout {
-  int K;
-  long nmax;
-  unsigned hcap;
+struct BeamLayout : Geometry {
   size_t off_lse, off_lpb, off_tc, off_tlp, off_par, off_lab, off_dep, off_hk, off_hv, off_carry, total;
 };
 
 // C = frames per launch (the per-frame scratch), Tcap = frames per beam (the trie); the one-shot search has C = Tcap = T
 inline BeamLayout beam_layout(int B, int C, int Tcap, int V, int W) {
-  BeamLayout L;
-  L.K = std::min(2 * W, V - 1);
-  L.nmax = 1 + (long)W * Tcap;  // at most W new nodes per frame
-  L.hcap = beam_trie::table_cap(L.nmax);
+  BeamLayout L{Geometry(Tcap, V, W)};
   const size_t rows = (size_t)B * C;
   size_t o = 0;
-  L.off_lse = o; o += beam_align(rows * 4);
-  L.off_lpb = o; o += beam_align(rows * 4);
-  L.off_tc = o; o += beam_align(rows * L.K * 4);
-  L.off_tlp = o; o += beam_align(rows * L.K * 4);
-  L.off_par = o; o += beam_align((size_t)B * L.nmax * 4);
-  L.off_lab = o; o += beam_align((size_t)B * L.nmax * 4);
-  L.off_dep = o; o += beam_align((size_t)B * L.nmax * 4);
-  L.off_hk = o; o += beam_align((size_t)B * L.hcap * 8);
-  L.off_hv = o; o += beam_align((size_t)B * L.hcap * 4);
-  L.off_carry = o; o += 6 * beam_align((size_t)B * W * 4) + beam_align((size_t)B * CC_N * 4);
+  L.off_lse = o; o += align256(rows * 4);
+  L.off_lpb = o; o += align256(rows * 4);
+  L.off_tc = o; o += align256(rows * L.K * 4);
+  L.off_tlp = o; o += align256(rows * L.K * 4);
+  L.off_par = o; o += align256((size_t)B * L.nmax * 4);
+  L.off_lab = o; o += align256((size_t)B * L.nmax * 4);
+  L.off_dep = o; o += align256((size_t)B * L.nmax * 4);
+  L.off_hk = o; o += align256((size_t)B * L.hcap * 8);
+  L.off_hv = o; o += align256((size_t)B * L.hcap * 4);
+  L.off_carry = o; o += 6 * align256((size_t)B * W * 4) + align256((size_t)B * CNT_N * 4);
   L.total = o;
   return L;
 }
@@ -583,7 +493,7 @@ inline BeamWs beam_carve(const BeamLayout& L, void* workspace, int B, int W) {
   w.lse = (float*)(ws + L.off_lse); w.lpb = (float*)(ws + L.off_lpb); w.tc = (int32_t*)(ws + L.off_tc); w.tlp = (float*)(ws + L.off_tlp);
   w.par = (int*)(ws + L.off_par); w.lab = (int*)(ws + L.off_lab); w.dep = (int*)(ws + L.off_dep);
   w.hk = (unsigned long long*)(ws + L.off_hk); w.hv = (int*)(ws + L.off_hv);
-  const size_t a = beam_align((size_t)B * W * 4);
+  const size_t a = align256((size_t)B * W * 4);
   char* c = ws + L.off_carry;
   w.cy = CtcCarry{(int*)c, (int*)(c + a), (int*)(c + 2 * a), (int*)(c + 3 * a), (float*)(c + 4 * a), (float*)(c + 5 * a), (int*)(c + 6 * a)};
   return w;
@@ -598,16 +508,13 @@ int beam_launch(const BeamLayout& L, const BeamWs& w, const void* logits, const 
     const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
     TFASR_KLAUNCH(ctc_beam_frame_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)logits, logit_len, w.lse, w.lpb, w.tc, w.tlp, B, C, V, L.K, blank);
   }
-  TFASR_KLAUNCH(ctc_beam_search_kernel<T>, dim3(B), dim3(BEAM_THREADS), 0, s, (const T*)logits, logit_len, w.lse, w.lpb, w.tc, w.tlp, w.par, w.lab,
+  TFASR_KLAUNCH(ctc_beam_search_kernel<T>, dim3(B), dim3(THREADS), 0, s, (const T*)logits, logit_len, w.lse, w.lpb, w.tc, w.tlp, w.par, w.lab,
                 w.dep, w.hk, w.hv, C, V, W, L.K, P, L.nmax, L.hcap, tokens, tokens_len, log_prob, w.cy, mode, Tcap, OW);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
 
-inline bool beam_shape_ok(int B, int T, int V, int W) {
-  // T * W bounded so that node ids and table sizes stay in int / unsigned range; V bounded by the candidate code's label field
-  return B > 0 && T > 0 && V >= 2 && V < (1 << 25) && W >= 1 && W <= BEAM_MAXW && (long)T * W < (1L << 28);
-}
+inline bool beam_shape_ok(int B, int T, int V, int W) { return B > 0 && shape_ok(T, V, W); }
 
 }  // namespace
 
@@ -652,7 +559,7 @@ extern "C" int tfasr_ctc_beam_reset(const int32_t* mask, int B, int C, int Tcap,
   const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
   if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
   const BeamWs w = beam_carve(L, workspace, B, beam_width);
-  TFASR_KLAUNCH(ctc_beam_reset_kernel, dim3(B), dim3(BEAM_THREADS), 0, (hipStream_t)stream_, mask, w.par, w.lab, w.dep, w.hk, w.cy, beam_width,
+  TFASR_KLAUNCH(ctc_beam_reset_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream_, mask, w.par, w.lab, w.dep, w.hk, w.cy, beam_width,
                 L.nmax, L.hcap);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;

@@ -8,14 +8,11 @@
 // search's continuation convention), plus the state after it and its prediction projection.  One frame t:
 //   rb_join_kernel   z = tanh(encj[b, t] + pred[row])                                             (every row of a live utterance)
 //   tfasr_gemm       logits = z @ vocab_w + vocab_b, exact f32 on the matrix cores
-//   rb_frame_kernel  one wave per live row: lse (ctc_beam_frame_kernel's arithmetic: f32 max, f64 sum of exp, f32 log) and the
-//                    row's top K = min(2W, V-1) non-blank classes by (lp desc, class asc), lp = (double)x - (double)lse
-//   rb_select_kernel one workgroup per utterance: stays, merged extensions ("specials") and each row's first W regular extensions as
-//                    candidates in LDS, rank = number of better candidates, trie nodes for new sequences, and the gather of the
-//                    next rows' pre-states (extension: the parent's post-state; stay and merge: the row's own pre-state)
+//   rb_frame_kernel  one wave per live row: beam_select.h's frame pass in f64, lp = (double)x - (double)lse
+//   rb_select_kernel one workgroup per utterance: beam_select.h's selection over at most W^2 + 2W candidates - the classes special to
+//                    a row are its merge targets (the labels of the beam rows whose parent it is) - and the gather of the next
+//                    rows' pre-states (extension: the parent's post-state; stay and merge: the row's own pre-state)
 //   prediction step  h_pre @ lstm_rk (tfasr_gemm) -> rb_cell_kernel (+ G[token] + b, LSTM cell, LayerNorm) -> @ joint_pred_w + b
-// Why K classes suffice: ctc_beam.hip's argument, with a row's merge targets (the labels of the beam rows whose parent it is) as its
-// special classes - they are scored explicitly from logits - lse, every other class adds the same row total to lp.
 // The prediction step runs for every row; a stay row recomputes its post-state and projection from unchanged inputs, and the f32
 // GEMM's k order per element does not depend on the row's position (split_k 1): the same bits as the cached values.
 // The search in pieces (tfasr_rnnt_beam_reset / _advance / _commit / _nbest_states, streaming sessions): the workspace sized with
@@ -23,27 +20,14 @@
 // frames + n-best).  Between two advances a beam is what the select leaves - node, total, token, gathered pre-state - and the
 // advance starts with the prediction step, which rebuilds the rest with the same bits.
 // Arithmetic: products f32 on the f32 master weights; totals, merges (max + log1p(exp(-|a-b|))) and comparisons f64; scores f32.
-#include "beam_trie.h"
-#include "common.h"
+#include "beam_select.h"
 #include <string.h>
-#include <algorithm>
 
 namespace {
 
-using beam_trie::Seq;
-using beam_trie::Trie;
+using namespace beam_select;
 
-constexpr int RB_MAXW = 64;
-constexpr int RB_MAXC = RB_MAXW * RB_MAXW + 2 * RB_MAXW;  // stays + specials (< W) + W regulars per row
-constexpr int RB_THREADS = 256;
-enum { CNT_LIVE = 0, CNT_NODES = 1, CNT_FRAMES = 2, CNT_N = 4 };  // per-utterance counters: live rows, trie nodes, frames selected
-
-__device__ __forceinline__ double lae(double a, double b) {  // log(exp(a) + exp(b))
-  if (a == -INFINITY) return b;
-  if (b == -INFINITY) return a;
-  const double m = a > b ? a : b;
-  return m + log1p(exp(-fabs(a - b)));
-}
+constexpr int RB_MAXC = MAXW * MAXW + 2 * MAXW;  // stays + specials (< W) + W regulars per row
 
 struct Ws {  // the workspace carved into its arrays (rb_layout)
   float *G, *hpre, *cpre, *hnx, *cnx, *hpost, *cpost, *y, *hr, *pred, *z, *logits, *lse;
@@ -52,20 +36,12 @@ struct Ws {  // the workspace carved into its arrays (rb_layout)
   unsigned long long* hk;
 };
 
-struct RbLayout {
-  int K;
-  long nmax;
-  unsigned hcap;
+struct RbLayout : Geometry {
   size_t off[24], total;
 };
 
-inline size_t rb_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline RbLayout rb_layout(int B, int T, int U, int J, int V, int W) {
-  RbLayout L;
-  L.K = W * 2 < V - 1 ? W * 2 : V - 1;
-  L.nmax = 1 + (long)W * T;  // at most W new nodes per frame
-  L.hcap = beam_trie::table_cap(L.nmax);
+  RbLayout L{Geometry(T, V, W)};
   const size_t R = (size_t)B * W;
   const size_t sz[24] = {(size_t)V * 4 * U * 4,                                               // G = emb @ lstm_k (no `packed`)
                          R * U * 4, R * U * 4, R * U * 4, R * U * 4, R * U * 4, R * U * 4, R * U * 4,  // hpre cpre hnx cnx hpost cpost y
@@ -75,7 +51,7 @@ inline RbLayout rb_layout(int B, int T, int U, int J, int V, int W) {
                          (size_t)B * L.nmax * 4, (size_t)B * L.nmax * 4, (size_t)B * L.nmax * 4,  // trie parent label depth
                          (size_t)B * L.hcap * 4 + (size_t)B * L.hcap * 8};                     // table values + keys
   size_t o = 0;
-  for (int i = 0; i < 24; ++i) { L.off[i] = o; o += rb_align(sz[i]); }
+  for (int i = 0; i < 24; ++i) { L.off[i] = o; o += align256(sz[i]); }
   L.total = o;
   return L;
 }
@@ -89,39 +65,35 @@ inline Ws rb_carve(const RbLayout& L, void* ws, int B) {
   s.tc = (int*)(w + L.off[16]); s.node = (int*)(w + L.off[17]); s.tok = (int*)(w + L.off[18]); s.cnt = (int*)(w + L.off[19]);
   s.par = (int*)(w + L.off[20]); s.lab = (int*)(w + L.off[21]); s.dep = (int*)(w + L.off[22]);
   s.hv = (int*)(w + L.off[23]);
-  s.hk = (unsigned long long*)(w + L.off[23] + rb_align((size_t)B * L.hcap * 4));
+  s.hk = (unsigned long long*)(w + L.off[23] + align256((size_t)B * L.hcap * 4));
   return s;
 }
 
 inline bool rb_shape_ok(int B, int T, int U, int J, int V, int W) {
-  // T * W bounded so that node ids and table sizes stay in int / unsigned range; V bounded by the candidate code's label field
-  return B > 0 && T > 0 && U > 0 && J > 0 && V >= 2 && V < (1 << 25) && W >= 1 && W <= RB_MAXW && (long)T * W < (1L << 28) &&
-         (long)B * W < (1L << 22);
+  return B > 0 && U > 0 && J > 0 && shape_ok(T, V, W) && (long)B * W < (1L << 22);
 }
 
 // ---- one empty hypothesis per utterance: row b*W = (empty sequence, total 0, initial token), the other rows dead; the initial
 // state goes to every row's gather slot (hnx / cnx) when the caller runs the prediction network.  `mask` [B] (optional) names the
 // utterances to begin: the others are not touched ----
-__global__ __launch_bounds__(RB_THREADS) void rb_begin_kernel(const int32_t* __restrict__ init_tok, const float* __restrict__ init_h,
-                                                             const float* __restrict__ init_c, const int32_t* __restrict__ mask, Ws s,
-                                                             int W, int U, int blank, long nmax, unsigned hcap, bool state) {
+__global__ __launch_bounds__(THREADS) void rb_begin_kernel(const int32_t* __restrict__ init_tok, const float* __restrict__ init_h,
+                                                          const float* __restrict__ init_c, const int32_t* __restrict__ mask, Ws s,
+                                                          int W, int U, int blank, long nmax, unsigned hcap, bool state) {
   const int b = blockIdx.x, tid = threadIdx.x;
   if (mask && !mask[b]) return;  // (tfasr_rnnt_beam_reset: the other streams keep their beams)
-  for (int i = tid; i < W; i += RB_THREADS) {
+  for (int i = tid; i < W; i += THREADS) {
     const long r = (long)b * W + i;
     s.node[r] = 0;
     s.tot[r] = i == 0 ? 0.0 : -INFINITY;
     s.tok[r] = init_tok ? init_tok[b] : blank;
   }
-  unsigned long long* hk = s.hk + (long)b * hcap;
-  for (unsigned i = tid; i < hcap; i += RB_THREADS) hk[i] = beam_trie::EMPTY;
+  clear_stream(trie_at(s.par, s.lab, s.dep, (long)b * nmax), s.hk + (long)b * hcap, hcap, tid);
   if (tid == 0) {
-    s.par[(long)b * nmax] = -1; s.lab[(long)b * nmax] = -1; s.dep[(long)b * nmax] = 0;
     int* cnt = s.cnt + b * CNT_N;
     cnt[CNT_LIVE] = 1; cnt[CNT_NODES] = 1; cnt[CNT_FRAMES] = 0;
   }
   if (state)
-    for (long e = tid; e < (long)W * U; e += RB_THREADS) {
+    for (long e = tid; e < (long)W * U; e += THREADS) {
       const int u = (int)(e % U);
       const long r = (long)b * W + e / U;
       s.hnx[r * U + u] = init_h ? init_h[(long)b * U + u] : 0.f;
@@ -131,16 +103,16 @@ __global__ __launch_bounds__(RB_THREADS) void rb_begin_kernel(const int32_t* __r
 
 // ---- LSTM cell + LayerNorm of one row per workgroup: z = (G[tok] + h_pre @ lstm_rk) + b (gate order i, f, c, o), the pre-state
 // moves from the gather slot to hpre / cpre, y = LN(h_post) (or h_post) feeds the prediction projection ----
-__global__ __launch_bounds__(RB_THREADS) void rb_cell_kernel(const float* __restrict__ G, int g_packed, const float* __restrict__ bias,
-                                                            const float* __restrict__ ln_g, const float* __restrict__ ln_b, Ws s, int U,
-                                                            int V, float ln_eps) {
-  __shared__ float red[RB_THREADS / 64];
+__global__ __launch_bounds__(THREADS) void rb_cell_kernel(const float* __restrict__ G, int g_packed, const float* __restrict__ bias,
+                                                         const float* __restrict__ ln_g, const float* __restrict__ ln_b, Ws s, int U,
+                                                         int V, float ln_eps) {
+  __shared__ float red[THREADS / 64];
   const long r = blockIdx.x;
   const int tid = threadIdx.x;
   const int tok = min(max(s.tok[r], 0), V - 1);
   const float* hr = s.hr + r * 4 * U;
   float part = 0.f;
-  for (int u = tid; u < U; u += RB_THREADS) {
+  for (int u = tid; u < U; u += THREADS) {
     float g4[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q)  // packed: decode_pack's G tiles, [V][U/4][16] with column (u % 4) * 4 + q inside a tile
@@ -163,14 +135,14 @@ __global__ __launch_bounds__(RB_THREADS) void rb_cell_kernel(const float* __rest
     __syncthreads();
     float t = 0.f;
 #pragma unroll
-    for (int w = 0; w < RB_THREADS / 64; ++w) t += red[w];
+    for (int w = 0; w < THREADS / 64; ++w) t += red[w];
     return t;
   };
   const float mu = block_sum(part) / U;
   part = 0.f;
-  for (int u = tid; u < U; u += RB_THREADS) { const float d = s.hpost[r * U + u] - mu; part += d * d; }
+  for (int u = tid; u < U; u += THREADS) { const float d = s.hpost[r * U + u] - mu; part += d * d; }
   const float rs = rsqrtf(block_sum(part) / U + ln_eps);
-  for (int u = tid; u < U; u += RB_THREADS) s.y[r * U + u] = (s.hpost[r * U + u] - mu) * rs * ln_g[u] + ln_b[u];
+  for (int u = tid; u < U; u += THREADS) s.y[r * U + u] = (s.hpost[r * U + u] - mu) * rs * ln_g[u] + ln_b[u];
 }
 
 // ---- z = tanh(encj[b, t] + pred[row]) for the rows of utterances that still have frame t (TransducerJointMerge add + tanh); C = the
@@ -189,9 +161,6 @@ __global__ __launch_bounds__(256) void rb_join_kernel(const float* __restrict__ 
 __device__ __forceinline__ bool utt_active(const int32_t* nframes, const int* cnt, int b, int t, int T) {
   return t < nframes[b] && cnt[b * CNT_N + CNT_FRAMES] < T;  // (a frame is selected at most T times: the trie holds T*W + 1 nodes)
 }
-// (lp, c) comes before (lq, d) in a row's class order
-__device__ __forceinline__ bool cls_before(double lp, int c, double lq, int d) { return lp > lq || (lp == lq && c < d); }
-
 // ---- one wave per live row of a live utterance: lse, lp(blank), top K non-blank classes ----
 __global__ __launch_bounds__(256) void rb_frame_kernel(const float* __restrict__ logits, const int32_t* __restrict__ nframes, Ws s, int B,
                                                       int T, int V, int W, int K, int blank, int t) {
@@ -237,13 +206,13 @@ __global__ __launch_bounds__(256) void rb_frame_kernel(const float* __restrict__
 }
 
 // ---- the next beam of one utterance ----
-__global__ __launch_bounds__(RB_THREADS) void rb_select_kernel(const float* __restrict__ logits, const int32_t* __restrict__ nframes, Ws s,
-                                                              int T, int U, int V, int W, int K, int t, long nmax, unsigned hcap, bool state) {
-  __shared__ int bnode[RB_MAXW], btok[RB_MAXW], merged[RB_MAXW], win[RB_MAXW];
-  __shared__ int nnode[RB_MAXW], npar[RB_MAXW], nlab[RB_MAXW], ndep[RB_MAXW], ntok[RB_MAXW], nsrc[RB_MAXW];
-  __shared__ double btot[RB_MAXW], bstay[RB_MAXW], ntot[RB_MAXW];
+__global__ __launch_bounds__(THREADS) void rb_select_kernel(const float* __restrict__ logits, const int32_t* __restrict__ nframes, Ws s,
+                                                           int T, int U, int V, int W, int K, int t, long nmax, unsigned hcap, bool state) {
+  __shared__ int bnode[MAXW], btok[MAXW], merged[MAXW], win[MAXW];
+  __shared__ int nnode[MAXW], npar[MAXW], nlab[MAXW], ndep[MAXW], ntok[MAXW], nsrc[MAXW];
+  __shared__ double btot[MAXW], bstay[MAXW], ntot[MAXW];
   __shared__ double ctot[RB_MAXC];
-  __shared__ unsigned ccode[RB_MAXC];  // row | (label + 1) << 6; label -1 = the row itself ("stay")
+  __shared__ unsigned ccode[RB_MAXC];
   __shared__ int s_nc;
 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -251,7 +220,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_select_kernel(const float* __re
   int* cnt = s.cnt + b * CNT_N;
   const int nb = cnt[CNT_LIVE];
   const long r0 = (long)b * W;
-  const Trie tr{s.par + (long)b * nmax, s.lab + (long)b * nmax, s.dep + (long)b * nmax};
+  const Trie tr = trie_at(s.par, s.lab, s.dep, (long)b * nmax);
   unsigned long long* hk = s.hk + (long)b * hcap;
   int* hv = s.hv + (long)b * hcap;
   if (tid < nb) {
@@ -277,67 +246,33 @@ __global__ __launch_bounds__(RB_THREADS) void rb_select_kernel(const float* __re
     unsigned code;
     if (p < 0) {
       tot = bstay[tid];
-      code = (unsigned)tid;
+      code = cand_code(tid, -1);
     } else {
       const int c = tr.label[bnode[tid]];
       const double ext = btot[p] + ((double)logits[(r0 + p) * V + c] - (double)s.lse[r0 + p]);
       tot = lae(ext, bstay[tid]);
-      code = (unsigned)p | ((unsigned)(c + 1) << 6);
+      code = cand_code(p, c);
     }
     const int q = atomicAdd(&s_nc, 1);
     ctot[q] = tot;
     ccode[q] = code;
   }
-  // --- regulars: wave per row, lane per top-K class; the row's first W classes that are no merge target of it
-  for (int p = wid; p < nb; p += RB_THREADS / 64) {
-    int seen = 0;
-    for (int k0 = 0; k0 < K && seen < W; k0 += 64) {
-      const int k = k0 + lane;
-      bool reg = false;
-      int c = -1;
-      if (k < K) {
-        c = s.tc[(r0 + p) * K + k];
-        reg = true;
-        for (int j = 0; j < nb && reg; ++j)
-          if (merged[j] == p && tr.label[bnode[j]] == c) reg = false;
-      }
-      const unsigned long long mask = __ballot(reg);
-      const int rank = seen + __popcll(mask & ((1ull << lane) - 1ull));
-      seen += __popcll(mask);
-      if (reg && rank < W) {
-        const double tot = btot[p] + s.tlp[(r0 + p) * K + k];
-        if (tot != -INFINITY) {
-          const int q = atomicAdd(&s_nc, 1);
-          ctot[q] = tot;
-          ccode[q] = (unsigned)p | ((unsigned)(c + 1) << 6);
-        }
-      }
-    }
-  }
+  // --- regulars: wave per row; special to row p = its merge targets
+  for (int p = wid; p < nb; p += THREADS / 64)
+    push_regulars(p, btot[p], s.tc + (r0 + p) * K, s.tlp + (r0 + p) * K, K, W, lane, [&](int c) {
+      bool special = false;
+      for (int j = 0; j < nb && !special; ++j) special = merged[j] == p && tr.label[bnode[j]] == c;
+      return special;
+    }, ctot, ccode, &s_nc);
   __syncthreads();
-  // --- the best `keep` candidates: rank = number of better candidates (exact order, so ranks are distinct)
   const int nc = s_nc, keep = min(W, nc);
-  for (int q = tid; q < nc; q += RB_THREADS) {
-    const double tq = ctot[q];
-    const unsigned cq = ccode[q];
-    const Seq sq{bnode[cq & 63], (int)(cq >> 6) - 1};
-    int rank = 0;
-    for (int p = 0; p < nc && rank < keep; ++p) {
-      const double tp = ctot[p];
-      if (tp > tq) ++rank;
-      else if (tp == tq && p != q) {
-        const unsigned cp = ccode[p];
-        if (beam_trie::seq_less(tr, Seq{bnode[cp & 63], (int)(cp >> 6) - 1}, sq)) ++rank;
-      }
-    }
-    if (rank < keep) win[rank] = q;
-  }
+  rank_candidates(ctot, ccode, nc, keep, bnode, tr, win, tid);
   __syncthreads();
   // --- the next rows: sequence node, token, state source (row | 64 = the parent's post-state, else the row's pre-state)
   bool fresh = false;
   if (tid < keep) {
     const unsigned code = ccode[win[tid]];
-    const int i = code & 63, c = (int)(code >> 6) - 1;
+    const int i = cand_row(code), c = cand_label(code);
     ntot[tid] = ctot[win[tid]];
     int child = -1;
     if (c >= 0)
@@ -354,18 +289,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_select_kernel(const float* __re
       fresh = node < 0;
     }
   }
-  // new nodes numbered in rank order (keep <= 64: wave 0 holds every winner)
-  int nfresh = 0;
-  if (wid == 0) {
-    const unsigned long long mask = __ballot(fresh);
-    nfresh = __popcll(mask);
-    if (fresh) {
-      const int node = cnt[CNT_NODES] + __popcll(mask & ((1ull << lane) - 1ull));
-      nnode[tid] = node;
-      tr.parent[node] = npar[tid]; tr.label[node] = nlab[tid]; tr.depth[node] = ndep[tid];
-      beam_trie::insert(hk, hv, hcap, npar[tid], nlab[tid], node);
-    }
-  }
+  const int nfresh = grow_trie(fresh, tid, cnt + CNT_NODES, tr, hk, hv, hcap, nnode, npar, nlab, ndep);
   __syncthreads();
   if (tid < W) {
     const bool live = tid < keep;
@@ -379,7 +303,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_select_kernel(const float* __re
     cnt[CNT_FRAMES] += 1;
   }
   if (state)  // gather: the prediction step of the next frame reads the new rows' pre-states from hnx / cnx
-    for (long e = tid; e < (long)keep * U; e += RB_THREADS) {
+    for (long e = tid; e < (long)keep * U; e += THREADS) {
       const int q = (int)(e / U), u = (int)(e % U), src = nsrc[q];
       const long from = (r0 + (src & 63)) * U + u, to = (r0 + q) * U + u;
       s.hnx[to] = (src & 64) ? s.hpost[from] : s.hpre[from];
@@ -389,38 +313,27 @@ __global__ __launch_bounds__(RB_THREADS) void rb_select_kernel(const float* __re
 
 // ---- the best P rows of every utterance: tokens [B,P,T] (blank padded), lengths, f32 scores, and the continuation (last token,
 // pre-state) when asked for ----
-__global__ __launch_bounds__(RB_THREADS) void rb_nbest_kernel(Ws s, int T, int U, int W, int P, int blank, long nmax,
-                                                             int32_t* __restrict__ tokens, int32_t* __restrict__ tokens_len,
-                                                             float* __restrict__ score, int32_t* __restrict__ next_tok,
-                                                             float* __restrict__ next_h, float* __restrict__ next_c) {
+__global__ __launch_bounds__(THREADS) void rb_nbest_kernel(Ws s, int T, int U, int W, int P, int blank, long nmax,
+                                                          int32_t* __restrict__ tokens, int32_t* __restrict__ tokens_len,
+                                                          float* __restrict__ score, int32_t* __restrict__ next_tok,
+                                                          float* __restrict__ next_h, float* __restrict__ next_c) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const int nb = s.cnt[b * CNT_N + CNT_LIVE];
   const long r0 = (long)b * W, o0 = (long)b * P;
-  const int* par = s.par + (long)b * nmax;
-  const int* lab = s.lab + (long)b * nmax;
-  const int* dep = s.dep + (long)b * nmax;
-  for (int p = tid; p < P; p += RB_THREADS) {
+  for (int p = tid; p < P; p += THREADS) {
     const bool live = p < nb;
-    tokens_len[o0 + p] = live ? dep[s.node[r0 + p]] : 0;
     score[o0 + p] = live ? (float)s.tot[r0 + p] : -INFINITY;
     if (next_tok) next_tok[o0 + p] = live ? s.tok[r0 + p] : blank;
   }
-  for (long e = tid; e < (long)P * T; e += RB_THREADS) {
-    const int p = (int)(e / T), pos = (int)(e % T);
-    if (p >= nb || pos >= dep[s.node[r0 + p]]) tokens[o0 * T + e] = blank;
-  }
   if (next_h)
-    for (long e = tid; e < (long)P * U; e += RB_THREADS) {
+    for (long e = tid; e < (long)P * U; e += THREADS) {
       const int p = (int)(e / U);
       const bool live = p < nb;
       next_h[o0 * U + e] = live ? s.hnx[r0 * U + e] : 0.f;  // (row p of the beam = element e of rows r0 ..)
       next_c[o0 * U + e] = live ? s.cnx[r0 * U + e] : 0.f;
     }
-  if (tid < min(nb, P)) {
-    int32_t* out = tokens + (o0 + tid) * T;
-    for (int n = s.node[r0 + tid], d = dep[n]; n > 0; n = par[n])
-      if (--d < T) out[d] = lab[n];  // (a row as wide as the frames searched holds every label)
-  }
+  write_paths(trie_at(s.par, s.lab, s.dep, (long)b * nmax), nb, P, T, blank, tid, [&](int p) { return s.node[r0 + p]; }, tokens + o0 * T,
+              tokens_len + o0);
 }
 
 // ---- tfasr_rnnt_beam_commit: one wave per stream, a lane per live row ----
@@ -429,12 +342,11 @@ __global__ __launch_bounds__(64) void rb_commit_kernel(Ws s, const int32_t* __re
                                                       long nmax) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nb = min(s.cnt[b * CNT_N + CNT_LIVE], W);
-  const Trie tr{s.par + (long)b * nmax, s.lab + (long)b * nmax, s.dep + (long)b * nmax};
   const bool live = lane < nb;
   const int node = live ? s.node[(long)b * W + lane] : 0;
-  int target = 0;
-  if (nb > 0) target = (fin && fin[b]) ? __shfl(node, 0, 64) : beam_trie::common_ancestor(tr, node, live);
-  beam_trie::commit_labels(tr, target, lane, committed + b, tokens + (long)b * width, ntokens + b, width, blank);
+  // (rows are kept best first: a final stream commits row 0)
+  commit_stream(trie_at(s.par, s.lab, s.dep, (long)b * nmax), node, live, nb, fin && fin[b] ? 0 : -1, lane, committed + b,
+                tokens + (long)b * width, ntokens + b, width, blank);
 }
 
 int rb_gemm(const float* A, const float* Bm, const float* bias, float* D, int M, int N, int Kd, hipStream_t st) {
@@ -449,7 +361,7 @@ int rb_gemm(const float* A, const float* Bm, const float* bias, float* D, int M,
 
 int rb_begin(const RbLayout& L, const Ws& s, const int32_t* init_tok, const float* init_h, const float* init_c, const int32_t* mask, int B, int U,
              int W, int blank, bool state, hipStream_t st) {
-  TFASR_KLAUNCH(rb_begin_kernel, dim3(B), dim3(RB_THREADS), 0, st, init_tok, init_h, init_c, mask, s, W, U, blank, L.nmax, L.hcap, state);
+  TFASR_KLAUNCH(rb_begin_kernel, dim3(B), dim3(THREADS), 0, st, init_tok, init_h, init_c, mask, s, W, U, blank, L.nmax, L.hcap, state);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
@@ -460,14 +372,14 @@ int rb_select(const RbLayout& L, const Ws& s, const float* logits, const int32_t
   const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
   TFASR_KLAUNCH(rb_frame_kernel, dim3(grid), dim3(256), 0, st, logits, nframes, s, B, T, V, W, L.K, blank, t);
   TFASR_CHECK_LAUNCH();
-  TFASR_KLAUNCH(rb_select_kernel, dim3(B), dim3(RB_THREADS), 0, st, logits, nframes, s, T, U, V, W, L.K, t, L.nmax, L.hcap, state);
+  TFASR_KLAUNCH(rb_select_kernel, dim3(B), dim3(THREADS), 0, st, logits, nframes, s, T, U, V, W, L.K, t, L.nmax, L.hcap, state);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
 
 int rb_nbest(const RbLayout& L, const Ws& s, int B, int T, int U, int W, int P, int blank, int32_t* tokens, int32_t* tokens_len, float* score,
              int32_t* next_tok, float* next_h, float* next_c, hipStream_t st) {
-  TFASR_KLAUNCH(rb_nbest_kernel, dim3(B), dim3(RB_THREADS), 0, st, s, T, U, W, P, blank, L.nmax, tokens, tokens_len, score, next_tok, next_h,
+  TFASR_KLAUNCH(rb_nbest_kernel, dim3(B), dim3(THREADS), 0, st, s, T, U, W, P, blank, L.nmax, tokens, tokens_len, score, next_tok, next_h,
                 next_c);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
@@ -478,7 +390,7 @@ struct PredW { const float *G, *lstm_rk, *lstm_b, *ln_g, *ln_b, *wjp, *bjp; int 
 // the prediction network for every row from its gathered pre-state: hr, then the cell (hpre/cpre <- hnx/cnx, hpost, cpost, y), pred
 int rb_predict(const Ws& s, const PredW& pw, int R, int U, int J, int V, float ln_eps, hipStream_t st) {
   RB_TRY(rb_gemm(s.hnx, pw.lstm_rk, nullptr, s.hr, R, 4 * U, U, st));
-  TFASR_KLAUNCH(rb_cell_kernel, dim3(R), dim3(RB_THREADS), 0, st, pw.G, pw.g_packed, pw.lstm_b, pw.ln_g, pw.ln_b, s, U, V, ln_eps);
+  TFASR_KLAUNCH(rb_cell_kernel, dim3(R), dim3(THREADS), 0, st, pw.G, pw.g_packed, pw.lstm_b, pw.ln_g, pw.ln_b, s, U, V, ln_eps);
   TFASR_CHECK_LAUNCH();
   return rb_gemm(s.y, pw.wjp, pw.bjp, s.pred, R, J, U, st);
 }

@@ -1117,19 +1117,32 @@ def ctc_beam_search(logits, logit_len, beam_width=10, blank_index=None):
     return torch.from_numpy(toks), torch.from_numpy(n), torch.from_numpy(lp)
 
 
+def _beam_args(what, V, beam_width, top_paths, blank, blank_name="blank"):
+    """The checks of every device beam search entry point `what`, before anything is queued -> (beam_width, top_paths, blank) as
+    ints."""
+    beam_width, top_paths, blank = int(beam_width), int(top_paths), int(blank)
+    if not 1 <= beam_width <= 64:
+        raise ValueError(f"{what}: beam_width {beam_width} outside [1, 64] (a beam lives in one workgroup's LDS)")
+    if not 1 <= top_paths <= beam_width:
+        raise ValueError(f"{what}: top_paths {top_paths} outside [1, beam_width = {beam_width}]")
+    if V < 2 or not 0 <= blank < V:
+        raise ValueError(f"{what}: {blank_name} {blank} outside [0, V = {V}) or V < 2")
+    return beam_width, top_paths, blank
+
+
+def _paths(B, P, L, dev):
+    """what an n-best list is returned in: tokens [B, P, L] int32, lengths [B, P] int32, scores [B, P] f32"""
+    return (torch.empty(B, P, L, dtype=torch.int32, device=dev), torch.empty(B, P, dtype=torch.int32, device=dev),
+            torch.empty(B, P, dtype=torch.float32, device=dev))
+
+
 def ctc_beam_search_device(logits, logit_len, beam_width=10, top_paths=1, blank_index=None):
     """The prefix beam search of ctc_beam_search on the device (tfasr_ctc_beam_search), stream ordered, with the n-best list:
     logits [B,T,V] f32 / bf16 on the GPU, logit_len [B] -> device tensors tokens [B,P,T] (0 padded), lengths [B,P], log_prob [B,P],
     best first; paths past the last live beam are empty with log_prob -inf.  blank_index=None: class V-1 (TF's convention)."""
     B, T, V = logits.shape
-    beam_width, top_paths = int(beam_width), int(top_paths)
-    bi = V - 1 if blank_index is None else int(blank_index)
-    if not 1 <= beam_width <= 64:
-        raise ValueError(f"tfasr_ctc_beam_search: beam_width {beam_width} outside [1, 64] (the beam lives in one workgroup's LDS)")
-    if not 1 <= top_paths <= beam_width:
-        raise ValueError(f"tfasr_ctc_beam_search: top_paths {top_paths} outside [1, beam_width = {beam_width}]")
-    if V < 2 or not 0 <= bi < V:
-        raise ValueError(f"tfasr_ctc_beam_search: blank_index {bi} outside [0, V = {V}) or V < 2")
+    bi = V - 1 if blank_index is None else blank_index
+    beam_width, top_paths, bi = _beam_args("tfasr_ctc_beam_search", V, beam_width, top_paths, bi, "blank_index")
     logits = logits.contiguous()
     dev = logits.device
     if not torch.is_tensor(logit_len):
@@ -1138,23 +1151,10 @@ def ctc_beam_search_device(logits, logit_len, beam_width=10, top_paths=1, blank_
     n = ctypes.c_size_t(0)
     check(_L().tfasr_ctc_beam_search_workspace_size(B, T, V, beam_width, ctypes.byref(n)), "ctc_beam_ws")
     ws = workspace(n.value, dev, "ctc_beam")
-    tokens = torch.empty(B, top_paths, T, dtype=torch.int32, device=dev)
-    lengths = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
-    log_prob = torch.empty(B, top_paths, dtype=torch.float32, device=dev)
+    tokens, lengths, log_prob = _paths(B, top_paths, T, dev)
     check(_L().tfasr_ctc_beam_search(_p(logits), _p(logit_len), B, T, V, beam_width, top_paths, bi, _dt(logits), _p(tokens), _p(lengths),
                                      _p(log_prob), _p(ws), ws.numel(), _stream()), "ctc_beam_search_device")
     return tokens, lengths, log_prob
-
-
-def _rnnt_beam_args(V, beam_width, top_paths, blank):
-    beam_width, top_paths, blank = int(beam_width), int(top_paths), int(blank)
-    if not 1 <= beam_width <= 64:
-        raise ValueError(f"tfasr_rnnt_beam_search: beam_width {beam_width} outside [1, 64] (a beam lives in one workgroup's LDS)")
-    if not 1 <= top_paths <= beam_width:
-        raise ValueError(f"tfasr_rnnt_beam_search: top_paths {top_paths} outside [1, beam_width = {beam_width}]")
-    if V < 2 or not 0 <= blank < V:
-        raise ValueError(f"tfasr_rnnt_beam_search: blank {blank} outside [0, V = {V}) or V < 2")
-    return beam_width, top_paths, blank
 
 
 def _i32(x, dev):
@@ -1177,15 +1177,13 @@ def rnnt_beam_search(emb, lstm_k, lstm_rk, lstm_b, ln_g, ln_b, wjp, bjp, wv, bv,
     B, T, J = encj.shape
     V, E = emb.shape
     U = lstm_rk.shape[0]
-    beam_width, top_paths, blank = _rnnt_beam_args(V, beam_width, top_paths, blank)
+    beam_width, top_paths, blank = _beam_args("tfasr_rnnt_beam_search", V, beam_width, top_paths, blank)
     dev = encj.device
     nframes = _i32(nframes, dev)
     if init_tok is not None:
         init_tok = _i32(init_tok, dev).reshape(B)
     ws = workspace(rnnt_beam_workspace_size(B, T, U, J, V, beam_width), dev, "rnnt_beam")
-    tokens = torch.empty(B, top_paths, T, dtype=torch.int32, device=dev)
-    lengths = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, top_paths, dtype=torch.float32, device=dev)
+    tokens, lengths, scores = _paths(B, top_paths, T, dev)
     next_tok = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
     next_h = torch.empty(B, top_paths, U, dtype=torch.float32, device=dev)
     next_c = torch.empty(B, top_paths, U, dtype=torch.float32, device=dev)
@@ -1201,7 +1199,7 @@ class RnntBeamSeam:
     which is how a test replaces the joint network by a model of its own."""
 
     def __init__(self, B, T, V, beam_width, blank=0, init_tok=None, device="cuda"):
-        self.beam_width, _, self.blank = _rnnt_beam_args(V, beam_width, 1, blank)
+        self.beam_width, _, self.blank = _beam_args("tfasr_rnnt_beam_search", V, beam_width, 1, blank)
         self.B, self.T, self.V, self.U, self.J = int(B), int(T), int(V), 1, 1
         self.ws = torch.empty(rnnt_beam_workspace_size(self.B, self.T, 1, 1, self.V, self.beam_width), dtype=torch.uint8, device=device)
         tok = None if init_tok is None else _i32(init_tok, self.ws.device)
@@ -1218,11 +1216,9 @@ class RnntBeamSeam:
 
     def nbest(self, top_paths=None):
         """the best top_paths rows (default: all) -> tokens [B,NP,T], lengths [B,NP], scores [B,NP]"""
-        _, top_paths, _ = _rnnt_beam_args(self.V, self.beam_width, top_paths or self.beam_width, self.blank)
+        _, top_paths, _ = _beam_args("tfasr_rnnt_beam_search", self.V, self.beam_width, top_paths or self.beam_width, self.blank)
         dev = self.ws.device
-        tokens = torch.empty(self.B, top_paths, self.T, dtype=torch.int32, device=dev)
-        lengths = torch.empty(self.B, top_paths, dtype=torch.int32, device=dev)
-        scores = torch.empty(self.B, top_paths, dtype=torch.float32, device=dev)
+        tokens, lengths, scores = _paths(self.B, top_paths, self.T, dev)
         check(_L().tfasr_rnnt_beam_nbest(self.B, self.T, self.U, self.J, self.V, self.beam_width, top_paths, self.blank, _p(tokens),
                                          _p(lengths), _p(scores), _p(self.ws), self.ws.numel(), _stream()), "rnnt_beam_nbest")
         return tokens, lengths, scores
@@ -1286,6 +1282,18 @@ class _BeamStream:
     def _width(self):
         return max(max(self.frames), 1)  # a hypothesis is never longer than the frames consumed
 
+    def commit(self, final_rows=()):
+        """-> (tokens [B, width] padded with the search's pad value (transducer: blank, CTC: 0), ntokens [B]) device tensors: the
+        labels new in the streams' stable prefixes (the part every live hypothesis shares); the streams in final_rows commit their
+        whole best hypothesis"""
+        dev, width = self.ws.device, self._width()
+        final_rows = list(final_rows)
+        fin = _row_mask(final_rows, self.B, dev) if final_rows else None
+        tokens = torch.empty(self.B, width, dtype=torch.int32, device=dev)
+        n = torch.empty(self.B, dtype=torch.int32, device=dev)
+        self._commit(_p(fin), _p(tokens), _p(n), width)
+        return tokens, n
+
 
 class RnntBeamStream(_BeamStream):
     """The transducer beam search in pieces (tfasr_rnnt_beam_reset / _advance / _commit / _nbest_states): B streams, each carrying its
@@ -1299,7 +1307,7 @@ class RnntBeamStream(_BeamStream):
         self.weights, self.packed, self.ln_eps = tuple(weights), packed, float(ln_eps)
         V, self.E = emb.shape
         self.U, self.J = lstm_rk.shape[0], wjp.shape[1]
-        self.beam_width, _, self.blank = _rnnt_beam_args(V, beam_width, 1, blank)
+        self.beam_width, _, self.blank = _beam_args("tfasr_rnnt_beam_search", V, beam_width, 1, blank)
         self._init_common(B, Tcap, V, beam_width, emb.device)
         self.ws = torch.empty(rnnt_beam_workspace_size(self.B, self.Tcap, self.U, self.J, self.V, self.beam_width), dtype=torch.uint8,
                               device=emb.device)
@@ -1328,26 +1336,16 @@ class RnntBeamStream(_BeamStream):
                                            _p(self.ws), self.ws.numel(), _stream()), "rnnt_beam_advance")
         self.frames = [f + v for f, v in zip(self.frames, nv)]
 
-    def commit(self, final_rows=()):
-        """-> (tokens [B, width] blank padded, ntokens [B]) device tensors: the labels new in the streams' stable prefixes (the part
-        every live hypothesis shares); the streams in final_rows commit their whole best hypothesis"""
-        dev, width = self.ws.device, self._width()
-        final_rows = list(final_rows)
-        fin = _row_mask(final_rows, self.B, dev) if final_rows else None
-        tokens = torch.empty(self.B, width, dtype=torch.int32, device=dev)
-        n = torch.empty(self.B, dtype=torch.int32, device=dev)
-        check(_L().tfasr_rnnt_beam_commit(_p(fin), _p(self.committed), _p(tokens), _p(n), *self._dims(), width, self.blank, _p(self.ws),
+    def _commit(self, fin, tokens, n, width):
+        check(_L().tfasr_rnnt_beam_commit(fin, _p(self.committed), tokens, n, *self._dims(), width, self.blank, _p(self.ws),
                                           self.ws.numel(), _stream()), "rnnt_beam_commit")
-        return tokens, n
 
     def nbest(self, top_paths=None):
         """the current beams as rnnt_beam_search returns them: (tokens [B, NP, L], lengths, scores, next_tok, next_h, next_c), L = the
         most frames a stream has consumed (at least 1)"""
-        _, top_paths, _ = _rnnt_beam_args(self.V, self.beam_width, top_paths or self.beam_width, self.blank)
+        _, top_paths, _ = _beam_args("tfasr_rnnt_beam_search", self.V, self.beam_width, top_paths or self.beam_width, self.blank)
         dev, width, B, U = self.ws.device, self._width(), self.B, self.U
-        tokens = torch.empty(B, top_paths, width, dtype=torch.int32, device=dev)
-        lengths = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
-        scores = torch.empty(B, top_paths, dtype=torch.float32, device=dev)
+        tokens, lengths, scores = _paths(B, top_paths, width, dev)
         next_tok = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
         next_h = torch.empty(B, top_paths, U, dtype=torch.float32, device=dev)
         next_c = torch.empty(B, top_paths, U, dtype=torch.float32, device=dev)
@@ -1364,15 +1362,11 @@ class CtcBeamStream(_BeamStream):
     what = "tfasr_ctc_beam_advance"
 
     def __init__(self, B, C, Tcap, V, beam_width, blank_index=None, device="cuda"):
-        self.C, self.beam_width = int(C), int(beam_width)
-        bi = int(V) - 1 if blank_index is None else int(blank_index)
-        if not 1 <= self.beam_width <= 64:
-            raise ValueError(f"tfasr_ctc_beam_advance: beam_width {self.beam_width} outside [1, 64] (the beam lives in one workgroup's LDS)")
-        if V < 2 or not 0 <= bi < V:
-            raise ValueError(f"tfasr_ctc_beam_advance: blank_index {bi} outside [0, V = {V}) or V < 2")
+        self.C = int(C)
+        bi = int(V) - 1 if blank_index is None else blank_index
+        self.beam_width, _, self.blank_index = _beam_args("tfasr_ctc_beam_advance", V, beam_width, 1, bi, "blank_index")
         if not 1 <= self.C <= int(Tcap):
             raise ValueError(f"tfasr_ctc_beam_advance: chunk capacity {self.C} outside [1, Tcap = {Tcap}]")
-        self.blank_index = bi
         self._init_common(B, Tcap, V, beam_width, device)
         n = ctypes.c_size_t(0)
         check(_L().tfasr_ctc_beam_stream_workspace_size(*self._dims(), ctypes.byref(n)), "ctc_beam_stream_ws")
@@ -1400,26 +1394,15 @@ class CtcBeamStream(_BeamStream):
                                           after, _p(self.ws), self.ws.numel(), _stream()), "ctc_beam_advance")
         self.frames = [f + v for f, v in zip(self.frames, nv)]
 
-    def commit(self, final_rows=()):
-        """-> (tokens [B, width] 0 padded, ntokens [B]) device tensors, as RnntBeamStream.commit"""
-        dev, width = self.ws.device, self._width()
-        final_rows = list(final_rows)
-        fin = _row_mask(final_rows, self.B, dev) if final_rows else None
-        tokens = torch.empty(self.B, width, dtype=torch.int32, device=dev)
-        n = torch.empty(self.B, dtype=torch.int32, device=dev)
-        check(_L().tfasr_ctc_beam_commit(_p(fin), _p(self.committed), _p(tokens), _p(n), *self._dims(), width, _p(self.ws),
-                                         self.ws.numel(), _stream()), "ctc_beam_commit")
-        return tokens, n
+    def _commit(self, fin, tokens, n, width):
+        check(_L().tfasr_ctc_beam_commit(fin, _p(self.committed), tokens, n, *self._dims(), width, _p(self.ws), self.ws.numel(),
+                                         _stream()), "ctc_beam_commit")
 
     def nbest(self, top_paths=None):
         """the current beams as ctc_beam_search_device returns them: (tokens [B, P, L] 0 padded, lengths [B, P], log_prob [B, P])"""
-        top_paths = int(top_paths or self.beam_width)
-        if not 1 <= top_paths <= self.beam_width:
-            raise ValueError(f"tfasr_ctc_beam_nbest: top_paths {top_paths} outside [1, beam_width = {self.beam_width}]")
+        _, top_paths, _ = _beam_args("tfasr_ctc_beam_nbest", self.V, self.beam_width, top_paths or self.beam_width, self.blank_index)
         dev, width, B = self.ws.device, self._width(), self.B
-        tokens = torch.empty(B, top_paths, width, dtype=torch.int32, device=dev)
-        lengths = torch.empty(B, top_paths, dtype=torch.int32, device=dev)
-        log_prob = torch.empty(B, top_paths, dtype=torch.float32, device=dev)
+        tokens, lengths, log_prob = _paths(B, top_paths, width, dev)
         check(_L().tfasr_ctc_beam_nbest(*self._dims(), top_paths, width, _p(tokens), _p(lengths), _p(log_prob), _p(self.ws),
                                         self.ws.numel(), _stream()), "ctc_beam_nbest")
         return tokens, lengths, log_prob
