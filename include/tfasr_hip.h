@@ -931,6 +931,13 @@ int tfasr_stream_kv_append(const void* qkv, void* kcache, void* vcache, const in
                            int dh, int hist, int dtype, void* stream);
 int tfasr_stream_glu_dwconv_fwd(const void* glu_x, void* state, const float* w, const float* bias, const int32_t* nvalid, void* y, int B,
                                 int C, int d, int K, int dtype, void* stream);
+/* DeepSpeech2's RowConv1D over one step (declaration added under ABI 44, nothing existing changes): x [B*C, d] -> causal depthwise conv WITHOUT bias (w [K, d] f32, K <= 32) over
+ * state [B, K-1, d] ++ the valid rows -> * scale + shift (the folded BatchNorm, [d] f32 each) -> ReLU -> y [B*C, d]; rows >= nvalid of y are
+ * zero; state = the last K-1 rows of the concatenation, in place (NULL allowed with K == 1); an idle stream's state is not written.  The
+ * valid rows are, bit for bit, those of tfasr_dwconv_fwd -> tfasr_channel_affine_fwd(relu) over the whole sequence.  UNSUPPORTED beyond
+ * C <= TFASR_STREAM_MAX_CHUNK, K <= 32, B <= 65535. */
+int tfasr_stream_rowconv_fwd(const void* x, void* state, const float* w, const float* scale, const float* shift, const int32_t* nvalid, void* y,
+                             int B, int C, int d, int K, int dtype, void* stream);
 /* The streaming Transformer encoder's step (plain attention over absolute positions; declarations added under ABI 44, nothing existing
  * changes).
  * tfasr_stream_attn_plain_fwd: tfasr_stream_attn_fwd without the relative-position term and WITH the ring append, in one launch.
@@ -1045,6 +1052,20 @@ int tfasr_channel_affine_fwd(const void* x, const float* scale, const float* shi
 int tfasr_lstm_infer_workspace_size(int B, int T, int P, int ndir, int dtype, size_t* bytes);
 int tfasr_lstm_infer_fwd(const void* xg, long ld_xg, const void* rk, const int32_t* lengths, void* y, long ld_y, float* h_last,
                          float* c_last, int B, int T, int P, int ndir, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+/* The same recurrence continued from a state (declaration added under ABI 44, nothing existing changes): h0 / c0 [B, P] f32, 16-byte aligned, are the h_last / c_last of the call
+ * that walked the frames in front of these; both NULL = the zero state, which is tfasr_lstm_infer_fwd (that entry is this one with both
+ * NULL).  h0 enters the recurrent product rounded to the activation type - exact for a carried value, since h_last holds numbers of
+ * that type.  On either route a sequence walked in several calls gives, bit for bit, the y / h_last / c_last of one call over all of
+ * it (on that route), and lengths keeps its meaning inside a call: a stream with lengths[b] == 0 gets its state back unchanged and
+ * zero rows.  The persistent launch is the same kernel: step 0 stages h0 where it staged zeros.  Same workspace size.
+ * INVALID_VALUE, before any launch: a state with ndir == 2 (a backward direction cannot be continued); one of h0 / c0 NULL alone;
+ * h_last or c_last overlapping h0 or c0 (every workgroup of the persistent launch reads all of h0 at step 0 while a finished one
+ * writes its slice of h_last, and with T == 1 no hand-off separates them: callers ping-pong two buffers); with a state, h_last /
+ * c_last not 8-byte aligned.  A state that cannot be taken is an argument that is wrong: these answers come before the shape's size is
+ * judged (UNSUPPORTED).  Without a state the entry answers exactly as tfasr_lstm_infer_fwd always did. */
+int tfasr_lstm_infer_fwd_state(const void* xg, long ld_xg, const void* rk, const int32_t* lengths, void* y, long ld_y, const float* h0,
+                               const float* c0, float* h_last, float* c_last, int B, int T, int P, int ndir, int dtype, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Plain (absolute-position) scaled dot-product attention, fused forward (csrc/attn_plain.hip; added under ABI 44): the attention of the

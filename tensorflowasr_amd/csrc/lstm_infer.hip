@@ -2,7 +2,8 @@
 // keras.layers.LSTM(return_sequences, zero_output_for_mask=True), alone or inside keras.layers.Bidirectional with the "concat" merge).
 //
 //   xg [B, T, ndir * 4P] (row stride ld_xg): x @ W_d + b_d of every direction side by side (one GEMM in front of this call)
-//   rk [ndir, P, 4P]; gates i, f, c, o; zero initial state
+//   rk [ndir, P, 4P]; gates i, f, c, o; zero initial state, or (tfasr_lstm_infer_fwd_state, one direction) h0 / c0 [B, P] f32: the
+//   h_last / c_last of the launch that walked the frames in front of these
 //   y  [B, T, ndir * P]  (row stride ld_y): direction d writes columns [d P, (d + 1) P) - already the concat merge
 // Direction 0 walks t = 0 .. T-1, direction 1 walks t = T-1 .. 0.  A step with t >= lengths[b] carries h and c and emits zeros, so the
 // reverse direction starts, in effect, at each utterance's last valid frame.  h_last / c_last [ndir, B, P] f32: the state after the last
@@ -16,6 +17,10 @@
 // counter, one lane polling relaxed, one agent-scope acquire after the match, every spin bounded by the wall clock, a timed-out
 // workgroup poisons what it owns of the remaining steps with NaN, and the launch is refused unless the whole grid can be resident.
 // The two directions never wait for each other.
+// With a state, step 0 stages h0 (rounded to bf16: exact for a carried value, h_last holds bf16-rounded numbers) where a stateless launch
+// stages zeros, and c starts from c0; after that it is a step like any other - the same instructions in the same order as a middle step
+// of one long launch, so a sequence walked in several launches gives the bits of one launch over all of it.  On the per-step route step 0
+// runs the recurrent GEMM on h0 (cast to the activation type) and takes c0 as c_prev.
 // Any other shape or type, and every call while tfasr_lstm_set_persist(0) / TFASR_LSTM_PERSIST=0 is in force: the per-step kernels
 // (recurrent tfasr_gemm + tfasr_lstm_step_fwd), direction 0 queued ascending, then direction 1 descending.
 #include "lstm_handoff.h"
@@ -26,6 +31,7 @@ namespace {
 template <int MT>  // MT = ceil(B / 16) batch row tiles
 __global__ __launch_bounds__(256) void lstm_infer_kernel(const bf16_t* __restrict__ xg, long ld_xg, const bf16_t* __restrict__ rk,
                                                          const int32_t* __restrict__ lengths, bf16_t* __restrict__ y, long ld_y, bf16_t* hbuf,
+                                                         const float* __restrict__ h0, const float* __restrict__ c0,
                                                          float* __restrict__ h_last, float* __restrict__ c_last, int B, int T, int P,
                                                          Sync* sync) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -61,12 +67,42 @@ __global__ __launch_bounds__(256) void lstm_infer_kernel(const bf16_t* __restric
   int len_b[NIT];
 #pragma unroll
   for (int i = 0; i < NIT; ++i) {
-    const int it = threadIdx.x + 256 * i, b = it / (PW / 2);
+    const int it = threadIdx.x + 256 * i, b = it / (PW / 2), u = (it % (PW / 2)) * 2;
     const bool in = it < Bp * (PW / 2) && b < B;
     c_st[i][0] = c_st[i][1] = h_st[i][0] = h_st[i][1] = 0.f;
+    if (in && h0) {  // (a state belongs to direction 0 alone: the host refuses it with two)
+      const float2 hv = *reinterpret_cast<const float2*>(h0 + (long)b * P + u0 + u), cv = *reinterpret_cast<const float2*>(c0 + (long)b * P + u0 + u);
+      h_st[i][0] = bf16_to_f32(f32_to_bf16(hv.x)); h_st[i][1] = bf16_to_f32(f32_to_bf16(hv.y));  // what step 0 stages
+      c_st[i][0] = cv.x; c_st[i][1] = cv.y;
+    }
     len_b[i] = in ? (lengths ? lengths[b] : T) : 0;
   }
 
+  if (h0) {
+    // step 0's tile from the state: h0 [B, P] f32 rounded to bf16 (rows >= B: zeros).  Its own loop in front of the recurrence, four
+    // 16-byte pieces a pass (their loads in flight together), so that the f32 values are never live beside the steps' staging registers
+    const int chunks = P / 8;
+#pragma unroll 1
+    for (int cf = threadIdx.x; cf < Bp * chunks; cf += 4 * 256) {
+      float4 lo[4], hi[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = cf + 256 * q, b = c / chunks, ch = c % chunks;
+        lo[q] = hi[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < Bp * chunks && b < B) {
+          lo[q] = *reinterpret_cast<const float4*>(h0 + (long)b * P + ch * 8);
+          hi[q] = *reinterpret_cast<const float4*>(h0 + (long)b * P + ch * 8 + 4);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = cf + 256 * q;
+        if (c < Bp * chunks)
+          *reinterpret_cast<uint4*>(sH + (long)(c / chunks) * ldh + (c % chunks) * 16) =
+              make_uint4(pack2_bf16(lo[q].x, lo[q].y), pack2_bf16(lo[q].z, lo[q].w), pack2_bf16(hi[q].x, hi[q].y), pack2_bf16(hi[q].z, hi[q].w));
+      }
+    }
+  }
   for (int s = 0; s < T; ++s) {
     const int t = d ? T - 1 - s : s, tp = d ? t + 1 : t - 1;  // this step's frame, the previous step's frame
     // input-projection terms of this step for the owned items (independent of the recurrence: in flight during the wait)
@@ -101,10 +137,12 @@ __global__ __launch_bounds__(256) void lstm_infer_kernel(const bf16_t* __restric
         if (b < B && s > 0) hv[i] = *reinterpret_cast<const uint4*>(hseq + ((long)b * T + tp) * P + ch * 8);
       }
     }
+    if (s > 0 || !h0) {  // (step 0 of a launch with a state: the tile was staged in front of the loop)
 #pragma unroll
-    for (int i = 0; i < NST; ++i) {
-      const int c = threadIdx.x + 256 * i;
-      if (c < Bp * chunks) *reinterpret_cast<uint4*>(sH + (long)(c / chunks) * ldh + (c % chunks) * 16) = hv[i];
+      for (int i = 0; i < NST; ++i) {
+        const int c = threadIdx.x + 256 * i;
+        if (c < Bp * chunks) *reinterpret_cast<uint4*>(sH + (long)(c / chunks) * ldh + (c % chunks) * 16) = hv[i];
+      }
     }
     __syncthreads();
     float4_t acc[MT];
@@ -172,6 +210,13 @@ __global__ __launch_bounds__(256) void state_out_kernel(const T* __restrict__ h,
   if (c_last) c_last[i] = c[i];
 }
 
+// the per-step route's initial h [B, P] f32 -> the activation type (exact for a carried value: it came out of that type)
+template <typename T>
+__global__ __launch_bounds__(256) void state_in_kernel(const float* __restrict__ h0, T* __restrict__ h, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) Num<T>::st(h + i, h0[i]);
+}
+
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // workspace layout: [ndir Sync records | persistent: h hand-off [ndir, B, T, P] bf16 | step route: per direction hr [B, 4P] f32,
@@ -196,6 +241,20 @@ int check_args(int B, int T, int P, int ndir, int dtype) {
   return TFASR_STATUS_SUCCESS;
 }
 
+// the rules of a call with a state (tfasr_lstm_infer_fwd_state), judged on the host before anything else about the call
+bool state_ok(const float* h0, const float* c0, const float* h_last, const float* c_last, int B, int T, int P, int ndir) {
+  if (B <= 0 || T <= 0 || P <= 0) return false;
+  if (!h0 || !c0) return false;   // one half of a state alone
+  if (ndir != 1) return false;    // a backward direction cannot be continued
+  if ((((uintptr_t)h0 | (uintptr_t)c0) & 15) != 0) return false;         // the persistent launch reads them 16 bytes at a time
+  if ((((uintptr_t)h_last | (uintptr_t)c_last) & 7) != 0) return false;  // ... and writes these 8 bytes at a time
+  // every workgroup of the persistent launch stages ALL of h0 at step 0 while a finished one writes its slice of h_last, and with
+  // T == 1 no hand-off lies between the two: the new state goes to other memory
+  const size_t n = (size_t)B * P * sizeof(float);
+  const auto overlap = [n](const float* a, const float* b) { return a && b && (uintptr_t)a < (uintptr_t)b + n && (uintptr_t)b < (uintptr_t)a + n; };
+  return !(overlap(h0, h_last) || overlap(h0, c_last) || overlap(c0, h_last) || overlap(c0, c_last));
+}
+
 }  // namespace
 
 extern "C" int tfasr_lstm_infer_workspace_size(int B, int T, int P, int ndir, int dtype, size_t* bytes) {
@@ -209,7 +268,16 @@ extern "C" int tfasr_lstm_infer_workspace_size(int B, int T, int P, int ndir, in
 extern "C" int tfasr_lstm_infer_fwd(const void* xg, long ld_xg, const void* rk, const int32_t* lengths, void* y, long ld_y, float* h_last,
                                     float* c_last, int B, int T, int P, int ndir, int dtype, void* workspace, size_t workspace_bytes,
                                     void* stream_) {
+  return tfasr_lstm_infer_fwd_state(xg, ld_xg, rk, lengths, y, ld_y, nullptr, nullptr, h_last, c_last, B, T, P, ndir, dtype, workspace,
+                                    workspace_bytes, stream_);
+}
+
+extern "C" int tfasr_lstm_infer_fwd_state(const void* xg, long ld_xg, const void* rk, const int32_t* lengths, void* y, long ld_y, const float* h0,
+                                          const float* c0, float* h_last, float* c_last, int B, int T, int P, int ndir, int dtype,
+                                          void* workspace, size_t workspace_bytes, void* stream_) {
   if (!xg || !rk || !y || !workspace) return TFASR_STATUS_INVALID_VALUE;
+  // a state that cannot be taken is an argument that is wrong: it wins over a shape that is merely too large (check_args' UNSUPPORTED)
+  if ((h0 || c0) && !state_ok(h0, c0, h_last, c_last, B, T, P, ndir)) return TFASR_STATUS_INVALID_VALUE;
   const int ca = check_args(B, T, P, ndir, dtype);
   if (ca != TFASR_STATUS_SUCCESS) return ca;
   if (ld_xg < (long)ndir * 4 * P || ld_y < (long)ndir * P || (ld_xg & 1) || (ld_y & 1)) return TFASR_STATUS_INVALID_VALUE;
@@ -228,7 +296,7 @@ extern "C" int tfasr_lstm_infer_fwd(const void* xg, long ld_xg, const void* rk, 
       if (!grid_fits(kernel, grid.x, smem)) { (void)hipGetLastError(); return TFASR_STATUS_UNSUPPORTED; }
       if (hipMemsetAsync(ws + l.sync, 0, (size_t)ndir * sizeof(Sync), s) != hipSuccess) return TFASR_STATUS_EXECUTION_FAILED;
       TFASR_KLAUNCH(kernel, grid, dim3(256), smem, s, (const bf16_t*)xg, ld_xg, (const bf16_t*)rk, lengths, (bf16_t*)y, ld_y, (bf16_t*)(ws + l.hbuf),
-                    h_last, c_last, B, T, P, (Sync*)(ws + l.sync));
+                    h0, c0, h_last, c_last, B, T, P, (Sync*)(ws + l.sync));
       TFASR_CHECK_LAUNCH();
       return TFASR_STATUS_SUCCESS;
     });
@@ -243,18 +311,25 @@ extern "C" int tfasr_lstm_infer_fwd(const void* xg, long ld_xg, const void* rk, 
   size_t off = l.step + align256((size_t)B * 4 * P * 4);
   for (int i = 0; i < 2; ++i) { hb[i] = ws + off; off += align256((size_t)B * P * esz); }
   for (int i = 0; i < 2; ++i) { cb[i] = (float*)(ws + off); off += align256((size_t)B * P * 4); }
+  if (h0) {  // (one direction) step 0's h_prev: the buffer step 0 would read had it a predecessor
+    const long n = (long)B * P;
+    if (dtype == TFASR_F32) TFASR_KLAUNCH(state_in_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h0, (float*)hb[1], n);
+    else TFASR_KLAUNCH(state_in_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h0, (bf16_t*)hb[1], n);
+    TFASR_CHECK_LAUNCH();
+  }
   for (int d = 0; d < ndir; ++d) {
     const char* rkd = (const char*)rk + (size_t)d * P * 4 * P * esz;
     for (int step = 0; step < T; ++step) {
       const int t = d ? T - 1 - step : step;
       const int cur = step & 1, prv = cur ^ 1;
-      if (step > 0) {
+      const bool prev = step > 0 || h0;
+      if (prev) {
         const tfasr_gemm_args a = recurrent_gemm_args(hb[prv], P, rkd, hr, B, P, dtype);
         const int st = tfasr_gemm(&a, stream_);
         if (st != TFASR_STATUS_SUCCESS) return st;
       }
-      const int st = tfasr_lstm_step_fwd((const char*)xg + ((long)t * ld_xg + (long)d * 4 * P) * esz, (long)T * ld_xg, step > 0 ? hr : nullptr,
-                                         step > 0 ? hb[prv] : nullptr, P, step > 0 ? cb[prv] : nullptr, P, lengths, t, nullptr, 0, cb[cur], P,
+      const int st = tfasr_lstm_step_fwd((const char*)xg + ((long)t * ld_xg + (long)d * 4 * P) * esz, (long)T * ld_xg, prev ? hr : nullptr,
+                                         prev ? hb[prv] : nullptr, P, step > 0 ? cb[prv] : c0, P, lengths, t, nullptr, 0, cb[cur], P,
                                          hb[cur], P, (char*)y + ((long)t * ld_y + (long)d * P) * esz, (long)T * ld_y, B, P, dtype, stream_);
       if (st != TFASR_STATUS_SUCCESS) return st;
     }

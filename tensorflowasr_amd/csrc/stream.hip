@@ -6,7 +6,8 @@
 //   stream_attn_kernel       : the chunk's queries against (key / value ring of the last `hist` frames) ++ (the chunk's own keys)
 //   stream_kv_append_kernel  : the chunk's keys / values into the ring (its own launch AFTER the attention: every head of the attention
 //                              launch still reads the slots this overwrites - they lie inside the chunk's window)
-//   stream_glu_dwconv_kernel : GLU + causal depthwise conv whose left context is a carried [K-1, d] state, updated in place
+//   stream_dwconv_kernel     : causal depthwise conv whose left context is a carried [K-1, d] state, updated in place: with the GLU in
+//                              front (Conformer) or as DeepSpeech2's RowConv1D with the folded BatchNorm affine and the ReLU behind
 // and for the streaming Transformer encoder (plain attention over absolute positions, no convolution module):
 //   stream_attn_plain_kernel : the same chunk attention without the relative-position term, keys and values staged in LDS block by
 //                              block (every ring or chunk row leaves global memory once per workgroup), optional causal mask inside the
@@ -127,12 +128,39 @@ __global__ __launch_bounds__(256) void stream_kv_append_kernel(const T* __restri
   }
 }
 
-// grid (ceil(d / 64), B), 256 threads = 64 channels x 4 row phases.  The K-1 state rows and the GLU of the chunk's valid rows go to LDS
-// first; outputs and the new state are computed from LDS only, so the state is updated in place.
-template <typename T>
-__global__ __launch_bounds__(256) void stream_glu_dwconv_kernel(const T* __restrict__ a, T* __restrict__ state, const float* __restrict__ w,
-                                                                const float* __restrict__ bias, const int32_t* __restrict__ nvalid,
-                                                                T* __restrict__ y, int C, int d, int K) {
+// Causal depthwise conv of one step over a carried [K-1, d] state, updated in place: ONE kernel for the Conformer's convolution module
+// and for DeepSpeech2's RowConv1D, which differ only in how a row enters (Op::load) and in what is done with a tap sum (Op::init /
+// Op::finish).  grid (ceil(d / 64), B), 256 threads = 64 channels x 4 row phases.  The K-1 state rows and the chunk's valid rows go to
+// LDS first; outputs and the new state are computed from LDS only, so the state is updated in place; an idle stream returns before any
+// barrier and nothing of its state is written.
+//   GluBias   : a row is the GLU of a [2d] row (rounded to the storage type, as the offline GLU's output tensor is); sum from the bias
+//   RowAffine : (encoders/deepspeech2.py:56-60: causal DepthwiseConv1D without bias -> BatchNormalization -> ReLU) a row as it lies; the
+//               sum from 0, rounded to the storage type (the intermediate tensor of the offline pair tfasr_dwconv_fwd ->
+//               tfasr_channel_affine_fwd), then a multiply and an add that stay TWO roundings (channel_affine_kernel's are: the empty
+//               asm keeps the compiler from contracting them here), then the ReLU - the offline pair bit for bit
+template <typename T> struct GluBias {
+  const float* bias;
+  static constexpr int IN = 2;  // input row width in units of d
+  __device__ __forceinline__ float load(const T* row, int c, int d) const { return round_as<T>(Num<T>::ld(row + c) * sigmoidf_(Num<T>::ld(row + d + c))); }
+  __device__ __forceinline__ float init(int c) const { return bias ? bias[c] : 0.f; }
+  __device__ __forceinline__ float finish(float acc, int) const { return acc; }
+};
+template <typename T> struct RowAffine {
+  const float *scale, *shift;
+  static constexpr int IN = 1;
+  __device__ __forceinline__ float load(const T* row, int c, int) const { return Num<T>::ld(row + c); }
+  __device__ __forceinline__ float init(int) const { return 0.f; }
+  __device__ __forceinline__ float finish(float acc, int c) const {
+    float v = round_as<T>(acc) * scale[c];
+    asm volatile("" : "+v"(v));
+    v += shift[c];
+    return fmaxf(v, 0.f);
+  }
+};
+
+template <typename T, typename Op>
+__global__ __launch_bounds__(256) void stream_dwconv_kernel(const T* __restrict__ a, T* __restrict__ state, const float* __restrict__ w, const Op op,
+                                                            const int32_t* __restrict__ nvalid, T* __restrict__ y, int C, int d, int K) {
   __shared__ float g[(32 - 1 + MAXC) * 64];
   const int b = blockIdx.y, cl = threadIdx.x & 63, ph = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
   const int nv = min(max(nvalid[b], 0), C), K1 = K - 1;
@@ -141,17 +169,14 @@ __global__ __launch_bounds__(256) void stream_glu_dwconv_kernel(const T* __restr
   if (nv == 0) return;
   if (c < d) {
     for (int r = ph; r < K1; r += 4) g[r * 64 + cl] = Num<T>::ld(state + ((long)b * K1 + r) * d + c);
-    for (int r = ph; r < nv; r += 4) {
-      const T* row = a + ((long)b * C + r) * 2 * d;
-      g[(K1 + r) * 64 + cl] = round_as<T>(Num<T>::ld(row + c) * sigmoidf_(Num<T>::ld(row + d + c)));
-    }
+    for (int r = ph; r < nv; r += 4) g[(K1 + r) * 64 + cl] = op.load(a + ((long)b * C + r) * Op::IN * d, c, d);
   }
   __syncthreads();
   if (c >= d) return;
   for (int r = ph; r < nv; r += 4) {
-    float acc = bias ? bias[c] : 0.f;
+    float acc = op.init(c);
     for (int k = 0; k < K; ++k) acc = fmaf(g[(r + k) * 64 + cl], w[k * d + c], acc);
-    Num<T>::st(y + ((long)b * C + r) * d + c, acc);
+    Num<T>::st(y + ((long)b * C + r) * d + c, op.finish(acc, c));
   }
   for (int r = ph; r < K1; r += 4) Num<T>::st(state + ((long)b * K1 + r) * d + c, g[(nv + r) * 64 + cl]);
 }
@@ -396,9 +421,29 @@ extern "C" int tfasr_stream_glu_dwconv_fwd(const void* glu_x, void* state, const
   hipStream_t s = (hipStream_t)stream_;
   const dim3 grid((d + 63) / 64, B);
   if (dtype == TFASR_F32)
-    TFASR_KLAUNCH(stream_glu_dwconv_kernel<float>, grid, dim3(256), 0, s, (const float*)glu_x, (float*)state, w, bias, nvalid, (float*)y, C, d, K);
+    TFASR_KLAUNCH((stream_dwconv_kernel<float, GluBias<float>>), grid, dim3(256), 0, s, (const float*)glu_x, (float*)state, w, GluBias<float>{bias},
+                  nvalid, (float*)y, C, d, K);
   else
-    TFASR_KLAUNCH(stream_glu_dwconv_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)glu_x, (bf16_t*)state, w, bias, nvalid, (bf16_t*)y, C, d, K);
+    TFASR_KLAUNCH((stream_dwconv_kernel<bf16_t, GluBias<bf16_t>>), grid, dim3(256), 0, s, (const bf16_t*)glu_x, (bf16_t*)state, w,
+                  GluBias<bf16_t>{bias}, nvalid, (bf16_t*)y, C, d, K);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_stream_rowconv_fwd(const void* x, void* state, const float* w, const float* scale, const float* shift, const int32_t* nvalid,
+                                        void* y, int B, int C, int d, int K, int dtype, void* stream_) {
+  if (!x || !w || !scale || !shift || !nvalid || !y || B <= 0 || C <= 0 || d <= 0 || K <= 0) return TFASR_STATUS_INVALID_VALUE;
+  if (K > 1 && !state) return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
+  if (C > MAXC || K > 32 || B > 65535) return TFASR_STATUS_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream_;
+  const dim3 grid((d + 63) / 64, B);
+  if (dtype == TFASR_F32)
+    TFASR_KLAUNCH((stream_dwconv_kernel<float, RowAffine<float>>), grid, dim3(256), 0, s, (const float*)x, (float*)state, w,
+                  RowAffine<float>{scale, shift}, nvalid, (float*)y, C, d, K);
+  else
+    TFASR_KLAUNCH((stream_dwconv_kernel<bf16_t, RowAffine<bf16_t>>), grid, dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)state, w,
+                  RowAffine<bf16_t>{scale, shift}, nvalid, (bf16_t*)y, C, d, K);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }

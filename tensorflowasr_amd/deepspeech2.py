@@ -29,8 +29,18 @@ such path: there a batch row equals the utterance alone.
 The CTC decoders (greedy, host and device beam search, n-best), forced alignment, evaluate, the precision switch (f32 twin by default,
 bf16 opt-in) and the .npz checkpoints are ConformerCTC's.  feature_type "spectrogram" (feature_extraction.py:233-235: ln(|STFT|^2 + eps),
 first num_feature_bins bins) runs on the log-mel kernel with the first F columns of the identity as its weight matrix.  Training,
-streaming (the unidirectional variant would carry LSTM states as call_next does), GRU / SimpleRNN, conv_type conv1d and .weights.h5
-import are not built: train_step / loss_and_backward / compile / stream / stream_state / encode_chunk raise.
+GRU / SimpleRNN, conv_type conv1d and .weights.h5 import are not built: train_step / loss_and_backward / compile raise.
+
+Streaming.  A config that is causal throughout (conv_padding "causal", rnn_bidirectional False: uni.yml.j2) opens the session of the
+other causal models: stream() / stream_state() / encode_chunk() (streaming.StreamingRecognizer, DS2StreamState, ds2_encode_chunk).
+Stream b holds, bit for bit, the encoder frames `encode` gives that utterance alone and the tokens `recognize` gives it, however the
+samples arrive and whatever the other streams do.  Carried per stream: the last kh - 1 input rows of every conv block, each LSTM's
+(h, c) and the last K - 1 input rows of every RowConv1D.  This is NOT what the reference's DeepSpeech2Encoder.call_next computes
+(encoders/deepspeech2.py:505-524): that carries the LSTM states only and runs the conv module and every RowConv1D on each chunk with
+fresh causal zero padding, so its chunked output differs from its own offline output in the first kh - 1 encoder frames of every chunk
+and in the 2w frames behind them in every RowConv1D.  The LSTM states carried here are the reference's, in its layout:
+DS2StreamState.reference_states() is [B, nlayers, 2, P], (h, c), what get_initial_state / call_next exchange.  Any other config
+(bidirectional, "same" padding) refuses all three calls with the reason, before it looks at an argument.
 """
 import numpy as np
 import torch
@@ -54,9 +64,31 @@ class DeepSpeech2CTC(ConformerCTC):
     # ------------------------------------------------------------------------------------------- inference only
     def _inference_only(self, *a, **k):
         raise NotImplementedError("DeepSpeech2CTC is inference only: the Conv2D / LSTM gradients and BatchNorm in batch-statistics mode are "
-                                  "not built, and neither is streaming (weights arrive through load_weights)")
+                                  "not built (weights arrive through load_weights)")
 
-    train_step = loss_and_backward = compile = stream = stream_state = encode_chunk = _inference_only
+    train_step = loss_and_backward = compile = _inference_only
+
+    # ------------------------------------------------------------------------------------------- streaming (the causal variant)
+    def stream_state(self, batch_size=1, precision=None):
+        from . import streaming
+
+        streaming.check_streamable(self)
+        return streaming.DS2StreamState(streaming._twin(self, precision), batch_size)
+
+    def encode_chunk(self, state, feats, nframes):
+        from . import streaming
+
+        streaming.check_streamable(self)
+        return streaming.ds2_encode_chunk(state, feats, nframes)
+
+    def stream(self, batch_size=1, chunk_frames=32, beam_width=0, max_frames=3000, precision=None):
+        """Incremental recognition session (streaming.StreamingRecognizer) over steps of `chunk_frames` feature frames, a positive multiple
+        of the product of the time strides.  Only a config that is causal throughout streams (see the module docstring); a stream then
+        holds bit for bit the frames `encode` gives the utterance alone.  beam_width as ConformerCTC's."""
+        from . import streaming
+
+        streaming.check_streamable(self)
+        return streaming.StreamingRecognizer(self, batch_size, precision, 1, beam_width, max_frames, chunk_frames=chunk_frames)
 
     def _encoder_length(self, t):
         return self.cfg.encoder_length(t)

@@ -1609,6 +1609,23 @@ def stream_glu_dwconv_fwd(glu_x, state, w, bias, nvalid, B, C, out=None):
     return out
 
 
+def stream_rowconv_fwd(x, state, w, scale, shift, nvalid, B, C, out=None):
+    """DeepSpeech2's RowConv1D over one step: causal depthwise conv without bias over state [B, K-1, d] ++ the valid rows of x [B*C, d], then
+    * scale + shift (the folded BatchNorm) and the ReLU -> [B*C, d], rows >= nvalid zero; state updated in place.  The valid rows are the
+    bits of dwconv_fwd -> channel_affine_fwd(relu=True) over the whole sequence."""
+    d, Kt = x.shape[-1], w.shape[0]
+    assert w.dtype == scale.dtype == shift.dtype == torch.float32 and w.shape[1] == d and scale.numel() == d and shift.numel() == d
+    assert nvalid.dtype == torch.int32 and nvalid.numel() == B and x.numel() == B * C * d and x.is_contiguous()
+    assert Kt == 1 or (state.shape == (B, Kt - 1, d) and state.dtype == x.dtype and state.is_contiguous())
+    if out is None:
+        out = torch.empty(B * C, d, dtype=x.dtype, device=x.device)
+    st = _L().tfasr_stream_rowconv_fwd(_p(x), _p(state), _p(w), _p(scale), _p(shift), _p(nvalid), _p(out), B, C, d, Kt, _dt(x), _stream())
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported(f"stream_rowconv_fwd: {C} rows / {Kt} taps beyond {STREAM_MAX_CHUNK} rows a step, 32 taps")
+    check(st, "stream_rowconv_fwd")
+    return out
+
+
 def logmel_stream(signal, nlen, prev, has_prev, T0, window, melw, band, frame_step, nfft, preemph, eps, out_dtype):
     """tfasr_logmel on the unconsumed samples of B streams: signal [B, N] f32, nlen [B] real samples per row, prev / has_prev [B] the sample
     in front of column 0 -> [B, T0, F]."""
@@ -1723,15 +1740,23 @@ def conv2d_pack_weight(w):
     return out
 
 
-def conv2d_fwd(x, w, shape, bias=None, scale=None, shift=None, relu=False, strides=(1, 1), padding="same", out=None):
+def conv2d_fwd(x, w, shape, bias=None, scale=None, shift=None, relu=False, strides=(1, 1), padding="same", out=None, lead=0):
     """Conv2D, channels-last: x [B, T, F, Cin] (f32 | bf16) -> [B, ceil(T / st), ceil(F / sf), Cout]; shape = (kh, kw, Cin, Cout); padding
     "same" or "causal" on both axes (conv_pad_out).  w: the Keras kernel (f32 activations) or conv2d_pack_weight's copy (bf16
-    activations).  Epilogue (acc + bias) * scale + shift [ReLU] in f32."""
+    activations).  Epilogue (acc + bias) * scale + shift [ReLU] in f32.
+    lead = kh - 1 (causal padding only): x is [tail | new rows], the first `lead` rows being real left context carried from the step in
+    front (zeros at a stream's start) in place of the causal zero padding: the time axis is convolved "valid" and the output has
+    ceil((T - lead) / st) rows, those of the new rows; the frequency axis keeps its causal padding."""
     kh, kw, Cin, Cout = (int(v) for v in shape)
     st, sf = (int(v) for v in strides)
     assert x.dim() == 4 and x.shape[3] == Cin
     B, T, F = x.shape[:3]
     (pad_t, To), (pad_f, Fo) = conv_pad_out(T, kh, st, padding), conv_pad_out(F, kw, sf, padding)
+    lead = int(lead)
+    if lead:
+        if padding != "causal" or lead != kh - 1 or T < lead:
+            raise ValueError(f"conv2d_fwd: lead = {lead} needs causal padding, lead == kh - 1 = {kh - 1} and at least that many rows")
+        pad_t, To = 0, -(-(T - lead) // st)
     if out is None:
         out = torch.empty(B, To, Fo, Cout, dtype=x.dtype, device=x.device)
     assert w.dtype == x.dtype and out.shape == (B, To, Fo, Cout) and out.dtype == x.dtype
@@ -1769,12 +1794,15 @@ def lstm_infer_workspace_size(B, T, P, ndir=1, dtype=TFASR_F32):
     return n.value
 
 
-def lstm_infer_fwd(xg, rk, lengths=None, ndir=1, y=None, want_state=False, ws=None):
+def lstm_infer_fwd(xg, rk, lengths=None, ndir=1, y=None, want_state=False, ws=None, state=None, state_out=None):
     """The inference recurrence of one (ndir 1) or two (ndir 2: keras Bidirectional, concat) LSTMs over xg [B, T, ndir * 4P] (input
     projections of the directions side by side), rk [ndir, P, 4P], lengths [B] int32 (device) or None -> y [B, T, ndir * P]; with
     want_state also (h_last, c_last) [ndir, B, P] f32.  One persistent launch where the shape allows it, else the per-step kernels
     (tfasr_lstm_infer_fwd decides).  ws: a uint8 workspace to use (its first ndir * 16 int32 words are the directions' {count, abort}
-    records, read by tests); default: the shared grow-only one."""
+    records, read by tests); default: the shared grow-only one.
+    state = (h0, c0) [B, P] f32: the recurrence continues from it (one direction only; tfasr_lstm_infer_fwd_state) - the h_last / c_last
+    of the call over the frames in front of these.  state_out = (h_last, c_last) [B, P] f32 buffers to fill, which must not be the
+    state's own (the library refuses aliases: callers ping-pong two pairs); they are returned as with want_state, shaped as given."""
     B, T, G = xg.shape
     P = G // (4 * ndir)
     assert G == ndir * 4 * P and rk.numel() == ndir * P * 4 * P and rk.dtype == xg.dtype and xg.is_contiguous()
@@ -1782,18 +1810,34 @@ def lstm_infer_fwd(xg, rk, lengths=None, ndir=1, y=None, want_state=False, ws=No
     if y is None:
         y = torch.empty(B, T, ndir * P, dtype=xg.dtype, device=xg.device)
     assert y.shape == (B, T, ndir * P) and y.dtype == xg.dtype
-    h_last = c_last = None
-    if want_state:
+    h_last = c_last = h0 = c0 = None
+    if state_out is not None:
+        h_last, c_last = state_out
+        want_state = True
+        for t in (h_last, c_last):
+            assert t.dtype == torch.float32 and t.numel() == ndir * B * P and t.is_contiguous() and t.device == xg.device
+    elif want_state:
         h_last = torch.empty(ndir, B, P, dtype=torch.float32, device=xg.device)
         c_last = torch.empty(ndir, B, P, dtype=torch.float32, device=xg.device)
+    if state is not None:
+        h0, c0 = state
+        for t in (h0, c0):
+            assert t.dtype == torch.float32 and t.shape == (B, P) and t.is_contiguous() and t.device == xg.device
     if B == 0 or T == 0:
+        if state is not None and want_state:
+            h_last.view(B, P).copy_(h0)
+            c_last.view(B, P).copy_(c0)
         return (y, h_last, c_last) if want_state else y
     nbytes = lstm_infer_workspace_size(B, T, P, ndir, _dt(xg))
     if ws is None:
         ws = workspace(nbytes, xg.device, "lstm_infer")
     assert ws.numel() >= nbytes
-    check(_L().tfasr_lstm_infer_fwd(_p(xg), G, _p(rk), _p(lengths), _p(y), ndir * P, _p(h_last), _p(c_last), B, T, P, ndir, _dt(xg), _p(ws),
-                                    ws.numel(), _stream()), "lstm_infer_fwd")
+    if state is None:
+        check(_L().tfasr_lstm_infer_fwd(_p(xg), G, _p(rk), _p(lengths), _p(y), ndir * P, _p(h_last), _p(c_last), B, T, P, ndir, _dt(xg), _p(ws),
+                                        ws.numel(), _stream()), "lstm_infer_fwd")
+    else:
+        check(_L().tfasr_lstm_infer_fwd_state(_p(xg), G, _p(rk), _p(lengths), _p(y), ndir * P, _p(h0), _p(c0), _p(h_last), _p(c_last), B, T, P,
+                                              ndir, _dt(xg), _p(ws), ws.numel(), _stream()), "lstm_infer_fwd_state")
     return (y, h_last, c_last) if want_state else y
 
 

@@ -14,6 +14,9 @@ The kernels that touch carried state are csrc/stream.hip; the dense pieces are t
 A Transformer with a chunked config streams under the same contract (TransformerStreamState, transformer_encode_chunk): its blocks carry
 the K / V rings only (there is no convolution module), the absolute position rows are taken at each stream's own offset, and the ring
 append is part of the attention launch.
+The unidirectional DeepSpeech2 (causal Conv2D, forward LSTMs, causal RowConv1D) streams under the same contract (DS2StreamState,
+ds2_encode_chunk): it carries the last kh - 1 input rows of every conv block, each LSTM's (h, c) and the last K - 1 input rows of every
+RowConv1D.
 """
 import math
 import typing
@@ -100,8 +103,23 @@ def _check_transformer(model):
         raise NotImplementedError(f"{type(model).__name__} is inference only, and this configuration cannot be streamed: {why}")
 
 
+def _check_ds2(model):
+    """A DeepSpeech2 streams when it is causal throughout: forward LSTMs only and causal convolutions.  Everything else is refused in the
+    words of the model's other refusals ("inference only") followed by the reason."""
+    c = model.cfg
+    why = None
+    if c.rnn_bidirectional:
+        why = "rnn_bidirectional (the backward direction starts at the utterance's last frame)"
+    elif c.conv_padding != "causal":
+        why = f"conv_padding = {c.conv_padding!r} (a 'same'-padded convolution reads frames that have not arrived yet)"
+    if why is not None:
+        raise NotImplementedError(f"{type(model).__name__} is inference only, and this configuration cannot be streamed: {why}")
+
+
 def check_streamable(model):
     c = model.cfg
+    if getattr(c, "encoder", "conformer") == "deepspeech2":
+        return _check_ds2(model)
     if getattr(c, "encoder", "conformer") == "jasper":
         return  # causal convolutions only: streams exactly (JasperStreamState)
     if getattr(c, "encoder", "conformer") == "transformer":
@@ -330,6 +348,91 @@ def jasper_encode_chunk(state, feats, nframes):
     return x, nv
 
 
+class DS2StreamState:
+    """Encoder state of `batch_size` streams of the unidirectional DeepSpeech2.  Per stream:
+        each conv block   the last kh - 1 rows of its input, [kh - 1, F_in * Cin] in the compute type (zeros = the causal padding)
+        each RnnBlock     h and c [P] f32 (h holds numbers of the compute type), and with a RowConv1D the last K - 1 rows of the LSTM's
+                          output, [K - 1, P] in the compute type
+    The recurrence reads one (h, c) pair and writes another (the library refuses aliases: tfasr_lstm_infer_fwd_state), so every RnnBlock
+    owns two pairs and `cur` says which one holds the state; export / load / reference_states speak of that one only."""
+
+    def __init__(self, model, batch_size):
+        check_streamable(model)
+        self.model, self.B = model, int(batch_size)
+        B, dev, dt, mods = self.B, model.device, model.dtype, model.modules
+        shapes = model.cfg.conv_shapes()
+        self.conv_tails = [torch.zeros(B, kh - 1, fi * ci, dtype=dt, device=dev) if kh > 1 else None for kh, _kw, ci, _co, _st, _sf, fi, _fo in shapes]
+        self.hc = [[tuple(torch.zeros(B, r["P"], dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)] for r in mods["rnns"]]
+        self.cur = [0] * len(mods["rnns"])
+        self.row_tails = [torch.zeros(B, r["K"] - 1, r["P"], dtype=dt, device=dev) if r["rowconv"] and r["K"] > 1 else None for r in mods["rnns"]]
+
+    def _tensors(self):
+        hc = [t for pairs, cur in zip(self.hc, self.cur) for t in pairs[cur]]
+        return [t for t in self.conv_tails if t is not None] + hc + [t for t in self.row_tails if t is not None]
+
+    reset, export, load = StreamState.reset, StreamState.export, StreamState.load
+
+    def reference_states(self):
+        """[B, nlayers, 2, P] f32, states ordered (h, c): what the reference's DeepSpeech2Encoder.get_initial_state / call_next exchange"""
+        return torch.stack([torch.stack(list(pairs[cur]), 1) for pairs, cur in zip(self.hc, self.cur)], 1)
+
+
+DS2_PERSIST_STREAMS = 64  # tfasr_lstm_infer_fwd's persistent launch takes up to 64 batch rows
+
+
+@torch.no_grad()
+def ds2_encode_chunk(state, feats, nframes):
+    """One encoder step of the unidirectional DeepSpeech2: feats [B, n, F] (compute type, device; n a multiple of the time reduction
+    factor), nframes [B] feature frames that are real per stream (0 = idle; n; fewer for a stream's last step) -> (enc [B, n / factor,
+    dmodel], nvalid [B] int32 device, reduced over the time strides as cfg.encoder_length does); advances state.  Each conv block
+    convolves [tail | rows] with the tail as real left context (conv2d_fwd's `lead`), then the tail moves to the last rows valid for the
+    stream; each RnnBlock is one GEMM, one recurrence continued from the carried state (tfasr_lstm_infer_fwd_state, lengths = the valid
+    rows) and one tfasr_stream_rowconv_fwd; then the FC blocks.  In bf16 more than 64 streams run the recurrence in slices of 64: every
+    slice stays on the persistent launch, the route the utterance alone takes (the per-step route rounds differently)."""
+    m = state.model
+    c, B = m.cfg, state.B
+    factor = int(c.time_reduction_factor)
+    host = [int(v) for v in (nframes.tolist() if isinstance(nframes, torch.Tensor) else nframes)]
+    if feats.dim() != 3 or feats.shape[0] != B or feats.shape[1] < factor or feats.shape[1] % factor or len(host) != B or min(host) < 0 or \
+            max(host) > feats.shape[1]:
+        raise ValueError(f"encode_chunk takes [B = {B}, n, F] feature frames, n a positive multiple of {factor}, and B frame counts within them")
+    nv = m._h2d(host)
+    x = feats.contiguous()
+    rows = x.shape[1]
+    for mod, tail in zip(m.modules["convs"], state.conv_tails):
+        w, bias, scale, shift = m._conv_consts(mod["name"])
+        shape = (mod["kh"], mod["kw"], mod["cin"], mod["cout"])
+        lead = 0 if tail is None else tail.shape[1]
+        win = x.view(B, rows, -1) if tail is None else torch.cat([tail, x.view(B, rows, -1)], 1)
+        x = K.conv2d_fwd(win.view(B, lead + rows, -1, mod["cin"]), w, shape, bias=bias, scale=scale, shift=shift, relu=True,
+                         strides=(mod["st"], mod["sf"]), padding="causal", lead=lead)
+        if tail is not None:
+            K.conv1d_tail_update(win, nv, tail)
+        if mod["st"] > 1:
+            nv = ((nv + (mod["st"] - 1)) // mod["st"]).to(torch.int32).contiguous()
+        rows = x.shape[1]
+    x = x.view(B, rows, -1)
+    sl = DS2_PERSIST_STREAMS if m.dtype != torch.float32 else B
+    for li, r in enumerate(m.modules["rnns"]):
+        k, b, rk = m._rnn_consts(r)
+        P = r["P"]
+        xg = K.matmul(x.view(B * rows, x.shape[2]), k, bias=b).view(B, rows, 4 * P)
+        (h0, c0), (h1, c1) = state.hc[li][state.cur[li]], state.hc[li][state.cur[li] ^ 1]
+        y = torch.empty(B, rows, P, dtype=xg.dtype, device=xg.device)
+        for b0 in range(0, B, sl):
+            e = min(b0 + sl, B)
+            K.lstm_infer_fwd(xg[b0:e], rk, nv[b0:e], y=y[b0:e], state=(h0[b0:e], c0[b0:e]), state_out=(h1[b0:e], c1[b0:e]))
+        state.cur[li] ^= 1
+        if r["rowconv"]:
+            scale, shift = m._affine(r["rowconv"] + "/bn")
+            y = K.stream_rowconv_fwd(y.view(B * rows, P), state.row_tails[li], m.ps.p(r["rowconv"] + "/conv/w"), scale, shift, nv, B, rows)
+        x = y.view(B, rows, P)
+    for f in m.modules["fcs"]:
+        w, bias = m._fc_consts(f)
+        x = K.conv1d_fwd(x, w, (1, f["din"], f["dout"]), bias=bias, relu=True)
+    return x.view(B, rows, c.dmodel), nv
+
+
 def check_stream_args(batch_size=1, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
     """The session arguments that need no device to judge -> them as ints.  beam_width 0 = the greedy session; 1 .. 64 = a beam of that
     many hypotheses per stream (the device searches keep a beam in one workgroup's LDS: 64 rows at most)."""
@@ -365,7 +468,8 @@ class StreamingRecognizer:
     A Jasper model (causal convolutions only) opens the same session through JasperCTC.stream(batch_size, chunk_frames=...): a step is
     chunk_frames feature frames instead of 4 * chunk_size, its encoder state is JasperStreamState (per layer with K > 1 taps the last
     (K - 1) * dilation input rows, sum over layers of B * (K - 1) * dilation * Cin elements), and in the CTC beam formula above chunk_size
-    reads chunk_frames / time_reduction_factor.
+    reads chunk_frames / time_reduction_factor.  The unidirectional DeepSpeech2 opens it the same way (DeepSpeech2CTC.stream); its encoder
+    state is DS2StreamState.
 
     A Transformer model with a chunked config (TransformerCTC.stream / TransformerTransducer.stream) takes the Conformer's step,
     4 * chunk_size feature frames, and the Conformer's frame reduction; its encoder state is TransformerStreamState (per block two rings of
@@ -380,20 +484,25 @@ class StreamingRecognizer:
         self.max_tokens_per_frame = int(max_tokens_per_frame)
         c = model.cfg
         self.jasper = getattr(c, "encoder", "conformer") == "jasper"
+        self.ds2 = getattr(c, "encoder", "conformer") == "deepspeech2"
         self._encode = encode_chunk
-        if self.jasper:
-            self._encode = jasper_encode_chunk
+        if self.jasper or self.ds2:
+            self._encode = jasper_encode_chunk if self.jasper else ds2_encode_chunk
             # a step is `chunk_frames` feature frames -> chunk_frames / factor encoder frames (a stream's last step: ceil of what is left)
             factor = int(c.time_reduction_factor)
             self.chunk_frames = int(chunk_frames if chunk_frames is not None else 32)
             if self.chunk_frames < factor or self.chunk_frames % factor:
                 raise ValueError(f"stream: chunk_frames {self.chunk_frames} must be a positive multiple of the time reduction factor {factor}")
-            self.state = JasperStreamState(self.enc_model, batch_size)
+            if self.ds2 and self.chunk_frames // factor > K.STREAM_MAX_CHUNK:
+                raise ValueError(f"stream: chunk_frames {self.chunk_frames} is more than {K.STREAM_MAX_CHUNK} encoder frames a step "
+                                 "(tfasr_stream_rowconv_fwd's limit)")
+            self.state = (JasperStreamState if self.jasper else DS2StreamState)(self.enc_model, batch_size)
             self.C = self.chunk_frames // factor
-            self._reduce = lambda t: -(-t // factor)
+            self._reduce = (lambda t: -(-t // factor)) if self.jasper else c.encoder_length
         else:
             if chunk_frames is not None:
-                raise ValueError("stream: chunk_frames belongs to the Jasper session; a Conformer's step is 4 * chunk_size feature frames")
+                raise ValueError("stream: chunk_frames belongs to the Jasper and DeepSpeech2 sessions; a Conformer's step is 4 * chunk_size "
+                                 "feature frames")
             if getattr(c, "encoder", "conformer") == "transformer":  # the Conformer's step and frame reduction, its own encoder state
                 self.state, self._encode = TransformerStreamState(self.enc_model, batch_size), transformer_encode_chunk
             else:
@@ -490,9 +599,11 @@ class StreamingRecognizer:
                     nlen[b] = len(seg)
             feats = K.logmel_stream(em._h2d(torch.from_numpy(sig), torch.float32), em._h2d(nlen), em._h2d(torch.from_numpy(self.prev.copy()), torch.float32),
                                     em._h2d(self.has_prev.copy()), self.chunk_frames, window, melw, band, c.frame_step, c.nfft, c.preemphasis,
-                                    c.epsilon, torch.float32 if self.jasper else em.dtype)
+                                    c.epsilon, torch.float32 if self.jasper or self.ds2 else em.dtype)
             if self.jasper:
                 feats = em._scale_feats(feats)
+            elif self.ds2 and em.dtype != torch.float32:  # DeepSpeech2CTC.frontend's route: f32 out of the kernel, then the cast
+                feats = K.cast(feats, torch.empty(feats.shape, dtype=em.dtype, device=feats.device))
             for b in range(B):
                 if take[b]:
                     used = take[b] * self.step
