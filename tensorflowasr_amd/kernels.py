@@ -518,8 +518,11 @@ def cast_colsum_many(x, y, stride, nmat, rows, C, colsums):
     for b0 in range(0, int(nmat), 64):
         n = min(64, int(nmat) - b0)
         arr = (ctypes.c_void_p * n)(*[(t.data_ptr() if t is not None else None) for t in colsums[b0:b0 + n]])
-        check(_L().tfasr_cast_colsum_many(x.data_ptr() + b0 * int(stride) * x.element_size(), y.data_ptr() + b0 * int(stride) * y.element_size(),
-                                          int(stride), n, int(rows), int(C), arr, _stream()), "cast_colsum_many")
+        st = _L().tfasr_cast_colsum_many(x.data_ptr() + b0 * int(stride) * x.element_size(), y.data_ptr() + b0 * int(stride) * y.element_size(),
+                                         int(stride), n, int(rows), int(C), arr, _stream())
+        if st == _lib.STATUS_UNSUPPORTED:
+            raise _lib.TfasrUnsupported(f"cast_colsum_many: C = {C} / stride = {stride} must be multiples of 4 and the buffers 16-byte aligned")
+        check(st, "cast_colsum_many")
     return y
 
 
