@@ -1087,6 +1087,26 @@ int tfasr_attn_plain_fwd(const void* qkv, const int32_t* lengths, void* out, flo
                          int dtype, void* stream);
 int tfasr_add_pe(const void* x, const float* pe, const int32_t* lengths, void* y, int B, int T, int d, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Tail of one RnnTransducerBlock (csrc/rnnt_block.hip; declaration added under ABI 44, nothing existing changes): LayerNormalization over
+ * the LSTM's units, Dense, and the bookkeeping of the TimeReduction behind it (encoders/rnnt.py:66-82, subsampling.py:34-40), one launch.
+ *   y [B, T, P], row stride ld_y elements (stream b starts at row b * T);  out [B, Tpad, N] contiguous;  gamma / beta [P], bias [N] f32
+ *   (bias may be NULL);  lengths, off int32 [B] or NULL (T, 0);  out_lengths int32 [B] or NULL.
+ *   out[b, off_b + t, :] = LN(y[b, t, :]) . W + bias for t < T, where a row with t >= lengths[b] is computed from an ALL-ZERO row whatever
+ *   y holds there (the masked LSTM's zeros: the row becomes beta . W + bias, not zero);  rows [off_b + T, Tpad) are written as zeros (the
+ *   tf.pad rows of a `post` reduction, which is then a view [B, Tpad / factor, factor * N]);  rows in front of off_b (a streaming step's
+ *   carried rows) are not touched and rows that would fall past Tpad are dropped;  out_lengths[b] = ceil((off_b + min(lengths[b], T)) / factor).
+ *   W: TFASR_F32 -> the Keras kernel [P, N] f32;  TFASR_BF16 -> the packed bf16 copy tfasr_conv1d_pack_weight writes for (K 1, Cin P,
+ *   Cout N).  bf16 runs on MFMA with f32 statistics and accumulation; the f32 twin is a plain FMA kernel.
+ * The bits of an output row depend on its input row and the weights only - not on T, B, off or the rows that share the launch (rows
+ * are normalised into LDS in one fixed order, the product runs over the whole reduction from there: no split, no atomics).
+ * P % 32 == 0 up to 2048, N % 16 == 0 up to 1024, B <= 65535: anything else is UNSUPPORTED (callers then run tfasr_layernorm_fwd +
+ * tfasr_gemm).  INVALID_VALUE: null y / gamma / beta / W / out, negative sizes, Tpad < T, factor < 1 or not a divisor of Tpad, ld_y < P,
+ * pointers or rows of y not 16-byte aligned.  All of it is decided on the host before any launch. */
+int tfasr_rnnt_block_tail_fwd(const void* y, long ld_y, const int32_t* lengths, const int32_t* off, const float* gamma, const float* beta,
+                              const void* W, const float* bias, void* out, int32_t* out_lengths, int B, int T, int Tpad, int P, int N,
+                              int factor, float eps, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

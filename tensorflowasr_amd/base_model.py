@@ -417,4 +417,8 @@ def model_from_config(model_config, device=None, dtype=torch.bfloat16, seed=0, d
 
         cls = transformer.TransformerCTC if key.startswith("ctc.") else transformer.TransformerTransducer
         return cls(configs.transformer_from_reference(conf, class_name=name), device, dtype=dtype, seed=seed, dp=dp)
+    if key == "transducer.rnnt.RnnTransducer":
+        from .rnnt import RnnTransducer
+
+        return RnnTransducer(configs.rnnt_from_reference(conf), device, dtype=dtype, seed=seed, dp=dp)
     raise NotImplementedError(f"{name}: not on the MI355X hot path (SURVEY.md section 8: Conformer transducer / CTC, ContextNet)")

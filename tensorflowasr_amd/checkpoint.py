@@ -137,9 +137,25 @@ def transformer_keras_path(name, *_):
     return {"enc": "encoder/", "dec": "decoder/"}[top] + head + "/" + kleaf
 
 
+def rnnt_keras_path(name, *_):
+    """Keras variable path of an RNN-Transducer tensor (models/transducer/rnnt.py:60-77: RnnTransducerEncoder "encoder"; layer names of
+    encoders/rnnt.py): enc/block_1/lstm/rk -> encoder/block_1/lstm/recurrent_kernel, enc/block_1/ln/b -> encoder/block_1/ln/beta,
+    enc/block_1/projection/w -> encoder/block_1/projection/kernel.  The prediction / joint variables keep the Conformer transducer's
+    paths (base_transducer.py)."""
+    if name.startswith(("pred/", "joint/")):
+        return _TAIL[name]
+    top, _, rest = name.partition("/")
+    head, _, leaf = rest.rpartition("/")
+    if top != "enc" or not head or leaf not in ("w", "k", "rk", "b", "g"):
+        raise KeyError(f"no Keras path is known for {name!r}")
+    kleaf = ("beta" if head.endswith("/ln") else "bias") if leaf == "b" else _DS2_LEAF[leaf]
+    return "encoder/" + head + "/" + kleaf
+
+
 def _path_fn(model):
     enc = getattr(model.cfg, "encoder", "conformer")
-    return {"jasper": jasper_keras_path, "deepspeech2": deepspeech2_keras_path, "transformer": transformer_keras_path}.get(enc, keras_path)
+    return {"jasper": jasper_keras_path, "deepspeech2": deepspeech2_keras_path, "transformer": transformer_keras_path,
+            "rnnt": rnnt_keras_path}.get(enc, keras_path)
 
 
 def _to_keras_layout(name, a):

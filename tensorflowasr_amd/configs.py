@@ -826,3 +826,181 @@ def transformer_schedule(step, dmodel, warmup_steps=10000, scale=2.0, max_lr=Non
     if min_lr is not None:
         lr = max(min_lr, lr)
     return lr
+
+
+# ------------------------------------------------------------------------------------------------------------------ RNN-Transducer
+@dataclass
+class RnnTransducerConfig:
+    """The keyword surface of tensorflow_asr.models.transducer.rnnt.RnnTransducer (models/transducer/rnnt.py:23-59) with `speech_config`
+    flattened as in ConformerConfig and the `encoder_` prefix dropped where no prediction keyword of the same name exists.  The defaults
+    are the shipped examples/models/transducer/rnnt/small.yml.j2 (the class's own defaults - two prediction LSTMs with a projection - are
+    not built).  Inference only: the regulariser is kept for the record and never applied."""
+    # speech_config
+    sample_rate: int = 16000
+    frame_ms: int = 25
+    stride_ms: int = 10
+    nfft: int = 512
+    num_feature_bins: int = 80
+    preemphasis: float = 0.97
+    epsilon: float = 1e-6
+    lower_edge_hertz: float = 0.0
+    upper_edge_hertz: float = 8000.0
+    # encoder (models/encoders/rnnt.py:131-146)
+    reduction_positions: list = field(default_factory=lambda: ["post", "post", "post", "post"])
+    reduction_factors: list = field(default_factory=lambda: [3, 0, 2, 0])
+    encoder_dmodel: int = 320   # the blocks' Dense "projection" width; `dmodel` below is the width of the encoder's OUTPUT rows
+    nlayers: int = 4
+    encoder_rnn_type: str = "lstm"
+    encoder_rnn_units: int = 1024
+    layer_norm: bool = True   # encoder_layer_norm
+    # prediction / joint (base_transducer.py), the names the shared head reads
+    embed_dim: int = 512
+    rnn_units: int = 1024     # prediction_rnn_units
+    joint_dim: int = 320
+    prediction_layer_norm: bool = True
+    vocab_size: int = 1000
+    blank: int = 0
+    l2: float = 1e-6
+    # what the shared model code reads from every config
+    encoder: str = "rnnt"
+    head: str = "transducer"
+    dropout: float = 0.0
+    chunk_size: int = None
+    history_size: int = None
+    time_masking: dict = None
+    freq_masking: dict = None
+    head_size: int = 64   # (no attention, no convolution: the values only keep ParamStore's head / filter padding off)
+    num_heads: int = 1
+    filters: int = 64
+
+    def __post_init__(self):
+        self.reduction_positions = [str(p) for p in self.reduction_positions]
+        self.reduction_factors = [int(f) for f in self.reduction_factors]
+        self.nlayers = int(self.nlayers)
+        if self.nlayers < 1:
+            raise ValueError("encoder_nlayers must be positive")
+        if len(self.reduction_positions) != self.nlayers:  # encoders/rnnt.py:147-148
+            raise ValueError("encoder_reduction_positions length must be equal to encoder_nlayers")
+        if len(self.reduction_factors) != self.nlayers:
+            raise ValueError("encoder_reduction_factors length must be equal to encoder_nlayers")
+        if any(p not in ("pre", "post") for p in self.reduction_positions):  # encoders/rnnt.py:43
+            raise ValueError("encoder_reduction_positions: every entry must be 'post' or 'pre'")
+        if any(f < 0 for f in self.reduction_factors):
+            raise ValueError("encoder_reduction_factors: every entry must be >= 0 (0: no reduction)")
+        if self.encoder_rnn_type != "lstm":
+            raise NotImplementedError(f"encoder_rnn_type={self.encoder_rnn_type!r}: only lstm is built (no GRU / SimpleRNN recurrence)")
+        if int(self.encoder_rnn_units) < 32 or int(self.encoder_rnn_units) % 32:
+            raise NotImplementedError(f"encoder_rnn_units={self.encoder_rnn_units}: a multiple of 32")
+        if int(self.encoder_dmodel) < 16 or int(self.encoder_dmodel) % 16:
+            raise NotImplementedError(f"encoder_dmodel={self.encoder_dmodel}: a multiple of 16")
+        for i, f in enumerate(self.factors):
+            if (self.block_in(i) * (f if self.reduction_positions[i] == "pre" else 1)) % 8:
+                raise NotImplementedError(f"block {i}: an LSTM input width of {self.block_in(i)} x {f} is not a multiple of 8")
+
+    @property
+    def factors(self):
+        """the blocks' effective reduction factors (0 = no TimeReduction layer = 1)"""
+        return [max(int(f), 1) for f in self.reduction_factors]
+
+    def block_in(self, i):
+        """width of block i's input rows in front of its own `pre` reduction"""
+        if i == 0:
+            return int(self.num_feature_bins)
+        return int(self.encoder_dmodel) * (self.factors[i - 1] if self.reduction_positions[i - 1] == "post" else 1)
+
+    def lstm_in(self, i):
+        return self.block_in(i) * (self.factors[i] if self.reduction_positions[i] == "pre" else 1)
+
+    @property
+    def dmodel(self):
+        """width of the encoder's output rows (what the joint network's encoder projection is built on): a `post` reduction of the LAST
+        block folds its factor into them"""
+        return int(self.encoder_dmodel) * (self.factors[-1] if self.reduction_positions[-1] == "post" else 1)
+
+    @property
+    def frame_length(self):
+        return int(round(self.sample_rate * self.frame_ms / 1000.0))
+
+    @property
+    def frame_step(self):
+        return int(round(self.sample_rate * self.stride_ms / 1000.0))
+
+    @property
+    def time_reduction_factor(self):
+        """encoders/rnnt.py:153-169: the product of the blocks' factors"""
+        return int(math.prod(self.factors))
+
+    def encoder_length(self, n):
+        """math_util.get_reduced_length layer by layer (subsampling.py:39): ceil(n / f) per reducing block"""
+        n = int(n)
+        for f in self.factors:
+            n = -(-n // f)
+        return n
+
+
+def rnnt(vocab_size=1000, **over):
+    """examples/models/transducer/rnnt/small.yml.j2: 4 x (LSTM(1024) -> LayerNorm -> Dense(320)), `post` reductions 3 and 2."""
+    kw = dict(vocab_size=vocab_size, time_masking=dict(prob=1.0, num_masks=5, mask_factor=-1, p_upperbound=0.05),
+              freq_masking=dict(prob=1.0, num_masks=1, mask_factor=27))
+    kw.update(over)
+    return RnnTransducerConfig(**kw)
+
+
+def rnnt_tiny(vocab_size=29, **over):
+    kw = dict(vocab_size=vocab_size, num_feature_bins=16, reduction_positions=["post", "post", "pre"], reduction_factors=[3, 0, 2], encoder_dmodel=16,
+              nlayers=3, encoder_rnn_units=32, embed_dim=24, rnn_units=24, joint_dim=40)
+    kw.update(over)
+    return RnnTransducerConfig(**kw)
+
+
+_RNNT_KEYS = {  # constructor keyword -> field (models/transducer/rnnt.py:23-59)
+    "encoder_reduction_positions": "reduction_positions", "encoder_reduction_factors": "reduction_factors", "encoder_dmodel": "encoder_dmodel",
+    "encoder_nlayers": "nlayers", "encoder_rnn_type": "encoder_rnn_type", "encoder_rnn_units": "encoder_rnn_units",
+    "encoder_layer_norm": "layer_norm", "prediction_embed_dim": "embed_dim", "prediction_rnn_units": "rnn_units",
+    "prediction_layer_norm": "prediction_layer_norm", "joint_dim": "joint_dim", "vocab_size": "vocab_size", "blank": "blank",
+}
+_RNNT_CLASS_DEFAULTS = {  # what the class takes for a keyword the mapping omits (rnnt.py:28-52)
+    "encoder_reduction_positions": ["pre"] * 8, "encoder_reduction_factors": [6, 0, 0, 0, 0, 0, 0, 0], "encoder_dmodel": 640,
+    "encoder_nlayers": 8, "encoder_rnn_type": "lstm", "encoder_rnn_units": 2048, "encoder_layer_norm": False, "prediction_embed_dim": 320,
+    "prediction_rnn_units": 2048, "prediction_layer_norm": False, "joint_dim": 640,
+    "prediction_label_encode_mode": "embedding", "prediction_num_rnns": 2, "prediction_rnn_type": "lstm", "prediction_projection_units": 640,
+    "joint_activation": "tanh", "prejoint_encoder_linear": True, "prejoint_prediction_linear": True, "postjoint_linear": False,
+    "joint_mode": "add",
+}
+_RNNT_ONLY = {  # keywords that change the network and are built for one value only (the head is ConformerTransducer's)
+    "encoder_trainable": (True,), "prediction_trainable": (True,), "joint_trainable": (True,), "bias_regularizer": (None,),
+    "activity_regularizer": (None,), "prediction_label_encode_mode": ("embedding",), "prediction_num_rnns": (1,),
+    "prediction_rnn_type": ("lstm",), "prediction_projection_units": (0,), "prediction_layer_norm": (True,), "joint_activation": ("tanh",),
+    "prejoint_encoder_linear": (True,), "prejoint_prediction_linear": (True,), "postjoint_linear": (False,), "joint_mode": ("add",),
+}
+_RNNT_IGNORED = ("name", "speech_config", "kernel_regularizer",
+                 # keras' LSTM implementation / unroll switches change nothing in the inference arithmetic
+                 "encoder_rnn_unroll", "prediction_rnn_implementation", "prediction_rnn_unroll")
+
+
+def rnnt_from_reference(config: dict):
+    """The YAML's `model_config.config` of tensorflow_asr.models.transducer.rnnt>RnnTransducer (small.yml.j2:3-49) -> RnnTransducerConfig.
+    A keyword the mapping omits takes the CLASS's default - so a mapping must say `prediction_num_rnns: 1`, `prediction_projection_units:
+    0` and `prediction_layer_norm: True`, as the shipped file does.  Every keyword is mapped or raises NotImplementedError with its name."""
+    c = dict(_RNNT_CLASS_DEFAULTS)
+    c.update(config)
+    sc = dict(c.get("speech_config") or {})
+    aug = (sc.get("augmentation_config") or {}).get("feature_augment", {}) or {}
+    for k, ok in _RNNT_ONLY.items():
+        if k in c and c[k] not in ok:
+            raise NotImplementedError(f"{k}={c[k]!r}: only {ok} is built")
+    reg = c.get("kernel_regularizer") or {}
+    if reg and (not isinstance(reg, dict) or str(reg.get("class_name", "l2")).lower() != "l2"):
+        raise NotImplementedError(f"kernel_regularizer={reg!r}: only an l2 regulariser is known")
+    kw = dict(**speech_kwargs(sc), l2=float((reg.get("config") or {}).get("l2", 0.0)) if reg else 0.0)
+    for k, v in c.items():
+        if k in _RNNT_IGNORED or (k in _RNNT_ONLY and k not in _RNNT_KEYS):
+            continue
+        if k not in _RNNT_KEYS:
+            raise NotImplementedError(f"{k}={v!r}: not a keyword of models/transducer/rnnt.py:23-59 that is built here")
+        kw[_RNNT_KEYS[k]] = v
+    if "time_masking" in aug:
+        kw["time_masking"] = dict(aug["time_masking"])
+    if "freq_masking" in aug:
+        kw["freq_masking"] = dict(aug["freq_masking"])
+    return RnnTransducerConfig(**kw)

@@ -1872,3 +1872,47 @@ def add_pe(x, pe, lengths=None, y=None):
         y = torch.empty_like(x)
     check(_L().tfasr_add_pe(_p(x), _p(pe), _p(lengths), _p(y), B, T, d, _dt(x), _stream()), "add_pe")
     return y
+
+
+# ------------------------------------------------------------------------------------------- RnnTransducerBlock tail (csrc/rnnt_block.hip)
+def rnnt_block_tail_supported(P, N):
+    """the range of tfasr_rnnt_block_tail_fwd (include/tfasr_hip.h); outside it callers run layernorm_fwd + gemm"""
+    return P % 32 == 0 and 0 < P <= 2048 and N % 16 == 0 and 0 < N <= 1024
+
+
+def rnnt_block_tail_fwd(y, gamma, beta, W, bias, N, lengths=None, off=None, factor=1, Tpad=None, out=None, out_lengths=None, eps=1e-3):
+    """out[b, off_b + t, :] = LayerNorm(y[b, t, :]) W + bias in one launch: y [B, T, P] (f32 | bf16; a view whose rows are strided is
+    fine), gamma / beta [P] f32, W the Keras kernel [P, N] f32 (f32 activations) or conv1d_pack_weight's copy of it as one tap (bf16),
+    bias [N] f32 or None -> out [B, Tpad, N], Tpad (default: T rounded up) a multiple of `factor`.  Rows t >= lengths[b] are computed
+    from zeros, rows [off_b + T, Tpad) are written as zeros, rows in front of off_b are left alone (pass `out` holding them);
+    out_lengths [B] int32 receives ceil((off_b + min(lengths[b], T)) / factor).  Returns (out, out_lengths); raises TfasrUnsupported
+    outside the kernel's range (rnnt_block_tail_supported) and launches nothing."""
+    B, T, P = y.shape
+    factor = max(int(factor), 1)
+    if Tpad is None:
+        Tpad = -(-T // factor) * factor
+    assert y.stride(2) == 1 and (B <= 1 or y.stride(0) == T * y.stride(1)), "y: [B, T, P] with one row stride"
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == P and beta.numel() == P
+    assert bias is None or (bias.dtype == torch.float32 and bias.numel() == N)
+    assert W.dtype == y.dtype
+    if rnnt_block_tail_supported(P, N):
+        want = ctypes.c_size_t(P * N)
+        if y.dtype != torch.float32:
+            _conv1d_check(_L().tfasr_conv1d_packed_weight_elems(1, P, N, ctypes.byref(want)), "conv1d_packed_weight_elems")
+        if W.numel() != want.value:
+            raise _lib.TfasrError(f"rnnt_block_tail_fwd: the kernel holds {W.numel()} elements, {want.value} expected for {(P, N)} in {y.dtype}")
+    for v in (lengths, off):
+        assert v is None or (v.dtype == torch.int32 and v.numel() == B)
+    if out is None:
+        out = torch.empty(B, Tpad, N, dtype=y.dtype, device=y.device)
+    assert out.shape == (B, Tpad, N) and out.dtype == y.dtype
+    if out_lengths is None:
+        out_lengths = torch.empty(B, dtype=torch.int32, device=y.device)
+    assert out_lengths.dtype == torch.int32 and out_lengths.numel() == B
+    st = _L().tfasr_rnnt_block_tail_fwd(_pv(y), y.stride(1), _p(lengths), _p(off), _p(gamma), _p(beta), _p(W), _p(bias), _p(out), _p(out_lengths),
+                                        B, T, Tpad, P, N, factor, float(eps), _dt(y), _stream())
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported(f"rnnt_block_tail_fwd: P={P} N={N}: P % 32 == 0 up to 2048 and N % 16 == 0 up to 1024")
+    check(st, "rnnt_block_tail_fwd")
+    return out, out_lengths
+

@@ -57,6 +57,9 @@ def param_specs(cfg, head_phys=None, filt_phys=None):
     if getattr(cfg, "encoder", "conformer") == "transformer":
         transformer_specs(cfg, add)
         return _tail_specs(cfg, add, s)
+    if getattr(cfg, "encoder", "conformer") == "rnnt":
+        rnnt_specs(cfg, add)
+        return _tail_specs(cfg, add, s)
     d, H, dh, Cl = cfg.dmodel, cfg.num_heads, cfg.head_size, cfg.filters
     C = filt_phys or Cl
     Kk, V, E, P, J = cfg.kernel_size, cfg.vocab_size, cfg.embed_dim, cfg.rnn_units, cfg.joint_dim
@@ -284,7 +287,28 @@ def transformer_specs(cfg, add):
         add(p + "/ln_2/g", (d,), True, "ones"); add(p + "/ln_2/b", (d,), True, "zeros")
 
 
+def rnnt_modules(cfg):
+    """The blocks of RnnTransducerEncoder (encoders/rnnt.py:150-169) in forward order under the reference's layer names:
+    [dict(name "enc/block_i", position, factor (>= 1), din (the LSTM's input width, behind a `pre` reduction), P, ln (bool), dout)]."""
+    return [dict(name=f"enc/block_{i}", position=cfg.reduction_positions[i], factor=cfg.factors[i], din=cfg.lstm_in(i),
+                 P=int(cfg.encoder_rnn_units), ln=bool(cfg.layer_norm), dout=int(cfg.encoder_dmodel)) for i in range(int(cfg.nlayers))]
+
+
+def rnnt_specs(cfg, add):
+    """keras LSTM kernel [Din, 4P], recurrent_kernel [P, 4P], bias [4P] (unit forget bias); LayerNormalization gamma / beta [P]; Dense
+    "projection" kernel [P, dmodel].  The regulariser covers the kernels and gamma / beta (encoders/rnnt.py:46-72)."""
+    for m in rnnt_modules(cfg):
+        add(m["name"] + "/lstm/k", (m["din"], 4 * m["P"]), True, "glorot")
+        add(m["name"] + "/lstm/rk", (m["P"], 4 * m["P"]), False, "orth")
+        add(m["name"] + "/lstm/b", (4 * m["P"],), False, "lstm_bias")
+        if m["ln"]:
+            add(m["name"] + "/ln/g", (m["P"],), True, "ones"); add(m["name"] + "/ln/b", (m["P"],), True, "zeros")
+        add(m["name"] + "/projection/w", (m["P"], m["dout"]), True, "glorot"); add(m["name"] + "/projection/b", (m["dout"],), False, "zeros")
+
+
 def bn_names(cfg):
+    if getattr(cfg, "encoder", "conformer") == "rnnt":
+        return []
     if getattr(cfg, "encoder", "conformer") == "transformer":
         return [c["bn"] for c in transformer_modules(cfg)["convs"] if c["bn"]]
     if getattr(cfg, "encoder", "conformer") == "deepspeech2":

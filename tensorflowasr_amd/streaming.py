@@ -17,6 +17,8 @@ append is part of the attention launch.
 The unidirectional DeepSpeech2 (causal Conv2D, forward LSTMs, causal RowConv1D) streams under the same contract (DS2StreamState,
 ds2_encode_chunk): it carries the last kh - 1 input rows of every conv block, each LSTM's (h, c) and the last K - 1 input rows of every
 RowConv1D.
+The RNN-Transducer (LSTM encoder with time reductions) streams under the same contract (RnntStreamState, rnnt_encode_chunk): it carries
+each block's LSTM (h, c) and, in front of every time reduction, the fewer-than-factor rows that do not fill a group yet.
 """
 import math
 import typing
@@ -124,6 +126,8 @@ def check_streamable(model):
         return  # causal convolutions only: streams exactly (JasperStreamState)
     if getattr(c, "encoder", "conformer") == "transformer":
         return _check_transformer(model)
+    if getattr(c, "encoder", "conformer") == "rnnt":
+        return  # forward LSTMs and row-wise layers only: streams exactly (RnntStreamState)
     if getattr(c, "encoder", "conformer") != "conformer":
         raise ValueError("streaming needs a Conformer encoder: ContextNet's squeeze-and-excite is a mean over the whole utterance")
     if c.chunk_size is None:
@@ -433,6 +437,157 @@ def ds2_encode_chunk(state, feats, nframes):
     return x.view(B, rows, c.dmodel), nv
 
 
+class RnntStreamState:
+    """Encoder state of `batch_size` streams of the RNN-Transducer encoder.  Per stream:
+        each block       h and c [rnn_units] f32 (h holds numbers of the compute type); the recurrence reads one pair and writes another
+                         (tfasr_lstm_infer_fwd_state refuses aliases), so every block owns two pairs and `cur` says which one is the state
+        each reduction   the rows that do not fill a group yet, [factor - 1, width] in the compute type, and their count: INPUT rows in
+                         front of a `pre` reduction, PROJECTED rows behind a `post` one
+    The reductions are kept per block BOUNDARY (RnnEncoderMixin.boundary_factors): boundary 0 is block 0's `pre` reduction, boundary i
+    block i - 1's `post` times block i's `pre` (a reduction by f followed by one by g groups f g consecutive rows - zero rows pad either,
+    and no layer sits between them), the last one the last block's `post`.  The counts live on the host (`cnt`, the step's launch
+    arguments are computed from them) and ride in export / load as one int32 tensor."""
+
+    def __init__(self, model, batch_size):
+        check_streamable(model)
+        self.model, self.B = model, int(batch_size)
+        B, dev, dt, mods = self.B, model.device, model.dtype, model.modules
+        self.fb = model.boundary_factors()
+        widths = [int(model.cfg.num_feature_bins)] + [m["dout"] for m in mods]
+        self.hc = [[tuple(torch.zeros(B, m["P"], dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)] for m in mods]
+        self.cur = [0] * len(mods)
+        self.carry = [torch.zeros(B, f - 1, w, dtype=dt, device=dev) if f > 1 else None for f, w in zip(self.fb, widths)]
+        self.cnt = [[0] * B for _ in self.fb]
+        self.last_nvalid = [0] * B  # encoder frames the last step gave each stream (host)
+
+    def _tensors(self):
+        hc = [t for pairs, cur in zip(self.hc, self.cur) for t in pairs[cur]]
+        return hc + [t for t in self.carry if t is not None]
+
+    def reset(self, rows=None):
+        StreamState.reset(self, rows)
+        for c in self.cnt:
+            for b in (range(self.B) if rows is None else rows):
+                c[b] = 0
+
+    def export(self):
+        """the carried tensors as one flat list (a copy): every block's (h, c), the leftover rows, and the counts [boundaries, B] int32"""
+        dev = self.model.device
+        return [t.clone() for t in self._tensors()] + [torch.tensor(self.cnt, dtype=torch.int32, device=dev)]
+
+    def load(self, tensors):
+        StreamState.load(self, tensors[:-1])
+        cnt = tensors[-1].cpu().tolist()
+        if len(cnt) != len(self.fb) or any(len(r) != self.B or min(r) < 0 or max(r) >= max(f, 1) for r, f in zip(cnt, self.fb)):
+            raise ValueError("encoder state of another model")
+        self.cnt = [[int(v) for v in r] for r in cnt]
+
+    def reference_states(self):
+        """[B, nlayers, 2, rnn_units] f32, states ordered (h, c): what the reference's RnnTransducerEncoder.get_initial_state / call_next
+        exchange (encoders/rnnt.py:171-211)"""
+        return torch.stack([torch.stack(list(pairs[cur]), 1) for pairs, cur in zip(self.hc, self.cur)], 1)
+
+    def out_rows(self, n):
+        """rows of the step's output buffer for n feature frames (the most frames one step can complete)"""
+        rows = n
+        for f in self.fb:
+            rows = -(-(f - 1 + rows) // f) if f > 1 else rows
+        return rows
+
+
+def _place(carry, cnt_dev, new, R):
+    """[carry rows 0 .. cnt - 1 | new rows] per stream as one [B, R, w] buffer (rows past cnt + new.shape[1] repeat the last row: callers
+    never read them, or zero them).  The ragged copy of a boundary no tail kernel writes: block 0's input, and the two-launch tail."""
+    B, n, w = new.shape
+    cat = torch.cat([carry, new], 1)
+    r = torch.arange(R, device=new.device)[None, :]
+    c = cnt_dev.long()[:, None]
+    idx = torch.where(r < c, r, r - c + carry.shape[1]).clamp_(max=cat.shape[1] - 1)
+    return torch.gather(cat, 1, idx[:, :, None].expand(B, R, w))
+
+
+RNNT_PERSIST_STREAMS = 64  # tfasr_lstm_infer_fwd's persistent launch takes up to 64 batch rows
+
+
+@torch.no_grad()
+def rnnt_encode_chunk(state, feats, nframes, final=()):
+    """One encoder step of the RNN-Transducer: feats [B, n, F] (compute type, device), nframes [B] feature frames that are real per stream
+    (0 = idle .. n), final = the streams whose utterance ends with these frames -> (enc [B, state.out_rows(n), cfg.dmodel], nvalid [B]
+    int32 device); advances state.  Every stream advances by its own number of frames: in front of each reduction its carried rows and
+    its new rows form groups, whole groups go on, the rest is carried; a final stream's last group is filled with zero rows, as tf.pad
+    fills it offline.  Per block: one GEMM, the recurrence continued from the carried state (tfasr_lstm_infer_fwd_state, lengths = the
+    stream's groups), and tfasr_rnnt_block_tail_fwd writing each stream's rows behind the rows the next reduction carries (`off`).
+    A boundary no tail kernel writes - block 0's `pre` reduction, the two-launch tail - is assembled by a gather instead.
+    In bf16 more than 64 streams run the recurrence in slices of 64 (the persistent launch, the route the utterance alone takes)."""
+    m = state.model
+    c, B, mods, fb = m.cfg, state.B, m.modules, state.fb
+    host = [int(v) for v in (nframes.tolist() if isinstance(nframes, torch.Tensor) else nframes)]
+    if feats.dim() != 3 or feats.shape[0] != B or feats.shape[1] < 1 or len(host) != B or min(host) < 0 or max(host) > feats.shape[1]:
+        raise ValueError(f"encode_chunk takes [B = {B}, n >= 1, F] feature frames and B frame counts within them")
+    fin = [False] * B
+    for b in final:
+        fin[int(b)] = True
+    # everything the launches need is known on the host: per boundary the carried count (the tail's `off`), the rows that enter (to zero
+    # a final stream's padding), the groups that go on (the block's lengths) and where the new carry starts
+    L = len(mods)
+    plan, come = [], host
+    for i, f in enumerate(fb):
+        cnt = state.cnt[i] if f > 1 else [0] * B
+        avail = [a + b for a, b in zip(cnt, come)]
+        groups = [(-(-a // f) if fin[b] else a // f) for b, a in enumerate(avail)]
+        plan.append(dict(cnt=list(cnt), avail=avail, groups=groups, start=[g * f for g in groups]))
+        if f > 1:
+            state.cnt[i] = [0 if fin[b] else a - g * f for b, (a, g) in enumerate(zip(avail, groups))]
+        come = groups
+    vec = m._h2d(np.asarray([p[k] for p in plan for k in ("cnt", "groups", "start")], np.int32))
+    dv = lambda i, k: vec[3 * i + ("cnt", "groups", "start").index(k)]
+
+    def reduce(i, x):
+        """boundary i over x [B, R, w] (R % f == 0, each stream's carried rows in front): -> [B, R / f, f w]; moves the carry"""
+        f = fb[i]
+        if f == 1:
+            return x
+        R, w = x.shape[1], x.shape[2]
+        for b in range(B):  # tf.pad's zero rows of a last, partial group
+            lo, hi = plan[i]["avail"][b], plan[i]["start"][b]
+            if fin[b] and hi > lo:
+                x[b, lo:hi].zero_()
+        K.conv1d_tail_update(x, dv(i, "start"), state.carry[i])
+        return x.view(B, R // f, f * w)
+
+    x = feats.contiguous()
+    if fb[0] > 1:
+        x = _place(state.carry[0], dv(0, "cnt"), x, -(-(fb[0] - 1 + x.shape[1]) // fb[0]) * fb[0])
+    sl = RNNT_PERSIST_STREAMS if m.dtype != torch.float32 else B
+    for i, mod in enumerate(mods):
+        x = reduce(i, x)
+        T, P, N = x.shape[1], mod["P"], mod["dout"]
+        lens = dv(i, "groups")
+        ps, p = m.ps, mod["name"] + "/lstm"
+        xg = K.matmul(x.reshape(B * T, x.shape[2]), ps.w2d(p + "/k"), bias=ps.p(p + "/b")).view(B, T, 4 * P)
+        rk = ps.w(p + "/rk").view(1, P, 4 * P)
+        (h0, c0), (h1, c1) = state.hc[i][state.cur[i]], state.hc[i][state.cur[i] ^ 1]
+        y = torch.empty(B, T, P, dtype=xg.dtype, device=xg.device)
+        for b0 in range(0, B, sl):
+            e = min(b0 + sl, B)
+            K.lstm_infer_fwd(xg[b0:e], rk, lens[b0:e], y=y[b0:e], state=(h0[b0:e], c0[b0:e]), state_out=(h1[b0:e], c1[b0:e]))
+        state.cur[i] ^= 1
+        f = fb[i + 1]
+        Tpad = -(-(f - 1 + T) // f) * f if f > 1 else T
+        if m._fused_tail(mod):
+            out = torch.empty(B, Tpad, N, dtype=y.dtype, device=y.device)
+            if f > 1:
+                out[:, :f - 1].copy_(state.carry[i + 1])
+            x, _ = m.tail_fwd(y, mod, lens, Tpad, 1, off=dv(i + 1, "cnt") if f > 1 else None, out=out)
+        else:
+            x, _ = m.tail_fwd(y, mod, lens, T, 1)
+            if f > 1:
+                x = _place(state.carry[i + 1], dv(i + 1, "cnt"), x, Tpad)
+    x = reduce(L, x)
+    state.last_nvalid = list(plan[L]["groups"])
+    return x.reshape(B, x.shape[1], c.dmodel), dv(L, "groups")
+
+
 def check_stream_args(batch_size=1, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
     """The session arguments that need no device to judge -> them as ints.  beam_width 0 = the greedy session; 1 .. 64 = a beam of that
     many hypotheses per stream (the device searches keep a beam in one workgroup's LDS: 64 rows at most)."""
@@ -473,7 +628,12 @@ class StreamingRecognizer:
 
     A Transformer model with a chunked config (TransformerCTC.stream / TransformerTransducer.stream) takes the Conformer's step,
     4 * chunk_size feature frames, and the Conformer's frame reduction; its encoder state is TransformerStreamState (per block two rings of
-    B * history_size * num_heads * head_size elements, plus the two subsampling carries)."""
+    B * history_size * num_heads * head_size elements, plus the two subsampling carries).
+
+    An RNN-Transducer (RnnTransducer.stream(batch_size, chunk_frames=...)) takes steps of any positive number of feature frames: its
+    encoder state is RnntStreamState (per block the LSTM's h and c, per time reduction the rows that do not fill a group yet), the encoder
+    frames a step gives depend on those carried rows, and finish() sends a final step that zero-pads each reduction's last group - a step
+    without feature frames when the utterance ended on a step boundary."""
 
     def __init__(self, model, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000, chunk_frames=None):
         batch_size, max_tokens_per_frame, self.beam_width, self.max_frames = check_stream_args(batch_size, max_tokens_per_frame, beam_width,
@@ -485,8 +645,18 @@ class StreamingRecognizer:
         c = model.cfg
         self.jasper = getattr(c, "encoder", "conformer") == "jasper"
         self.ds2 = getattr(c, "encoder", "conformer") == "deepspeech2"
+        self.rnnt = getattr(c, "encoder", "conformer") == "rnnt"
         self._encode = encode_chunk
-        if self.jasper or self.ds2:
+        if self.rnnt:
+            # a step is `chunk_frames` feature frames, any positive number: what does not fill a reduction's group is carried, so the
+            # encoder frames a step gives depend on the state (state.last_nvalid), state.out_rows(chunk_frames) at the most
+            self.chunk_frames = int(chunk_frames if chunk_frames is not None else 32)
+            if self.chunk_frames < 1:
+                raise ValueError(f"stream: chunk_frames {self.chunk_frames} must be positive")
+            self.state, self._encode = RnntStreamState(self.enc_model, batch_size), rnnt_encode_chunk
+            self.C = self.state.out_rows(self.chunk_frames)
+            self._reduce = c.encoder_length
+        elif self.jasper or self.ds2:
             self._encode = jasper_encode_chunk if self.jasper else ds2_encode_chunk
             # a step is `chunk_frames` feature frames -> chunk_frames / factor encoder frames (a stream's last step: ceil of what is left)
             factor = int(c.time_reduction_factor)
@@ -528,6 +698,7 @@ class StreamingRecognizer:
             self.emitted = [0] * B  # feature frames consumed
             self.frames = [0] * B  # encoder frames emitted
             self.finished = [False] * B
+            self.flushed = [False] * B  # (RNN-Transducer) the encoder's carried rows went out with a final step
             self.beam = None
             if self.beam_width:
                 self.beam = self._new_beam()
@@ -545,7 +716,7 @@ class StreamingRecognizer:
             self.buf[b] = np.zeros(0, np.float32)
             self.prev[b], self.has_prev[b] = 0.0, 0
             self.total[b] = self.emitted[b] = self.frames[b] = 0
-            self.finished[b] = False
+            self.finished[b] = self.flushed[b] = False
         r = torch.as_tensor(rows, dtype=torch.long, device=dev)
         if self.beam is not None:
             self.beam.reset(rows)
@@ -587,7 +758,11 @@ class StreamingRecognizer:
         window, melw, band = em._frontend_consts()
         while True:
             take = [self._ready(b, b in flush_rows) for b in range(B)]
-            if max(take) == 0:
+            final = ()
+            if self.rnnt:  # the streams whose utterance ends with this step: their carried rows go out, the last group zero-padded
+                final = [b for b in flush_rows if not self.finished[b] and not self.flushed[b]
+                         and -(-self.total[b] // self.step) - self.emitted[b] - take[b] == 0]
+            if max(take) == 0 and not final:
                 break
             # one front-end launch per chunk on exactly the samples the chunk's frames cover: the same frames whatever the arrival
             sig = np.zeros((B, self.chunk_samples), np.float32)
@@ -597,9 +772,12 @@ class StreamingRecognizer:
                     seg = self.buf[b][:self.chunk_samples]
                     sig[b, :len(seg)] = seg
                     nlen[b] = len(seg)
-            feats = K.logmel_stream(em._h2d(torch.from_numpy(sig), torch.float32), em._h2d(nlen), em._h2d(torch.from_numpy(self.prev.copy()), torch.float32),
-                                    em._h2d(self.has_prev.copy()), self.chunk_frames, window, melw, band, c.frame_step, c.nfft, c.preemphasis,
-                                    c.epsilon, torch.float32 if self.jasper or self.ds2 else em.dtype)
+            if max(take) == 0:  # (RNN-Transducer) nothing but carried encoder rows is left to flush: no frame is read
+                feats = torch.zeros(B, self.chunk_frames, c.num_feature_bins, dtype=em.dtype, device=dev)
+            else:
+                feats = K.logmel_stream(em._h2d(torch.from_numpy(sig), torch.float32), em._h2d(nlen), em._h2d(torch.from_numpy(self.prev.copy()), torch.float32),
+                                        em._h2d(self.has_prev.copy()), self.chunk_frames, window, melw, band, c.frame_step, c.nfft, c.preemphasis,
+                                        c.epsilon, torch.float32 if self.jasper or self.ds2 else em.dtype)
             if self.jasper:
                 feats = em._scale_feats(feats)
             elif self.ds2 and em.dtype != torch.float32:  # DeepSpeech2CTC.frontend's route: f32 out of the kernel, then the cast
@@ -611,8 +789,14 @@ class StreamingRecognizer:
                         self.prev[b], self.has_prev[b] = self.buf[b][used - 1], 1
                     self.buf[b] = self.buf[b][used:]
                     self.emitted[b] += take[b]
-            enc, nvalid = self._encode(self.state, feats, take)
-            nv = [self._reduce(t) for t in take]
+            if self.rnnt:
+                enc, nvalid = self._encode(self.state, feats, take, final)
+                nv = list(self.state.last_nvalid)
+                for b in final:
+                    self.flushed[b] = True
+            else:
+                enc, nvalid = self._encode(self.state, feats, take)
+                nv = [self._reduce(t) for t in take]
             if self.encoded_log is not None:
                 self.encoded_log.append((enc, nv))
             self.chunks_run += 1
@@ -660,6 +844,8 @@ class StreamingRecognizer:
                 if take <= 0:
                     break
                 n, emitted, frames = max(n - take * self.step, 0), emitted + take, frames + self._reduce(take)
+            if self.rnnt:  # a step's frames depend on the carried rows; all steps together never give more than the utterance so far
+                frames = self._reduce(emitted)
             if frames > self.max_frames:
                 raise RuntimeError(f"stream {b} would pass max_frames = {self.max_frames} encoder frames ({self.frames[b]} so far, {frames} after "
                                    "this call): reset it, or open the session with a larger max_frames")
