@@ -433,6 +433,38 @@ def layernorm_bwd_fold(dy, x, gamma, mean, rstd, dgamma, dbeta, add=None):
     return dx
 
 
+def layernorm_bwd_part_n(dy, x, gamma, mean, rstd, part, nblk=None, add=None, dx=None, dropped=None, drop_p=0.0, drop_seed=0):
+    """tfasr_layernorm_bwd_part_n: dx, and the gamma / beta gradients as `nblk` per-block partial sums part[nblk][2C] (slots whose block has
+    no rows are zeroed).  nblk None: tfasr_layernorm_bwd_part with its own slot count, tfasr_layernorm_bwd_part_blocks(rows, C)."""
+    rows, C = x.numel() // x.shape[-1], x.shape[-1]
+    if dx is None:
+        dx = torch.empty_like(x)
+    if nblk is None:
+        check(_L().tfasr_layernorm_bwd_part(_p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(add), _p(dx), _p(part), _p(dropped), float(drop_p),
+                                            int(drop_seed), rows, C, _dt(x), _stream()), "layernorm_bwd_part")
+    else:
+        check(_L().tfasr_layernorm_bwd_part_n(_p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(add), _p(dx), _p(part), int(nblk), _p(dropped),
+                                              float(drop_p), int(drop_seed), rows, C, _dt(x), _stream()), "layernorm_bwd_part_n")
+    return dx
+
+
+def _ptr_table(ts):
+    return (ctypes.c_void_p * len(ts))(*[None if t is None else _p(t).value for t in ts])
+
+
+def layernorm_bwd_fold_parts(part, nblk, C, dgammas, dbetas):
+    """tfasr_layernorm_bwd_fold over len(dgammas) <= 8 sets that lie back to back in `part` ([nsets][nblk][2C]): dgammas[i] / dbetas[i] +=
+    the column sums of set i (a None entry is skipped)."""
+    check(_L().tfasr_layernorm_bwd_fold(_p(part), len(dgammas), int(nblk), int(C), _ptr_table(dgammas), _ptr_table(dbetas), _stream()),
+          "layernorm_bwd_fold")
+
+
+def layernorm_bwd_fold_sets(parts, nblk, C, dgammas, dbetas):
+    """tfasr_layernorm_bwd_fold_sets: the same for up to 128 sets in separate buffers parts[i] ([nblk][2C] each)."""
+    check(_L().tfasr_layernorm_bwd_fold_sets(_ptr_table(parts), len(parts), int(nblk), int(C), _ptr_table(dgammas), _ptr_table(dbetas), _stream()),
+          "layernorm_bwd_fold_sets")
+
+
 def dense_ln_bwd(dy, W, x, gamma, mean, rstd, dgamma, dbeta, add=None, dropped=None, drop_p=0.0, drop_seed=0, alpha=1.0):
     """tfasr_dense_ln_bwd: dx of `Dense(LayerNorm(x))` in one launch (dln = alpha * dy @ W^T never stored), gamma / beta gradients through
     partial sums + tfasr_layernorm_bwd_fold.  dy [rows, K], W [d, K] (the Dense kernel as stored).  Returns dx, or None when the shape is
