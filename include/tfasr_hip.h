@@ -131,6 +131,17 @@ int tfasr_ctc_loss(const void* logits, void* grads, const int32_t* labels, const
                    float* costs, void* workspace, size_t workspace_bytes, void* stream);
 int tfasr_ctc_greedy_decode(const void* logits, const int32_t* logit_len, int32_t* workspace_argmax, int32_t* tokens,
                             int32_t* tokens_len, int B, int T, int V, int blank, int dtype, void* stream);
+/* tfasr_ctc_greedy_decode with the span and the confidence of every token (two launches; tokens and tokens_len are bit-equal to
+ * tfasr_ctc_greedy_decode's).  All token buffers are [B,T]; for token i < tokens_len[b]: starts = the first frame of its run of equal
+ * arg-max classes, ends = one past the run's last frame, tok_logp = the frames' maximal log-softmax values summed over the run in frame
+ * order (f32), tok_entropy = the mean over the run of the frame entropy H = -sum_v p_v log p_v (nats, f32; a class whose exp underflows
+ * to 0 contributes 0).  Past tokens_len: starts = ends = -1, tok_logp = tok_entropy = 0.  score [B] = the sum of the maximal
+ * log-probabilities over all logit_len[b] frames, blanks included: the log-probability of the best path (0 for a row without frames).
+ * starts / ends / tok_logp / score follow tfasr_ctc_align's definitions.  workspace: 3*B*T 4-byte words (arg-max, frame log-probability,
+ * frame entropy). */
+int tfasr_ctc_greedy_decode_detail(const void* logits, const int32_t* logit_len, int32_t* workspace, int32_t* tokens, int32_t* tokens_len,
+                                   int32_t* starts, int32_t* ends, float* tok_logp, float* tok_entropy, float* score, int B, int T, int V,
+                                   int blank, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GEMM family (Dense / EinsumDense / pointwise Conv1D / attention products / joint vocab projection:
@@ -557,6 +568,29 @@ int tfasr_decode_update(const void* logits, const int32_t* active, const int32_t
                         int32_t* prev_tok, int32_t* tok_idx, int32_t* tokens, int32_t* per_frame, const void* h_new,
                         const float* c_new, void* h, float* c, int B, int V, int P, int max_tokens, int blank, int mode,
                         int max_tokens_per_frame, int dtype, void* stream);
+/* tfasr_decode_update / tfasr_decode_steps that also say when each symbol was emitted and how sure the model was (same launches, same
+ * results in every buffer the plain entry points write; modes 0, 1, 2; f32 and bf16 logits).  Three more buffers shaped like `tokens`,
+ * initialised by the caller (tok_frames with -1): exactly where the bookkeeping writes an emitted symbol cur != blank into tokens[idx] it
+ * also writes
+ *   tok_frames[idx]  = the encoder frame the row read for the decision, max(min(frame_idx, nframes - 1), 0) (nframes <= T is the caller's
+ *                      contract, as for the search itself; a finished row of mode 0 records its last frame),
+ *   tok_logp[idx]    = the f32 log-softmax value of cur,
+ *   tok_entropy[idx] = H = -sum_v p_v log p_v of the decision's distribution in nats, accumulated in f32; a class whose exp underflows to 0
+ *                      (a logit of -inf included) contributes 0.
+ * Nothing else writes them: not the blank of column 0 (mode 0), not the re-write of tokens[tok_idx] on a blank (mode 1), not a symbol
+ * dropped past the buffer (mode 2), not a call with active[0] == 0.  Mode 0's overwrite of the last column overwrites the details too.
+ * tfasr_decode_steps_detail refuses what tfasr_decode_steps refuses (UNSUPPORTED: use the per-op loop with tfasr_decode_update_detail). */
+int tfasr_decode_update_detail(const void* logits, const int32_t* active, const int32_t* nframes, int32_t* frame_idx,
+                               int32_t* prev_tok, int32_t* tok_idx, int32_t* tokens, int32_t* per_frame, const void* h_new,
+                               const float* c_new, void* h, float* c, int32_t* tok_frames, float* tok_logp, float* tok_entropy, int B,
+                               int V, int P, int max_tokens, int blank, int mode, int max_tokens_per_frame, int dtype, void* stream);
+int tfasr_decode_steps_detail(const float* emb, const float* lstm_k, const float* lstm_rk, const float* lstm_b, const float* ln_g,
+                              const float* ln_b, const float* joint_pred_w, const float* joint_pred_b, const float* vocab_w,
+                              const float* vocab_b, const float* packed, const float* encj, const int32_t* nframes, int32_t* frame_idx,
+                              int32_t* tok_idx, int32_t* prev_tok, float* h, float* c, int32_t* active, float* h_new, float* c_new,
+                              float* z, float* logits, int32_t* tokens, int32_t* per_frame, int32_t* tok_frames, float* tok_logp,
+                              float* tok_entropy, int B, int T, int E, int P, int J, int V, int max_tokens, int blank, int mode,
+                              int max_tokens_per_frame, float ln_eps, int iters, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Conv2dSubsampling pieces (subsampling.py:163-254; causal 3x3 stride 2, convolution.py:25-37,132-144)

@@ -19,7 +19,7 @@ from . import kernels as K
 from .base_model import BaseModel
 from .kernels import ACT_NONE, ACT_SWISH, ACT_TANH_OUT
 from .params import ParamStore
-from .schemas import AlignOutput, PredictInput, PredictOutput, TrainData, TrainInput, TrainOutput
+from .schemas import AlignOutput, PredictInput, PredictOutput, RecognizeOutput, TrainData, TrainInput, TrainOutput
 
 
 class SingleProcess:
@@ -1732,6 +1732,33 @@ class ConformerTransducer(BaseModel):
     @torch.no_grad()
     def recognize_encoded(self, enc, elen, previous_tokens=None, previous_decoder_states=None, max_tokens_per_frame=3,
                           check_every=16):
+        return self._greedy_search(enc, elen, previous_tokens, previous_decoder_states, max_tokens_per_frame, check_every, False)[0]
+
+    @torch.no_grad()
+    def recognize_detailed(self, inputs: PredictInput, max_tokens_per_frame=3, check_every=16, precision=None):
+        """recognize that also says when each token was spoken and how sure the model was -> RecognizeOutput (schemas.token_times,
+        token_confidences, word_details read it).  Same search, same tokens: the bookkeeping kernel keeps, next to every symbol it writes,
+        the frame, the log-probability and the entropy of the decision (tfasr_decode_update_detail) - no second pass over the encoder."""
+        enc, elen = self.encode(inputs.inputs, inputs.inputs_length, precision)
+        out = self.recognize_encoded_detailed(enc, elen, inputs.previous_tokens, inputs.previous_decoder_states, max_tokens_per_frame,
+                                              check_every)
+        if inputs.previous_encoder_states is not None:
+            out = out._replace(predict=out.predict._replace(next_encoder_states=inputs.previous_encoder_states))
+        return out
+
+    @torch.no_grad()
+    def recognize_encoded_detailed(self, enc, elen, previous_tokens=None, previous_decoder_states=None, max_tokens_per_frame=3,
+                                   check_every=16):
+        """recognize_encoded -> RecognizeOutput: frames / log_probs / entropies [B, W] column-aligned with predict.tokens (a batch: symbols
+        from column 2; -1 / 0 where no symbol sits), ends None, scores [B] = the sum of the emitted tokens' log-probabilities."""
+        out, (frames, logp, ent) = self._greedy_search(enc, elen, previous_tokens, previous_decoder_states, max_tokens_per_frame,
+                                                       check_every, True)
+        scores = torch.where(frames >= 0, logp, torch.zeros_like(logp)).sum(1)
+        return RecognizeOutput(out, frames, None, logp, ent, scores, self.seconds_per_frame, self.cfg.vocab_size)
+
+    def _greedy_search(self, enc, elen, previous_tokens, previous_decoder_states, max_tokens_per_frame, check_every, detail):
+        """The greedy search of recognize_encoded -> (PredictOutput, None), or with `detail` (PredictOutput, (tok_frames, tok_logp,
+        tok_entropy)): the same launches with the detail variant of the bookkeeping kernel."""
         ps, c, dev = self.ps, self.cfg, self.device
         B, T, d = enc.shape
         E, P, J, V = c.embed_dim, c.rnn_units, c.joint_dim, c.vocab_size
@@ -1749,6 +1776,10 @@ class ConformerTransducer(BaseModel):
         encj = K.matmul(enc32, ps.p2d("joint/enc/w"), bias=ps.p("joint/enc/b")).view(B, T, J)
         max_tokens = int(elen[0]) * max_tokens_per_frame if mode == 1 else 2 * T + 1
         tokens = torch.full((B, max(max_tokens, 1)), self.blank, dtype=torch.int32, device=dev)
+        det = ()  # detail buffers, shaped like `tokens`
+        if detail:
+            det = (torch.full_like(tokens, -1), torch.zeros(tokens.shape, dtype=f32, device=dev), torch.zeros(tokens.shape, dtype=f32, device=dev))
+        steps, update = (K.decode_steps_detail, K.decode_update_detail) if detail else (K.decode_steps, K.decode_update)
         frame_idx = torch.zeros(B, dtype=torch.int32, device=dev)
         tok_idx = torch.full((B,), -1 if mode == 1 else 1, dtype=torch.int32, device=dev)
         prev_tok = (torch.full((B,), self.blank, dtype=torch.int32, device=dev) if previous_tokens is None
@@ -1787,9 +1818,9 @@ class ConformerTransducer(BaseModel):
             n = min(max(need, check_every) if fused else check_every, max_iters - it)
             if fused:
                 # `n` iterations = 3 skinny-product launches + the bookkeeping kernel each (csrc/decode_step.hip), queued by one host call
-                fused = K.decode_steps(ps.p("pred/emb"), Wk, Wrk, ps.p("pred/lstm/b"), lng, lnb, Wjp, ps.p("joint/pred/b"), Wv,
-                                       ps.p("joint/vocab/b"), encj, nframes, frame_idx, tok_idx, prev_tok, h, cst, active, h_new, c_new, zbuf,
-                                       logits, tokens, per_frame, max_tokens, self.blank, mode, max_tokens_per_frame, n, packed=packed)
+                fused = steps(ps.p("pred/emb"), Wk, Wrk, ps.p("pred/lstm/b"), lng, lnb, Wjp, ps.p("joint/pred/b"), Wv,
+                              ps.p("joint/vocab/b"), encj, nframes, frame_idx, tok_idx, prev_tok, h, cst, active, h_new, c_new, zbuf,
+                              logits, tokens, per_frame, *det, max_tokens, self.blank, mode, max_tokens_per_frame, n, packed=packed)
                 if fused:
                     it += n
                     left = (nframes - 1 - frame_idx).clamp_(min=0).max()
@@ -1810,15 +1841,16 @@ class ConformerTransducer(BaseModel):
                 K.matmul(y, Wjp, bias=ps.p("joint/pred/b"), out=pj)
                 z = K.joint_fwd(ecur.view(B, 1, J), pj.view(B, 1, J))
                 K.matmul(z.view(B, J), Wv, bias=ps.p("joint/vocab/b"), out=logits)
-                K.decode_update(logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, h_new, c_new, h, cst,
-                                max_tokens, self.blank, mode, max_tokens_per_frame)
+                update(logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, h_new, c_new, h, cst, *det,
+                       max_tokens, self.blank, mode, max_tokens_per_frame)
                 it += 1
             if int(active.item()) == 0:
                 break
         self.last_search_iterations = it  # (queued iterations incl. the no-op tail of the last batch; bench.py reports it)
         states = torch.stack([h, cst], dim=1).unsqueeze(1)  # [B, 1, 2, P]
-        return PredictOutput(tokens=tokens[:, :max_tokens], next_tokens=prev_tok.view(B, 1), next_encoder_states=None,
-                             next_decoder_states=states)
+        out = PredictOutput(tokens=tokens[:, :max_tokens], next_tokens=prev_tok.view(B, 1), next_encoder_states=None,
+                            next_decoder_states=states)
+        return out, (tuple(t[:, :max_tokens] for t in det) if detail else None)
 
     # ----------------------------------------------------------------- timing hooks (bench.py)
     def _tick(self, name):

@@ -160,6 +160,94 @@ __global__ void ctc_collapse_kernel(const int32_t* __restrict__ amax, const int3
   if (last && Tl > 0) last[b] = prev;
 }
 
+// The per-frame pass of tfasr_ctc_greedy_decode_detail: ctc_lse_kernel's arg-max (same loop, same tie rule: the tokens are those of
+// tfasr_ctc_greedy_decode) plus the arg-max's log-softmax value, -log(sum_v e_v) with e_v = exp(x_v - max), and the entropy of the frame's
+// distribution H = -sum_v p_v log p_v = log(sum_v e_v) + sum_v e_v (max - x_v) / sum_v e_v (two non-negative terms; a class with
+// e_v == 0 is left out, so a logit of -inf contributes 0 and 0 * -inf never forms).  One wave per frame, grid-stride over the frames.
+template <typename T>
+__global__ __launch_bounds__(256) void ctc_frame_detail_kernel(const T* __restrict__ logits, int32_t* __restrict__ amax, float* __restrict__ frame_lp,
+                                                               float* __restrict__ frame_ent, long rows, int V) {
+  const int lane = threadIdx.x & 63;
+  const long w0 = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (long)gridDim.x * (blockDim.x >> 6);
+  for (long r = w0; r < rows; r += nw) {
+    const T* row = logits + r * V;
+    float m = -INFINITY;
+    int mi = 0x7fffffff;
+    for (int v = lane; v < V; v += 64) { const float x = Num<T>::ld(row + v); if (x > m) { m = x; mi = v; } }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float om = __shfl_xor(m, o, 64);
+      const int oi = __shfl_xor(mi, o, 64);
+      if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+    }
+    float s = 0.f, a = 0.f;
+    for (int v = lane; v < V; v += 64) {
+      const float d = Num<T>::ld(row + v) - m, e = expf(d);
+      s += e;
+      if (e > 0.f) a -= e * d;
+    }
+    s = wave_sum(s);
+    a = wave_sum(a);
+    if (lane == 0) {
+      const float ls = logf(s);
+      amax[r] = mi;
+      frame_lp[r] = -ls;
+      frame_ent[r] = ls + a / s;
+    }
+  }
+}
+
+// ctc_collapse_kernel with the span of every token: [starts, ends) = its run of equal arg-max classes, tok_logp = the frame log-probabilities
+// summed over the run in frame order, tok_entropy = the mean frame entropy of the run; score = the sum over all valid frames, blanks
+// included (the log-probability of the best path).  One thread per utterance.
+__global__ void ctc_collapse_detail_kernel(const int32_t* __restrict__ amax, const float* __restrict__ frame_lp, const float* __restrict__ frame_ent,
+                                           const int32_t* __restrict__ logit_len, int32_t* __restrict__ out, int32_t* __restrict__ out_len,
+                                           int32_t* __restrict__ starts, int32_t* __restrict__ ends, float* __restrict__ tok_logp,
+                                           float* __restrict__ tok_entropy, float* __restrict__ score, int B, int Tm, int blank) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int Tl = min(logit_len[b], Tm);
+  const long base = (long)b * Tm;
+  int prev = -1, n = 0, start = 0;
+  bool open = false;  // a token's run is being summed
+  float lp_run = 0.f, ent_run = 0.f, total = 0.f;
+  for (int t = 0; t <= Tl; ++t) {
+    const int c = t < Tl ? amax[base + t] : -1;  // (t == Tl: closes a run that reaches the last valid frame)
+    if (c != prev || t == Tl) {
+      if (open) {
+        ends[base + n - 1] = t;
+        tok_logp[base + n - 1] = lp_run;
+        tok_entropy[base + n - 1] = ent_run / (float)(t - start);
+        open = false;
+      }
+      if (t < Tl && c != blank) {
+        out[base + n] = c;
+        starts[base + n] = t;
+        ++n;
+        start = t;
+        lp_run = 0.f;
+        ent_run = 0.f;
+        open = true;
+      }
+    }
+    if (t < Tl) {
+      const float lp = frame_lp[base + t];
+      total += lp;
+      if (open) { lp_run += lp; ent_run += frame_ent[base + t]; }
+    }
+    prev = c;
+  }
+  for (int i = n; i < Tm; ++i) {
+    out[base + i] = blank;
+    starts[base + i] = -1;
+    ends[base + i] = -1;
+    tok_logp[base + i] = 0.f;
+    tok_entropy[base + i] = 0.f;
+  }
+  out_len[b] = n;
+  score[b] = total;
+}
+
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -236,6 +324,27 @@ extern "C" int tfasr_ctc_greedy_decode_carry(const void* logits, const int32_t* 
   else if (dtype == TFASR_BF16) TFASR_KLAUNCH(ctc_lse_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)logits, (float*)nullptr, workspace_argmax, rows, V);
   else return TFASR_STATUS_INVALID_VALUE;
   TFASR_KLAUNCH(ctc_collapse_kernel, dim3((B + 63) / 64), dim3(64), 0, s, workspace_argmax, logit_len, tokens, tokens_len, B, T, blank, last_class);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_greedy_decode_detail(const void* logits, const int32_t* logit_len, int32_t* workspace, int32_t* tokens, int32_t* tokens_len,
+                                              int32_t* starts, int32_t* ends, float* tok_logp, float* tok_entropy, float* score, int B, int T,
+                                              int V, int blank, int dtype, void* stream_) {
+  if (!logits || !logit_len || !workspace || !tokens || !tokens_len || !starts || !ends || !tok_logp || !tok_entropy || !score || B <= 0 ||
+      T <= 0 || V <= 0)
+    return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t s = (hipStream_t)stream_;
+  const long rows = (long)B * T;
+  const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
+  int32_t* amax = workspace;
+  float* frame_lp = (float*)(workspace + rows);
+  float* frame_ent = (float*)(workspace + 2 * rows);
+  if (dtype == TFASR_F32) TFASR_KLAUNCH(ctc_frame_detail_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)logits, amax, frame_lp, frame_ent, rows, V);
+  else TFASR_KLAUNCH(ctc_frame_detail_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)logits, amax, frame_lp, frame_ent, rows, V);
+  TFASR_KLAUNCH(ctc_collapse_detail_kernel, dim3((B + 63) / 64), dim3(64), 0, s, amax, frame_lp, frame_ent, logit_len, tokens, tokens_len, starts, ends,
+                tok_logp, tok_entropy, score, B, T, blank);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }

@@ -40,15 +40,33 @@ __global__ void decode_prepare_kernel(const T* __restrict__ encj, const int32_t*
   }
 }
 
-template <typename T>
+// DETAIL (tfasr_decode_update_detail): next to every emitted symbol written into tokens[idx] the kernels also write tok_frames[idx] (the
+// encoder frame the row read), tok_logp[idx] (`best`, the symbol's f32 log-softmax) and tok_entropy[idx]: H = -sum_v p_v log p_v =
+// lse + sum_v e_v (m - x_v) / sum_v e_v with e_v = exp(x_v - m), two non-negative terms; the second sum rides in the pass that forms the
+// first (one more reduction, no further pass over the row).  A class with e_v == 0 is left out (0 * -inf never forms).  Without DETAIL
+// none of it is compiled: the instantiation is the kernel as it was.
+struct DecodeDetail {
+  int32_t* frames;
+  float* logp;
+  float* entropy;
+};
+
+__device__ __forceinline__ void decode_detail_write(const DecodeDetail& d, long idx, int fi, int nfr, float best, float ent) {
+  d.frames[idx] = max(min(fi, nfr - 1), 0);
+  d.logp[idx] = best;
+  d.entropy[idx] = ent;
+}
+
+template <typename T, bool DETAIL>
 __global__ __launch_bounds__(256) void decode_update_kernel(
     const T* __restrict__ logits, const int32_t* __restrict__ active, const int32_t* __restrict__ nframes,
     int32_t* __restrict__ frame_idx, int32_t* __restrict__ prev_tok, int32_t* __restrict__ tok_idx,
     int32_t* __restrict__ tokens, int32_t* __restrict__ per_frame, const T* __restrict__ h_new,
     const float* __restrict__ c_new, T* __restrict__ h, float* __restrict__ c, int B, int V, int P, int max_tokens,
-    int blank, int mode, int max_tokens_per_frame) {
+    int blank, int mode, int max_tokens_per_frame, DecodeDetail det) {
   if (!active[0]) return;
   __shared__ float red_v[4];
+  __shared__ float red_a[4];
   __shared__ int red_i[4];
   __shared__ int s_keep;  // 1 -> keep previous decoder state (blank / finished)
   const int b = blockIdx.x;
@@ -61,12 +79,20 @@ __global__ __launch_bounds__(256) void decode_update_kernel(
   __syncthreads();
   m = fmaxf(fmaxf(red_v[0], red_v[1]), fmaxf(red_v[2], red_v[3]));
   __syncthreads();
-  float s = 0.f;
-  for (int v = threadIdx.x; v < V; v += blockDim.x) s += expf(Num<T>::ld(row + v) - m);
+  float s = 0.f, a = 0.f;
+  for (int v = threadIdx.x; v < V; v += blockDim.x) {
+    const float d = Num<T>::ld(row + v) - m, e = expf(d);
+    s += e;
+    if (DETAIL && e > 0.f) a -= e * d;
+  }
   s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red_v[threadIdx.x >> 6] = s;
+  if (DETAIL) a = wave_sum(a);
+  if ((threadIdx.x & 63) == 0) { red_v[threadIdx.x >> 6] = s; if (DETAIL) red_a[threadIdx.x >> 6] = a; }
   __syncthreads();
-  const float lse = logf(red_v[0] + red_v[1] + red_v[2] + red_v[3]);
+  const float ssum = red_v[0] + red_v[1] + red_v[2] + red_v[3];
+  const float lse = logf(ssum);
+  float ent = 0.f;
+  if (DETAIL) ent = lse + (red_a[0] + red_a[1] + red_a[2] + red_a[3]) / ssum;
   __syncthreads();
   float best = -INFINITY;
   int bi = 0x7fffffff;
@@ -91,6 +117,7 @@ __global__ __launch_bounds__(256) void decode_update_kernel(
       const bool eq_blank = (cur == blank) || (ti >= max_tokens) || (fi > nframes[b]);
       const int nxt = min(ti + 1, max_tokens - 1);
       tokens[(long)b * max_tokens + (eq_blank ? 0 : nxt)] = eq_blank ? blank : cur;
+      if (DETAIL && !eq_blank) decode_detail_write(det, (long)b * max_tokens + nxt, fi, nframes[b], best, ent);
       if (!eq_blank) { tok_idx[b] = nxt; prev_tok[b] = cur; }
       else frame_idx[b] = fi + 1;
       s_keep = eq_blank ? 1 : 0;
@@ -105,7 +132,11 @@ __global__ __launch_bounds__(256) void decode_update_kernel(
         per_frame[b] = next ? 0 : nf;
         if (next) frame_idx[b] = fi + 1;
         const int ti = tok_idx[b] + 1;
-        if (!is_blank && ti < max_tokens) { tok_idx[b] = ti; tokens[(long)b * max_tokens + ti] = cur; }
+        if (!is_blank && ti < max_tokens) {
+          tok_idx[b] = ti;
+          tokens[(long)b * max_tokens + ti] = cur;
+          if (DETAIL) decode_detail_write(det, (long)b * max_tokens + ti, fi, nframes[b], best, ent);
+        }
         if (!is_blank) prev_tok[b] = cur;
         s_keep = is_blank ? 1 : 0;
       }
@@ -118,6 +149,7 @@ __global__ __launch_bounds__(256) void decode_update_kernel(
       int ti = tok_idx[b];  // token_index, starts at -1
       if (!is_blank) { ti += 1; tok_idx[b] = ti; prev_tok[b] = cur; }
       if (ti >= 0) tokens[ti] = prev_tok[b];
+      if (DETAIL && !is_blank) decode_detail_write(det, ti, fi, nframes[b], best, ent);
       s_keep = is_blank ? 1 : 0;
     }
   }
@@ -130,13 +162,14 @@ __global__ __launch_bounds__(256) void decode_update_kernel(
 // and reads the counters and the new state only after its reductions - six dependent round trips (~6.7 us per search iteration for a
 // few hundred bytes of work).  Here a thread keeps its NV logits, the counters and its share of h_new / c_new in registers from the
 // first instruction on; what remains is three LDS reductions.  Arithmetic and tie-breaks are those of decode_update_kernel.
-template <int NV>
+template <int NV, bool DETAIL>
 __global__ __launch_bounds__(256) void decode_update_regs_kernel(
     const float* __restrict__ logits, const int32_t* __restrict__ active, const int32_t* __restrict__ nframes,
     int32_t* __restrict__ frame_idx, int32_t* __restrict__ prev_tok, int32_t* __restrict__ tok_idx, int32_t* __restrict__ tokens,
     int32_t* __restrict__ per_frame, const float* __restrict__ h_new, const float* __restrict__ c_new, float* __restrict__ h,
-    float* __restrict__ c, int B, int V, int P, int max_tokens, int blank, int mode, int max_tokens_per_frame) {
+    float* __restrict__ c, int B, int V, int P, int max_tokens, int blank, int mode, int max_tokens_per_frame, DecodeDetail det) {
   __shared__ float red_v[4];
+  __shared__ float red_a[4];
   __shared__ int red_i[4];
   __shared__ int s_keep;
   const int b = blockIdx.x;
@@ -165,14 +198,22 @@ __global__ __launch_bounds__(256) void decode_update_regs_kernel(
   __syncthreads();
   m = fmaxf(fmaxf(red_v[0], red_v[1]), fmaxf(red_v[2], red_v[3]));
   __syncthreads();
-  float s = 0.f;
+  float s = 0.f, a = 0.f;
 #pragma unroll
   for (int t = 0; t < NV; ++t)
-    if (threadIdx.x + 256 * t < V) s += expf(x[t] - m);
+    if (threadIdx.x + 256 * t < V) {
+      const float d = x[t] - m, e = expf(d);
+      s += e;
+      if (DETAIL && e > 0.f) a -= e * d;
+    }
   s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red_v[threadIdx.x >> 6] = s;
+  if (DETAIL) a = wave_sum(a);
+  if ((threadIdx.x & 63) == 0) { red_v[threadIdx.x >> 6] = s; if (DETAIL) red_a[threadIdx.x >> 6] = a; }
   __syncthreads();
-  const float lse = logf(red_v[0] + red_v[1] + red_v[2] + red_v[3]);
+  const float ssum = red_v[0] + red_v[1] + red_v[2] + red_v[3];
+  const float lse = logf(ssum);
+  float ent = 0.f;
+  if (DETAIL) ent = lse + (red_a[0] + red_a[1] + red_a[2] + red_a[3]) / ssum;
   __syncthreads();
   float best = -INFINITY;
   int bi = 0x7fffffff;
@@ -200,6 +241,7 @@ __global__ __launch_bounds__(256) void decode_update_regs_kernel(
       const bool eq_blank = (cur == blank) || (ti >= max_tokens) || (fi > nfr);
       const int nxt = min(ti + 1, max_tokens - 1);
       tokens[(long)b * max_tokens + (eq_blank ? 0 : nxt)] = eq_blank ? blank : cur;
+      if (DETAIL && !eq_blank) decode_detail_write(det, (long)b * max_tokens + nxt, fi, nfr, best, ent);
       if (!eq_blank) { tok_idx[b] = nxt; prev_tok[b] = cur; }
       else frame_idx[b] = fi + 1;
       s_keep = eq_blank ? 1 : 0;
@@ -211,7 +253,11 @@ __global__ __launch_bounds__(256) void decode_update_regs_kernel(
         const bool next = is_blank || nf >= max_tokens_per_frame;
         per_frame[b] = next ? 0 : nf;
         if (next) frame_idx[b] = fi + 1;
-        if (!is_blank && ti + 1 < max_tokens) { tok_idx[b] = ti + 1; tokens[(long)b * max_tokens + ti + 1] = cur; }
+        if (!is_blank && ti + 1 < max_tokens) {
+          tok_idx[b] = ti + 1;
+          tokens[(long)b * max_tokens + ti + 1] = cur;
+          if (DETAIL) decode_detail_write(det, (long)b * max_tokens + ti + 1, fi, nfr, best, ent);
+        }
         if (!is_blank) prev_tok[b] = cur;
         s_keep = is_blank ? 1 : 0;
       }
@@ -222,6 +268,7 @@ __global__ __launch_bounds__(256) void decode_update_regs_kernel(
       int t2 = ti;  // token_index, starts at -1
       if (!is_blank) { t2 += 1; tok_idx[b] = t2; prev_tok[b] = cur; }
       if (t2 >= 0) tokens[t2] = is_blank ? ptok : cur;
+      if (DETAIL && !is_blank) decode_detail_write(det, t2, fi, nfr, best, ent);
       s_keep = is_blank ? 1 : 0;
     }
   }
@@ -251,6 +298,31 @@ extern "C" int tfasr_decode_prepare(const void* encj, const int32_t* nframes, co
   return TFASR_STATUS_SUCCESS;
 }
 
+namespace {
+
+// the launch of tfasr_decode_update (DETAIL = false: what it always launched) and of tfasr_decode_update_detail
+template <bool DETAIL>
+int launch_decode_update(const void* logits, const int32_t* active, const int32_t* nframes, int32_t* frame_idx, int32_t* prev_tok,
+                         int32_t* tok_idx, int32_t* tokens, int32_t* per_frame, const void* h_new, const float* c_new, void* h, float* c, int B,
+                         int V, int P, int max_tokens, int blank, int mode, int max_tokens_per_frame, int dtype, DecodeDetail det, hipStream_t s) {
+  if (dtype == TFASR_F32 && P <= 1024 && V <= 4096) {
+#define TFASR_DU(NV) TFASR_KLAUNCH((decode_update_regs_kernel<NV, DETAIL>), dim3(B), dim3(256), 0, s, (const float*)logits, active, nframes, frame_idx, prev_tok, \
+                                        tok_idx, tokens, per_frame, (const float*)h_new, c_new, (float*)h, c, B, V, P, max_tokens, blank, mode, max_tokens_per_frame, det)
+    if (V <= 1024) TFASR_DU(4);
+    else if (V <= 2048) TFASR_DU(8);
+    else TFASR_DU(16);
+#undef TFASR_DU
+  } else if (dtype == TFASR_F32)
+    TFASR_KLAUNCH((decode_update_kernel<float, DETAIL>), dim3(B), dim3(256), 0, s, (const float*)logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, (const float*)h_new, c_new, (float*)h, c, B, V, P, max_tokens, blank, mode, max_tokens_per_frame, det);
+  else if (dtype == TFASR_BF16)
+    TFASR_KLAUNCH((decode_update_kernel<bf16_t, DETAIL>), dim3(B), dim3(256), 0, s, (const bf16_t*)logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, (const bf16_t*)h_new, c_new, (bf16_t*)h, c, B, V, P, max_tokens, blank, mode, max_tokens_per_frame, det);
+  else return TFASR_STATUS_INVALID_VALUE;
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+}  // namespace
+
 extern "C" int tfasr_decode_update(const void* logits, const int32_t* active, const int32_t* nframes, int32_t* frame_idx,
                                    int32_t* prev_tok, int32_t* tok_idx, int32_t* tokens, int32_t* per_frame,
                                    const void* h_new, const float* c_new, void* h, float* c, int B, int V, int P,
@@ -258,19 +330,20 @@ extern "C" int tfasr_decode_update(const void* logits, const int32_t* active, co
   if (!logits || !active || !nframes || !frame_idx || !prev_tok || !tok_idx || !tokens || !h_new || !c_new || !h || !c)
     return TFASR_STATUS_INVALID_VALUE;
   if (B <= 0 || V <= 0 || P <= 0 || (mode == 1 && (B != 1 || !per_frame)) || (mode == 2 && !per_frame)) return TFASR_STATUS_INVALID_VALUE;
-  hipStream_t s = (hipStream_t)stream_;
-  if (dtype == TFASR_F32 && P <= 1024 && V <= 4096) {
-#define TFASR_DU(NV) TFASR_KLAUNCH(decode_update_regs_kernel<NV>, dim3(B), dim3(256), 0, s, (const float*)logits, active, nframes, frame_idx, prev_tok, \
-                                        tok_idx, tokens, per_frame, (const float*)h_new, c_new, (float*)h, c, B, V, P, max_tokens, blank, mode, max_tokens_per_frame)
-    if (V <= 1024) TFASR_DU(4);
-    else if (V <= 2048) TFASR_DU(8);
-    else TFASR_DU(16);
-#undef TFASR_DU
-  } else if (dtype == TFASR_F32)
-    TFASR_KLAUNCH(decode_update_kernel<float>, dim3(B), dim3(256), 0, s, (const float*)logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, (const float*)h_new, c_new, (float*)h, c, B, V, P, max_tokens, blank, mode, max_tokens_per_frame);
-  else if (dtype == TFASR_BF16)
-    TFASR_KLAUNCH(decode_update_kernel<bf16_t>, dim3(B), dim3(256), 0, s, (const bf16_t*)logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, (const bf16_t*)h_new, c_new, (bf16_t*)h, c, B, V, P, max_tokens, blank, mode, max_tokens_per_frame);
-  else return TFASR_STATUS_INVALID_VALUE;
-  TFASR_CHECK_LAUNCH();
-  return TFASR_STATUS_SUCCESS;
+  return launch_decode_update<false>(logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, h_new, c_new, h, c, B, V, P, max_tokens,
+                                     blank, mode, max_tokens_per_frame, dtype, DecodeDetail{nullptr, nullptr, nullptr}, (hipStream_t)stream_);
+}
+
+extern "C" int tfasr_decode_update_detail(const void* logits, const int32_t* active, const int32_t* nframes, int32_t* frame_idx,
+                                          int32_t* prev_tok, int32_t* tok_idx, int32_t* tokens, int32_t* per_frame, const void* h_new,
+                                          const float* c_new, void* h, float* c, int32_t* tok_frames, float* tok_logp, float* tok_entropy,
+                                          int B, int V, int P, int max_tokens, int blank, int mode, int max_tokens_per_frame, int dtype,
+                                          void* stream_) {
+  if (!logits || !active || !nframes || !frame_idx || !prev_tok || !tok_idx || !tokens || !h_new || !c_new || !h || !c || !tok_frames ||
+      !tok_logp || !tok_entropy)
+    return TFASR_STATUS_INVALID_VALUE;
+  if (B <= 0 || V <= 0 || P <= 0 || mode < 0 || mode > 2 || (mode == 1 && (B != 1 || !per_frame)) || (mode == 2 && !per_frame))
+    return TFASR_STATUS_INVALID_VALUE;
+  return launch_decode_update<true>(logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, h_new, c_new, h, c, B, V, P, max_tokens,
+                                    blank, mode, max_tokens_per_frame, dtype, DecodeDetail{tok_frames, tok_logp, tok_entropy}, (hipStream_t)stream_);
 }

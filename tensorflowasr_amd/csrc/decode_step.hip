@@ -656,20 +656,28 @@ extern "C" int tfasr_decode_step(const float* emb, const float* lstm_k, const fl
 // `iters` search iterations (fused step + bookkeeping each) queued by ONE host call: the Python host costs ~100 us per iteration
 // in ctypes argument marshalling alone, more than the four launches themselves.  Iterations after the loop condition turned false
 // are no-ops on the device (active[0] == 0), so the caller checks `active` only every `iters` iterations.
-extern "C" int tfasr_decode_steps(const float* emb, const float* lstm_k, const float* lstm_rk, const float* lstm_b, const float* ln_g,
-                                  const float* ln_b, const float* joint_pred_w, const float* joint_pred_b, const float* vocab_w,
-                                  const float* vocab_b, const float* packed, const float* encj, const int32_t* nframes, int32_t* frame_idx,
-                                  int32_t* tok_idx, int32_t* prev_tok, float* h, float* c, int32_t* active, float* h_new, float* c_new, float* z,
-                                  float* logits, int32_t* tokens, int32_t* per_frame, int B, int T, int E, int P, int J, int V, int max_tokens,
-                                  int blank, int mode, int max_tokens_per_frame, float ln_eps, int iters, void* stream_) {
+namespace {
+
+// tfasr_decode_steps (detail buffers NULL: tfasr_decode_update, what it always queued) and tfasr_decode_steps_detail
+int decode_steps_impl(const float* emb, const float* lstm_k, const float* lstm_rk, const float* lstm_b, const float* ln_g,
+                      const float* ln_b, const float* joint_pred_w, const float* joint_pred_b, const float* vocab_w,
+                      const float* vocab_b, const float* packed, const float* encj, const int32_t* nframes, int32_t* frame_idx,
+                      int32_t* tok_idx, int32_t* prev_tok, float* h, float* c, int32_t* active, float* h_new, float* c_new, float* z,
+                      float* logits, int32_t* tokens, int32_t* per_frame, int32_t* tok_frames, float* tok_logp, float* tok_entropy, int B, int T,
+                      int E, int P, int J, int V, int max_tokens, int blank, int mode, int max_tokens_per_frame, float ln_eps, int iters,
+                      void* stream_) {
   if (iters <= 0 || !tokens) return TFASR_STATUS_INVALID_VALUE;
   for (int i = 0; i < iters; ++i) {
     int st = tfasr_decode_step(emb, lstm_k, lstm_rk, lstm_b, ln_g, ln_b, joint_pred_w, joint_pred_b, vocab_w, vocab_b, packed, encj, nframes,
                                frame_idx, tok_idx, prev_tok, h, c, active, h_new, c_new, z, logits, B, T, E, P, J, V, max_tokens, mode, ln_eps,
                                stream_);
     if (st != TFASR_STATUS_SUCCESS) return st;
-    st = tfasr_decode_update(logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, h_new, c_new, h, c, B, V, P, max_tokens, blank,
-                             mode, max_tokens_per_frame, TFASR_F32, stream_);
+    if (tok_frames)
+      st = tfasr_decode_update_detail(logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, h_new, c_new, h, c, tok_frames, tok_logp,
+                                      tok_entropy, B, V, P, max_tokens, blank, mode, max_tokens_per_frame, TFASR_F32, stream_);
+    else
+      st = tfasr_decode_update(logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, h_new, c_new, h, c, B, V, P, max_tokens, blank,
+                               mode, max_tokens_per_frame, TFASR_F32, stream_);
     if (st != TFASR_STATUS_SUCCESS) return st;
   }
 #ifdef TFASR_DECODE_TIMING
@@ -686,4 +694,30 @@ extern "C" int tfasr_decode_steps(const float* emb, const float* lstm_k, const f
   }
 #endif
   return TFASR_STATUS_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" int tfasr_decode_steps(const float* emb, const float* lstm_k, const float* lstm_rk, const float* lstm_b, const float* ln_g,
+                                  const float* ln_b, const float* joint_pred_w, const float* joint_pred_b, const float* vocab_w,
+                                  const float* vocab_b, const float* packed, const float* encj, const int32_t* nframes, int32_t* frame_idx,
+                                  int32_t* tok_idx, int32_t* prev_tok, float* h, float* c, int32_t* active, float* h_new, float* c_new, float* z,
+                                  float* logits, int32_t* tokens, int32_t* per_frame, int B, int T, int E, int P, int J, int V, int max_tokens,
+                                  int blank, int mode, int max_tokens_per_frame, float ln_eps, int iters, void* stream_) {
+  return decode_steps_impl(emb, lstm_k, lstm_rk, lstm_b, ln_g, ln_b, joint_pred_w, joint_pred_b, vocab_w, vocab_b, packed, encj, nframes, frame_idx, tok_idx,
+                           prev_tok, h, c, active, h_new, c_new, z, logits, tokens, per_frame, nullptr, nullptr, nullptr, B, T, E, P, J, V, max_tokens, blank,
+                           mode, max_tokens_per_frame, ln_eps, iters, stream_);
+}
+
+extern "C" int tfasr_decode_steps_detail(const float* emb, const float* lstm_k, const float* lstm_rk, const float* lstm_b, const float* ln_g,
+                                         const float* ln_b, const float* joint_pred_w, const float* joint_pred_b, const float* vocab_w,
+                                         const float* vocab_b, const float* packed, const float* encj, const int32_t* nframes,
+                                         int32_t* frame_idx, int32_t* tok_idx, int32_t* prev_tok, float* h, float* c, int32_t* active,
+                                         float* h_new, float* c_new, float* z, float* logits, int32_t* tokens, int32_t* per_frame,
+                                         int32_t* tok_frames, float* tok_logp, float* tok_entropy, int B, int T, int E, int P, int J, int V,
+                                         int max_tokens, int blank, int mode, int max_tokens_per_frame, float ln_eps, int iters, void* stream_) {
+  if (!tok_frames || !tok_logp || !tok_entropy) return TFASR_STATUS_INVALID_VALUE;
+  return decode_steps_impl(emb, lstm_k, lstm_rk, lstm_b, ln_g, ln_b, joint_pred_w, joint_pred_b, vocab_w, vocab_b, packed, encj, nframes, frame_idx, tok_idx,
+                           prev_tok, h, c, active, h_new, c_new, z, logits, tokens, per_frame, tok_frames, tok_logp, tok_entropy, B, T, E, P, J, V,
+                           max_tokens, blank, mode, max_tokens_per_frame, ln_eps, iters, stream_);
 }

@@ -16,7 +16,7 @@ import torch
 
 from . import kernels as K
 from .conformer import ConformerTransducer
-from .schemas import AlignOutput, PredictInput, PredictOutput, TrainData, TrainInput, TrainOutput
+from .schemas import AlignOutput, PredictInput, PredictOutput, RecognizeOutput, TrainData, TrainInput, TrainOutput
 
 
 class ConformerCTC(ConformerTransducer):
@@ -94,6 +94,18 @@ class ConformerCTC(ConformerTransducer):
         return PredictOutput(tokens=tokens[:, :width], next_tokens=None, next_encoder_states=None, next_decoder_states=None)
 
     @torch.no_grad()
+    def recognize_detailed(self, inputs: PredictInput, **kwargs):
+        """recognize with the span and the confidence of every token (tfasr_ctc_greedy_decode_detail, two launches over the logits of
+        _infer_logits) -> RecognizeOutput: token i of utterance b holds the frames [frames[b, i], ends[b, i]) (AlignOutput's definitions),
+        log_probs is summed and entropies averaged over them, scores is the log-probability of the best path."""
+        logits, elen = self._infer_logits(inputs)
+        tokens, tlen, starts, ends, logp, ent, score = K.ctc_greedy_decode_detail(logits, self._h2d(elen), blank=self.blank)
+        width = max(int(tlen.max().item()), 1)
+        predict = PredictOutput(tokens=tokens[:, :width], next_tokens=None, next_encoder_states=None, next_decoder_states=None)
+        return RecognizeOutput(predict, starts[:, :width], ends[:, :width], logp[:, :width], ent[:, :width], score, self.seconds_per_frame,
+                               self.cfg.vocab_size)
+
+    @torch.no_grad()
     def recognize_beam(self, inputs: PredictInput, beam_width=10, device_search=False, **kwargs):
         """CtcModel.recognize_beam (base_ctc.py:128-149): tf.nn.ctc_beam_search_decoder(beam_width) - top path, dense.  TF's beam
         search decoder treats the LAST class as blank (the reference does not pass blank_index there): reproduced.
@@ -131,6 +143,9 @@ class ConformerCTC(ConformerTransducer):
         raise NotImplementedError("the transducer lattice does not apply to a CTC model: use align")
 
     def recognize_encoded(self, *a, **k):
+        raise NotImplementedError("transducer greedy search does not apply to a CTC model")
+
+    def recognize_encoded_detailed(self, *a, **k):
         raise NotImplementedError("transducer greedy search does not apply to a CTC model")
 
     def recognize_beam_encoded(self, *a, **k):

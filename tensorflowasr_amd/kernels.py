@@ -1114,6 +1114,43 @@ def decode_update(logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens,
                                    max_tokens_per_frame, _dt(logits), _stream()), "decode_update")
 
 
+def _check_detail_buffers(what, tokens, tok_frames, tok_logp, tok_entropy):
+    for t, dt in ((tok_frames, torch.int32), (tok_logp, torch.float32), (tok_entropy, torch.float32)):
+        if t.dtype != dt or t.numel() != tokens.numel() or not t.is_contiguous():
+            raise ValueError(f"{what}: the detail buffers are contiguous int32 / f32 / f32 tensors shaped like tokens")
+
+
+def decode_update_detail(logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, h_new, c_new, h, c, tok_frames, tok_logp,
+                         tok_entropy, max_tokens, blank, mode, max_tokens_per_frame):
+    """decode_update that also writes, next to every emitted symbol, its encoder frame, log-probability and the entropy of its decision into
+    tok_frames (int32, caller-filled with -1) / tok_logp / tok_entropy (f32), all shaped like `tokens`."""
+    B, V = logits.shape
+    P = h.shape[1]
+    _check_detail_buffers("decode_update_detail", tokens, tok_frames, tok_logp, tok_entropy)
+    check(_L().tfasr_decode_update_detail(_p(logits), _p(active), _p(nframes), _p(frame_idx), _p(prev_tok), _p(tok_idx), _p(tokens),
+                                          _p(per_frame), _p(h_new), _p(c_new), _p(h), _p(c), _p(tok_frames), _p(tok_logp), _p(tok_entropy),
+                                          B, V, P, max_tokens, blank, mode, max_tokens_per_frame, _dt(logits), _stream()), "decode_update_detail")
+
+
+def decode_steps_detail(emb, lstm_k, lstm_rk, lstm_b, ln_g, ln_b, wjp, bjp, wv, bv, encj, nframes, frame_idx, tok_idx, prev_tok, h, c, active,
+                        h_new, c_new, z, logits, tokens, per_frame, tok_frames, tok_logp, tok_entropy, max_tokens, blank, mode,
+                        max_tokens_per_frame, iters, ln_eps=1e-3, packed=None):
+    """decode_steps with the detail bookkeeping of decode_update_detail; False when the shapes need the per-op route."""
+    B, T, J = encj.shape
+    V, E = emb.shape
+    P = h.shape[1]
+    _check_detail_buffers("decode_steps_detail", tokens, tok_frames, tok_logp, tok_entropy)
+    st = _L().tfasr_decode_steps_detail(_p(emb), _p(lstm_k), _p(lstm_rk), _p(lstm_b), _p(ln_g), _p(ln_b), _p(wjp), _p(bjp), _p(wv), _p(bv),
+                                        _p(packed), _p(encj), _p(nframes), _p(frame_idx), _p(tok_idx), _p(prev_tok), _p(h), _p(c), _p(active),
+                                        _p(h_new), _p(c_new), _p(z), _p(logits), _p(tokens), _p(per_frame), _p(tok_frames), _p(tok_logp),
+                                        _p(tok_entropy), B, T, E, P, J, V, max_tokens, blank, mode, max_tokens_per_frame, ln_eps, int(iters),
+                                        _stream())
+    if st == _lib.STATUS_UNSUPPORTED:
+        return False
+    check(st, "decode_steps_detail")
+    return True
+
+
 # ------------------------------------------------------------------------------------------------ CTC
 def ctc_loss_fwd_bwd(logits, labels, label_len, logit_len, grad_scale=None, grads=None, want_grads=True, blank=0):
     """logits [B,T,V] -> (costs [B], grads or None); tf.nn.ctc_loss semantics (losses/ctc_loss.py:57-66)."""
@@ -1450,6 +1487,21 @@ def ctc_greedy_decode(logits, logit_len, blank=0):
     tlen = torch.empty(B, dtype=torch.int32, device=logits.device)
     check(_L().tfasr_ctc_greedy_decode(_p(logits), _p(logit_len), _p(am), _p(tokens), _p(tlen), B, T, V, blank, _dt(logits), _stream()), "ctc_greedy")
     return tokens, tlen
+
+
+def ctc_greedy_decode_detail(logits, logit_len, blank=0):
+    """ctc_greedy_decode with spans and confidences: (tokens [B,T], tokens_len [B], starts [B,T], ends [B,T], tok_logp [B,T], tok_entropy
+    [B,T], score [B]); token i of row b holds the frames [starts, ends), -1 past tokens_len (include/tfasr_hip.h)."""
+    B, T, V = logits.shape
+    dev = logits.device
+    ws = torch.empty(3 * B * T, dtype=torch.int32, device=dev)
+    tokens, starts, ends = (torch.empty(B, T, dtype=torch.int32, device=dev) for _ in range(3))
+    tok_logp, tok_entropy = (torch.empty(B, T, dtype=torch.float32, device=dev) for _ in range(2))
+    tlen = torch.empty(B, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    check(_L().tfasr_ctc_greedy_decode_detail(_p(logits), _p(logit_len), _p(ws), _p(tokens), _p(tlen), _p(starts), _p(ends), _p(tok_logp),
+                                              _p(tok_entropy), _p(score), B, T, V, blank, _dt(logits), _stream()), "ctc_greedy_detail")
+    return tokens, tlen, starts, ends, tok_logp, tok_entropy, score
 
 
 # --------------------------------------------------------------------------------- native Conformer-block executor
