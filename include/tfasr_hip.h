@@ -1005,6 +1005,29 @@ int tfasr_logmel_stream(const float* signal, const int32_t* nlen, const float* p
  * (in / out; -1 = none yet) is the arg-max class of the stream's previous frame; rows with logit_len == 0 keep theirs. */
 int tfasr_ctc_greedy_decode_carry(const void* logits, const int32_t* logit_len, int32_t* last_class, int32_t* workspace_argmax,
                                   int32_t* tokens, int32_t* tokens_len, int B, int T, int V, int blank, int dtype, void* stream);
+/* tfasr_ctc_greedy_decode_carry with the span and the confidence of every token (declaration added under ABI 44, nothing existing
+ * changes): one chunk logits [B, C, V] per stream (C >= 1, logit_len[b] in [0, C] valid frames), ONE launch, one workgroup per stream.
+ * Cut a [B, T, V] buffer into consecutive chunks however you like, rows without frames in some calls included: the closed tokens of all
+ * calls in order are, bit for bit, what one tfasr_ctc_greedy_decode_detail call gives for the whole buffer (tokens, starts, ends, tok_logp,
+ * tok_entropy), and the carried score is its score: the frame arithmetic is the same code and the sums continue in frame order.
+ * Frames are GLOBAL: counted from the stream's reset.
+ * Carried state, in / out, reset = {-1, 0, 0, 0} / {0, 0, 0}:
+ *   state_i [B, 4] int32: the arg-max class of the previous frame (-1: none yet); the frames seen so far; 1 while a token is open (its run
+ *                         reached the end of the stream's last frame); the open token's first frame.  (Its run length is seen - first.)
+ *   state_f [B, 3] f32:   the open token's log-probability sum; its entropy sum; the path score (all frames, blanks included).
+ * final_flag [B]: != 0 closes the row's open token at the end of its valid frames, as the end of the buffer does offline; it works with
+ * logit_len[b] == 0.  A row with logit_len[b] == 0 and no flag leaves its state untouched.
+ * Outputs, all [B, C + 1]; tokens_len [B] = n, the tokens that START in this call:
+ *   column 0       the token that was open on entry (tokens = its class), starts = -1 and tokens = blank if there was none;
+ *   columns 1..n   the tokens that start in this call, columns 1..n of `tokens` and n bit-equal to tfasr_ctc_greedy_decode_carry's;
+ *   per column     starts = the token's first frame; ends = one past its last frame if its run closed in this call, else -1 (only the last
+ *                  occupied column can be open); tok_logp / tok_entropy as tfasr_ctc_greedy_decode_detail's when closed, the sum / the mean
+ *                  over the frames so far when open;
+ *   unoccupied     tokens = blank, starts = ends = -1, tok_logp = tok_entropy = 0.
+ * INVALID_VALUE before any launch: a null pointer, B < 1, C < 1, V < 2, blank outside [0, V), a dtype other than f32 / bf16. */
+int tfasr_ctc_greedy_decode_carry_detail(const void* logits, const int32_t* logit_len, const int32_t* final_flag, int32_t* state_i,
+                                         float* state_f, int32_t* tokens, int32_t* tokens_len, int32_t* starts, int32_t* ends,
+                                         float* tok_logp, float* tok_entropy, int B, int C, int V, int blank, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Scoring (csrc/edit_distance.hip; declarations added under ABI 44, nothing existing changes): edit distance with unit costs of P pairs

@@ -1677,6 +1677,12 @@ class ConformerTransducer(BaseModel):
 
         return streaming.StreamingRecognizer(self, batch_size, precision, max_tokens_per_frame, beam_width, max_frames)
 
+    def stream_detailed(self, *args, **kwargs):
+        """stream(...) of this class with the same arguments, opened as a detail session (greedy only; a beam raises ValueError): the
+        outputs also say when each token was spoken and how sure the model was (streaming.StreamDetailOutput, rec.recognized(),
+        DESIGN.md 4b-3).  One method for every streamable class: their stream() signatures differ and stay as they are."""
+        return self.stream(*args, **kwargs).detailed()
+
     def recognize_beam(self, inputs: PredictInput, beam_width=10, device_search=False, precision=None, **kw):
         """The reference's recognize_beam falls back to greedy (base_transducer.py:841-842), and so does this one by default.
         device_search=True runs the modified beam search on the device (csrc/rnnt_beam.hip: at most one symbol per frame, equal label

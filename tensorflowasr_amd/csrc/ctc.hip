@@ -164,36 +164,156 @@ __global__ void ctc_collapse_kernel(const int32_t* __restrict__ amax, const int3
 // tfasr_ctc_greedy_decode) plus the arg-max's log-softmax value, -log(sum_v e_v) with e_v = exp(x_v - max), and the entropy of the frame's
 // distribution H = -sum_v p_v log p_v = log(sum_v e_v) + sum_v e_v (max - x_v) / sum_v e_v (two non-negative terms; a class with
 // e_v == 0 is left out, so a logit of -inf contributes 0 and 0 * -inf never forms).  One wave per frame, grid-stride over the frames.
+// ctc_frame_detail is one frame of it, by one wave: every lane returns the arg-max mi and the wave sums s = sum_v e_v and a = sum_v e_v (max -
+// x_v); the offline kernel and the streamed one (ctc_carry_detail_kernel) finish them with the same three expressions, so both give a
+// frame the same bits.
+struct CtcFrame { int mi; float s, a; };
+
+template <typename T>
+__device__ __forceinline__ CtcFrame ctc_frame_detail(const T* __restrict__ row, int V, int lane) {
+  float m = -INFINITY;
+  int mi = 0x7fffffff;
+  for (int v = lane; v < V; v += 64) { const float x = Num<T>::ld(row + v); if (x > m) { m = x; mi = v; } }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64);
+    const int oi = __shfl_xor(mi, o, 64);
+    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+  }
+  float s = 0.f, a = 0.f;
+  for (int v = lane; v < V; v += 64) {
+    const float d = Num<T>::ld(row + v) - m, e = expf(d);
+    s += e;
+    if (e > 0.f) a -= e * d;
+  }
+  s = wave_sum(s);
+  a = wave_sum(a);
+  return {mi, s, a};
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void ctc_frame_detail_kernel(const T* __restrict__ logits, int32_t* __restrict__ amax, float* __restrict__ frame_lp,
                                                                float* __restrict__ frame_ent, long rows, int V) {
   const int lane = threadIdx.x & 63;
   const long w0 = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (long)gridDim.x * (blockDim.x >> 6);
   for (long r = w0; r < rows; r += nw) {
-    const T* row = logits + r * V;
-    float m = -INFINITY;
-    int mi = 0x7fffffff;
-    for (int v = lane; v < V; v += 64) { const float x = Num<T>::ld(row + v); if (x > m) { m = x; mi = v; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float om = __shfl_xor(m, o, 64);
-      const int oi = __shfl_xor(mi, o, 64);
-      if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-    }
-    float s = 0.f, a = 0.f;
-    for (int v = lane; v < V; v += 64) {
-      const float d = Num<T>::ld(row + v) - m, e = expf(d);
-      s += e;
-      if (e > 0.f) a -= e * d;
-    }
-    s = wave_sum(s);
-    a = wave_sum(a);
+    const CtcFrame f = ctc_frame_detail(logits + r * V, V, lane);
     if (lane == 0) {
-      const float ls = logf(s);
-      amax[r] = mi;
+      const float ls = logf(f.s);
+      amax[r] = f.mi;
       frame_lp[r] = -ls;
-      frame_ent[r] = ls + a / s;
+      frame_ent[r] = ls + f.a / f.s;
     }
+  }
+}
+
+// tfasr_ctc_greedy_decode_carry_detail: one chunk [C, V] of a stream per workgroup, ONE launch.  The waves take the chunk's valid frames in
+// tiles of CTC_CARRY_TILE (one wave per frame, ctc_frame_detail), the tile's arg-max / log-probability / entropy wait in LDS, and after the
+// barrier thread 0 continues ctc_collapse_detail_kernel's serial loop over them from the carried state: the same additions in the same
+// frame order, so a token's sums do not depend on where the chunks were cut.  Frames are global: g = seen + t.
+// sti [B, 4] = {class of the previous frame (-1: none), frames seen, a token is open, its first frame}; stf [B, 3] = {its log-probability
+// sum, its entropy sum, the path score}.  Output row b, C + 1 columns: column 0 = the token open on entry, columns 1 .. n = the tokens that
+// start in this chunk.
+constexpr int CTC_CARRY_TILE = 32;
+constexpr int CTC_CARRY_THREADS = 1024;
+
+template <typename T>
+__global__ __launch_bounds__(CTC_CARRY_THREADS) void ctc_carry_detail_kernel(
+    const T* __restrict__ logits, const int32_t* __restrict__ logit_len, const int32_t* __restrict__ final_flag, int32_t* __restrict__ sti,
+    float* __restrict__ stf, int32_t* __restrict__ out, int32_t* __restrict__ out_len, int32_t* __restrict__ starts, int32_t* __restrict__ ends,
+    float* __restrict__ tok_logp, float* __restrict__ tok_entropy, int C, int V, int blank) {
+  __shared__ int32_t s_amax[CTC_CARRY_TILE];
+  __shared__ float s_lp[CTC_CARRY_TILE], s_ent[CTC_CARRY_TILE];
+  __shared__ int s_n;
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const int Tl = min(max(logit_len[b], 0), C);  // (uniform over the workgroup: every thread meets every barrier)
+  const bool fin = final_flag[b] != 0;
+  const long base = (long)b * (C + 1);
+  // thread 0's registers: the collapse's state
+  int prev = -1, seen = 0, start = 0, n = 0, col = 0;  // col: the column of the open token
+  bool open = false;
+  float lp_run = 0.f, ent_run = 0.f, total = 0.f;
+  if (threadIdx.x == 0) {  // (nothing depends on these loads before the first barrier: their latency hides behind the frame pass)
+    prev = sti[b * 4 + 0];
+    seen = sti[b * 4 + 1];
+    open = sti[b * 4 + 2] != 0;
+    start = sti[b * 4 + 3];
+    lp_run = stf[b * 3 + 0];
+    ent_run = stf[b * 3 + 1];
+    total = stf[b * 3 + 2];
+  }
+  const bool open0 = open;  // column 0: the token open on entry
+  const int cls0 = prev, start0 = start;
+  for (int t0 = 0; t0 < Tl; t0 += CTC_CARRY_TILE) {
+    const int nt = min(CTC_CARRY_TILE, Tl - t0);
+    for (int i = wave; i < nt; i += nwaves) {
+      const CtcFrame f = ctc_frame_detail(logits + ((long)b * C + t0 + i) * V, V, lane);
+      if (lane == 0) {
+        const float ls = logf(f.s);
+        s_amax[i] = f.mi;
+        s_lp[i] = -ls;
+        s_ent[i] = ls + f.a / f.s;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int i = 0; i < nt; ++i) {
+        const int c = s_amax[i], g = seen + t0 + i;
+        if (c != prev) {
+          if (open) {
+            ends[base + col] = g;
+            tok_logp[base + col] = lp_run;
+            tok_entropy[base + col] = ent_run / (float)(g - start);
+            open = false;
+          }
+          if (c != blank) {
+            col = ++n;
+            out[base + col] = c;
+            starts[base + col] = g;
+            start = g;
+            lp_run = 0.f;
+            ent_run = 0.f;
+            open = true;
+          }
+        }
+        const float lp = s_lp[i];
+        total += lp;
+        if (open) { lp_run += lp; ent_run += s_ent[i]; }
+        prev = c;
+      }
+    }
+    __syncthreads();  // (the next tile overwrites the LDS rows)
+  }
+  if (threadIdx.x == 0) {
+    const int g = seen + Tl;
+    out[base] = open0 ? cls0 : blank;
+    starts[base] = open0 ? start0 : -1;
+    if (!open0) { ends[base] = -1; tok_logp[base] = 0.f; tok_entropy[base] = 0.f; }
+    if (open) {  // closed by the final flag, or left open with the sum and the mean over its frames so far
+      ends[base + col] = fin ? g : -1;
+      tok_logp[base + col] = lp_run;
+      tok_entropy[base + col] = ent_run / (float)(g - start);
+      if (fin) open = false;
+    }
+    out_len[b] = n;
+    if (Tl > 0 || fin) {  // (a row without frames and without the flag keeps its state)
+      sti[b * 4 + 0] = prev;
+      sti[b * 4 + 1] = g;
+      sti[b * 4 + 2] = open ? 1 : 0;
+      sti[b * 4 + 3] = start;
+      stf[b * 3 + 0] = lp_run;
+      stf[b * 3 + 1] = ent_run;
+      stf[b * 3 + 2] = total;
+    }
+    s_n = n;
+  }
+  __syncthreads();
+  for (int i = s_n + 1 + threadIdx.x; i <= C; i += blockDim.x) {
+    out[base + i] = blank;
+    starts[base + i] = -1;
+    ends[base + i] = -1;
+    tok_logp[base + i] = 0.f;
+    tok_entropy[base + i] = 0.f;
   }
 }
 
@@ -345,6 +465,24 @@ extern "C" int tfasr_ctc_greedy_decode_detail(const void* logits, const int32_t*
   else TFASR_KLAUNCH(ctc_frame_detail_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)logits, amax, frame_lp, frame_ent, rows, V);
   TFASR_KLAUNCH(ctc_collapse_detail_kernel, dim3((B + 63) / 64), dim3(64), 0, s, amax, frame_lp, frame_ent, logit_len, tokens, tokens_len, starts, ends,
                 tok_logp, tok_entropy, score, B, T, blank);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_greedy_decode_carry_detail(const void* logits, const int32_t* logit_len, const int32_t* final_flag, int32_t* state_i,
+                                                    float* state_f, int32_t* tokens, int32_t* tokens_len, int32_t* starts, int32_t* ends,
+                                                    float* tok_logp, float* tok_entropy, int B, int C, int V, int blank, int dtype, void* stream_) {
+  if (!logits || !logit_len || !final_flag || !state_i || !state_f || !tokens || !tokens_len || !starts || !ends || !tok_logp || !tok_entropy)
+    return TFASR_STATUS_INVALID_VALUE;
+  if (B <= 0 || C <= 0 || V < 2 || blank < 0 || blank >= V) return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t s = (hipStream_t)stream_;
+  if (dtype == TFASR_F32)
+    TFASR_KLAUNCH(ctc_carry_detail_kernel<float>, dim3(B), dim3(CTC_CARRY_THREADS), 0, s, (const float*)logits, logit_len, final_flag, state_i, state_f,
+                  tokens, tokens_len, starts, ends, tok_logp, tok_entropy, C, V, blank);
+  else
+    TFASR_KLAUNCH(ctc_carry_detail_kernel<bf16_t>, dim3(B), dim3(CTC_CARRY_THREADS), 0, s, (const bf16_t*)logits, logit_len, final_flag, state_i, state_f,
+                  tokens, tokens_len, starts, ends, tok_logp, tok_entropy, C, V, blank);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }

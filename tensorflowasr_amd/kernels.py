@@ -1736,6 +1736,62 @@ def ctc_greedy_decode_carry(logits, logit_len, last_class, blank=0):
     return tokens, tlen
 
 
+class CtcDetailState:
+    """What tfasr_ctc_greedy_decode_carry_detail carries per stream (include/tfasr_hip.h): ints [B, 4] = previous class (-1: none), frames
+    seen, a token is open, its first frame; floats [B, 3] = the open token's log-probability sum, its entropy sum, the path score."""
+
+    def __init__(self, B, device="cuda"):
+        self.B = int(B)
+        self.ints = torch.empty(self.B, 4, dtype=torch.int32, device=device)
+        self.floats = torch.empty(self.B, 3, dtype=torch.float32, device=device)
+        self.reset()
+
+    def reset(self, rows=None):
+        r = slice(None) if rows is None else torch.as_tensor(list(rows), dtype=torch.long, device=self.ints.device)
+        self.ints[r] = 0
+        self.ints[r, 0] = -1
+        self.floats[r] = 0
+
+    @property
+    def seen(self):
+        return self.ints[:, 1]
+
+    @property
+    def open(self):
+        return self.ints[:, 2] != 0
+
+    @property
+    def score(self):
+        return self.floats[:, 2]
+
+
+def ctc_greedy_decode_carry_detail(logits, logit_len, state, final=None, blank=0, packed=False):
+    """One chunk [B, C, V] per stream with spans and confidences, one launch; `state` (CtcDetailState) is carried in place, final [B]
+    int32 (default: none) closes the rows' open tokens.  -> (tokens, tokens_len [B], starts, ends, tok_logp, tok_entropy), all [B, C + 1]:
+    column 0 = the token open on entry, columns 1 .. tokens_len = the tokens that start in this chunk, frames counted from the stream's
+    reset, ends = -1 for a token still open (include/tfasr_hip.h).  packed=True: the same as ([3, B, C + 1] int32 = tokens, starts, ends;
+    [2, B, C + 1] f32 = tok_logp, tok_entropy; tokens_len)."""
+    B, C, V = logits.shape
+    dev = logits.device
+    if state.B != B or state.ints.device != dev:
+        raise ValueError(f"ctc_greedy_decode_carry_detail: a state of {state.B} streams on {state.ints.device} for {B} rows on {dev}")
+    if final is None:
+        final = torch.zeros(B, dtype=torch.int32, device=dev)
+    for t, what in ((logit_len, "logit_len"), (final, "final")):
+        if t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous():
+            raise ValueError(f"ctc_greedy_decode_carry_detail: {what} is a contiguous int32 tensor of {B} rows")
+    ibuf = torch.empty(3, B, C + 1, dtype=torch.int32, device=dev)  # tokens, starts, ends
+    fbuf = torch.empty(2, B, C + 1, dtype=torch.float32, device=dev)  # tok_logp, tok_entropy
+    tokens, starts, ends, tok_logp, tok_entropy = ibuf[0], ibuf[1], ibuf[2], fbuf[0], fbuf[1]
+    tlen = torch.empty(B, dtype=torch.int32, device=dev)
+    check(_L().tfasr_ctc_greedy_decode_carry_detail(_p(logits), _p(logit_len), _p(final), _p(state.ints), _p(state.floats), _p(tokens), _p(tlen),
+                                                    _p(starts), _p(ends), _p(tok_logp), _p(tok_entropy), B, C, V, blank, _dt(logits), _stream()),
+          "ctc_greedy_decode_carry_detail")
+    if packed:  # (a session fetches two buffers instead of five)
+        return ibuf, fbuf, tlen
+    return tokens, tlen, starts, ends, tok_logp, tok_entropy
+
+
 # ------------------------------------------------------------------------------------------- causal dense Conv1D (csrc/conv1d.hip)
 def _conv1d_check(st, what):
     if st == _lib.STATUS_UNSUPPORTED:

@@ -7,7 +7,8 @@ session do.  State carried per stream:
     frontend      unconsumed samples (host side, < frame_length + frame_step + one chunk) and the last consumed raw sample
     subsampling   the last 2 feature frames and the last 2 frames of the first convolution's activation (zeros = the causal padding)
     each block    K and V of the last `history_size` frames (rings), the last kernel_size - 1 GLU outputs of the conv module
-    search        last token, LSTM h / c (transducer); the class of the last frame (CTC)
+    search        last token, LSTM h / c (transducer); the class of the last frame (CTC); a detail session's CTC head carries
+                  K.CtcDetailState instead (that class, the frames seen, the open token's start and sums, the path score)
     beam search   (beam_width >= 1) the whole beam: rows, f64 totals, label trie + table, prediction states (K.RnntBeamStream); the
                   CTC search's rows and trie (K.CtcBeamStream); the depth committed so far
 The kernels that touch carried state are csrc/stream.hip; the dense pieces are the forward kernels of training with T = chunk_size.
@@ -34,6 +35,18 @@ class StreamOutput(typing.NamedTuple):
     tokens: torch.Tensor  # [B, W] int32 on the host: the tokens NEW in this call, blank padded
     tokens_length: torch.Tensor  # [B] int32
     frames: torch.Tensor  # [B] int32: encoder frames emitted so far
+
+
+class StreamDetailOutput(typing.NamedTuple):
+    """What a detail session (model.stream_detailed) returns: StreamOutput's three fields, then the time and the confidence of every token of the
+    call, column-aligned with `tokens` (-1 / 0 where no token sits).  Frames count from the stream's reset."""
+    tokens: torch.Tensor
+    tokens_length: torch.Tensor
+    frames: torch.Tensor
+    token_frames: torch.Tensor  # [B, W] int32: transducer = the encoder frame whose decision emitted the token; CTC = the first frame of its run
+    token_ends: typing.Optional[torch.Tensor]  # [B, W] int32, CTC only: one past the run's last frame, -1 while the run is open; None for the transducer
+    log_probs: torch.Tensor  # [B, W] f32 (CTC: summed over the run; over its frames so far while it is open)
+    entropies: torch.Tensor  # [B, W] f32 (CTC: mean over the run; over its frames so far while it is open)
 
 
 class StreamState:
@@ -603,6 +616,29 @@ def check_stream_args(batch_size=1, max_tokens_per_frame=3, beam_width=0, max_fr
     return batch_size, max_tokens_per_frame, beam_width, max_frames
 
 
+class _TokenRecord:
+    """The tokens of one stream of a detail session since its reset, on the host: class, frame (CTC: the first frame of the run), end (CTC:
+    one past the run's last frame, -1 while the run is open; transducer: frame + 1), log-probability, entropy."""
+
+    def __init__(self):
+        self.tokens, self.frames, self.ends, self.logp, self.ent = [], [], [], [], []
+
+    def extend(self, tokens, frames, ends, logp, ent):
+        self.tokens += tokens
+        self.frames += frames
+        self.ends += [f + 1 for f in frames] if ends is None else ends
+        self.logp += logp
+        self.ent += ent
+
+    def update_last(self, end, logp, ent):
+        """the CTC token that was open went on, or closed"""
+        self.ends[-1], self.logp[-1], self.ent[-1] = end, logp, ent
+
+    @property
+    def open(self):
+        return bool(self.ends) and self.ends[-1] < 0
+
+
 class StreamingRecognizer:
     """model.stream(): accept() PCM as it arrives, get the new tokens back; finish() flushes a stream's tail.
 
@@ -633,11 +669,20 @@ class StreamingRecognizer:
     An RNN-Transducer (RnnTransducer.stream(batch_size, chunk_frames=...)) takes steps of any positive number of feature frames: its
     encoder state is RnntStreamState (per block the LSTM's h and c, per time reduction the rows that do not fill a group yet), the encoder
     frames a step gives depend on those carried rows, and finish() sends a final step that zero-pads each reduction's last group - a step
-    without feature frames when the utterance ended on a step boundary."""
+    without feature frames when the utterance ended on a step boundary.
 
-    def __init__(self, model, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000, chunk_frames=None):
+    A detail session (model.stream_detailed(...) with stream()'s arguments, or detail=True here; greedy only): accept / finish return a StreamDetailOutput - the same tokens, plus the frame, the
+    log-probability and the entropy of each, frames counted from the stream's reset - and the session keeps every stream's record:
+    recognized() is what recognize_detailed gives the utterance so far, open_tokens() the CTC streams whose last token's run may still
+    go on, trailing_blank_frames() the frames since the last token.  The transducer's search runs the detail variants of the same mode-2
+    launches; the CTC head runs tfasr_ctc_greedy_decode_carry_detail (one launch) on a carried K.CtcDetailState, and finish() closes an
+    open run with the final flag."""
+
+    def __init__(self, model, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000, chunk_frames=None,
+                 detail=False):
         batch_size, max_tokens_per_frame, self.beam_width, self.max_frames = check_stream_args(batch_size, max_tokens_per_frame, beam_width,
                                                                                              max_frames)
+        self.detail = self._check_detail(detail)
         self.model = model
         self.enc_model = _twin(model, precision)
         self.B = int(batch_size)
@@ -700,8 +745,12 @@ class StreamingRecognizer:
             self.finished = [False] * B
             self.flushed = [False] * B  # (RNN-Transducer) the encoder's carried rows went out with a final step
             self.beam = None
+            if self.detail:  # the record of every stream since its reset: what recognized() returns
+                self.record = [_TokenRecord() for _ in range(B)]
             if self.beam_width:
                 self.beam = self._new_beam()
+            elif self.ctc and self.detail:
+                self.ctc_state = K.CtcDetailState(B, dev)
             elif self.ctc:
                 self.last_class = torch.full((B,), -1, dtype=torch.int32, device=dev)
             else:
@@ -718,8 +767,13 @@ class StreamingRecognizer:
             self.total[b] = self.emitted[b] = self.frames[b] = 0
             self.finished[b] = self.flushed[b] = False
         r = torch.as_tensor(rows, dtype=torch.long, device=dev)
+        if self.detail:
+            for b in rows:
+                self.record[b] = _TokenRecord()
         if self.beam is not None:
             self.beam.reset(rows)
+        elif self.ctc and self.detail:
+            self.ctc_state.reset(rows)
         elif self.ctc:
             self.last_class[r] = -1
         else:
@@ -755,6 +809,7 @@ class StreamingRecognizer:
         m, em, dev, B = self.model, self.enc_model, self.model.device, self.B
         c = m.cfg
         new = [[] for _ in range(B)]
+        mark = [len(r.tokens) for r in self.record] if self.detail else None  # where this call's tokens begin in the record
         window, melw, band = em._frontend_consts()
         while True:
             take = [self._ready(b, b in flush_rows) for b in range(B)]
@@ -812,12 +867,25 @@ class StreamingRecognizer:
             ct, cn = self.beam.commit(final_rows=sorted(flush_rows))
             th, tl = ct.cpu(), cn.cpu()
             new = [th[b, :int(tl[b])].tolist() for b in range(B)]
+        if self.detail and self.ctc:
+            closing = [b for b in flush_rows if not self.finished[b] and self.record[b].open]
+            if closing:  # the utterance is over: close the run that reached its last frame (a call without frames, the final flag alone)
+                self._ctc_detail(torch.zeros(B, 1, c.vocab_size, dtype=torch.float32, device=dev), em._h2d([0] * B),
+                                 em._h2d([int(b in closing) for b in range(B)]))
         W = max(max(len(t) for t in new), 1)
         out = torch.full((B, W), m.blank, dtype=torch.int32)
         for b in range(B):
             if new[b]:
                 out[b, :len(new[b])] = torch.tensor(new[b], dtype=torch.int32)
-        return StreamOutput(out, torch.tensor([len(t) for t in new], dtype=torch.int32), torch.tensor(self.frames, dtype=torch.int32))
+        plain = StreamOutput(out, torch.tensor([len(t) for t in new], dtype=torch.int32), torch.tensor(self.frames, dtype=torch.int32))
+        if not self.detail:
+            return plain
+        assert all(r.tokens[k:] == t for r, k, t in zip(self.record, mark, new))  # the record's new part is the call's tokens
+        pad = lambda rows, fill, dtype: torch.tensor([row[k:] + [fill] * (W - len(row) + k) for row, k in zip(rows, mark)], dtype=dtype)
+        rec = self.record
+        return StreamDetailOutput(*plain, pad([r.frames for r in rec], -1, torch.int32),
+                                  pad([r.ends for r in rec], -1, torch.int32) if self.ctc else None,
+                                  pad([r.logp for r in rec], 0.0, torch.float32), pad([r.ent for r in rec], 0.0, torch.float32))
 
     # ------------------------------------------------------------------------------------------- beam sessions
     def _new_beam(self):
@@ -886,7 +954,13 @@ class StreamingRecognizer:
         encj = K.matmul(self._enc32(enc), ps.p2d("joint/enc/w"), bias=ps.p("joint/enc/b")).view(B, C, J)
         mtpf = self.max_tokens_per_frame
         max_tokens = C * mtpf
-        tokens = torch.full((B, max_tokens), m.blank, dtype=torch.int32, device=dev)
+        if self.detail:  # tokens + frames and log-probabilities + entropies in two buffers (two fetches, not four), pre-filled blank / -1 / 0 / 0
+            ibuf = torch.full((2, B, max_tokens), -1, dtype=torch.int32, device=dev)
+            ibuf[0] = m.blank
+            fbuf = torch.zeros(2, B, max_tokens, dtype=f32, device=dev)
+            tokens, detail = ibuf[0], (ibuf[1], fbuf[0], fbuf[1])
+        else:
+            tokens = torch.full((B, max_tokens), m.blank, dtype=torch.int32, device=dev)
         frame_idx = torch.zeros(B, dtype=torch.int32, device=dev)
         tok_idx = torch.full((B,), -1, dtype=torch.int32, device=dev)
         per_frame = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -902,7 +976,11 @@ class StreamingRecognizer:
         need = max(nv_host)
         while it < max_iters:
             n = min(max(need, 4), max_iters - it)
-            if fused:
+            if fused and self.detail:
+                fused = K.decode_steps_detail(ps.p("pred/emb"), Wk, Wrk, ps.p("pred/lstm/b"), lng, lnb, Wjp, ps.p("joint/pred/b"), Wv,
+                                              ps.p("joint/vocab/b"), encj, nvalid, frame_idx, tok_idx, self.prev_tok, self.h, self.c, active, h_new,
+                                              c_new, zbuf, logits, tokens, per_frame, *detail, max_tokens, m.blank, 2, mtpf, n, packed=self._packed)
+            elif fused:
                 fused = K.decode_steps(ps.p("pred/emb"), Wk, Wrk, ps.p("pred/lstm/b"), lng, lnb, Wjp, ps.p("joint/pred/b"), Wv, ps.p("joint/vocab/b"),
                                        encj, nvalid, frame_idx, tok_idx, self.prev_tok, self.h, self.c, active, h_new, c_new, zbuf, logits, tokens,
                                        per_frame, max_tokens, m.blank, 2, mtpf, n, packed=self._packed)
@@ -919,13 +997,24 @@ class StreamingRecognizer:
                     K.matmul(y, Wjp, bias=ps.p("joint/pred/b"), out=pj)
                     z = K.joint_fwd(ecur.view(B, 1, J), pj.view(B, 1, J))
                     K.matmul(z.view(B, J), Wv, bias=ps.p("joint/vocab/b"), out=logits)
-                    K.decode_update(logits, active, nvalid, frame_idx, self.prev_tok, tok_idx, tokens, per_frame, h_new, c_new, self.h, self.c,
-                                    max_tokens, m.blank, 2, mtpf)
+                    if self.detail:
+                        K.decode_update_detail(logits, active, nvalid, frame_idx, self.prev_tok, tok_idx, tokens, per_frame, h_new, c_new, self.h,
+                                               self.c, *detail, max_tokens, m.blank, 2, mtpf)
+                    else:
+                        K.decode_update(logits, active, nvalid, frame_idx, self.prev_tok, tok_idx, tokens, per_frame, h_new, c_new, self.h, self.c,
+                                        max_tokens, m.blank, 2, mtpf)
             it += n
             left = (nvalid - frame_idx).clamp_(min=0).max()
             need = int(left.item())  # (one sync per batch of iterations)
             if need == 0:
                 break
+        if self.detail:
+            (toks, frames), (logp, ent), tl = ibuf.cpu().tolist(), fbuf.cpu().tolist(), tok_idx.cpu().tolist()  # (plain lists: the rows are short)
+            for b in range(B):
+                n = tl[b] + 1
+                # the kernel's frame is chunk-local: self.frames[b] is the stream's frame count in front of this chunk
+                self.record[b].extend(toks[b][:n], [f + self.frames[b] for f in frames[b][:n]], None, logp[b][:n], ent[b][:n])
+            return [toks[b][:tl[b] + 1] for b in range(B)]
         th, tl = tokens.cpu(), tok_idx.cpu()  # the fetch of the new tokens: the one host round trip of a chunk besides the loop check
         return [th[b, :int(tl[b]) + 1].tolist() for b in range(B)]
 
@@ -934,9 +1023,26 @@ class StreamingRecognizer:
         ps = m.ps
         B, C, _ = enc.shape
         logits = K.matmul(self._enc32(enc), ps.p2d("dec/logits/w"), bias=ps.p("dec/logits/b")).view(B, C, m.cfg.vocab_size)
+        if self.detail:
+            return self._ctc_detail(logits, nvalid)
         tokens, tlen = K.ctc_greedy_decode_carry(logits, nvalid, self.last_class, blank=m.blank)
         th, tl = tokens.cpu(), tlen.cpu()
         return [th[b, :int(tl[b])].tolist() for b in range(B)]
+
+    def _ctc_detail(self, logits, nvalid, final=None):
+        """One launch of tfasr_ctc_greedy_decode_carry_detail on the session's carried state, its result merged into the record: column 0
+        updates the token that was open, columns 1 .. n are appended -> the new tokens per stream."""
+        B, C, _ = logits.shape
+        out = K.ctc_greedy_decode_carry_detail(logits, nvalid, self.ctc_state, final, blank=self.model.blank, packed=True)
+        (toks, starts, ends), (logp, ent), tl = (t.cpu().tolist() for t in out)  # (plain lists: the rows are short)
+        new = []
+        for b in range(B):
+            rec, cols = self.record[b], slice(1, tl[b] + 1)
+            if starts[b][0] >= 0:
+                rec.update_last(ends[b][0], logp[b][0], ent[b][0])
+            rec.extend(toks[b][cols], starts[b][cols], ends[b][cols], logp[b][cols], ent[b][cols])
+            new.append(toks[b][cols])
+        return new
 
     # ------------------------------------------------------------------------------------------- public
     def accept(self, pcm, lengths=None):
@@ -969,3 +1075,62 @@ class StreamingRecognizer:
             self.finished[b] = True
             self.buf[b] = np.zeros(0, np.float32)
         return out
+
+    # ------------------------------------------------------------------------------------------- detail sessions
+    def _check_detail(self, detail):
+        if detail and self.beam_width:
+            raise ValueError("stream: detail=True belongs to the greedy session (beam_width=0): beam sessions keep their outputs, their "
+                             "searches record no token times or confidences")
+        return bool(detail)
+
+    def detailed(self):
+        """This session, which has taken no audio yet, as a detail session (what model.stream_detailed returns) -> self."""
+        if any(self.total) or self.chunks_run:
+            raise RuntimeError("stream: detailed() opens a detail session and comes before the first accept()")
+        self.detail = self._check_detail(True)
+        self._init_rows(range(self.B), first=True)  # the search state of a detail session (the record; the CTC head's carried state)
+        return self
+
+    def _need_detail(self, what):
+        if not self.detail:
+            raise ValueError(f"{what} needs a detail session: open it with model.stream_detailed(...)")
+
+    def open_tokens(self):
+        """[B] bool: the stream's last token is a CTC run that reached the last frame seen, so its end and its values can still change
+        (never for a transducer, never after finish())."""
+        self._need_detail("open_tokens()")
+        return torch.tensor([r.open for r in self.record], dtype=torch.bool)
+
+    def recognized(self, rows=None):
+        """Everything the given streams (default: all) have emitted since their reset -> schemas.RecognizeOutput on the host, row i =
+        stream rows[i], what model.recognize_detailed gives the utterance so far (schemas.token_times / token_confidences / word_details
+        read it).  Every closed token holds its final values; a CTC stream's open token (open_tokens()) holds ends = the frames seen so far
+        and the sum / the mean over its frames so far.  scores: transducer = the sum of the tokens' log_probs, CTC = the carried path score."""
+        self._need_detail("recognized()")
+        from .schemas import PredictOutput, RecognizeOutput
+
+        rows = list(range(self.B)) if rows is None else [int(b) for b in rows]
+        recs = [self.record[b] for b in rows]
+        R, W = len(rows), max([len(r.tokens) for r in recs] + [1])
+        tokens = torch.full((R, W), self.model.blank, dtype=torch.int32)
+        frames, ends = torch.full((R, W), -1, dtype=torch.int32), torch.full((R, W), -1, dtype=torch.int32)
+        logp, ent = torch.zeros(R, W, dtype=torch.float32), torch.zeros(R, W, dtype=torch.float32)
+        for i, (b, r) in enumerate(zip(rows, recs)):
+            n = len(r.tokens)
+            if n:
+                tokens[i, :n] = torch.tensor(r.tokens, dtype=torch.int32)
+                frames[i, :n] = torch.tensor(r.frames, dtype=torch.int32)
+                ends[i, :n] = torch.tensor(r.ends[:-1] + [self.frames[b] if r.open else r.ends[-1]], dtype=torch.int32)
+                logp[i, :n] = torch.tensor(r.logp, dtype=torch.float32)
+                ent[i, :n] = torch.tensor(r.ent, dtype=torch.float32)
+        scores = self.ctc_state.score.cpu()[rows] if self.ctc else logp.sum(1)
+        predict = PredictOutput(tokens=tokens, next_tokens=None, next_encoder_states=None, next_decoder_states=None)
+        return RecognizeOutput(predict, frames, ends if self.ctc else None, logp, ent, scores, self.model.seconds_per_frame,
+                               self.model.cfg.vocab_size)
+
+    def trailing_blank_frames(self):
+        """[B] int32: the encoder frames since the end of each stream's last token (CTC: one past its run, 0 while the run is open;
+        transducer: after the frame that emitted it); the whole stream when nothing was emitted.  What an endpointing rule reads."""
+        self._need_detail("trailing_blank_frames()")
+        return torch.tensor([0 if r.open else self.frames[b] - (r.ends[-1] if r.ends else 0) for b, r in enumerate(self.record)],
+                            dtype=torch.int32)
