@@ -763,6 +763,51 @@ int tfasr_ctc_beam_commit(const int32_t* final_mask, int32_t* committed, int32_t
 int tfasr_ctc_beam_nbest(int B, int C, int Tcap, int V, int beam_width, int top_paths, int width, int32_t* tokens, int32_t* tokens_len,
                          float* log_prob, void* workspace, size_t workspace_bytes, void* stream);
 
+/* N-gram LM shallow fusion in the CTC prefix beam search (declarations added under ABI 44, nothing existing changes;
+ * csrc/ctc_beam.hip, csrc/ngram_lm.h).  The search maximises log P_ctc(y | x) + lm(y) over label sequences y.
+ *
+ * tfasr_ngram_lm_t is a backoff n-gram model in flat form (tensorflowasr_amd/lm.py NGramLM.tables builds it): node n is one n-gram,
+ * node 0 the empty context; (keys, vals) is an open-addressing (node, token) -> node table of table_size slots (a power of two,
+ * load factor <= 1/2): key = node << 32 | token, free slots hold ~0, slot = the trie table's hash & (table_size - 1), linear
+ * probing.  wlogp[n] = float(alpha * ln p + beta), wbow[n] = float(alpha * ln backoff), weos[n] = float(alpha * ln p) of the
+ * end-of-sentence entries, suffix[n] = the node of n's sequence without its first token, depth[n] = its length.  `start` is the state
+ * a sequence begins in, `eos` the token id of the end of a sentence in the table (-1: the model has none).  alpha and beta are
+ * folded in by whoever builds the tables: the searches only add float values, in this order:
+ *     acc = 0;  while (state, token) has no child: acc += wbow[state], state = suffix[state];  inc = acc + wlogp[child];
+ *     next state = child when depth[child] < order, else suffix[child]
+ * and lm(y) is the sum of inc over the tokens of y, each added to the sum so far, from `start`.  Every non-blank class needs a
+ * unigram (a child of node 0).  The arrays are device memory for tfasr_ctc_beam_search_lm, host memory for the host routine.
+ *
+ * The search is tfasr_ctc_beam_search with three differences.  (1) A candidate ranks by float(acoustic total + lm of its label
+ * sequence); exact ties as before.  (2) Per frame only the K = min(2 * beam_width, V - 1) acoustically best non-blank classes (lp
+ * desc, class asc) extend a row, ALL of them (plus, always, a repeat of the row's last label and the labels whose extension merges
+ * with another row's stay); this pruning is part of the decoder's definition and the host routine applies it too.  (3) The final
+ * order adds the end-of-sentence term (walked on weos from the path's state; 0 without </s>): lm_score = lm + that term,
+ * log_prob = the acoustic total as in tfasr_ctc_beam_search, score = float(log_prob + lm_score); paths are ordered by score.
+ * With all wlogp = wbow = 0 the search returns the tokens, lengths and log_prob of tfasr_ctc_beam_search bit for bit.
+ * 1 <= beam_width <= TFASR_CTC_LM_MAX_BEAM (the candidate list of a frame, at most 3W + W*K entries, lives in LDS): a larger width
+ * is TFASR_STATUS_UNSUPPORTED.  Outputs tokens [B,P,T] (0 padded), tokens_len / score / log_prob / lm_score [B,P], P = top_paths,
+ * best first; paths past the last live beam are empty with score = log_prob = -inf and lm_score 0.  NaN logits are outside the
+ * contract (the routines stay in bounds, the result is unspecified and host and device may differ). */
+#define TFASR_CTC_LM_MAX_BEAM 32
+typedef struct {
+  const uint64_t* keys;   /* [table_size] */
+  const int32_t* vals;    /* [table_size] */
+  const float* wlogp;     /* [nodes] */
+  const float* wbow;      /* [nodes] */
+  const float* weos;      /* [nodes] */
+  const int32_t* suffix;  /* [nodes] */
+  const int32_t* depth;   /* [nodes] */
+  int32_t nodes, table_size, order, start, eos;
+} tfasr_ngram_lm_t;
+int tfasr_ctc_beam_search_lm_host(const float* logits, const int32_t* logit_len, int B, int T, int V, int beam_width, int top_paths,
+                                  int blank_index, const tfasr_ngram_lm_t* lm, int32_t* tokens, int32_t* tokens_len, float* score,
+                                  float* log_prob, float* lm_score);
+int tfasr_ctc_beam_search_lm_workspace_size(int B, int T, int V, int beam_width, size_t* bytes);
+int tfasr_ctc_beam_search_lm(const void* logits, const int32_t* logit_len, int B, int T, int V, int beam_width, int top_paths,
+                             int blank_index, int dtype, const tfasr_ngram_lm_t* lm, int32_t* tokens, int32_t* tokens_len, float* score,
+                             float* log_prob, float* lm_score, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Forced alignment on the device (ABI 44 addition; csrc/align.hip): the best single path through the lattice the loss sums over,
  * and when it emits each label.  All pointers are device pointers, label_len / logit_len [B] int32 are clamped to the padded
  * sizes, nothing synchronises with the host, and every argument is checked on the host before any launch.

@@ -263,7 +263,7 @@ class BaseModel:
 
     @torch.no_grad()
     def evaluate(self, data, output_file_path=None, names=None, beam_width=0, top_paths=0, device_search=True, cer_unit="char",
-                 device_metrics=True, batch_size=None):
+                 device_metrics=True, batch_size=None, lm=None, lm_alpha=0.5, lm_beta=0.0):
         """What scripts/test.py does with predict + PredictLogger + evaluate_hypotheses, in one pass: recognise every batch of `data`
         (an iterable of TrainData, or an ASRSliceDataset read in file order in batches of `batch_size`), score it, and optionally write
         the results file (PATH, GROUND_TRUTH, GREEDY, BEAM_SEARCH; `names` defaults to the dataset's paths, else to running numbers).
@@ -278,7 +278,11 @@ class BaseModel:
 
         -> {"greedy": row, "beam": row[, "oracle": row]}, row = {wer, cer, mer, wil, wip, ter, words, chars, tokens, utterances}: rates as
         metrics.ErrorStats defines them (not multiplied by 100; ter = token error rate), the three raw count sums, and the number of
-        utterances.  An utterance with an empty reference counts in the sums and cannot divide by zero on its own."""
+        utterances.  An utterance with an empty reference counts in the sums and cannot divide by zero on its own.
+
+        lm (an lm.NGramLM) fuses the n-gram model into the beam search: the beam column then comes from `recognize_beam_lm(lm,
+        beam_width, lm_alpha, lm_beta, device_search)` and the oracle row from `recognize_nbest_lm`.  Only the CTC models have these
+        (the transducers carry an internal LM): any other model raises NotImplementedError.  lm=None changes nothing."""
         import numpy as np
 
         from . import metrics
@@ -287,6 +291,9 @@ class BaseModel:
         if tok is None:
             raise ValueError("evaluate needs model.tokenizer (texts are scored, not only tokens)")
         dev, blank = self.device, int(self.blank)
+        if lm is not None and not (hasattr(self, "recognize_beam_lm") and hasattr(self, "recognize_nbest_lm")):
+            raise NotImplementedError(f"{type(self).__name__}.evaluate(lm=...): LM shallow fusion exists for the CTC prefix beam search only "
+                                      "(recognize_beam_lm / recognize_nbest_lm); a transducer's prediction network is its LM")
         rows = ["greedy", "beam"] + (["oracle"] if top_paths > 0 else [])
         stats = {r: {u: metrics.ErrorStats() for u in ("words", "chars", "tokens")} for r in rows}
         names = None if names is None else list(names)
@@ -310,8 +317,12 @@ class BaseModel:
                 labels = y.labels.to(dev).to(torch.int32).contiguous()
                 llen = y.labels_length.to(dev).to(torch.int32).clamp(0, labels.shape[1])
                 hyp = {"greedy": self.recognize(inputs).tokens.to(torch.int32).contiguous()}
-                hyp["beam"] = (self.recognize_beam(inputs, beam_width=beam_width, device_search=device_search).tokens.to(torch.int32).contiguous()
-                               if beam_width > 0 else hyp["greedy"])
+                if beam_width > 0 and lm is not None:
+                    hyp["beam"] = self.recognize_beam_lm(inputs, lm, beam_width=beam_width, alpha=lm_alpha, beta=lm_beta,
+                                                         device_search=device_search).tokens.to(torch.int32).contiguous()
+                else:
+                    hyp["beam"] = (self.recognize_beam(inputs, beam_width=beam_width, device_search=device_search).tokens.to(torch.int32).contiguous()
+                                   if beam_width > 0 else hyp["greedy"])
                 for r in ("greedy", "beam"):
                     stats[r]["tokens"].update(count(hyp[r], labels, None, llen, blank))
                 past = torch.arange(labels.shape[1], device=dev)[None] >= llen[:, None]
@@ -321,7 +332,11 @@ class BaseModel:
                     stats[r]["words"].update(count_texts(text[r], refs, "word"))
                     stats[r]["chars"].update(count_texts(text[r], refs, cer_unit))
                 if top_paths > 0:
-                    nb, nlen, score = self.recognize_nbest(inputs, beam_width=max(beam_width, top_paths), top_paths=top_paths)
+                    if lm is not None:
+                        nb, nlen, score = self.recognize_nbest_lm(inputs, lm, beam_width=max(beam_width, top_paths), top_paths=top_paths,
+                                                                  alpha=lm_alpha, beta=lm_beta)[:3]
+                    else:
+                        nb, nlen, score = self.recognize_nbest(inputs, beam_width=max(beam_width, top_paths), top_paths=top_paths)
                     NP = nb.shape[1]
                     nb = nb.to(torch.int32)
                     nlen = nlen.to(dev).to(torch.int32)

@@ -91,6 +91,24 @@ __device__ __forceinline__ void push_regulars(int row, S tot, const int* kc, con
   }
 }
 
+// The same under LM fusion (ctc_beam.hip): EVERY top-K class with !special(c) becomes a candidate, at (tot + lp) + lm_of(c), lm_of(c)
+// = the LM score of the row's sequence extended by c.  The total is no longer monotone in lp, so the first W are not enough.
+template <class S, class Special, class LmOf>
+__device__ __forceinline__ void push_all_regulars(int row, S tot, const int* kc, const S* klp, int K, int lane, Special special, LmOf lm_of,
+                                                  S* ctot, unsigned* ccode, int* nc) {
+  if (tot == -INFINITY) return;
+  for (int k = lane; k < K; k += 64) {
+    const int c = kc[k];
+    if (special(c)) continue;
+    const S t = tot + klp[k];
+    if (t == -INFINITY) continue;
+    const S key = t + lm_of(c);
+    const int q = atomicAdd(nc, 1);
+    ctot[q] = key;
+    ccode[q] = cand_code(row, c);
+  }
+}
+
 // The whole workgroup: win[r] = the candidate of rank r < keep; bnode[i] = the node of beam row i.
 template <class S>
 __device__ __forceinline__ void rank_candidates(const S* ctot, const unsigned* ccode, int nc, int keep, const int* bnode, const Trie& tr,

@@ -33,13 +33,13 @@ __device__ inline bool seq_less(const Trie& tr, Seq a, Seq b) {
   return ea < eb;
 }
 
-__device__ __forceinline__ unsigned hash(int par, int c, unsigned mask) {
+__host__ __device__ __forceinline__ unsigned hash(int par, int c, unsigned mask) {
   return ((unsigned)par * 0x9E3779B1u ^ ((unsigned)c + 0x7F4A7C15u) * 0x85EBCA77u) & mask;
 }
-__device__ __forceinline__ unsigned long long key(int par, int c) { return ((unsigned long long)(unsigned)par << 32) | (unsigned)c; }
+__host__ __device__ __forceinline__ unsigned long long key(int par, int c) { return ((unsigned long long)(unsigned)par << 32) | (unsigned)c; }
 
-// node of (par, c) or -1
-__device__ inline int lookup(const unsigned long long* hk, const int* hv, unsigned hcap, int par, int c) {
+// node of (par, c) or -1 (also called by host code: the n-gram tables of ngram_lm.h have this layout)
+__host__ __device__ inline int lookup(const unsigned long long* hk, const int* hv, unsigned hcap, int par, int c) {
   const unsigned long long k = key(par, c);
   unsigned h = hash(par, c, hcap - 1);
   for (unsigned probe = 0; probe < hcap; ++probe, h = (h + 1) & (hcap - 1)) {

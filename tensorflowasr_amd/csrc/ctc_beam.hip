@@ -8,6 +8,7 @@
 // host passes V-1 to reproduce recognize_beam, 0 for a self-consistent decoder.
 #include "common.h"
 #include "beam_select.h"
+#include "ngram_lm.h"
 #include <algorithm>
 #include <cmath>
 #include <unordered_map>
@@ -168,6 +169,181 @@ extern "C" int tfasr_ctc_beam_search_host(const float* logits, const int32_t* lo
   return TFASR_STATUS_SUCCESS;
 }
 
+// ---- the same search with an n-gram LM fused in (tfasr_hip.h, "N-gram LM shallow fusion"): the structure above with three
+// differences - the ranking key is float(acoustic total + lm of the label sequence), a row is extended only by the frame's K =
+// min(2W, V-1) acoustically best non-blank classes and by the classes special to it, and the final order adds the end-of-sentence
+// term.  The pb / pnb bookkeeping is untouched.  A trie node carries lm of its sequence and the LM state after it.
+namespace {
+struct LmNode { int parent, label, depth, state; float lm; };
+struct LmCand { float key; int src; int label; };
+}  // namespace
+
+extern "C" int tfasr_ctc_beam_search_lm_host(const float* logits, const int32_t* logit_len, int B, int T, int V, int beam_width, int top_paths,
+                                             int blank_index, const tfasr_ngram_lm_t* lm_, int32_t* tokens, int32_t* tokens_len, float* score,
+                                             float* log_prob, float* lm_score) {
+  if (!logits || !logit_len || !tokens || !tokens_len || !score || !log_prob || !lm_score || !ngram_lm::tables_ok(lm_))
+    return TFASR_STATUS_INVALID_VALUE;
+  if (B <= 0 || T <= 0 || V <= 1 || beam_width <= 0 || top_paths < 1 || top_paths > beam_width || blank_index < 0 || blank_index >= V)
+    return TFASR_STATUS_INVALID_VALUE;
+  if (beam_width > TFASR_CTC_LM_MAX_BEAM) return TFASR_STATUS_UNSUPPORTED;
+  const ngram_lm::Tables lm = ngram_lm::tables_of(*lm_);
+  const int W = beam_width, P = top_paths, K = std::min(2 * W, V - 1);
+  std::vector<float> lp(V);
+  std::vector<LmNode> trie;
+  std::vector<Beam> beams, next;
+  std::vector<float> ext, ext_pb;  // as in tfasr_ctc_beam_search_host
+  std::vector<char> cand_of;       // [nb][V] class c extends beam i: listed this frame, or special to the beam
+  std::vector<int> listed(V), merged_into;
+  std::vector<LmCand> cand;
+  std::vector<int32_t> pa, pc;
+  std::unordered_map<uint64_t, int> child;
+  auto prefix_of = [&](int node, std::vector<int32_t>& out) {
+    out.clear();
+    for (int n = node; n > 0; n = trie[n].parent) out.push_back(trie[n].label);
+    std::reverse(out.begin(), out.end());
+  };
+  for (int b = 0; b < B; ++b) {
+    const int Tb = std::min(std::max(logit_len[b], 0), T);
+    trie.clear();
+    child.clear();
+    trie.push_back(LmNode{-1, -1, 0, lm.start, 0.f});
+    beams.assign(1, Beam{0, 0.f, NEG_INF});
+    for (int t = 0; t < Tb; ++t) {
+      const float* x = logits + ((size_t)b * T + t) * V;
+      float mx = x[0];
+      for (int v = 1; v < V; ++v) mx = std::max(mx, x[v]);
+      double se = 0.0;
+      for (int v = 0; v < V; ++v) se += std::exp((double)x[v] - mx);
+      const float lz = mx + (float)std::log(se);
+      for (int v = 0; v < V; ++v) lp[v] = x[v] - lz;
+      // the frame's K best non-blank classes by (lp desc, class asc)
+      int nl = 0;
+      for (int v = 0; v < V; ++v)
+        if (v != blank_index) listed[nl++] = v;
+      // (NaN logits are outside the contract; a NaN counts as -inf here so that the comparator stays a strict weak order)
+      auto rank_lp = [&](int c) { return std::isnan(lp[c]) ? NEG_INF : lp[c]; };
+      std::partial_sort(listed.begin(), listed.begin() + K, listed.begin() + nl, [&](int c, int d) {
+        const float a = rank_lp(c), e = rank_lp(d);
+        return a > e || (a == e && c < d);
+      });
+      const int nb = (int)beams.size();
+      ext.assign((size_t)nb * V, NEG_INF);
+      ext_pb.assign((size_t)nb * V, NEG_INF);
+      cand_of.assign((size_t)nb * V, 0);
+      merged_into.assign(nb, -1);
+      for (int i = 0; i < nb; ++i) {
+        const LmNode& nd = trie[beams[i].node];
+        if (nd.parent < 0) continue;
+        for (int j = 0; j < nb; ++j)
+          if (beams[j].node == nd.parent) { merged_into[i] = j; break; }
+      }
+      cand.clear();
+      for (int i = 0; i < nb; ++i) {
+        const float pb = beams[i].pb, ptot = lse2(pb, beams[i].pnb);
+        const LmNode& nd = trie[beams[i].node];
+        float* row = ext.data() + (size_t)i * V;
+        char* use = cand_of.data() + (size_t)i * V;
+        for (int k = 0; k < K; ++k) use[listed[k]] = 1;
+        if (nd.parent >= 0) use[nd.label] = 1;  // a repeat of the row's own last label
+        for (int c = 0; c < V; ++c) {
+          if (c == blank_index) continue;
+          const float add = (nd.label == c && nd.parent >= 0) ? pb : ptot;  // a repeat needs a blank in between
+          if (add != NEG_INF) row[c] = add + lp[c];
+        }
+      }
+      for (int i = 0; i < nb; ++i) {
+        const LmNode& nd = trie[beams[i].node];
+        const float s_pb = lse2(beams[i].pb, beams[i].pnb) + lp[blank_index];
+        const float s_pnb = nd.parent >= 0 ? beams[i].pnb + lp[nd.label] : NEG_INF;
+        if (merged_into[i] >= 0) {
+          const size_t k = (size_t)merged_into[i] * V + nd.label;
+          ext_pb[k] = s_pb;
+          ext[k] = lse2(ext[k], s_pnb);
+          cand_of[k] = 1;  // a merge target of the parent's row
+        } else {
+          cand.push_back(LmCand{lse2(s_pb, s_pnb) + nd.lm, i, -1});
+        }
+      }
+      for (int i = 0; i < nb; ++i) {
+        const LmNode& nd = trie[beams[i].node];
+        for (int c = 0; c < V; ++c) {
+          const size_t k = (size_t)i * V + c;
+          if (!cand_of[k] || (ext[k] == NEG_INF && ext_pb[k] == NEG_INF)) continue;
+          int st;
+          const float lmv = nd.lm + ngram_lm::walk(lm, lm.wlogp, nd.state, c, &st);
+          cand.push_back(LmCand{lse2(ext_pb[k], ext[k]) + lmv, i, c});
+        }
+      }
+      const size_t keep = std::min<size_t>(W, cand.size());
+      auto better = [&](const LmCand& a, const LmCand& c) {
+        if (a.key != c.key) return a.key > c.key;
+        prefix_of(beams[a.src].node, pa);
+        if (a.label >= 0) pa.push_back(a.label);
+        prefix_of(beams[c.src].node, pc);
+        if (c.label >= 0) pc.push_back(c.label);
+        return pa < pc;
+      };
+      std::partial_sort(cand.begin(), cand.begin() + keep, cand.end(), better);
+      next.clear();
+      for (size_t q = 0; q < keep; ++q) {
+        const LmCand& cd = cand[q];
+        if (cd.label < 0) {
+          const Beam& bm = beams[cd.src];
+          const LmNode& nd = trie[bm.node];
+          const float ptot = lse2(bm.pb, bm.pnb);
+          next.push_back(Beam{bm.node, ptot + lp[blank_index], nd.parent >= 0 ? bm.pnb + lp[nd.label] : NEG_INF});
+        } else {
+          const size_t k = (size_t)cd.src * V + cd.label;
+          const int par = beams[cd.src].node;
+          const uint64_t key = (uint64_t)par * (uint64_t)V + (uint64_t)cd.label;
+          int node;
+          auto it = child.find(key);
+          if (it != child.end()) {
+            node = it->second;
+          } else {
+            int st;
+            const float lmv = trie[par].lm + ngram_lm::walk(lm, lm.wlogp, trie[par].state, cd.label, &st);
+            trie.push_back(LmNode{par, cd.label, trie[par].depth + 1, st, lmv});
+            node = (int)trie.size() - 1;
+            child.emplace(key, node);
+          }
+          next.push_back(Beam{node, ext_pb[k], ext[k]});
+        }
+      }
+      beams.swap(next);
+    }
+    // the final beam by score = acoustic total + (lm + end-of-sentence term), ties: the smaller label sequence
+    const int nb = (int)beams.size();
+    std::vector<float> ac(nb), lmt(nb), sc(nb);
+    std::vector<int> order(nb);
+    for (int i = 0; i < nb; ++i) {
+      const LmNode& nd = trie[beams[i].node];
+      ac[i] = lse2(beams[i].pb, beams[i].pnb);
+      lmt[i] = nd.lm + ngram_lm::end_of_sentence(lm, nd.state);
+      sc[i] = ac[i] + lmt[i];
+      order[i] = i;
+    }
+    std::sort(order.begin(), order.end(), [&](int a, int c) {
+      if (sc[a] != sc[c]) return sc[a] > sc[c];
+      prefix_of(beams[a].node, pa);
+      prefix_of(beams[c].node, pc);
+      return pa < pc;
+    });
+    for (int p = 0; p < P; ++p) {
+      int32_t* out = tokens + ((size_t)b * P + p) * T;
+      std::vector<int32_t> seq;
+      if (p < nb) prefix_of(beams[order[p]].node, seq);
+      const int n = (int)seq.size();
+      for (int i = 0; i < T; ++i) out[i] = i < n ? seq[i] : 0;
+      tokens_len[(size_t)b * P + p] = n;
+      score[(size_t)b * P + p] = p < nb ? sc[order[p]] : NEG_INF;
+      log_prob[(size_t)b * P + p] = p < nb ? ac[order[p]] : NEG_INF;
+      lm_score[(size_t)b * P + p] = p < nb ? lmt[order[p]] : 0.f;
+    }
+  }
+  return TFASR_STATUS_SUCCESS;
+}
+
 // ================================================================================================================================
 // Device prefix beam search (tfasr_ctc_beam_search): the same decoder as tfasr_ctc_beam_search_host above, stream ordered, with the
 // top `top_paths` paths of the final beam.  Two launches:
@@ -242,13 +418,17 @@ __global__ __launch_bounds__(256) void ctc_beam_frame_kernel(const T* __restrict
 struct CtcCarry { int *node, *par, *lab, *dep; float *pb, *pnb; int* cnt; };
 enum { BEAM_LOAD = 1, BEAM_STORE = 2, BEAM_OUTPUT = 4 };  // one-shot search: BEAM_OUTPUT alone
 
-template <typename T>
+// LM fusion (the LM = true instantiation, one-shot searches only): the tables, per trie node lm of its sequence and the LM state after
+// it (written when the node is created, beside the trie's three arrays), and the two extra outputs
+struct LmDev { ngram_lm::Tables t; float* node_lm; int* node_state; float *score, *lm_score; };
+
+template <typename T, bool LM>
 __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
     const T* __restrict__ logits, const int32_t* __restrict__ logit_len, const float* __restrict__ lse_ws,
     const float* __restrict__ lpb_ws, const int32_t* __restrict__ top_c, const float* __restrict__ top_lp, int* trie_parent,
     int* trie_label, int* trie_depth, unsigned long long* hkeys, int* hvals, int Tm, int V, int W, int K, int P, long nmax,
     unsigned hcap, int32_t* __restrict__ tokens, int32_t* __restrict__ tokens_len, float* __restrict__ log_prob, CtcCarry cy, int mode,
-    int Tcap, int OW) {
+    int Tcap, int OW, LmDev lmd) {
   // Tm = frames per utterance of `logits` (the whole utterance or one chunk), OW = the row width of `tokens`, Tcap = the most frames a
   // carried beam takes (its trie holds 1 + W * Tcap nodes)
   // beam state (node, its parent / last label / depth, probabilities) and per-frame scratch
@@ -261,6 +441,10 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
   __shared__ float ctot[BEAM_MAXC];
   __shared__ unsigned ccode[BEAM_MAXC];
   __shared__ int s_nc, s_nb, s_ntrie;
+  // LM only.  The plain instantiation (LM = false) must not reference these four arrays or lm_ext below outside `if constexpr (LM)`:
+  // unreferenced, they are dropped from its LDS and it compiles to the code it was before the fusion existed.
+  __shared__ float blm[MAXW], nlm[MAXW];  // lm of each row's sequence, and of the next beam's
+  __shared__ int blms[MAXW], nlms[MAXW];  // the LM state after it
 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   int Tb = logit_len ? min(max(logit_len[b], 0), Tm) : 0;
@@ -268,6 +452,14 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
   const Trie tr = trie_at(trie_parent, trie_label, trie_depth, (long)b * nmax);
   unsigned long long* hk = hkeys + (long)b * hcap;
   int* hv = hvals + (long)b * hcap;
+  float* node_lm = nullptr;
+  int* node_state = nullptr;
+  if constexpr (LM) { node_lm = lmd.node_lm + (long)b * nmax; node_state = lmd.node_state + (long)b * nmax; }
+  // lm of row i's sequence extended by class c
+  auto lm_ext = [&](int i, int c) {
+    int st;
+    return blm[i] + ngram_lm::walk(lmd.t, lmd.t.wlogp, blms[i], c, &st);
+  };
   int frames0 = 0;
   if (mode & BEAM_LOAD) {
     const int* cnt = cy.cnt + b * CNT_N;
@@ -285,6 +477,7 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
     if (tid == 0) {
       bnode[0] = 0; bpar[0] = -1; blab[0] = -1; bdep[0] = 0; bpb[0] = 0.f; bpnb[0] = -INFINITY;
       s_nb = 1; s_ntrie = 1;
+      if constexpr (LM) { blm[0] = 0.f; blms[0] = lmd.t.start; node_lm[0] = 0.f; node_state[0] = lmd.t.start; }
     }
   }
   if (tid < MAXW) win[tid] = 0;
@@ -316,7 +509,8 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
     // --- candidates: stays not merged into a parent's extension
     if (tid < nb && merged[tid] < 0) {
       const int q = atomicAdd(&s_nc, 1);
-      ctot[q] = lae(spb[tid], spnb[tid]);
+      if constexpr (LM) ctot[q] = lae(spb[tid], spnb[tid]) + blm[tid];
+      else ctot[q] = lae(spb[tid], spnb[tid]);
       ccode[q] = cand_code(tid, -1);
     }
     // --- specials: pair (i, j): beam j's stay merged into (beam i, label of j); (i, i): beam i repeating its own last label
@@ -340,18 +534,23 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
       if (child >= 0) { ext_pb = spb[child]; ext = lae(ext, spnb[child]); }
       const float tot = lae(ext_pb, ext);
       if (tot != -INFINITY) {
+        float key = tot;
+        if constexpr (LM) key = tot + (child >= 0 ? blm[child] : lm_ext(i, c));  // a merged child holds that very sequence
         const int q = atomicAdd(&s_nc, 1);
-        ctot[q] = tot;
+        ctot[q] = key;
         ccode[q] = cand_code(i, c);
       }
     }
     // --- regulars: wave per beam; special to row i = its own last label and its merge targets
-    for (int i = wid; i < nb; i += THREADS / 64)
-      push_regulars(i, bptot[i], kc, klp, K, W, lane, [&](int c) {
+    for (int i = wid; i < nb; i += THREADS / 64) {
+      auto special_to_row = [&](int c) {
         bool special = bpar[i] >= 0 && c == blab[i];
         for (int j = 0; j < nb && !special; ++j) special = merged[j] == i && blab[j] == c;
         return special;
-      }, ctot, ccode, &s_nc);
+      };
+      if constexpr (LM) push_all_regulars(i, bptot[i], kc, klp, K, lane, special_to_row, [&](int c) { return lm_ext(i, c); }, ctot, ccode, &s_nc);
+      else push_regulars(i, bptot[i], kc, klp, K, W, lane, special_to_row, ctot, ccode, &s_nc);
+    }
     __syncthreads();
     const int nc = s_nc, keep = min(W, nc);
     rank_candidates(ctot, ccode, nc, keep, bnode, tr, win, tid);
@@ -364,6 +563,7 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
       if (c < 0) {
         nnode[tid] = bnode[i]; npar[tid] = bpar[i]; nlab[tid] = blab[i]; ndep[tid] = bdep[i];
         npb[tid] = spb[i]; npnb[tid] = spnb[i];
+        if constexpr (LM) { nlm[tid] = blm[i]; nlms[tid] = blms[i]; }
       } else {
         const bool rep = bpar[i] >= 0 && c == blab[i];
         const float add = rep ? bpb[i] : bptot[i];
@@ -375,13 +575,25 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
         const int node = beam_trie::lookup(hk, hv, hcap, bnode[i], c);
         nnode[tid] = node;
         fresh = node < 0;
+        if constexpr (LM) {
+          if (node >= 0) {
+            nlm[tid] = node_lm[node]; nlms[tid] = node_state[node];
+          } else {
+            int st;
+            nlm[tid] = blm[i] + ngram_lm::walk(lmd.t, lmd.t.wlogp, blms[i], c, &st);
+            nlms[tid] = st;
+          }
+        }
       }
     }
     const int nfresh = grow_trie(fresh, tid, &s_ntrie, tr, hk, hv, hcap, nnode, npar, nlab, ndep);
+    if constexpr (LM)
+      if (fresh) { node_lm[nnode[tid]] = nlm[tid]; node_state[nnode[tid]] = nlms[tid]; }  // (fresh lanes are wave 0's: nnode is their own)
     __syncthreads();
     if (tid < keep) {
       bnode[tid] = nnode[tid]; bpar[tid] = npar[tid]; blab[tid] = nlab[tid]; bdep[tid] = ndep[tid];
       bpb[tid] = npb[tid]; bpnb[tid] = npnb[tid];
+      if constexpr (LM) { blm[tid] = nlm[tid]; blms[tid] = nlms[tid]; }
     }
     if (tid == 0) {
       s_nb = keep;
@@ -403,6 +615,34 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
     }
   }
   if (!(mode & BEAM_OUTPUT)) return;
+  const long obase = (long)b * P;
+  if constexpr (LM) {
+    // final beam by score = acoustic total + (lm + the end-of-sentence term), ties: smaller label sequence
+    if (tid < nb) {
+      bptot[tid] = lae(bpb[tid], bpnb[tid]);
+      nlm[tid] = blm[tid] + ngram_lm::end_of_sentence(lmd.t, blms[tid]);
+      spb[tid] = bptot[tid] + nlm[tid];
+    }
+    __syncthreads();
+    if (tid < nb) {
+      const float sq = spb[tid];
+      int rank = 0;
+      for (int p = 0; p < nb; ++p) {
+        const float sp = spb[p];
+        if (sp > sq || (sp == sq && p != tid && seq_less(tr, Seq{bnode[p], -1}, Seq{bnode[tid], -1}))) ++rank;
+      }
+      if (rank < P) win[rank] = tid;
+    }
+    __syncthreads();
+    for (int p = tid; p < P; p += THREADS) {
+      const int i = p < nb ? win[p] : 0;
+      log_prob[obase + p] = p < nb ? bptot[i] : -INFINITY;
+      lmd.lm_score[obase + p] = p < nb ? nlm[i] : 0.f;
+      lmd.score[obase + p] = p < nb ? spb[i] : -INFINITY;
+    }
+    write_paths(tr, nb, P, OW, 0, tid, [&](int p) { return bnode[win[p]]; }, tokens + obase * OW, tokens_len + obase);
+    return;
+  }
   // final beam, best first (ties: smaller label sequence); top P paths, dense and 0 padded
   if (tid < nb) {
     const float tq = lae(bpb[tid], bpnb[tid]);
@@ -417,7 +657,6 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
     }
   }
   __syncthreads();
-  const long obase = (long)b * P;
   for (int p = tid; p < P; p += THREADS) log_prob[obase + p] = p < nb ? npb[p] : -INFINITY;
   write_paths(tr, nb, P, OW, 0, tid, [&](int p) { return bnode[win[p]]; }, tokens + obase * OW, tokens_len + obase);
 }
@@ -500,16 +739,16 @@ inline BeamWs beam_carve(const BeamLayout& L, void* workspace, int B, int W) {
 }
 
 // the frame kernel over logits [B, C, V], then the search kernel: both searches, whole and in pieces
-template <typename T>
+template <typename T, bool LM = false>
 int beam_launch(const BeamLayout& L, const BeamWs& w, const void* logits, const int32_t* logit_len, int B, int C, int Tcap, int V, int W, int P,
-                int blank, int mode, int OW, int32_t* tokens, int32_t* tokens_len, float* log_prob, hipStream_t s) {
+                int blank, int mode, int OW, int32_t* tokens, int32_t* tokens_len, float* log_prob, hipStream_t s, const LmDev& lmd = LmDev{}) {
   if (logit_len) {
     const long rows = (long)B * C;
     const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
     TFASR_KLAUNCH(ctc_beam_frame_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)logits, logit_len, w.lse, w.lpb, w.tc, w.tlp, B, C, V, L.K, blank);
   }
-  TFASR_KLAUNCH(ctc_beam_search_kernel<T>, dim3(B), dim3(THREADS), 0, s, (const T*)logits, logit_len, w.lse, w.lpb, w.tc, w.tlp, w.par, w.lab,
-                w.dep, w.hk, w.hv, C, V, W, L.K, P, L.nmax, L.hcap, tokens, tokens_len, log_prob, w.cy, mode, Tcap, OW);
+  TFASR_KLAUNCH((ctc_beam_search_kernel<T, LM>), dim3(B), dim3(THREADS), 0, s, (const T*)logits, logit_len, w.lse, w.lpb, w.tc, w.tlp, w.par,
+                w.lab, w.dep, w.hk, w.hv, C, V, W, L.K, P, L.nmax, L.hcap, tokens, tokens_len, log_prob, w.cy, mode, Tcap, OW, lmd);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
@@ -539,6 +778,45 @@ extern "C" int tfasr_ctc_beam_search(const void* logits, const int32_t* logit_le
   if (dtype == TFASR_F32)
     return beam_launch<float>(L, w, logits, logit_len, B, T, T, V, beam_width, top_paths, blank_index, BEAM_OUTPUT, T, tokens, tokens_len, log_prob, s);
   return beam_launch<bf16_t>(L, w, logits, logit_len, B, T, T, V, beam_width, top_paths, blank_index, BEAM_OUTPUT, T, tokens, tokens_len, log_prob, s);
+}
+
+// ---- the fused search: the workspace of the plain search, then lm and LM state per trie node ----
+namespace {
+inline size_t lm_node_bytes(int B, const BeamLayout& L) { return align256((size_t)B * L.nmax * 4); }
+}  // namespace
+
+extern "C" int tfasr_ctc_beam_search_lm_workspace_size(int B, int T, int V, int beam_width, size_t* bytes) {
+  if (!bytes || !beam_shape_ok(B, T, V, beam_width)) return TFASR_STATUS_INVALID_VALUE;
+  if (beam_width > TFASR_CTC_LM_MAX_BEAM) return TFASR_STATUS_UNSUPPORTED;
+  const BeamLayout L = beam_layout(B, T, T, V, beam_width);
+  *bytes = L.total + 2 * lm_node_bytes(B, L);
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_search_lm(const void* logits, const int32_t* logit_len, int B, int T, int V, int beam_width, int top_paths,
+                                        int blank_index, int dtype, const tfasr_ngram_lm_t* lm, int32_t* tokens, int32_t* tokens_len,
+                                        float* score, float* log_prob, float* lm_score, void* workspace, size_t workspace_bytes,
+                                        void* stream_) {
+  if (!logits || !logit_len || !tokens || !tokens_len || !score || !log_prob || !lm_score || !workspace || !ngram_lm::tables_ok(lm))
+    return TFASR_STATUS_INVALID_VALUE;
+  if (!beam_shape_ok(B, T, V, beam_width) || top_paths < 1 || top_paths > beam_width || blank_index < 0 || blank_index >= V)
+    return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
+  // a frame's candidate list (W stays, <= 2W specials, W * K regulars) must fit the LDS arrays sized for the plain search
+  static_assert(3 * TFASR_CTC_LM_MAX_BEAM + TFASR_CTC_LM_MAX_BEAM * 2 * TFASR_CTC_LM_MAX_BEAM <= BEAM_MAXC, "fused candidate list exceeds LDS");
+  if (beam_width > TFASR_CTC_LM_MAX_BEAM) return TFASR_STATUS_UNSUPPORTED;
+  const BeamLayout L = beam_layout(B, T, T, V, beam_width);
+  const size_t nb = lm_node_bytes(B, L);
+  if (workspace_bytes < L.total + 2 * nb) return TFASR_STATUS_INVALID_VALUE;
+  const BeamWs w = beam_carve(L, workspace, B, beam_width);
+  char* extra = (char*)workspace + L.total;
+  const LmDev lmd{ngram_lm::tables_of(*lm), (float*)extra, (int*)(extra + nb), score, lm_score};
+  hipStream_t s = (hipStream_t)stream_;
+  if (dtype == TFASR_F32)
+    return beam_launch<float, true>(L, w, logits, logit_len, B, T, T, V, beam_width, top_paths, blank_index, BEAM_OUTPUT, T, tokens, tokens_len,
+                                    log_prob, s, lmd);
+  return beam_launch<bf16_t, true>(L, w, logits, logit_len, B, T, T, V, beam_width, top_paths, blank_index, BEAM_OUTPUT, T, tokens, tokens_len,
+                                   log_prob, s, lmd);
 }
 
 // ---- the search in pieces (streaming sessions).  The workspace (tfasr_ctc_beam_stream_workspace_size) IS the carried state of B

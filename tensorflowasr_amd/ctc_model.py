@@ -126,6 +126,39 @@ class ConformerCTC(ConformerTransducer):
         logits, elen = self._infer_logits(inputs)
         return K.ctc_beam_search_device(logits, self._h2d(elen), beam_width=beam_width, top_paths=top_paths, blank_index=None)
 
+    def _check_lm(self, lm):
+        if int(lm.vocab_size) != int(self.cfg.vocab_size) or int(lm.blank) != int(self.blank):
+            raise ValueError(f"the language model was built for vocab_size {lm.vocab_size} with blank {lm.blank}; this model has "
+                             f"vocab_size {self.cfg.vocab_size} with blank {self.blank}")
+
+    @torch.no_grad()
+    def recognize_beam_lm(self, inputs: PredictInput, lm, beam_width=10, alpha=0.5, beta=0.0, device_search=True):
+        """The prefix beam search with the n-gram model `lm` (lm.NGramLM) fused in: the top path of argmax_y log P_ctc(y | x) + alpha *
+        ln P_lm(y) + beta * |y| (+ alpha * ln P_lm(</s> | y) in the final order), on the GPU (tfasr_ctc_beam_search_lm) or, with
+        device_search=False, by the host routine.  1 <= beam_width <= 32.  The blank is the model's own, self.blank - not TF's
+        last-class convention that recognize_beam reproduces: there is no reference call to mirror here.  An lm built for another vocabulary size or blank is refused."""
+        self._check_lm(lm)
+        logits, elen = self._infer_logits(inputs)
+        tables = lm.tables(alpha, beta)
+        if device_search:
+            toks, n = K.ctc_beam_search_lm(logits, self._h2d(elen), tables, beam_width=beam_width, top_paths=1, blank_index=self.blank)[:2]
+        else:
+            toks, n = K.ctc_beam_search_lm_host(logits, torch.tensor(elen, dtype=torch.int32), tables, beam_width=beam_width, top_paths=1,
+                                                blank_index=self.blank)[:2]
+        toks, n = toks[:, 0], n[:, 0]
+        width = max(int(n.max().item()), 1)
+        return PredictOutput(tokens=toks[:, :width].to(self.device), next_tokens=None, next_encoder_states=None, next_decoder_states=None)
+
+    @torch.no_grad()
+    def recognize_nbest_lm(self, inputs: PredictInput, lm, beam_width=10, top_paths=4, alpha=0.5, beta=0.0):
+        """n-best list of recognize_beam_lm's search, on the GPU: tokens [B, P, T'] (0 padded), lengths [B, P], score [B, P], log_prob
+        [B, P] (acoustic), lm_score [B, P], best first by score = log_prob + lm_score; P = top_paths <= beam_width <= 32.  The blank
+        is self.blank (see recognize_beam_lm), not TF's last class."""
+        self._check_lm(lm)
+        logits, elen = self._infer_logits(inputs)
+        return K.ctc_beam_search_lm(logits, self._h2d(elen), lm.tables(alpha, beta), beam_width=beam_width, top_paths=top_paths,
+                                    blank_index=self.blank)
+
     @torch.no_grad()
     def align(self, data: TrainData, precision=None):
         """CTC forced alignment of data.labels over the f32 logits of _infer_logits (csrc/align.hip) -> AlignOutput: label u holds the

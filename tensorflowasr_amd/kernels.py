@@ -1229,6 +1229,93 @@ def ctc_beam_search_device(logits, logit_len, beam_width=10, top_paths=1, blank_
     return tokens, lengths, log_prob
 
 
+CTC_LM_MAX_BEAM = 32  # TFASR_CTC_LM_MAX_BEAM
+
+
+class NGramLmStruct(ctypes.Structure):  # tfasr_ngram_lm_t
+    _fields_ = [("keys", ctypes.c_void_p), ("vals", ctypes.c_void_p), ("wlogp", ctypes.c_void_p), ("wbow", ctypes.c_void_p),
+                ("weos", ctypes.c_void_p), ("suffix", ctypes.c_void_p), ("depth", ctypes.c_void_p),
+                ("nodes", ctypes.c_int32), ("table_size", ctypes.c_int32), ("order", ctypes.c_int32), ("start", ctypes.c_int32),
+                ("eos", ctypes.c_int32)]
+
+
+_LM_ARRAYS = ("keys", "vals", "wlogp", "wbow", "weos", "suffix", "depth")
+
+
+def _lm_struct(t, ptrs):
+    return NGramLmStruct(*ptrs, t.nodes, t.table_size, t.order, t.start, t.eos)
+
+
+def _lm_host(t):
+    """tfasr_ngram_lm_t over the NumPy arrays of lm.NGramTables"""
+    if t._struct is None:
+        t._struct = _lm_struct(t, [getattr(t, a).ctypes.data for a in _LM_ARRAYS])
+    return t._struct
+
+
+def _lm_device(t, dev):
+    """the same over device copies, uploaded once per (tables, device); the tables are cached per (alpha, beta) by the NGramLM"""
+    key = str(dev)
+    if key not in t._device:
+        import numpy as np
+
+        tens = [torch.from_numpy(getattr(t, a).view(np.int64) if a == "keys" else getattr(t, a)).to(dev) for a in _LM_ARRAYS]
+        t._device[key] = (tens, _lm_struct(t, [x.data_ptr() for x in tens]))
+    return t._device[key][1]
+
+
+def _lm_beam_args(what, V, beam_width, top_paths, blank, lm_tables):
+    if int(lm_tables.vocab_size) != int(V) or int(lm_tables.blank) != int(blank):
+        raise ValueError(f"{what}: the language model was built for vocab_size {lm_tables.vocab_size} with blank {lm_tables.blank}, the "
+                         f"logits have V = {V} with blank_index {int(blank)} (another vocabulary would score <s> / </s> or a missing "
+                         "unigram as a class)")
+    if not 1 <= int(beam_width) <= CTC_LM_MAX_BEAM:
+        raise ValueError(f"{what}: beam_width {int(beam_width)} outside [1, {CTC_LM_MAX_BEAM}] (the fused candidate list of a frame, "
+                         f"3W + W * min(2W, V-1) entries, lives in one workgroup's LDS)")
+    return _beam_args(what, V, beam_width, top_paths, blank, "blank_index")
+
+
+def ctc_beam_search_lm_host(logits, logit_len, lm_tables, beam_width=10, top_paths=1, blank_index=0):
+    """The prefix beam search with an n-gram LM fused in, host routine (tfasr_ctc_beam_search_lm_host): maximises log P_ctc(y | x) +
+    lm(y).  lm_tables = NGramLM.tables(alpha, beta).  -> CPU tensors tokens [B,P,T] (0 padded), lengths [B,P], score [B,P], log_prob
+    [B,P] (the acoustic total), lm_score [B,P] (lm + the end-of-sentence term), best first by score = log_prob + lm_score; paths past
+    the last live beam are empty with score = log_prob = -inf.  Per frame only the min(2W, V-1) acoustically best non-blank classes
+    extend a row (the device search's pruning, part of the decoder's definition).  blank_index is the model's blank (default 0)."""
+    import numpy as np
+
+    x = logits.detach().float().cpu().contiguous().numpy()
+    B, T, V = x.shape
+    W, P, bi = _lm_beam_args("tfasr_ctc_beam_search_lm_host", V, beam_width, top_paths, blank_index, lm_tables)
+    ln = np.ascontiguousarray(logit_len.detach().cpu().numpy() if hasattr(logit_len, "detach") else logit_len, dtype=np.int32)
+    toks, n = np.zeros((B, P, T), np.int32), np.zeros((B, P), np.int32)
+    sc, lp, ls = np.zeros((B, P), np.float32), np.zeros((B, P), np.float32), np.zeros((B, P), np.float32)
+    st = _lm_host(lm_tables)
+    check(_L().tfasr_ctc_beam_search_lm_host(x.ctypes.data, ln.ctypes.data, B, T, V, W, P, bi, ctypes.addressof(st), toks.ctypes.data,
+                                             n.ctypes.data, sc.ctypes.data, lp.ctypes.data, ls.ctypes.data), "ctc_beam_search_lm_host")
+    return tuple(torch.from_numpy(a) for a in (toks, n, sc, lp, ls))
+
+
+def ctc_beam_search_lm(logits, logit_len, lm_tables, beam_width=10, top_paths=1, blank_index=0):
+    """ctc_beam_search_lm_host on the device (tfasr_ctc_beam_search_lm), stream ordered: logits [B,T,V] f32 / bf16 on the GPU ->
+    device tensors tokens [B,P,T], lengths [B,P], score [B,P], log_prob [B,P], lm_score [B,P], best first.  1 <= beam_width <= 32.
+    With alpha = beta = 0 the tokens, lengths and log_prob are those of ctc_beam_search_device, bit for bit."""
+    B, T, V = logits.shape
+    W, P, bi = _lm_beam_args("tfasr_ctc_beam_search_lm", V, beam_width, top_paths, blank_index, lm_tables)
+    logits = logits.contiguous()
+    dev = logits.device
+    logit_len = _i32(logit_len, dev)
+    st = _lm_device(lm_tables, dev)
+    n = ctypes.c_size_t(0)
+    check(_L().tfasr_ctc_beam_search_lm_workspace_size(B, T, V, W, ctypes.byref(n)), "ctc_beam_lm_ws")
+    ws = workspace(n.value, dev, "ctc_beam_lm")
+    tokens, lengths, score = _paths(B, P, T, dev)
+    log_prob, lm_score = torch.empty_like(score), torch.empty_like(score)
+    check(_L().tfasr_ctc_beam_search_lm(_p(logits), _p(logit_len), B, T, V, W, P, bi, _dt(logits), ctypes.addressof(st), _p(tokens),
+                                        _p(lengths), _p(score), _p(log_prob), _p(lm_score), _p(ws), ws.numel(), _stream()),
+          "ctc_beam_search_lm")
+    return tokens, lengths, score, log_prob, lm_score
+
+
 def _i32(x, dev):
     if not torch.is_tensor(x):
         x = torch.tensor(x, dtype=torch.int32)
