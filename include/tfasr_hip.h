@@ -31,6 +31,7 @@
  *       TFASR_NATIVE_BLOCK=0     per-kernel Python path instead of the native block executor
  *       TFASR_ATTN_UNFUSED=1     unfused attention (score matrices in HBM; what f32 models always take)
  *       TFASR_CONV2_IM2COL=1     im2col route of the subsampling's second convolution
+ *       TFASR_SUB_TAIL=0         conv2 forward over every row tile instead of the tiles with real rows + tfasr_s2d_tail_fill
  *       TFASR_NO_PRED_STREAM=1, TFASR_PRED_SLICES=<n>   prediction network in line / in n slices between the encoder blocks
  *       TFASR_WGRAD_STREAM=0|1, TFASR_BLOCK_HOIST=0|1, TFASR_DEFER_SIDE=0, TFASR_FRONT_EARLY=0   stream placement of the weight gradients,
  *                                the hoisted per-block launches, the deferred small gradients, the front end (DESIGN.md section 2 "Streams")
@@ -214,6 +215,12 @@ typedef struct {
      [M, N] (compute dtype, row stride ldd). */
   const void* bns_x; const float* bns_fin; float* bns_out; int bns_copies;
   int bns_c;  /* > 0: the N columns are (position, channel) pairs, channel = column % bns_c (bns_fin [4][bns_c], bns_out [copies][2][bns_c]); 0: N channels */
+  /* Optional row-tile table (K-segmented products only, trans_a == 0, no split-K, no batch; anything else: UNSUPPORTED and nothing is
+     launched): a DEVICE array of n_row_tiles indices of 256-row blocks of the output, 0 <= index < ceil(M / 256).  Only the listed
+     blocks of D are computed - each exactly as the full product computes it, by the kernel the full product would run on - and the
+     other rows of D are left untouched.  One launch; a block that is not listed costs nothing.  (Conv2dSubsampling over a padded
+     batch: the blocks that hold only padding rows are filled by tfasr_s2d_tail_fill instead.) */
+  const int32_t* row_tiles; int n_row_tiles;
 } tfasr_gemm_args;
 
 int tfasr_gemm(const tfasr_gemm_args* args, void* stream);
@@ -641,6 +648,14 @@ int tfasr_conv1_bn_bwd_finalize(const double* gram, const float* w, const float*
                                 const float* pbuf, float* dw, float* db, int C, void* stream);
 int tfasr_halo_zero(void* x, int B, int T2, int F2, int W, int dtype, void* stream);
 int tfasr_s2d_edge_zero(void* x, int B, int T1, int F1, int C, int dtype, void* stream);
+/* Padded tail of a [B, T2+1, F2+1, C] tensor (bf16, C % 8 == 0, 16-byte aligned): in front of the encoder's first dropout every row of
+   an utterance's padding holds what one representative time row holds, so a product with a row-tile table
+   (tfasr_gemm_args.row_tiles) skips the 256-row blocks that hold nothing else and this call fills them: every row (b, tt, ff) of the
+   `n_tiles` blocks listed in `tiles` (DEVICE array, the blocks the product did NOT compute) becomes a copy of row (b, rep_tt[b], ff)
+   (DEVICE array [B], 1 <= rep_tt[b] <= T2, a row of a computed block).  Whole 16-byte stores; other rows are untouched.
+   UNSUPPORTED: f32, C % 8 != 0, unaligned x. */
+int tfasr_s2d_tail_fill(void* x, const int32_t* tiles, int n_tiles, const int32_t* rep_tt, int B, int T2, int F2, int C, int dtype,
+                        void* stream);
 int tfasr_im2col_3x3s2(const void* x, void* col, int B, int T1, int F1, int C, int dtype, void* stream);
 int tfasr_col2im_3x3s2(const void* dcol, void* dx, int B, int T1, int F1, int C, int dtype, void* stream);
 

@@ -35,6 +35,7 @@ class GemmArgs(Structure):
         ("seg_a_off", c_void_p), ("seg_b_off", c_void_p), ("seg_k", c_int),
         ("rgrad_coef", c_void_p),
         ("bns_x", c_void_p), ("bns_fin", c_void_p), ("bns_out", c_void_p), ("bns_copies", c_int), ("bns_c", c_int),
+        ("row_tiles", c_void_p), ("n_row_tiles", c_int),
     ]
 
 

@@ -74,6 +74,10 @@ class ConformerTransducer(BaseModel):
         self._bn1_sums_in_gemm = True  # subsampling BatchNorm1 backward sums in the linear layer's data gradient
         self._bn_stats_copies = 8  # ConvModule BatchNorm statistics inside the depthwise conv, atomics spread over this many copies; 1: the two launches (tests)
         self._conv1_gram = True  # conv1 / BatchNorm0 sums through the patch Gram matrix (one backward pass); False: the two-pass kernels (tests)
+        # conv2 forward over the row tiles that hold real rows only; the padded tail of its output is one representative row per utterance,
+        # copied (DESIGN.md section 2 "Padded tail").  False / TFASR_SUB_TAIL=0: every tile is computed
+        self._sub_tail_once = os.environ.get("TFASR_SUB_TAIL", "1") != "0"
+        self._front_tail = None
         # SpecAugment draws and dropout masks are per replica (MirroredStrategy draws independent randomness on every
         # replica); the parameter initialisation seed above is shared by all ranks
         self._rng = np.random.default_rng([seed + 1000, int(self.dp.rank)])
@@ -232,7 +236,72 @@ class ConformerTransducer(BaseModel):
             fm, tm = masks
             if fm is not None or tm is not None:
                 K.specaugment(feats, None if fm is None else self._h2d(fm), None if tm is None else self._h2d(tm), 0.0)
+        self._front_tail = (feats, self._feature_tail(signals_length, masks[1] if training else None))
         return feats, flen
+
+    def _feature_tail(self, signals_length, tm):
+        """Per utterance the first frame from which the feature map is constant in time, or None when that is not known on the host.
+        Samples behind signals_length are 0 (the padded-batch contract, datasets.py), pre-emphasis leaves sample n = -coef * x[n-1] != 0
+        and framing is pad_end (csrc/logmel.hip), so every frame t with t * frame_step >= n + 1 is ln(eps) in every bin; frequency masks
+        cover whole utterances, time masks (host tensors [B, masks, (start, width)]) end where they say."""
+        step = self.cfg.frame_step
+        tf = -(-(np.asarray([int(n) for n in signals_length], dtype=np.int64) + 1) // step)
+        if tm is not None:
+            if not isinstance(tm, torch.Tensor) or tm.device.type != "cpu":
+                return None
+            m = tm.numpy().astype(np.int64)
+            if m.shape[1] > 0:
+                tf = np.maximum(tf, (m[:, :, 0] + m[:, :, 1]).max(axis=1))
+        return tuple(int(v) for v in tf)
+
+    @staticmethod
+    def _tail_rows(tf, T0):
+        """First constant row per utterance of the feature map, of a1 (time rows of the S layout), and of o / a2, from the first
+        constant feature frame `tf` (array).  Both causal stride-2 convolutions read output row t from input rows 2t-2 .. 2t: a row is
+        constant only if the FIRST row it reads is.  conv1 row t1 >= tf/2 + 1; S row tt (1-based) holds t1 = 2tt-2, 2tt-1; conv2's
+        output row tt reads S rows tt-1 and tt.  A value behind the last row (T2) means: no tail."""
+        tf = np.asarray(tf, dtype=np.int64)
+        t1c = (tf + 1) // 2 + 1
+        a1 = (t1c + 1) // 2 + 1
+        return dict(feats=tf, a1=a1, o=a1 + 1, a2=a1 + 1)
+
+    @classmethod
+    def _tail_blocks(cls, tf, B, T0, T2, F2):
+        """Host arrays (computed 256-row blocks, skipped blocks, representative time row per utterance) of the conv2 output
+        [B, T2+1, F2+1, C].  A block is skipped when it holds only padding rows behind the representative row (the first constant one,
+        which counts as a real row and so always lies in computed blocks) and halo rows tt = 0; an utterance without a tail has
+        representative row 1."""
+        rep = cls._tail_rows(tf, T0)["o"]
+        has = rep + 1 <= T2
+        rep = np.where(has, rep, 1)
+        end = np.where(has, rep + 1, T2 + 1)  # real time rows of utterance b: [1, end)
+        nblk = -(-(B * (T2 + 1) * (F2 + 1)) // 256)
+        base = np.arange(B, dtype=np.int64) * (T2 + 1)
+        lo = (base + 1) * (F2 + 1) // 256
+        hi = ((base + end) * (F2 + 1) - 1) // 256
+        mark = np.zeros(nblk + 1, np.int64)
+        np.add.at(mark, lo, 1)
+        np.add.at(mark, hi + 1, -1)
+        real = np.cumsum(mark[:nblk]) > 0
+        return np.flatnonzero(real), np.flatnonzero(~real), rep
+
+    def _tail_tables(self, tf, B, T0, T2, F2):
+        """_tail_blocks as device i32 tensors (one pinned upload), or None when fewer than one block in 16 can be skipped (the fill
+        launch then costs what the skipped tiles save).  Cached per tuple of lengths; a handful of entries are kept."""
+        key = ("tail", tf, T0, F2)
+        hit = self._consts.get(key, 0)
+        if hit != 0:
+            return hit
+        comp, skip, rep = self._tail_blocks(tf, B, T0, T2, F2)
+        out = None
+        if skip.size * 16 >= comp.size + skip.size:
+            dev = self._h2d(np.concatenate([comp, skip, rep]).astype(np.int32))
+            out = (dev[:comp.size], dev[comp.size:comp.size + skip.size], dev[comp.size + skip.size:])
+        old = [k for k in self._consts if isinstance(k, tuple) and k[:1] == ("tail",)]
+        for k in old[:max(0, len(old) - 7)]:
+            del self._consts[k]
+        self._consts[key] = out
+        return out
 
     def draw_specaugment(self, flen):
         """Random draws of FreqMasking/TimeMasking.augment (specaugment.py:72-77,122-131; freq before time:
@@ -417,7 +486,19 @@ class ConformerTransducer(BaseModel):
                 K.gemm(flat[base + shift[i] * 4 * C + blk[i] * C:], W[i * C:(i + 1) * C], o, rows, C, C, 4 * C, C, C,
                        bias=ps.p("enc/sub/conv1/b") if i == 0 else None, accumulate=i > 0)
         else:
-            K.gemm(a1, W, o, rows, C, 9 * C, 4 * C, C, C, bias=ps.p("enc/sub/conv1/b"), seg=fwd_a)
+            # padded tail: only the row tiles with real rows, the rest copied from one representative row per utterance - bitwise what
+            # the full product writes there (only for the feature map this model's front end has just produced)
+            tail, ft, self._front_tail = None, self._front_tail, None
+            if self._sub_tail_once and ft is not None and ft[0] is feats and ft[1] is not None and len(ft[1]) == B:
+                tail = self._tail_tables(ft[1], B, T0, T2, F2)
+            if tail is not None:
+                try:
+                    K.gemm(a1, W, o, rows, C, 9 * C, 4 * C, C, C, bias=ps.p("enc/sub/conv1/b"), seg=fwd_a, row_tiles=tail[0])
+                    K.s2d_tail_fill(o, tail[1], tail[2], B, T2, F2, C)
+                except K._lib.TfasrUnsupported:
+                    tail = None
+            if tail is None:
+                K.gemm(a1, W, o, rows, C, 9 * C, 4 * C, C, C, bias=ps.p("enc/sub/conv1/b"), seg=fwd_a)
         K.halo_zero(o, B, T2, F2, C)
         _, a2 = self._salloc(rows, C, 0)
         _, bn1 = self._bn_fwd(o, "enc/sub/bn1", training, ACT_SWISH, rows=B * T2 * F2, y=a2)

@@ -624,6 +624,27 @@ __global__ __launch_bounds__(256) void s2d_edge_zero_kernel(T* __restrict__ x, i
   }
 }
 
+// Padded tail of a [B, T2+1, F2+1, C] bf16 tensor: the rows of the listed 256-row blocks (blocks a product with a row-tile table left
+// out: they hold padding rows and halo rows only) become copies of their utterance's representative time row, same frequency slot.
+// A quarter block per workgroup, 16 bytes per lane; the representative rows (21 x C per utterance) stay in L2.  Indices read from the
+// tables are clamped to the tensor.
+__global__ __launch_bounds__(256) void s2d_tail_fill_kernel(uint4* __restrict__ x, const int32_t* __restrict__ tiles, const int32_t* __restrict__ rep_tt,
+                                                            int T2, int F2, int c8n, long rows) {
+  const long nblk = (rows + 255) / 256;
+  const long tile = min(max((long)tiles[blockIdx.x >> 2], 0L), nblk - 1);
+  const long r0 = tile * 256 + (blockIdx.x & 3) * 64;
+  const int per_b = (T2 + 1) * (F2 + 1);
+  for (int i = threadIdx.x; i < 64 * c8n; i += 256) {
+    const long row = r0 + i / c8n;
+    if (row >= rows) break;
+    const int c8 = i % c8n;
+    const int b = (int)(row / per_b), ff = (int)(row % (F2 + 1));
+    const int rt = min(max(rep_tt[b], 1), T2);
+    const long src = ((long)b * (T2 + 1) + rt) * (F2 + 1) + ff;
+    if (src != row) x[row * c8n + c8] = x[src * c8n + c8];
+  }
+}
+
 }  // namespace
 
 #define DISPATCH_T(dtype, CALL_F32, CALL_BF16) \
@@ -803,6 +824,18 @@ extern "C" int tfasr_s2d_edge_zero(void* x, int B, int T1, int F1, int C, int dt
   const int grid = flat_grid((long)B * (((T1 & 1) ? F2 * 2 : 0) + ((F1 & 1) ? T2 * 2 : 0)) * (C / 8));
   DISPATCH_T(dtype, TFASR_KLAUNCH(s2d_edge_zero_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)x, B, T1, F1, T2, F2, C),
              TFASR_KLAUNCH(s2d_edge_zero_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (bf16_t*)x, B, T1, F1, T2, F2, C));
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_s2d_tail_fill(void* x, const int32_t* tiles, int n_tiles, const int32_t* rep_tt, int B, int T2, int F2, int C, int dtype,
+                                   void* stream_) {
+  if (!x || !tiles || !rep_tt || B <= 0 || T2 <= 0 || F2 <= 0 || C <= 0 || n_tiles < 0) return TFASR_STATUS_INVALID_VALUE;
+  const long rows = (long)B * (T2 + 1) * (F2 + 1);
+  if (n_tiles > (rows + 255) / 256) return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_BF16 || C % 8 || (((uintptr_t)x) & 15)) return TFASR_STATUS_UNSUPPORTED;
+  if (n_tiles == 0) return TFASR_STATUS_SUCCESS;
+  TFASR_KLAUNCH(s2d_tail_fill_kernel, dim3(4 * n_tiles), dim3(256), 0, (hipStream_t)stream_, (uint4*)x, tiles, rep_tt, T2, F2, C / 8, rows);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }

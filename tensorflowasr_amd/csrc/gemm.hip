@@ -438,6 +438,10 @@ extern "C" int tfasr_gemm(const tfasr_gemm_args* args, void* stream_) {
   if (a.split_k > 1 && (a.res || a.dact_z || a.prez || a.act != TFASR_ACT_NONE || a.drop_p > 0.f)) return TFASR_STATUS_INVALID_VALUE;
   if (a.drop_p < 0.f || a.drop_p >= 1.f) return TFASR_STATUS_INVALID_VALUE;
   if (a.colsum && !(a.accumulate && a.trans_a && !a.trans_b && a.nb1 * a.nb2 == 1)) return TFASR_STATUS_INVALID_VALUE;
+  if (a.row_tiles) {  // row-tile table: the K-segmented NN / NT products only, every entry count the tile grid can hold
+    if (a.n_row_tiles <= 0 || a.n_row_tiles > (a.M + 255) / 256) return TFASR_STATUS_INVALID_VALUE;
+    if (!a.seg_a_off || a.trans_a || a.accumulate || a.split_k > 1 || a.nb1 * a.nb2 != 1 || a.dtype != TFASR_BF16) return TFASR_STATUS_UNSUPPORTED;
+  }
   hipStream_t stream = (hipStream_t)stream_;
   if (a.dtype == TFASR_BF16 && use_fast_path()) {
     const int st = tfasr_gemm_fast_try(a, stream);

@@ -127,6 +127,9 @@ void gemm_big_kernel(const tfasr_gemm_args p, const int gx, const int gy, const 
     const int tx = t % gx, ty = t / gx;
     T.ok = 1;
     T.m0 = ty * BMB;
+    // row-tile table (K-segmented products only): gy counts the table's entries, entry ty names the 256-row block to compute.  An
+    // entry outside the operand is clamped to the last block (written twice with the same values) instead of leaving the operand.
+    if constexpr (SEG) { if (p.row_tiles) T.m0 = min(max(p.row_tiles[ty], 0), (p.M + BMB - 1) / BMB - 1) * BMB; }
     T.m0s = min(T.m0, p.M - BMB);
     T.n0 = tx * BN_;
     T.n0s = TB ? min(T.n0, p.N - BN_) : T.n0;  // k-contiguous B: the last column tile is shifted back like the last row tile
@@ -753,10 +756,13 @@ int launch_big(const tfasr_gemm_args& a, bool generic, int need, bool tanh_out, 
   if (TB && !seg && !a.lse_part && (a.N % 320) == 0) bn = 320;
   else if (a.N >= (TB ? 256 : 192) && ((a.N % 256) == 0 || (a.N % 256) >= 192)) bn = 256;
   if (!bn) return TFASR_STATUS_UNSUPPORTED;
-  const int gx = (a.N + bn - 1) / bn, gy = (a.M + 255) / 256;
-  const long ntiles = (long)gx * gy;
+  int gx = (a.N + bn - 1) / bn, gy = (a.M + 255) / 256;
+  long ntiles = (long)gx * gy;
   static const long min_tiles = 2L * num_cus();
   if (ntiles < min_tiles || ntiles > 0x7fffffffL) return TFASR_STATUS_UNSUPPORTED;
+  // a row-tile table never changes WHICH kernel runs (the rule above counts the full product's tiles): a listed 256-row block is
+  // computed exactly as the full product computes it
+  if (a.row_tiles) { gy = a.n_row_tiles; ntiles = (long)gx * gy; }
   if (tanh_out && (!TB || seg || a.lse_part)) return TFASR_STATUS_UNSUPPORTED;
   if (a.lse_part && !(a.row_label && a.pick && bn == 256 && a.lse_parts == ((a.N + 127) / 128) * 2)) return TFASR_STATUS_UNSUPPORTED;
   if (a.rgrad_coef && (TB || seg || tanh_out || bn != 256 || !a.row_label)) return TFASR_STATUS_UNSUPPORTED;

@@ -361,6 +361,8 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
     T.B = (const bf16_t*)p.B + b1 * p.sB1 + b2 * p.sB2;
     T.doff = b1 * p.sD1 + b2 * p.sD2;
     T.m0 = ty * BM;
+    // row-tile table (K-segmented products only; entries name 256-row blocks = two of this kernel's tiles, clamped to the operand)
+    if constexpr (SEG) { if (p.row_tiles) T.m0 = min(max(p.row_tiles[ty >> 1], 0) * 256 + (ty & 1) * BM, ((p.M + BM - 1) / BM - 1) * BM); }
     T.n0 = tx * BN;
     T.ks = ks;
     T.k_begin = ks * kchunk;
@@ -1043,7 +1045,7 @@ int launch_one(const tfasr_gemm_args& a, hipStream_t stream) {
     if constexpr (!TA) {
       if (!generic && need == 0 && !a.accumulate && split == 1 && a.nb1 * a.nb2 == 1 && a.seg_k > 0 && (a.seg_k % BK) == 0 && (a.K % a.seg_k) == 0 &&
           a.K / BK <= 64 && !a.lse_part) {
-        dim3 g128((a.N + 127) / 128, (a.M + BM - 1) / BM, 1);
+        dim3 g128((a.N + 127) / 128, a.row_tiles ? 2 * a.n_row_tiles : (a.M + BM - 1) / BM, 1);
         const long ntiles = (long)g128.x * g128.y;
         const int slots = 2 * num_cus();
         int G = (int)(ntiles < slots ? ntiles : slots);

@@ -274,7 +274,7 @@ def edit_distance(hyp, ref, hyp_len=None, ref_len=None, skip_id=-1):
 # ---------------------------------------------------------------------------------------------- GEMM
 def gemm(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, bias=None, res=None, dact_z=None,
          prez=None, alpha=1.0, beta=1.0, act=ACT_NONE, dact=ACT_NONE, nb1=1, nb2=1, sA=(0, 0), sB=(0, 0), sD=(0, 0),
-         accumulate=False, split_k=1, drop_p=0.0, drop_seed=0, colsum=None, lse=None, seg=None, rgrad=None, bns=None):
+         accumulate=False, split_k=1, drop_p=0.0, drop_seed=0, colsum=None, lse=None, seg=None, rgrad=None, bns=None, row_tiles=None):
     """Raw strided (two-level batched) GEMM; see include/tfasr_hip.h.  bns = (x [M, N], fin [4N] f32, out [copies, 2N] f32): the BatchNorm
     backward sums of the output in the epilogue (tfasr_gemm_args.bns_*; raises TfasrUnsupported when the product is not the plain NT one).  lse = (lse_part [M, parts, 2] f32, row_label [M] i32,
     pick [M, 2] f32): fused log-softmax statistics of the output rows (raises TfasrUnsupported when the fast path cannot); with it
@@ -289,6 +289,9 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, bias=N
     if seg is not None:  # (seg_a_off i64 device tensor, seg_b_off or None, seg_k): K-segmented operands
         a.seg_a_off, a.seg_b_off, a.seg_k = seg[0].data_ptr(), (seg[1].data_ptr() if seg[1] is not None else None), int(seg[2])
         assert seg[0].dtype == torch.int64 and seg[0].is_cuda
+    if row_tiles is not None:  # i32 device tensor: the 256-row blocks of `out` to compute (tfasr_gemm_args.row_tiles; K-segmented products only)
+        assert seg is not None and row_tiles.dtype == torch.int32 and row_tiles.is_cuda and row_tiles.is_contiguous()
+        a.row_tiles, a.n_row_tiles = row_tiles.data_ptr(), row_tiles.numel()
     if bns is not None:
         bx, bfin, bout = bns[:3]
         bc = int(bns[3]) if len(bns) > 3 else N   # channels (the columns are (position, channel) pairs when < N)
@@ -1020,6 +1023,16 @@ def halo_zero(x, B, T2, F2, W):
 
 def s2d_edge_zero(x, B, T1, F1, C):
     check(_L().tfasr_s2d_edge_zero(_p(x), B, T1, F1, C, _dt(x), _stream()), "s2d_edge_zero")
+
+
+def s2d_tail_fill(x, tiles, rep_tt, B, T2, F2, C):
+    """rows of the listed 256-row blocks of the [B, T2+1, F2+1, C] tensor x <- their utterance's representative time row (tfasr_s2d_tail_fill);
+    raises TfasrUnsupported outside bf16 / C % 8 == 0."""
+    assert tiles.dtype == torch.int32 and rep_tt.dtype == torch.int32 and tiles.is_cuda and rep_tt.is_cuda and rep_tt.numel() == B
+    st = _L().tfasr_s2d_tail_fill(_p(x), _p(tiles), tiles.numel(), _p(rep_tt), B, T2, F2, C, _dt(x), _stream())
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported("s2d_tail_fill: bf16 tensors with C % 8 == 0 only")
+    check(st, "s2d_tail_fill")
     return x
 
 
