@@ -32,6 +32,7 @@
  *       TFASR_ATTN_UNFUSED=1     unfused attention (score matrices in HBM; what f32 models always take)
  *       TFASR_CONV2_IM2COL=1     im2col route of the subsampling's second convolution
  *       TFASR_SUB_TAIL=0         conv2 forward over every row tile instead of the tiles with real rows + tfasr_s2d_tail_fill
+ *       TFASR_SUB_TAIL_BWD=0     subsampling backward over every row instead of the folded padded tail (tfasr_s2d_tail_fold + k_tiles / row_tiles / row list)
  *       TFASR_NO_PRED_STREAM=1, TFASR_PRED_SLICES=<n>   prediction network in line / in n slices between the encoder blocks
  *       TFASR_WGRAD_STREAM=0|1, TFASR_BLOCK_HOIST=0|1, TFASR_DEFER_SIDE=0, TFASR_FRONT_EARLY=0   stream placement of the weight gradients,
  *                                the hoisted per-block launches, the deferred small gradients, the front end (DESIGN.md section 2 "Streams")
@@ -221,6 +222,14 @@ typedef struct {
      other rows of D are left untouched.  One launch; a block that is not listed costs nothing.  (Conv2dSubsampling over a padded
      batch: the blocks that hold only padding rows are filled by tfasr_s2d_tail_fill instead.) */
   const int32_t* row_tiles; int n_row_tiles;
+  /* Optional K-block table (added under ABI 44, zero = off; bf16 weight gradients only: trans_a == 1, trans_b == 0, accumulate, no batch, no workspace, no
+     K-segments, single and grouped launch; anything else: UNSUPPORTED and nothing is launched): a DEVICE array of n_k_tiles
+     ASCENDING indices of 256-row blocks of K, 0 <= index < ceil(K / 256).  Only the listed blocks are summed, into D and into colsum;
+     the rows of A and B in the other blocks are not read.  The k-slices of the split run over the compacted list (choose split_k for
+     K = 256 * n_k_tiles), so slices and atomics fall with the rows; the last block of K may be partial.  Within a grouped launch either
+     every product carries a table or none does.  (Conv2dSubsampling's weight gradient over a padded batch whose gradient was folded by
+     tfasr_s2d_tail_fold: the blocks that hold nothing but zero gradient rows are left out.) */
+  const int32_t* k_tiles; int n_k_tiles;
 } tfasr_gemm_args;
 
 int tfasr_gemm(const tfasr_gemm_args* args, void* stream);
@@ -644,6 +653,10 @@ int tfasr_conv1_gram(const void* x, double* gram, int B, int T0, int F0, int dty
 int tfasr_conv1_stats_from_gram(const double* gram, const float* w, const float* bias, float* stats, int C, void* stream);
 int tfasr_conv1_bn_bwd_onepass_s2d(const void* x, const float* w, const float* bias, const float* fin, const void* dy, float* bstats,
                                    float* pbuf, int B, int T0, int F0, int C, int dtype, void* stream);
+/* ... over a row list (declaration added under ABI 44; NULL = every row, the call above): DEVICE array of n_rows output rows b * T1 + t of conv1, the only rows
+   whose gradient is read and summed (the others count as zero gradient; entries are clamped to the tensor). */
+int tfasr_conv1_bn_bwd_onepass_s2d_rows(const void* x, const float* w, const float* bias, const float* fin, const void* dy, float* bstats,
+                                        float* pbuf, int B, int T0, int F0, int C, int dtype, const int32_t* row_list, int n_rows, void* stream);
 int tfasr_conv1_bn_bwd_finalize(const double* gram, const float* w, const float* bias, const float* fin, const float* bstats, float count,
                                 const float* pbuf, float* dw, float* db, int C, void* stream);
 int tfasr_halo_zero(void* x, int B, int T2, int F2, int W, int dtype, void* stream);
@@ -656,6 +669,16 @@ int tfasr_s2d_edge_zero(void* x, int B, int T1, int F1, int C, int dtype, void* 
    UNSUPPORTED: f32, C % 8 != 0, unaligned x. */
 int tfasr_s2d_tail_fill(void* x, const int32_t* tiles, int n_tiles, const int32_t* rep_tt, int B, int T2, int F2, int C, int dtype,
                         void* stream);
+/* Padded tail of the GRADIENT w.r.t. conv2's output, x [B, T2+1, F2+1, C] (bf16, C % 8 == 0, 16-byte aligned; declaration added under ABI 44), in place: what
+   consumes it (conv2's weight / bias / data gradient, conv1 + BatchNorm0's one-pass backward) is linear in it with coefficients that do
+   not depend on the time row behind r = r_tt[b] (DEVICE array [B]: the first constant time row of conv2's output, 1-based), so rows
+   r .. T2 are replaced by their f32 sum over time, split into three bf16 terms: row r = bf16(sum), row r + 1 = bf16(sum - row r),
+   row r + 2 = bf16(the rest); time rows
+   r + 3 .. that a 256-row block holding a row <= r + 2 of this utterance or a row of the next one can reach (its own rows and F2 + 2 rows
+   either side) become zero, the others keep stale values.  Rows < r are untouched; an utterance with r < 1 or r + 3 > T2 is left
+   alone.  scratch: f32 [B, F2+1, C], ZEROED by the caller.  Two launches (sums by f32 atomics, then the two rows).
+   UNSUPPORTED: f32, C % 8 != 0, unaligned pointers. */
+int tfasr_s2d_tail_fold(void* x, const int32_t* r_tt, float* scratch, int B, int T2, int F2, int C, int dtype, void* stream);
 int tfasr_im2col_3x3s2(const void* x, void* col, int B, int T1, int F1, int C, int dtype, void* stream);
 int tfasr_col2im_3x3s2(const void* dcol, void* dx, int B, int T1, int F1, int C, int dtype, void* stream);
 

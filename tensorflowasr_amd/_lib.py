@@ -36,6 +36,7 @@ class GemmArgs(Structure):
         ("rgrad_coef", c_void_p),
         ("bns_x", c_void_p), ("bns_fin", c_void_p), ("bns_out", c_void_p), ("bns_copies", c_int), ("bns_c", c_int),
         ("row_tiles", c_void_p), ("n_row_tiles", c_int),
+        ("k_tiles", c_void_p), ("n_k_tiles", c_int),
     ]
 
 

@@ -77,6 +77,8 @@ class ConformerTransducer(BaseModel):
         # conv2 forward over the row tiles that hold real rows only; the padded tail of its output is one representative row per utterance,
         # copied (DESIGN.md section 2 "Padded tail").  False / TFASR_SUB_TAIL=0: every tile is computed
         self._sub_tail_once = os.environ.get("TFASR_SUB_TAIL", "1") != "0"
+        # ... and the subsampling's backward folds the gradient of each utterance's padded tail into three rows
+        self._sub_tail_bwd = os.environ.get("TFASR_SUB_TAIL_BWD", "1") != "0"
         self._front_tail = None
         # SpecAugment draws and dropout masks are per replica (MirroredStrategy draws independent randomness on every
         # replica); the parameter initialisation seed above is shared by all ranks
@@ -275,6 +277,12 @@ class ConformerTransducer(BaseModel):
         has = rep + 1 <= T2
         rep = np.where(has, rep, 1)
         end = np.where(has, rep + 1, T2 + 1)  # real time rows of utterance b: [1, end)
+        real = cls._real_blocks(end, B, T2, F2)
+        return np.flatnonzero(real), np.flatnonzero(~real), rep
+
+    @staticmethod
+    def _real_blocks(end, B, T2, F2):
+        """bool per 256-row block of a [B, T2+1, F2+1, .] tensor: does it hold a row of the time rows [1, end[b]) of some utterance b"""
         nblk = -(-(B * (T2 + 1) * (F2 + 1)) // 256)
         base = np.arange(B, dtype=np.int64) * (T2 + 1)
         lo = (base + 1) * (F2 + 1) // 256
@@ -282,8 +290,22 @@ class ConformerTransducer(BaseModel):
         mark = np.zeros(nblk + 1, np.int64)
         np.add.at(mark, lo, 1)
         np.add.at(mark, hi + 1, -1)
-        real = np.cumsum(mark[:nblk]) > 0
-        return np.flatnonzero(real), np.flatnonzero(~real), rep
+        return np.cumsum(mark[:nblk]) > 0
+
+    @classmethod
+    def _tail_bwd_geometry(cls, tf, B, T0, T2, F2):
+        """Host arrays of the backward over folded tails (tfasr_s2d_tail_fold): (computed 256-row blocks, skipped blocks, r per utterance,
+        conv1 output rows b * T1 + t1 whose gradient is read).  r = first constant time row of o; an utterance is folded when r + 3 <= T2: its
+        gradient rows r .. T2 become three bf16 terms of their sum in rows r, r + 1, r + 2, so its real rows are [1, r + 3) and conv1's rows
+        below 2 (r + 2) (the S rows <= r + 2 their data gradient reaches).  Every row of the other utterances counts as real."""
+        T1 = (T0 + 1) // 2
+        r = cls._tail_rows(tf, T0)["o"]
+        fold = r + 3 <= T2
+        end = np.where(fold, r + 3, T2 + 1)
+        real = cls._real_blocks(end, B, T2, F2)
+        n1 = np.where(fold, np.minimum(T1, 2 * (r + 2)), T1)
+        rows = np.concatenate([b * T1 + np.arange(n1[b], dtype=np.int64) for b in range(B)])
+        return np.flatnonzero(real), np.flatnonzero(~real), np.where(fold, r, T2 + 1), rows
 
     def _tail_tables(self, tf, B, T0, T2, F2):
         """_tail_blocks as device i32 tensors (one pinned upload), or None when fewer than one block in 16 can be skipped (the fill
@@ -295,8 +317,14 @@ class ConformerTransducer(BaseModel):
         comp, skip, rep = self._tail_blocks(tf, B, T0, T2, F2)
         out = None
         if skip.size * 16 >= comp.size + skip.size:
-            dev = self._h2d(np.concatenate([comp, skip, rep]).astype(np.int32))
-            out = (dev[:comp.size], dev[comp.size:comp.size + skip.size], dev[comp.size + skip.size:])
+            # the backward's tables ride in the same upload: (computed blocks, r per utterance, conv1 row list), or None under the same rule
+            parts = [comp, skip, rep]
+            bcomp, bskip, r, rows = self._tail_bwd_geometry(tf, B, T0, T2, F2)
+            if bskip.size * 16 >= bcomp.size + bskip.size:
+                parts += [bcomp, r, rows]
+            dev = self._h2d(np.concatenate(parts).astype(np.int32))
+            out = tuple(torch.split(dev, [p.size for p in parts]))
+            out = out[:3] + (out[3:] if len(out) > 3 else None,)
         old = [k for k in self._consts if isinstance(k, tuple) and k[:1] == ("tail",)]
         for k in old[:max(0, len(old) - 7)]:
             del self._consts[k]
@@ -455,7 +483,7 @@ class ConformerTransducer(BaseModel):
         w0, b0 = ps.p("enc/sub/conv0/w"), ps.p("enc/sub/conv0/b")
         fin0 = torch.empty(4 * C, dtype=torch.float32, device=self.device)
         nm = "enc/sub/bn0"
-        gram = None
+        gram, tail_bwd = None, None
         if training:
             stats = self._zeros_f32(2 * C + 1)[:2 * C + 1]
             if self._conv1_gram:
@@ -489,8 +517,12 @@ class ConformerTransducer(BaseModel):
             # padded tail: only the row tiles with real rows, the rest copied from one representative row per utterance - bitwise what
             # the full product writes there (only for the feature map this model's front end has just produced)
             tail, ft, self._front_tail = None, self._front_tail, None
-            if self._sub_tail_once and ft is not None and ft[0] is feats and ft[1] is not None and len(ft[1]) == B:
+            if (self._sub_tail_once or self._sub_tail_bwd) and ft is not None and ft[0] is feats and ft[1] is not None and len(ft[1]) == B:
                 tail = self._tail_tables(ft[1], B, T0, T2, F2)
+            if tail is not None and training and self._sub_tail_bwd and gram is not None:
+                tail_bwd = tail[3]
+            if not self._sub_tail_once:
+                tail = None
             if tail is not None:
                 try:
                     K.gemm(a1, W, o, rows, C, 9 * C, 4 * C, C, C, bias=ps.p("enc/sub/conv1/b"), seg=fwd_a, row_tiles=tail[0])
@@ -513,7 +545,7 @@ class ConformerTransducer(BaseModel):
         elen = [-(-(-(-n // 2)) // 2) for n in flen]
         if ctx is not None:
             ctx["sub"] = dict(s2d=True, feats=feats, bn0=bn0, a1=a1, a1_full=a1_full, o=o, bn1=bn1, a2=a2,
-                              dims=(B, T0, F0, T1, F1, T2, F2), drop=drop)
+                              dims=(B, T0, F0, T1, F1, T2, F2), drop=drop, tail_bwd=tail_bwd)
         return x0, T2, elen
 
     def _subsampling_bwd_s2d(self, dx0, ctx):
@@ -554,13 +586,23 @@ class ConformerTransducer(BaseModel):
             K.bn_apply_bwd(s["o"], da2, fin1, bst, count1, ACT_SWISH, dx=do, dgamma=ps.g("enc/sub/bn1/g"), dbeta=ps.g("enc/sub/bn1/b"),
                            grad_scale=1.0 / self.dp.world, copies=ncp)
         K.halo_zero(do, B, T2, F2, C)
+        # padded tails: everything below is linear in `do` with coefficients that do not depend on the time row behind an utterance's first
+        # constant row, so each tail's gradient is folded into three rows (its f32 sum as three bf16 terms) and the three consumers run
+        # over the 256-row blocks / conv1 rows that are left.  Support is decided here, before `do` is modified: what the launches check.
+        tb = s.get("tail_bwd") if self._sub_tail_bwd else None
+        if tb is not None and not (self.dtype == torch.bfloat16 and C % 64 == 0 and s["bn0"][2] is not None and do.data_ptr() % 16 == 0):
+            tb = None
+        if tb is not None:
+            K.s2d_tail_fold(do, tb[1], self._zeros_f32(B * (F2 + 1) * C)[:B * (F2 + 1) * C], B, T2, F2, C)
+        kt, nk = (None, rows) if tb is None else (tb[0], 256 * tb[0].numel())
         # conv2 weight gradient: 9 products gW[tap] += a1[rows shifted by the tap]^T @ do; bias gradient = column sums of do
         a1_full, base = s["a1_full"], slack * 4 * C
         gW = ps.g2d("enc/sub/conv1/w")
         calls = []
         for i in range(9):
             calls.append(dict(A=a1_full[base + shift[i] * 4 * C + blk[i] * C:], B=do, out=gW[i * C:(i + 1) * C], M=C, N=C, K=rows, lda=4 * C, ldb=C,
-                              ldd=C, trans_a=True, accumulate=True, split_k=_split_k(C, C, rows), colsum=ps.g("enc/sub/conv1/b") if i == 0 else None))
+                              ldd=C, trans_a=True, accumulate=True, split_k=_split_k(C, C, nk), colsum=ps.g("enc/sub/conv1/b") if i == 0 else None,
+                              k_tiles=kt))
         K.gemm_group(calls)
         # conv2 data gradient, one product per parity block of the S layout: da1[:, block] = sum over its taps of do[rows shifted back] @ W[tap]^T
         W = ps.w2d("enc/sub/conv1/w")
@@ -573,14 +615,15 @@ class ConformerTransducer(BaseModel):
                 for j, i in enumerate(segs):
                     K.gemm(do_full[dobase - shift[i] * C:], W[i * C:(i + 1) * C], out, rows, C, C, C, C, 4 * C, trans_b=True, accumulate=j > 0)
             else:
-                K.gemm(do, W, out, rows, C, len(segs) * C, C, C, 4 * C, trans_b=True, seg=(a_off, b_off, C // (a_off.numel() // len(segs))))
+                K.gemm(do, W, out, rows, C, len(segs) * C, C, C, 4 * C, trans_b=True, seg=(a_off, b_off, C // (a_off.numel() // len(segs))),
+                       row_tiles=None if tb is None else tb[0])
         # BatchNorm0 + conv1 backward from the feature map (only the valid slots of da1 are read: its halos need no clearing)
         fin0, count0, gram = s["bn0"]
         w0, b0 = ps.p("enc/sub/conv0/w"), ps.p("enc/sub/conv0/b")
         if gram is not None:
             zz = self._zeros_f32(12 * C)
             bstats, pbuf = zz[:2 * C], zz[2 * C:12 * C]
-            K.conv1_bn_bwd_onepass_s2d(s["feats"], w0, b0, fin0, da1, bstats, pbuf)
+            K.conv1_bn_bwd_onepass_s2d(s["feats"], w0, b0, fin0, da1, bstats, pbuf, row_list=None if tb is None else tb[2])
             self.dp.allreduce_stats_(bstats)
             K.conv1_bn_bwd_finalize(gram, w0, b0, fin0, bstats, count0, pbuf, ps.g("enc/sub/conv0/w"), ps.g("enc/sub/conv0/b"))
         else:

@@ -306,7 +306,8 @@ template <typename T, int MODE, int CPT>
 __global__ __launch_bounds__(256) void conv1_bn_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                        const float* __restrict__ fin, const float* __restrict__ bstats, float inv_count,
                                                        T* __restrict__ y, const T* __restrict__ dy, float* __restrict__ out0,
-                                                       float* __restrict__ out1, int B, int T0, int F0, int T1, int F1, int C) {
+                                                       float* __restrict__ out1, int B, int T0, int F0, int T1, int F1, int C,
+                                                       const int32_t* __restrict__ row_list, int n_list) {
   extern __shared__ float sm[];
   float* xs = sm;                       // [3][F0 + 2] input rows of the current output row (zero padded)
   float* red = sm + 3 * (F0 + 2);       // [NQ][C] block reduction
@@ -345,8 +346,12 @@ __global__ __launch_bounds__(256) void conv1_bn_kernel(const T* __restrict__ x, 
   for (int q = 0; q < NQ; ++q)
 #pragma unroll
     for (int k = 0; k < CP2; ++k) acc2[q][k] = c1f2_t{0.f, 0.f};
-  const int nrows = B * T1;
-  for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
+  // MODE 4 with a row list: only the listed output rows b * T1 + t (a padded batch whose incoming gradient was folded onto a few rows per
+  // utterance, tfasr_s2d_tail_fold: the other rows' gradient is zero by construction and is not read at all)
+  const bool listed = MODE == 4 && row_list != nullptr;
+  const int nrows = listed ? n_list : B * T1;
+  for (int it = blockIdx.x; it < nrows; it += gridDim.x) {
+    const int row = listed ? min(max(row_list[it], 0), B * T1 - 1) : it;
     const int b = row / T1, t = row - b * T1;
     __syncthreads();
     for (int i = threadIdx.x; i < 3 * (F0 + 2); i += 256) {  // xs[kh][fi + 2] = x[b, 2t+kh-2, fi], zero outside
@@ -645,6 +650,65 @@ __global__ __launch_bounds__(256) void s2d_tail_fill_kernel(uint4* __restrict__ 
   }
 }
 
+
+// Padded tail of a GRADIENT [B, T2+1, F2+1, C] bf16 (the gradient w.r.t. conv2's output): behind time row r = r_tt[b] everything that
+// consumes it multiplies it by values that do not depend on the time row, so only the SUM over the tail counts.
+// The sum (f32) goes into rows r, r + 1, r + 2 as three bf16 terms (its rounding, the rounded remainder, and the remainder of that: 24 bits;
+// two terms left 2^-18 of a sum of like-signed gradients, 30 x the f32 summation error of the full route); the rows behind them that a
+// computed 256-row block of a consumer can reach - `zr` time rows behind r + 2 and the last `zr` of the utterance, which share blocks with
+// the next utterance's first rows - become zero.  Utterances with r_tt[b] + 3 > T2 (or < 1) are left alone.
+// s2d_tail_sum: one workgroup per (chunk of FOLD_TT time rows, utterance), a lane per 8 channels of a (ff, c) slot; f32 atomics into
+// scratch [B, F2+1, C] (zeroed by the caller).  s2d_tail_put: scratch -> the hi / lo rows.
+constexpr int FOLD_TT = 32;
+__global__ __launch_bounds__(256) void s2d_tail_sum_kernel(bf16_t* __restrict__ x, const int32_t* __restrict__ r_tt, float* __restrict__ scratch,
+                                                           int T2, int F2, int C, int zr) {
+  const int b = blockIdx.y, r = r_tt[b];
+  if (r < 1 || r + 3 > T2) return;
+  const int t0 = max(r, 1 + (int)blockIdx.x * FOLD_TT), t1 = min(T2 + 1, 1 + ((int)blockIdx.x + 1) * FOLD_TT);
+  if (t0 >= t1) return;
+  const int per_t = (F2 + 1) * C;
+  const float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = threadIdx.x * 8; i < per_t; i += 256 * 8) {
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int tt = t0; tt < t1; ++tt) {
+      bf16_t* p = x + ((long)b * (T2 + 1) + tt) * per_t + i;
+      float v[8];
+      ld8(p, v);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] += v[k];
+      if (tt >= r + 3 && (tt < r + 3 + zr || tt > T2 - zr)) st8(p, z);
+    }
+    float* s = scratch + (long)b * per_t + i;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) atomicAdd(s + k, acc[k]);
+  }
+}
+__global__ __launch_bounds__(256) void s2d_tail_put_kernel(bf16_t* __restrict__ x, const int32_t* __restrict__ r_tt, const float* __restrict__ scratch,
+                                                           int B, int T2, int F2, int C) {
+  const int per_t = (F2 + 1) * C;
+  const long n = (long)B * per_t / 8;
+  for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(j * 8 / per_t), i = (int)(j * 8 - (long)b * per_t);
+    const int r = r_tt[b];
+    if (r < 1 || r + 3 > T2) continue;
+    float s[8], hi[8], mid[8];
+    ld8(scratch + (long)b * per_t + i, s);
+    bf16_t* p = x + ((long)b * (T2 + 1) + r) * per_t + i;
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) {  // (the subtractions are exact: a bf16 rounding keeps the leading bits of an f32)
+      const uint32_t h = pack2_bf16(s[k], s[k + 1]);
+      hi[k] = __uint_as_float(h << 16); hi[k + 1] = __uint_as_float(h & 0xffff0000u);
+      s[k] -= hi[k]; s[k + 1] -= hi[k + 1];
+      const uint32_t m = pack2_bf16(s[k], s[k + 1]);
+      mid[k] = __uint_as_float(m << 16); mid[k + 1] = __uint_as_float(m & 0xffff0000u);
+      s[k] -= mid[k]; s[k + 1] -= mid[k + 1];
+    }
+    st8(p, hi);
+    st8(p + per_t, mid);
+    st8(p + 2 * per_t, s);
+  }
+}
+
 }  // namespace
 
 #define DISPATCH_T(dtype, CALL_F32, CALL_BF16) \
@@ -717,8 +781,10 @@ extern "C" int tfasr_conv1_bwd_weight_s2d(const void* x, const void* dy, float* 
 
 template <int MODE>
 static int conv1_bn_launch(const void* x, const float* w, const float* bias, const float* fin, const float* bstats, float count, void* y,
-                           const void* dy, float* out0, float* out1, int B, int T0, int F0, int C, int dtype, void* stream_) {
+                           const void* dy, float* out0, float* out1, int B, int T0, int F0, int C, int dtype, void* stream_,
+                           const int32_t* row_list = nullptr, int n_list = 0) {
   if (!x || !w || B <= 0 || T0 <= 0 || F0 <= 0 || C <= 0 || C > 256 || (C % 8)) return TFASR_STATUS_INVALID_VALUE;
+  if (row_list && (MODE != 4 || n_list <= 0 || n_list > (long)B * ((T0 + 1) / 2))) return TFASR_STATUS_INVALID_VALUE;
   constexpr int CPT = MODE >= 2 ? 4 : 8;
   constexpr int NQL = MODE == 3 ? 10 : (MODE == 4 ? 11 : 2);
   const int T1 = (T0 + 1) / 2, F1 = (F0 + 1) / 2;
@@ -740,14 +806,14 @@ static int conv1_bn_launch(const void* x, const float* w, const float* bias, con
     res_blocks[di] = (e == hipSuccess && per > 0 && cus > 0) ? per * cus : 768;
     res_smem[di] = smem_q;
   }
-  const int grid = std::min(B * T1, MODE == 1 ? 8192 : std::max(64, env_grid ? env_grid : res_blocks[di]));
+  const int grid = std::min(row_list ? n_list : B * T1, MODE == 1 ? 8192 : std::max(64, env_grid ? env_grid : res_blocks[di]));
   const size_t smem = (size_t)(3 * (F0 + 2) + NQL * C) * sizeof(float);
   const float inv = count > 0.f ? 1.f / count : 0.f;
   DISPATCH_T(dtype,
              TFASR_KLAUNCH((conv1_bn_kernel<float, MODE, CPT>), dim3(grid), dim3(256), smem, s, (const float*)x, w, bias, fin, bstats, inv, (float*)y,
-                                (const float*)dy, out0, out1, B, T0, F0, T1, F1, C),
+                                (const float*)dy, out0, out1, B, T0, F0, T1, F1, C, row_list, n_list),
              TFASR_KLAUNCH((conv1_bn_kernel<bf16_t, MODE, CPT>), dim3(grid), dim3(256), smem, s, (const bf16_t*)x, w, bias, fin, bstats, inv, (bf16_t*)y,
-                                (const bf16_t*)dy, out0, out1, B, T0, F0, T1, F1, C));
+                                (const bf16_t*)dy, out0, out1, B, T0, F0, T1, F1, C, row_list, n_list));
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
@@ -792,10 +858,15 @@ extern "C" int tfasr_conv1_stats_from_gram(const double* gram, const float* w, c
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
+extern "C" int tfasr_conv1_bn_bwd_onepass_s2d_rows(const void* x, const float* w, const float* bias, const float* fin, const void* dy, float* bstats,
+                                                   float* pbuf, int B, int T0, int F0, int C, int dtype, const int32_t* row_list, int n_rows,
+                                                   void* stream_) {
+  if (!fin || !dy || !bstats || !pbuf) return TFASR_STATUS_INVALID_VALUE;
+  return conv1_bn_launch<4>(x, w, bias, fin, nullptr, 0.f, nullptr, dy, bstats, pbuf, B, T0, F0, C, dtype, stream_, row_list, row_list ? n_rows : 0);
+}
 extern "C" int tfasr_conv1_bn_bwd_onepass_s2d(const void* x, const float* w, const float* bias, const float* fin, const void* dy, float* bstats,
                                               float* pbuf, int B, int T0, int F0, int C, int dtype, void* stream_) {
-  if (!fin || !dy || !bstats || !pbuf) return TFASR_STATUS_INVALID_VALUE;
-  return conv1_bn_launch<4>(x, w, bias, fin, nullptr, 0.f, nullptr, dy, bstats, pbuf, B, T0, F0, C, dtype, stream_);
+  return tfasr_conv1_bn_bwd_onepass_s2d_rows(x, w, bias, fin, dy, bstats, pbuf, B, T0, F0, C, dtype, nullptr, 0, stream_);
 }
 extern "C" int tfasr_conv1_bn_bwd_finalize(const double* gram, const float* w, const float* bias, const float* fin, const float* bstats,
                                            float count, const float* pbuf, float* dw, float* db, int C, void* stream_) {
@@ -836,6 +907,20 @@ extern "C" int tfasr_s2d_tail_fill(void* x, const int32_t* tiles, int n_tiles, c
   if (dtype != TFASR_BF16 || C % 8 || (((uintptr_t)x) & 15)) return TFASR_STATUS_UNSUPPORTED;
   if (n_tiles == 0) return TFASR_STATUS_SUCCESS;
   TFASR_KLAUNCH(s2d_tail_fill_kernel, dim3(4 * n_tiles), dim3(256), 0, (hipStream_t)stream_, (uint4*)x, tiles, rep_tt, T2, F2, C / 8, rows);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_s2d_tail_fold(void* x, const int32_t* r_tt, float* scratch, int B, int T2, int F2, int C, int dtype, void* stream_) {
+  if (!x || !r_tt || !scratch || B <= 0 || T2 <= 0 || F2 <= 0 || C <= 0) return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_BF16 || C % 8 || (((uintptr_t)x) & 15) || (((uintptr_t)scratch) & 15) || B > 65535) return TFASR_STATUS_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream_;
+  // rows a computed 256-row block can reach behind the last folded row / in front of the next utterance: 255 rows of the block + the
+  // F2 + 2 rows of the shifted reads, in time rows of F2 + 1, rounded up, + 1 for the row the block starts in
+  const int zr = (255 + F2 + 2 + F2) / (F2 + 1) + 1;
+  TFASR_KLAUNCH(s2d_tail_sum_kernel, dim3((T2 + FOLD_TT - 1) / FOLD_TT, B), dim3(256), 0, s, (bf16_t*)x, r_tt, scratch, T2, F2, C, zr);
+  TFASR_CHECK_LAUNCH();
+  TFASR_KLAUNCH(s2d_tail_put_kernel, dim3(flat_grid((long)B * (F2 + 1) * C / 8)), dim3(256), 0, s, (bf16_t*)x, r_tt, scratch, B, T2, F2, C);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }

@@ -442,11 +442,16 @@ extern "C" int tfasr_gemm(const tfasr_gemm_args* args, void* stream_) {
     if (a.n_row_tiles <= 0 || a.n_row_tiles > (a.M + 255) / 256) return TFASR_STATUS_INVALID_VALUE;
     if (!a.seg_a_off || a.trans_a || a.accumulate || a.split_k > 1 || a.nb1 * a.nb2 != 1 || a.dtype != TFASR_BF16) return TFASR_STATUS_UNSUPPORTED;
   }
+  if (a.k_tiles) {  // K-block table: the bf16 transposed-A weight gradient only, every entry count the K range can hold
+    if (a.n_k_tiles <= 0 || a.n_k_tiles > (a.K + 255) / 256) return TFASR_STATUS_INVALID_VALUE;
+    if (!a.trans_a || a.trans_b || !a.accumulate || a.nb1 * a.nb2 != 1 || a.dtype != TFASR_BF16 || a.seg_a_off || a.row_tiles || a.ws) return TFASR_STATUS_UNSUPPORTED;
+  }
   hipStream_t stream = (hipStream_t)stream_;
   if (a.dtype == TFASR_BF16 && use_fast_path()) {
     const int st = tfasr_gemm_fast_try(a, stream);
     if (st != TFASR_STATUS_UNSUPPORTED) return st;
   }
+  if (a.k_tiles) return TFASR_STATUS_UNSUPPORTED;  // only the bf16 fast path reads the table
   if (a.lse_part || a.rgrad_coef || a.bns_out) return TFASR_STATUS_UNSUPPORTED;  // only the bf16 fast path's epilogues produce the row statistics / the loss gradient / the BatchNorm sums
   if (a.seg_a_off) return TFASR_STATUS_UNSUPPORTED;  // K-segments: bf16 fast path only (the f32 host path issues one product per segment)
   if (a.colsum) {  // the generic kernels do not fuse the bias gradient: one extra pass over B = dy

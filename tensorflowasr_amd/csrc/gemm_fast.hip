@@ -283,7 +283,10 @@ enum : int { E_ACT = 1 /* swish(+prez) */, E_DACT = 2 /* * swish'(dact_z) */, E_
 // ONE: every workgroup owns exactly ONE tile (the grid is the tile list): no cross-tile prefetch, so the epilogue strips may lie OVER the
 // (then dead) stage buffers - 48 KiB of LDS for the 64-column variant = 39 granules = THREE workgroups per CU (with its own strips it is
 // 46 granules = two; 596 tiles on 512 persistent slots also ran as two rounds).
-template <bool TA, bool TB, int BN_, int EPI, int NST = 2, bool FIXED = false, bool SEG = false, bool ONE = false>
+// KT: K-block table (tfasr_gemm_args.k_tiles; transposed-A weight gradients): the k loop runs over the COMPACTED list of 256-row blocks -
+// slab c of the compacted range reads rows k_tiles[c / 4] * 256 + (c % 4) * 64, one uniform table lookup per slab, requested in front of
+// the wait for the slab in flight.  Its own instantiations: the kernels without a table are compiled exactly as before.
+template <bool TA, bool TB, int BN_, int EPI, int NST = 2, bool FIXED = false, bool SEG = false, bool ONE = false, bool KT = false>
 __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const int gx, const int gy, const int gz, const int ntiles, const int bid, const int G) {
   constexpr bool GEN = (EPI & E_GEN) != 0;
   constexpr bool C_ACT = GEN || (EPI & E_ACT), C_DACT = GEN || (EPI & E_DACT), C_DROP = GEN || (EPI & E_DROP), C_RES = GEN || (EPI & E_RES);
@@ -300,8 +303,20 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = w >> 1, wn = w & 1;
   const int r = lane & 15, g = lane >> 4;
-  int kchunk = (p.K + split - 1) / split;
+  // KT: K of the compacted list (only its last entry can be the partial last block of the operands)
+  int Keff = p.K;
+  if constexpr (KT) {
+    const int nkt = p.n_k_tiles, last = min(max(p.k_tiles[nkt - 1], 0), (p.K - 1) / 256);
+    Keff = (nkt - 1) * 256 + min(256, p.K - last * 256);
+  }
+  int kchunk = (Keff + split - 1) / split;
   kchunk = ((kchunk + BK - 1) / BK) * BK;
+  // first physical row of compacted slab c (KT)
+  auto kt_row = [&](int c) -> long {
+    const int blk = min(max(p.k_tiles[min(c >> 2, p.n_k_tiles - 1)], 0), (p.K - 1) / 256);
+    return (long)blk * 256 + (c & 3) * BK;
+  };
+  long kt_dA = 0, kt_dB = 0;  // KT: operand offsets of the slab about to be issued (set by kt_set)
 
   __shared__ long seg_tab[SEG ? 2 : 1][SEG ? 64 : 1];  // per-slab element offsets of op(A) / op(B) (K-segment mode)
   if constexpr (SEG) {
@@ -366,13 +381,21 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
     T.n0 = tx * BN;
     T.ks = ks;
     T.k_begin = ks * kchunk;
-    T.k_end = min(p.K, T.k_begin + kchunk);
+    T.k_end = min(Keff, T.k_begin + kchunk);
     const int len = max(T.k_end - T.k_begin, 0);
     T.nfull = len / BK;
     T.tail = (len % BK) != 0;
-    if (TA) prep_trans<128>(T.sa, T.A, p.lda, T.m0, p.M, T.k_begin, w, lane); else prep_direct<128>(T.sa, T.A, p.lda, T.m0, p.M, T.k_begin, w, lane);
-    if (TB) prep_direct<BN_>(T.sb, T.B, p.ldb, T.n0, p.N, T.k_begin, w, lane); else prep_trans<BN_>(T.sb, T.B, p.ldb, T.n0, p.N, T.k_begin, w, lane);
+    const int kp = KT ? 0 : T.k_begin;  // KT: slab offsets are absolute rows (kt_set)
+    if (TA) prep_trans<128>(T.sa, T.A, p.lda, T.m0, p.M, kp, w, lane); else prep_direct<128>(T.sa, T.A, p.lda, T.m0, p.M, kp, w, lane);
+    if (TB) prep_direct<BN_>(T.sb, T.B, p.ldb, T.n0, p.N, kp, w, lane); else prep_trans<BN_>(T.sb, T.B, p.ldb, T.n0, p.N, kp, w, lane);
     return T;
+  };
+  static_assert(!KT || (TA && !TB && !SEG), "K-block table: transposed-A weight gradients only");
+  auto kt_set = [&](const Tile& T, int slab) {
+    if constexpr (KT) {
+      const long row = kt_row(T.k_begin / BK + slab);
+      kt_dA = row * p.lda; kt_dB = row * p.ldb;
+    }
   };
   const long stepA = TA ? (long)BK * p.lda : (long)BK, stepB = TB ? (long)BK : (long)BK * p.ldb;  // elements per slab
   auto issue = [&](const Tile& T, int slab, int stage) {
@@ -381,6 +404,9 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
     if constexpr (SEG) {
       issue_from<128>(sA, T.sa, seg_tab[0][slab], w);
       issue_from<BN_>(sB, T.sb, seg_tab[1][slab], w);
+    } else if constexpr (KT) {
+      issue_from<128>(sA, T.sa, kt_dA, w);
+      issue_from<BN_>(sB, T.sb, kt_dB, w);
     } else {
       issue_from<128>(sA, T.sa, slab * stepA, w);
       issue_from<BN_>(sB, T.sb, slab * stepB, w);
@@ -393,14 +419,15 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
     char* sB = sA + A_BYTES;
     long dA_, dB_;
     if constexpr (SEG) { dA_ = seg_tab[0][slab]; dB_ = seg_tab[1][slab]; }
+    else if constexpr (KT) { dA_ = kt_dA; dB_ = kt_dB; }
     else { dA_ = slab * stepA; dB_ = slab * stepB; }
     if (q < 4) glds16(T.sa[q] + dA_, sA + __builtin_amdgcn_readfirstlane((w * 4 + q) * 1024));
     else glds16(T.sb[q - 4] + dB_, sB + __builtin_amdgcn_readfirstlane((w * (BN_ / 32) + (q - 4)) * 1024));
   };
   Tile cur = tile_of(0);
   if (cur.nfull < 0) return;
-  if (cur.nfull > 0) issue(cur, 0, 0);
-  if (cur.nfull > 1) issue(cur, 1, 1);
+  if (cur.nfull > 0) { kt_set(cur, 0); issue(cur, 0, 0); }
+  if (cur.nfull > 1) { kt_set(cur, 1); issue(cur, 1, 1); }
   bool drained = false;  // true after a tile boundary: slabs 0 and 1 of `cur` have landed
 
   for (int it = 0;; ++it) {
@@ -460,6 +487,7 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
     if constexpr (NST == 3) {
       for (int s = 0; s < n; ++s) {
         const int stage = s % 3;
+        if (s + 2 < n) kt_set(cur, s + 2);
         if (!(drained && s < 2)) {
           if (s + 1 < n) { if (GI == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
           else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -476,6 +504,7 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
   #ifdef TFASR_GEMM_TIMING
         long long tp = __builtin_readcyclecounter();
   #endif
+        if (s + 2 < n) kt_set(cur, s + 2);
         if (!(drained && s < 2)) {
           // this wave's DMA pieces of slab s have landed; slab s+1 (when it exists) stays in flight
           if (s + 1 < n) { if (GI == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
@@ -513,9 +542,11 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
     if (cur.tail) {
       char* sA = smem;
       char* sB = smem + A_BYTES;
-      const int kt = cur.k_begin + n * BK;
-      if (TA) tail_trans<128>(sA, cur.A, p.lda, cur.m0, p.M, kt, cur.k_end); else tail_direct<128>(sA, cur.A, p.lda, cur.m0, p.M, kt, cur.k_end);
-      if (TB) tail_direct<BN_>(sB, cur.B, p.ldb, cur.n0, p.N, kt, cur.k_end); else tail_trans<BN_>(sB, cur.B, p.ldb, cur.n0, p.N, kt, cur.k_end);
+      // KT: a partial slab exists only at the end of the operands' partial last block, so its rows end at K
+      const int kt = KT ? (int)kt_row(cur.k_begin / BK + n) : cur.k_begin + n * BK;
+      const int ke = KT ? p.K : cur.k_end;
+      if (TA) tail_trans<128>(sA, cur.A, p.lda, cur.m0, p.M, kt, ke); else tail_direct<128>(sA, cur.A, p.lda, cur.m0, p.M, kt, ke);
+      if (TB) tail_direct<BN_>(sB, cur.B, p.ldb, cur.n0, p.N, kt, ke); else tail_trans<BN_>(sB, cur.B, p.ldb, cur.n0, p.N, kt, ke);
       __syncthreads();
       mma_slab<TA, TB, BN_, C_CS>(sA, sB, wm, wn, lane, acc, accb, do_cs);
       __syncthreads();
@@ -526,8 +557,8 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
     if constexpr (ONE) nxt.nfull = -1;
     else {
       nxt = tile_of(it + 1);
-      if (nxt.nfull > 0) issue(nxt, 0, 0);
-      if (nxt.nfull > 1) issue(nxt, 1, 1);
+      if (nxt.nfull > 0) { kt_set(nxt, 0); issue(nxt, 0, 0); }
+      if (nxt.nfull > 1) { kt_set(nxt, 1); issue(nxt, 1, 1); }
     }
 #ifdef TFASR_GEMM_TIMING
     const long long t_main = __builtin_readcyclecounter();
@@ -851,6 +882,12 @@ __global__ __launch_bounds__(256, 2) void gemm_seg_kernel(const tfasr_gemm_args 
   gemm_fast_body<TA, TB, 128, 0, 2, false, true>(p, gx, gy, gz, ntiles, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// transposed-A weight gradient over a K-block table (tfasr_gemm_args.k_tiles): the persistent 128 x 128 kernel with the column-sum row
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void gemm_ktab_kernel(const tfasr_gemm_args p, const int gx, const int gy, const int gz, const int ntiles) {
+  gemm_fast_body<true, false, 128, EPI, 2, false, false, false, true>(p, gx, gy, gz, ntiles, (int)blockIdx.x, (int)gridDim.x);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Grouped weight gradients: the ~9 Dense-layer gradients  gW += x^T dy  of one Conformer block (K = B*T rows, a few 128x64 output
 // tiles each) in ONE launch.  Launched one by one each of them has to split K 8-16 ways to occupy the chip - and pays
@@ -871,7 +908,7 @@ struct GroupArgs {
 // panel march through k together, so the panel comes out of HBM once and its re-reads hit that XCD's L2.  (With the tiles of a
 // product dealt over all XCDs the panels were re-fetched per XCD: 1.5 GB of fabric traffic per block for 0.32 GB of operands,
 // and the launch ran at the fabric's rate, 156 us; 3 LDS stages instead of 2 changed nothing.)
-template <int EPI, int NST, int BN_>
+template <int EPI, int NST, int BN_, bool KT = false>
 __global__ __launch_bounds__(256, 2) void wgrad_group_kernel(const GroupArgs ga) {
   const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int nu = ga.nunit[x];
@@ -882,7 +919,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_group_kernel(const GroupArgs ga)
   if (u < 0) return;
   const int q = ga.uq[x][u], ks = ga.uks[x][u], t = j - ga.j0[x][u];
   const tfasr_gemm_args* pp = ga.p + q;
-  gemm_fast_body<true, false, BN_, EPI, NST, true>(*pp, ga.gx[q], ga.gy[q], 1, ga.gx[q] * ga.gy[q], t, ks);
+  gemm_fast_body<true, false, BN_, EPI, NST, true, false, false, KT>(*pp, ga.gx[q], ga.gy[q], 1, ga.gx[q] * ga.gy[q], t, ks);
 }
 
 // second pass of the workspace split-K: D[m, n] += sum_s ws[s][m][n]
@@ -913,6 +950,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 
 int num_cus();
+// what a product with a K-block table must be (tfasr_gemm_args.k_tiles); the entry count is checked by the callers
+inline bool ktab_eligible(const tfasr_gemm_args& a) {
+  return a.dtype == TFASR_BF16 && a.trans_a && !a.trans_b && a.accumulate && a.nb1 * a.nb2 <= 1 && !a.ws && !a.seg_a_off && !a.row_tiles && !a.lse_part &&
+         !a.rgrad_coef && !a.bns_out && a.n_k_tiles > 0 && a.n_k_tiles <= (a.K + 255) / 256;
+}
 
 int num_cus() {
   static int n = 0;
@@ -956,6 +998,23 @@ int launch_epi(const tfasr_gemm_args& a, dim3 tiles, hipStream_t stream) {
 template <bool TA, bool TB>
 int launch_one(const tfasr_gemm_args& a, hipStream_t stream) {
   const int split = a.split_k > 1 ? a.split_k : 1;
+  if (a.k_tiles) {  // K-block table: the accumulating x^T dy product on 128-wide tiles, or nothing at all
+    if constexpr (TA && !TB) {
+      if (ktab_eligible(a) && a.out_f32) {
+        dim3 grid((a.N + 127) / 128, (a.M + BM - 1) / BM, split);
+        if ((long)grid.x * grid.y * grid.z > 0x7fffffffL) return TFASR_STATUS_INVALID_VALUE;
+        const long ntiles = (long)grid.x * grid.y * grid.z;
+        const int slots = 2 * num_cus();
+        int G = (int)(ntiles < slots ? ntiles : slots);
+        if (ntiles >= slots) G &= ~7;
+        constexpr int SMEM = 2 * (A_BYTES + 128 * BK * 2) + 4 * (64 / (128 / 16)) * (128 / 2 + 4) * 4;
+        TFASR_KLAUNCH((gemm_ktab_kernel<E_CSUM>), dim3(G), dim3(256), SMEM, stream, a, (int)grid.x, (int)grid.y, (int)grid.z, (int)ntiles);
+        TFASR_CHECK_LAUNCH();
+        return TFASR_STATUS_SUCCESS;
+      }
+    }
+    return TFASR_STATUS_UNSUPPORTED;
+  }
   // 128x64 tiles: per-head attention products (N = head size: halves the wasted B tile) and every product whose 128x128 tiling
   // would leave at most one workgroup per CU (the N = 256 Dense layers of a Conformer block: 190 tiles): with a single resident
   // workgroup the DMA issue, the fragment reads and the MFMAs of a slab serialise (1530 cycles / slab measured); two 128x64
@@ -1087,7 +1146,7 @@ inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 bool group_eligible(const tfasr_gemm_args& a) {
   return a.dtype == TFASR_BF16 && a.trans_a && !a.trans_b && a.accumulate && a.out_f32 && a.nb1 * a.nb2 <= 1 && !a.ws && !a.bias && !a.res &&
          !a.dact_z && !a.prez && a.act == TFASR_ACT_NONE && a.drop_p == 0.f && al16(a.A) && al16(a.B) && !(a.lda & 7) && !(a.ldb & 7) &&
-         ((a.M + 7) & ~7) <= a.lda && ((a.N + 7) & ~7) <= a.ldb && a.K >= 8 && a.N > 64 && a.M > 0;
+         ((a.M + 7) & ~7) <= a.lda && ((a.N + 7) & ~7) <= a.ldb && a.K >= 8 && a.N > 64 && a.M > 0 && (!a.k_tiles || ktab_eligible(a));
 }
 
 }  // namespace
@@ -1100,7 +1159,10 @@ int g_tfasr_group_beside = 0;
 int tfasr_gemm_group_fast_try(const tfasr_gemm_args* a, int n, hipStream_t stream) {
   if (n < 2 || n > GROUP_MAX) return TFASR_STATUS_UNSUPPORTED;
   for (int i = 0; i < n; ++i)
-    if (!group_eligible(a[i])) return TFASR_STATUS_UNSUPPORTED;
+    if (!group_eligible(a[i]) || (a[i].k_tiles != nullptr) != (a[0].k_tiles != nullptr)) return TFASR_STATUS_UNSUPPORTED;
+  const bool ktab = a[0].k_tiles != nullptr;
+  // K the k loop runs over: the compacted block list of a product with a K-block table
+  auto keff = [](const tfasr_gemm_args& g) -> long { return g.k_tiles ? 256L * g.n_k_tiles : (long)g.K; };
   GroupArgs ga;
   memset(&ga, 0, sizeof(ga));
   long total = 0;
@@ -1118,7 +1180,7 @@ int tfasr_gemm_group_fast_try(const tfasr_gemm_args* a, int n, hipStream_t strea
   // slots for every group of the step: -0.28 / -0.33 ms per step against 512, of which the block groups beside the chain are 0.04.
   static const long env_slots = 0;
   long kmax = 0;
-  for (int i = 0; i < n; ++i) kmax = a[i].K > kmax ? a[i].K : kmax;
+  for (int i = 0; i < n; ++i) kmax = keff(a[i]) > kmax ? keff(a[i]) : kmax;
   const long slots = env_slots > 0 ? env_slots : ((g_tfasr_group_beside || kmax >= 131072) ? num_cus() * 5L / 4 : 2L * num_cus());
   long split = slots / (total > 0 ? total : 1);
   if (split < 1) split = 1;
@@ -1133,7 +1195,7 @@ int tfasr_gemm_group_fast_try(const tfasr_gemm_args* a, int n, hipStream_t strea
   int nu = 0;
   for (int i = 0; i < n; ++i) {
     long sp = split;
-    if (a[i].K / 512 < sp) sp = a[i].K / 512;
+    if (keff(a[i]) / 512 < sp) sp = keff(a[i]) / 512;
     if (sp < 1) sp = 1;
     if (sp > 64) sp = 64;
     ga.p[i] = a[i];
@@ -1172,7 +1234,8 @@ int tfasr_gemm_group_fast_try(const tfasr_gemm_args* a, int n, hipStream_t strea
     else TFASR_KLAUNCH((wgrad_group_kernel<E_CSUM, 2, 64>), dim3(8 * maxload), dim3(256), 2 * STAGE, stream, ga);
   } else {
     constexpr int STAGE = A_BYTES + 128 * BK * 2;
-    TFASR_KLAUNCH((wgrad_group_kernel<E_CSUM, 2, 128>), dim3(8 * maxload), dim3(256), 2 * STAGE, stream, ga);
+    if (ktab) TFASR_KLAUNCH((wgrad_group_kernel<E_CSUM, 2, 128, true>), dim3(8 * maxload), dim3(256), 2 * STAGE, stream, ga);
+    else TFASR_KLAUNCH((wgrad_group_kernel<E_CSUM, 2, 128>), dim3(8 * maxload), dim3(256), 2 * STAGE, stream, ga);
   }
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;

@@ -274,14 +274,16 @@ def edit_distance(hyp, ref, hyp_len=None, ref_len=None, skip_id=-1):
 # ---------------------------------------------------------------------------------------------- GEMM
 def gemm(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, bias=None, res=None, dact_z=None,
          prez=None, alpha=1.0, beta=1.0, act=ACT_NONE, dact=ACT_NONE, nb1=1, nb2=1, sA=(0, 0), sB=(0, 0), sD=(0, 0),
-         accumulate=False, split_k=1, drop_p=0.0, drop_seed=0, colsum=None, lse=None, seg=None, rgrad=None, bns=None, row_tiles=None):
+         accumulate=False, split_k=1, drop_p=0.0, drop_seed=0, colsum=None, lse=None, seg=None, rgrad=None, bns=None, row_tiles=None,
+         k_tiles=None):
     """Raw strided (two-level batched) GEMM; see include/tfasr_hip.h.  bns = (x [M, N], fin [4N] f32, out [copies, 2N] f32): the BatchNorm
     backward sums of the output in the epilogue (tfasr_gemm_args.bns_*; raises TfasrUnsupported when the product is not the plain NT one).  lse = (lse_part [M, parts, 2] f32, row_label [M] i32,
     pick [M, 2] f32): fused log-softmax statistics of the output rows (raises TfasrUnsupported when the fast path cannot); with it
     `out` may be None (statistics only).  rgrad = (coef [M, 4] f32, row_label [M] i32): the product is a re-computed logit tile and the
-    epilogue stores the RNN-T loss gradient instead (tfasr_gemm_args.rgrad_coef)."""
+    epilogue stores the RNN-T loss gradient instead (tfasr_gemm_args.rgrad_coef).  k_tiles: i32 device tensor, the ascending 256-row blocks
+    of K a transposed-A weight gradient sums over (tfasr_gemm_args.k_tiles; raises TfasrUnsupported for any other product)."""
     a = _gemm_args(A, B, out, M, N, K, lda, ldb, ldd, trans_a, trans_b, bias, res, dact_z, prez, alpha, beta, act, dact, nb1, nb2, sA, sB, sD,
-                   accumulate, split_k, drop_p, drop_seed, colsum)
+                   accumulate, split_k, drop_p, drop_seed, colsum, k_tiles)
     if rgrad is not None:
         coef, row_label = rgrad
         assert coef.dtype == torch.float32 and coef.is_contiguous() and row_label.dtype == torch.int32
@@ -303,24 +305,28 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, bias=N
         assert part.dtype == torch.float32 and pick.dtype == torch.float32 and row_label.dtype == torch.int32
         a.lse_part, a.lse_parts, a.row_label, a.pick = part.data_ptr(), part.shape[1], row_label.data_ptr(), pick.data_ptr()
     st = _lib.load().tfasr_gemm(ctypes.byref(a), _stream())
-    if (lse is not None or seg is not None or rgrad is not None or bns is not None) and st == _lib.STATUS_UNSUPPORTED:
-        raise _lib.TfasrUnsupported("gemm: fused row statistics / K-segments / gradient epilogue are not available for this product")
+    if (lse is not None or seg is not None or rgrad is not None or bns is not None or k_tiles is not None) and st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported("gemm: fused row statistics / K-segments / gradient epilogue / K-block table are not available for this product")
     check(st, "gemm")
     return out
 
 
 def gemm_group(calls):
     """Several independent products in one launch when they qualify (tfasr_gemm_group: bf16 weight gradients), else one by
-    one.  `calls` = list of dicts with gemm()'s keyword arguments."""
+    one.  `calls` = list of dicts with gemm()'s keyword arguments.  With k_tiles in the calls a product the library cannot run over the
+    table raises TfasrUnsupported (nothing of that product has been launched; earlier products of the list may have been)."""
     arr = (GemmArgs * len(calls))()
     for i, kw in enumerate(calls):
         arr[i] = _gemm_args(**kw)
-    check(_lib.load().tfasr_gemm_group(arr, len(calls), _stream()), "gemm_group")
+    st = _lib.load().tfasr_gemm_group(arr, len(calls), _stream())
+    if st == _lib.STATUS_UNSUPPORTED and any(kw.get("k_tiles") is not None for kw in calls):
+        raise _lib.TfasrUnsupported("gemm_group: K-block table not available for these products")
+    check(st, "gemm_group")
 
 
 def _gemm_args(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, bias=None, res=None, dact_z=None,
                prez=None, alpha=1.0, beta=1.0, act=ACT_NONE, dact=ACT_NONE, nb1=1, nb2=1, sA=(0, 0), sB=(0, 0), sD=(0, 0),
-               accumulate=False, split_k=1, drop_p=0.0, drop_seed=0, colsum=None):
+               accumulate=False, split_k=1, drop_p=0.0, drop_seed=0, colsum=None, k_tiles=None):
     a = GemmArgs()
     a.A, a.B, a.D = A.data_ptr(), B.data_ptr(), (out.data_ptr() if out is not None else None)
     a.bias = bias.data_ptr() if bias is not None else None
@@ -341,9 +347,12 @@ def _gemm_args(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, 
     a.split_k = split_k
     a.drop_p, a.drop_seed = drop_p, drop_seed
     a.colsum = colsum.data_ptr() if colsum is not None else None
+    if k_tiles is not None:
+        assert k_tiles.dtype == torch.int32 and k_tiles.is_cuda and k_tiles.is_contiguous()
+        a.k_tiles, a.n_k_tiles = k_tiles.data_ptr(), k_tiles.numel()
     if accumulate:
         assert out.dtype == torch.float32
-        if _SPLITK_WS and split_k > 1 and nb1 * nb2 == 1:  # opt-in: k-slices reduce through a workspace (deterministic sums)
+        if _SPLITK_WS and split_k > 1 and nb1 * nb2 == 1 and k_tiles is None:  # opt-in: k-slices reduce through a workspace (deterministic sums)
             ws = workspace(4 * split_k * M * N, out.device, "splitk_%d" % (_raw_stream(torch.cuda.current_device()) if _raw_stream else 0))
             a.ws, a.ws_elems = ws.data_ptr(), ws.numel() // 4
     return a
@@ -1005,10 +1014,12 @@ def conv1_stats_from_gram(gram, w, bias, stats):
     check(_L().tfasr_conv1_stats_from_gram(_p(gram), _p(w), _p(bias), _p(stats), w.shape[-1], _stream()), "conv1_stats_from_gram")
 
 
-def conv1_bn_bwd_onepass_s2d(x, w, bias, fin, dy, bstats, pbuf):
+def conv1_bn_bwd_onepass_s2d(x, w, bias, fin, dy, bstats, pbuf, row_list=None):
+    """row_list: i32 device tensor of conv1 output rows b * T1 + t, the only rows of dy that are read (None: every row)"""
     B, T0, F0 = x.shape[:3]
-    check(_L().tfasr_conv1_bn_bwd_onepass_s2d(_p(x), _p(w), _p(bias), _p(fin), _p(dy), _p(bstats), _p(pbuf), B, T0, F0, w.shape[-1], _dt(x),
-                                              _stream()), "conv1_bn_bwd_onepass")
+    assert row_list is None or (row_list.dtype == torch.int32 and row_list.is_cuda and row_list.is_contiguous())
+    check(_L().tfasr_conv1_bn_bwd_onepass_s2d_rows(_p(x), _p(w), _p(bias), _p(fin), _p(dy), _p(bstats), _p(pbuf), B, T0, F0, w.shape[-1], _dt(x),
+                                                   _p(row_list), 0 if row_list is None else row_list.numel(), _stream()), "conv1_bn_bwd_onepass")
 
 
 def conv1_bn_bwd_finalize(gram, w, bias, fin, bstats, count, pbuf, dw, db):
@@ -1033,6 +1044,18 @@ def s2d_tail_fill(x, tiles, rep_tt, B, T2, F2, C):
     if st == _lib.STATUS_UNSUPPORTED:
         raise _lib.TfasrUnsupported("s2d_tail_fill: bf16 tensors with C % 8 == 0 only")
     check(st, "s2d_tail_fill")
+    return x
+
+
+def s2d_tail_fold(x, r_tt, scratch, B, T2, F2, C):
+    """in place on the gradient x [B, T2+1, F2+1, C]: time rows r_tt[b] .. T2 -> their f32 sum as a bf16 hi / lo pair in rows r_tt[b], r_tt[b] + 1
+    and zeros behind (tfasr_s2d_tail_fold); scratch f32 [B, F2+1, C], zeroed by the caller.  Raises TfasrUnsupported outside bf16 / C % 8 == 0."""
+    assert r_tt.dtype == torch.int32 and r_tt.is_cuda and r_tt.numel() == B
+    assert scratch.dtype == torch.float32 and scratch.is_cuda and scratch.numel() >= B * (F2 + 1) * C
+    st = _L().tfasr_s2d_tail_fold(_p(x), _p(r_tt), _p(scratch), B, T2, F2, C, _dt(x), _stream())
+    if st == _lib.STATUS_UNSUPPORTED:
+        raise _lib.TfasrUnsupported("s2d_tail_fold: bf16 tensors with C % 8 == 0 only")
+    check(st, "s2d_tail_fold")
     return x
 
 
