@@ -119,7 +119,8 @@ class BaseModel:
             logits = [b, t_out, u1, c.vocab_size]
         return TrainOutput(logits=logits, logits_length=[b])
 
-    def _encoder_length(self, t):
+    @staticmethod
+    def _encoder_length(t):
         """frames -> encoder frames (math_util.conv_output_length "causal" twice for the Conformer; models override)."""
         return -(-(-(-int(t) // 2)) // 2)
 

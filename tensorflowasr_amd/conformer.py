@@ -1781,16 +1781,20 @@ class ConformerTransducer(BaseModel):
 
     # =================================================================================== streaming (streaming.py, csrc/stream.hip)
     def stream_state(self, batch_size=1, precision=None):
-        """Encoder state of `batch_size` streams for encode_chunk.  precision as encode: "f32" (default) = the inference twin."""
+        """Encoder state of `batch_size` streams for encode_chunk (the class streaming.STREAM_STATES names for the encoder, after its refusal
+        rule).  precision as encode: "f32" (default) = the inference twin."""
         from . import streaming
 
-        return streaming.StreamState(streaming._twin(self, precision), batch_size)
+        return streaming.check_streamable(self)(streaming._twin(self, precision), batch_size)
 
-    def encode_chunk(self, state, feats, nframes):
-        """One chunk of the streaming encoder: feats [B, n <= 4 chunk_size, F], nframes [B] -> (enc [B, chunk_size, dmodel], nvalid [B])."""
+    def encode_chunk(self, state, feats, nframes, final=()):
+        """One step of the streaming encoder (the state's `encode`): feats [B, n, F] (the Conformer: n <= 4 chunk_size), nframes [B], final
+        = the streams that end with these frames (RnntStreamState) -> (enc [B, rows, dmodel] (the Conformer: chunk_size rows), nvalid [B])."""
         from . import streaming
 
-        return streaming.encode_chunk(state, feats, nframes)
+        if not isinstance(state, streaming.check_streamable(self)):
+            raise ValueError("encoder state of another model")
+        return streaming.encode_chunk(state, feats, nframes, final)
 
     def stream(self, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
         """Incremental recognition session (streaming.StreamingRecognizer): accept(pcm) ... finish().  Refused, with the reason, for a

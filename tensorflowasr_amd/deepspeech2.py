@@ -69,18 +69,6 @@ class DeepSpeech2CTC(ConformerCTC):
     train_step = loss_and_backward = compile = _inference_only
 
     # ------------------------------------------------------------------------------------------- streaming (the causal variant)
-    def stream_state(self, batch_size=1, precision=None):
-        from . import streaming
-
-        streaming.check_streamable(self)
-        return streaming.DS2StreamState(streaming._twin(self, precision), batch_size)
-
-    def encode_chunk(self, state, feats, nframes):
-        from . import streaming
-
-        streaming.check_streamable(self)
-        return streaming.ds2_encode_chunk(state, feats, nframes)
-
     def stream(self, batch_size=1, chunk_frames=32, beam_width=0, max_frames=3000, precision=None):
         """Incremental recognition session (streaming.StreamingRecognizer) over steps of `chunk_frames` feature frames, a positive multiple
         of the product of the time strides.  Only a config that is causal throughout streams (see the module docstring); a stream then

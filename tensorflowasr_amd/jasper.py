@@ -129,16 +129,6 @@ class JasperCTC(ConformerCTC):
         return {1 + i * n for i in range(len(self.cfg.block_channels))}
 
     # ------------------------------------------------------------------------------------------- streaming
-    def stream_state(self, batch_size=1, precision=None):
-        from . import streaming
-
-        return streaming.JasperStreamState(streaming._twin(self, precision), batch_size)
-
-    def encode_chunk(self, state, feats, nframes):
-        from . import streaming
-
-        return streaming.jasper_encode_chunk(state, feats, nframes)
-
     def stream(self, batch_size=1, chunk_frames=32, beam_width=0, max_frames=3000, precision=None):
         """Incremental recognition session (streaming.StreamingRecognizer) over steps of `chunk_frames` feature frames (even: the first
         block strides by 2).  Jasper is causal throughout, so a stream carries only the last (K - 1) * dilation input rows of every layer

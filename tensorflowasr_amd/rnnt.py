@@ -54,6 +54,14 @@ def _round_up(n, m):
     return -(-int(n) // m) * m
 
 
+def boundary_factors(mods):
+    """The time reductions per block BOUNDARY of rnnt_modules(cfg): [pre_0, post_0 * pre_1, ..., post_{L-1}].  A `post` reduction by f
+    followed by the next block's `pre` reduction by g groups f g consecutive rows (zero rows pad either; no layer sits between them)."""
+    pre = [m["factor"] if m["position"] == "pre" else 1 for m in mods]
+    post = [m["factor"] if m["position"] == "post" else 1 for m in mods]
+    return [pre[0]] + [post[i] * pre[i + 1] for i in range(len(mods) - 1)] + [post[-1]]
+
+
 class RnnEncoderMixin:
     """encoder_fwd and what it needs; mixed in front of ConformerTransducer"""
 
@@ -87,26 +95,8 @@ class RnnEncoderMixin:
 
         return streaming.StreamingRecognizer(self, batch_size, precision, max_tokens_per_frame, beam_width, max_frames, chunk_frames=chunk_frames)
 
-    def stream_state(self, batch_size=1, precision=None):
-        """Encoder state of `batch_size` streams for encode_chunk (streaming.RnntStreamState).  precision as encode."""
-        from . import streaming
-
-        return streaming.RnntStreamState(streaming._twin(self, precision), batch_size)
-
-    def encode_chunk(self, state, feats, nframes, final=()):
-        """One step of the streaming encoder: feats [B, n, F], nframes [B], final = the streams that end with these frames ->
-        (enc [B, state.out_rows(n), cfg.dmodel], nvalid [B]); streaming.rnnt_encode_chunk."""
-        from . import streaming
-
-        return streaming.rnnt_encode_chunk(state, feats, nframes, final)
-
     def boundary_factors(self):
-        """The time reductions per block BOUNDARY: [pre_0, post_0 * pre_1, ..., post_{L-1}].  A `post` reduction by f followed by the next
-        block's `pre` reduction by g groups f g consecutive rows (zero rows pad either; no layer sits between them)."""
-        mods = self.modules
-        pre = [m["factor"] if m["position"] == "pre" else 1 for m in mods]
-        post = [m["factor"] if m["position"] == "post" else 1 for m in mods]
-        return [pre[0]] + [post[i] * pre[i + 1] for i in range(len(mods) - 1)] + [post[-1]]
+        return boundary_factors(self.modules)
 
     def _encoder_length(self, t):
         return self.cfg.encoder_length(t)

@@ -12,6 +12,7 @@ session do.  State carried per stream:
     beam search   (beam_width >= 1) the whole beam: rows, f64 totals, label trie + table, prediction states (K.RnntBeamStream); the
                   CTC search's rows and trie (K.CtcBeamStream); the depth committed so far
 The kernels that touch carried state are csrc/stream.hip; the dense pieces are the forward kernels of training with T = chunk_size.
+Everything the session knows about an encoder is EncoderStream, the base of the five state classes (STREAM_STATES: cfg.encoder -> class).
 A Transformer with a chunked config streams under the same contract (TransformerStreamState, transformer_encode_chunk): its blocks carry
 the K / V rings only (there is no convolution module), the absolute position rows are taken at each stream's own offset, and the ring
 append is part of the attention launch.
@@ -28,7 +29,10 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from .base_model import BaseModel
 from .kernels import ACT_SWISH
+from .params import rnnt_modules
+from .rnnt import boundary_factors
 
 
 class StreamOutput(typing.NamedTuple):
@@ -49,13 +53,133 @@ class StreamDetailOutput(typing.NamedTuple):
     entropies: torch.Tensor  # [B, W] f32 (CTC: mean over the run; over its frames so far while it is open)
 
 
-class StreamState:
-    """Encoder state of `batch_size` streams (device tensors) plus the per-layer constant position tables."""
+def _refuse(model, why):
+    """the refusal of the inference-only models, in the words of their other refusals ("inference only") followed by the reason"""
+    raise NotImplementedError(f"{type(model).__name__} is inference only, and this configuration cannot be streamed: {why}")
+
+
+def _frame_counts(model, feats, nframes, keep_device=False, upload=True):
+    """nframes [B], the feature frames of feats [B, n, F] that are real per stream -> (host list, device int32 vector - None without
+    `upload`); B counts in 0 .. n or ValueError.  keep_device: a tensor goes to the device as it is, without being read back (host list
+    None, no range check)."""
+    if keep_device and isinstance(nframes, torch.Tensor):
+        return None, nframes.to(model.device).to(torch.int32).contiguous()
+    host = [int(v) for v in (nframes.tolist() if isinstance(nframes, torch.Tensor) else nframes)]
+    if len(host) != feats.shape[0] or min(host) < 0 or max(host) > feats.shape[1]:
+        raise ValueError(f"encode_chunk takes B = {feats.shape[0]} frame counts within its {feats.shape[1]} feature frames")
+    return host, model._h2d(host) if upload else None
+
+
+class EncoderStream:
+    """Encoder state of `batch_size` streams, and everything a session (StreamingRecognizer) knows about the encoder; what a new encoder
+    supplies to stream ("The encoder-stream interface"):
+        check(model)                   the refusal rule: raises, with the reason, for a config that cannot stream (check_streamable)
+        step_rule(cfg, chunk_frames)   host only -> (feature frames of a step, encoder rows of a step's output buffer, reduce(t) = the
+                                       encoder frames of t feature frames); ValueError for a chunk_frames the encoder cannot take
+        f32_features, prepare(feats)   the front end writes f32 (else the compute type); what happens to its output before the encoder
+        encode(feats, nframes, final)  one step -> (enc [B, rows, dmodel], nvalid [B] int32 device, nvalid host list); advances the state
+        uses_final                     the encoder carries rows that only a final step sends out (`final` = the streams that end here)
+        reset / export / load          here, over _tensors() (the carried device tensors) and the _host_* hooks (counters on the host)"""
+    f32_features = False
+    uses_final = False
+    host_tensors = 0  # tensors export() appends to the carried ones for the state kept on the host
 
     def __init__(self, model, batch_size):
-        c, ps, dev, dt = model.cfg, model.ps, model.device, model.dtype
-        check_streamable(model)
+        self.check(model)
         self.model, self.B = model, int(batch_size)
+
+    @staticmethod
+    def check(model):
+        pass
+
+    def prepare(self, feats):
+        return feats
+
+    def _reduced(self, host):
+        return None if host is None else [self.model._encoder_length(t) for t in host]
+
+    _host_reset = _host_load = lambda self, arg: None  # hooks: reset(rows) and load(what _host_export appended) of state kept on the host
+    _host_export = lambda self: []
+
+    def reset(self, rows=None):
+        for t in self._tensors():
+            if rows is None:
+                t.zero_()
+            else:
+                t[torch.as_tensor(list(rows), dtype=torch.long, device=t.device)] = 0
+        self._host_reset(range(self.B) if rows is None else rows)
+
+    def export(self):
+        """The carried tensors as one flat list (a copy): what PredictOutput.next_encoder_states holds."""
+        return [t.clone() for t in self._tensors()] + self._host_export()
+
+    def load(self, tensors):
+        mine = self._tensors()
+        if len(tensors) != len(mine) + self.host_tensors:
+            raise ValueError("encoder state of another model")
+        for a, b in zip(mine, tensors):
+            a.copy_(b)
+        self._host_load(tensors[len(mine):])
+
+
+def _chunked_step(cfg, chunk_frames, reduce):
+    """the step of the chunked-attention encoders: 4 * chunk_size feature frames -> chunk_size encoder frames"""
+    if chunk_frames is not None:
+        raise ValueError("stream: chunk_frames belongs to the Jasper and DeepSpeech2 sessions; a Conformer's step is 4 * chunk_size "
+                         "feature frames")
+    return 4 * int(cfg.chunk_size), int(cfg.chunk_size), reduce
+
+
+def _strided_step(cfg, chunk_frames=None, most=None, limit=""):
+    """the step of the strided causal encoders: `chunk_frames` feature frames -> chunk_frames / factor encoder frames (a stream's last
+    step: ceil of what is left), `most` rows at the most"""
+    factor = int(cfg.time_reduction_factor)
+    n = int(chunk_frames if chunk_frames is not None else 32)
+    if n < factor or n % factor:
+        raise ValueError(f"stream: chunk_frames {n} must be a positive multiple of the time reduction factor {factor}")
+    if most is not None and n // factor > most:
+        raise ValueError(f"stream: chunk_frames {n} is more than {most} encoder frames a step ({limit})")
+    return n, n // factor, cfg.encoder_length
+
+
+@torch.no_grad()
+def _causal_stem(state, feats, nframes, conv_norm1, conv_norm2, keep_device=False):
+    """The causal two-convolution subsampling of one step with its two carries: feats [B, n <= 4C, F] -> (x [B*C, dmodel], frame counts
+    on the host, nvalid [B] int32 device).  conv_norm1(carry ++ rows [B, 4C + 2, F]) -> [B, 2C + 1, F1, C0] and conv_norm2(im2col rows)
+    -> [B (C + 1) F2, C1] are the model's convolution + norm pairs."""
+    m = state.model
+    c, ps, dev = m.cfg, m.ps, m.device
+    B, C = state.B, int(c.chunk_size)
+    n0 = 4 * C
+    if feats.shape[0] != B or feats.shape[1] > n0:
+        raise ValueError(f"encode_chunk takes [B = {B}, <= {n0}, F] feature frames")
+    host, nf = _frame_counts(m, feats, nframes, keep_device)
+    cat = torch.zeros(B, n0 + 2, c.num_feature_bins, dtype=m.dtype, device=dev)
+    cat[:, :2] = state.feat_carry
+    cat[:, 2:2 + feats.shape[1]] = feats
+    n1 = (nf + 1) // 2
+    nvalid = ((n1 + 1) // 2).to(torch.int32).contiguous()
+    two = torch.arange(2, device=dev)
+    # the carries move to the last two VALID rows (rows nf, nf + 1 of carry ++ new; nf == 0 picks the carry itself)
+    idx = (nf.long()[:, None] + two[None, :])
+    state.feat_carry.copy_(torch.gather(cat, 1, idx[:, :, None].expand(B, 2, cat.shape[2])))
+    # causal 3x3 stride-2 convs on carry(2) ++ new(n): output 0 belongs to the previous chunk, outputs 1.. are the originals
+    a1 = conv_norm1(cat)
+    F1, C0 = a1.shape[2], a1.shape[3]
+    cat1 = torch.cat([state.conv_carry, a1[:, 1:]], 1).contiguous()  # [B, 2C + 2, F1, C0]
+    idx1 = (n1.long()[:, None] + two[None, :])
+    state.conv_carry.copy_(torch.gather(cat1, 1, idx1[:, :, None, None].expand(B, 2, F1, C0)))
+    a2 = conv_norm2(K.im2col_3x3s2(cat1))
+    merged = a2.view(B, C + 1, -1)[:, 1:].reshape(B * C, -1)
+    return K.matmul(merged, ps.w2d("enc/linear/w"), bias=ps.p("enc/linear/b")), host, nvalid
+
+
+class StreamState(EncoderStream):
+    """Encoder state of `batch_size` Conformer streams (device tensors) plus the per-layer constant position tables."""
+
+    def __init__(self, model, batch_size):
+        super().__init__(model, batch_size)
+        c, ps, dev, dt = model.cfg, model.ps, model.device, model.dtype
         B, C, hist = self.B, int(c.chunk_size), int(c.history_size)
         HD = c.num_heads * ps.head_phys
         F1 = (c.num_feature_bins + 1) // 2
@@ -75,162 +199,81 @@ class StreamState:
         pe = torch.from_numpy(pe).to(dev).to(dt).contiguous()
         self.pext = [K.matmul(pe, ps.w2d(f"enc/block{i}/mhsa/pos/w"), bias=ps.p(f"enc/block{i}/mhsa/pos/b")) for i in range(nb)]
 
+    @staticmethod
+    def check(model):
+        c = model.cfg
+        if c.chunk_size is None:
+            raise ValueError("streaming needs a streaming config: chunk_size is None (full-context attention sees the whole utterance)")
+        if c.history_size is None or int(c.history_size) < 0:
+            raise ValueError("streaming needs history_size >= 0: unlimited history would need an unbounded key / value cache")
+        C, hist = int(c.chunk_size), int(c.history_size)
+        if C < 1 or C > K.STREAM_MAX_CHUNK or hist + C > K.STREAM_MAX_KEYS or model.ps.head_phys > K.STREAM_MAX_HEAD or c.kernel_size > 32:
+            raise ValueError(f"chunk_size {C} / history_size {hist} / head {model.ps.head_phys} / kernel {c.kernel_size} beyond the streaming "
+                             f"kernels' limits (chunk <= {K.STREAM_MAX_CHUNK}, history + chunk <= {K.STREAM_MAX_KEYS}, head <= "
+                             f"{K.STREAM_MAX_HEAD}, kernel <= 32)")
+
+    @staticmethod
+    def step_rule(cfg, chunk_frames=None):
+        return _chunked_step(cfg, chunk_frames, BaseModel._encoder_length)
+
     def _tensors(self):
         return [self.seen, self.feat_carry, self.conv_carry] + self.kcache + self.vcache + self.dwstate
 
-    def reset(self, rows=None):
-        for t in self._tensors():
-            if rows is None:
-                t.zero_()
+    @torch.no_grad()
+    def encode(self, feats, nframes, final=()):
+        """One encoder step: feats [B, n <= 4C, F] (compute dtype, device), nframes [B] int32 feature frames that are real per stream: 0
+        (idle), 4C (a full chunk) or in between for a stream's last chunk -> (enc [B, C, dmodel], nvalid [B] int32 device, nvalid on the
+        host - None for a device tensor of counts, which is not read back); advances state."""
+        m = self.model
+        c, ps = m.cfg, m.ps
+        B, C, hist = self.B, int(c.chunk_size), int(c.history_size)
+        H, dh, d = c.num_heads, ps.head_phys, c.dmodel
+        Cp = ps.filt_phys
+
+        def conv_norm1(cat):
+            c1 = K.conv1_fwd(cat, ps.p("enc/sub/conv0/w"), ps.p("enc/sub/conv0/b"))  # [B, 2C + 1, F1, Cp]
+            return m._sub_norm_fwd(c1.view(-1, Cp), "enc/sub/bn0", False)[0].view(c1.shape)
+
+        def conv_norm2(col):
+            return m._sub_norm_fwd(K.matmul(col, ps.w2d("enc/sub/conv1/w"), bias=ps.p("enc/sub/conv1/b")), "enc/sub/bn1", False)[0]
+
+        x, host, nvalid = _causal_stem(self, feats, nframes, conv_norm1, conv_norm2, keep_device=True)
+        scale = 1.0 / math.sqrt(c.head_size)
+        for i in range(c.num_blocks):
+            p = f"enc/block{i}/"
+            x = m._ffm_fwd(x, p + "ff1/", None, 0, False)
+            pfx = p + "mhsa/"
+            ln, _, _ = K.layernorm_fwd(x, ps.p(pfx + "ln/g"), ps.p(pfx + "ln/b"))
+            qkv = K.matmul(ln, ps.w2d(pfx + "qkv/w"), bias=ps.p(pfx + "qkv/b"))
+            ub, vb = m._uv(pfx)
+            att = K.stream_attn_fwd(qkv, ub, vb, self.pext[i], self.kcache[i], self.vcache[i], self.seen, nvalid, B, C, H, dh, hist, scale)
+            K.stream_kv_append(qkv, self.kcache[i], self.vcache[i], self.seen, nvalid, B, C, H, dh, hist)  # after every head has read the ring
+            x = K.matmul(att, ps.w2d(pfx + "o/w"), bias=ps.p(pfx + "o/b"), res=x, beta=c.mhsam_residual)
+            pfx = p + "conv/"
+            ln, _, _ = K.layernorm_fwd(x, ps.p(pfx + "ln/g"), ps.p(pfx + "ln/b"))
+            a = K.matmul(ln, ps.w2d(pfx + "pw1/w"), bias=ps.p(pfx + "pw1/b"))
+            cv = K.stream_glu_dwconv_fwd(a, self.dwstate[i], ps.p(pfx + "dw/w"), ps.p(pfx + "dw/b"), nvalid, B, C)
+            if c.convm_dw_norm == "layer":
+                yn, _, _ = K.layernorm_fwd(cv, ps.p(pfx + "bn/g"), ps.p(pfx + "bn/b"))
+                sw = K.add_act_fwd(yn, None, ACT_SWISH)
             else:
-                t[torch.as_tensor(list(rows), dtype=torch.long, device=t.device)] = 0
-
-    def export(self):
-        """The carried tensors as one flat list (a copy): what PredictOutput.next_encoder_states holds."""
-        return [t.clone() for t in self._tensors()]
-
-    def load(self, tensors):
-        mine = self._tensors()
-        if len(tensors) != len(mine):
-            raise ValueError("encoder state of another model")
-        for a, b in zip(mine, tensors):
-            a.copy_(b)
+                sw, _ = m._bn_fwd(cv, pfx + "bn", False, ACT_SWISH)
+            x = K.matmul(sw, ps.w2d(pfx + "pw2/w"), bias=ps.p(pfx + "pw2/b"), res=x, beta=c.convm_residual)
+            x = m._ffm_fwd(x, p + "ff2/", None, 0, False)
+            x, _, _ = K.layernorm_fwd(x, ps.p(p + "ln/g"), ps.p(p + "ln/b"))
+        self.seen += nvalid
+        return x.view(B, C, d), nvalid, self._reduced(host)
 
 
-def _check_transformer(model):
-    """A Transformer streams when its attention mask is the chunked one (use_attention_auto_mask, chunk_size, history_size >= 0) and the
-    sizes fit tfasr_stream_attn_plain_fwd; the causal flag is allowed (the kernel has it).  Everything else is refused in the words of the
-    model's other refusals ("inference only") followed by the reason."""
-    c = model.cfg
-    why = None
-    if c.chunk_size is None:
-        why = "chunk_size is None (full-context attention sees the whole utterance)"
-    elif not c.use_attention_auto_mask:
-        why = "use_attention_auto_mask is off (no mask is computed: every frame attends over the whole utterance)"
-    elif c.history_size is None or int(c.history_size) < 0:
-        why = "unlimited history would need an unbounded key / value cache"
-    else:
-        C, hist, dh = int(c.chunk_size), int(c.history_size), int(c.head_size)
-        if C < 1 or C > K.STREAM_MAX_CHUNK or hist + C > K.STREAM_MAX_KEYS or dh > K.STREAM_MAX_HEAD:
-            why = (f"chunk_size {C} / history_size {hist} / head {dh} beyond the streaming kernels' limits (chunk <= {K.STREAM_MAX_CHUNK}, "
-                   f"history + chunk <= {K.STREAM_MAX_KEYS}, head <= {K.STREAM_MAX_HEAD})")
-    if why is not None:
-        raise NotImplementedError(f"{type(model).__name__} is inference only, and this configuration cannot be streamed: {why}")
-
-
-def _check_ds2(model):
-    """A DeepSpeech2 streams when it is causal throughout: forward LSTMs only and causal convolutions.  Everything else is refused in the
-    words of the model's other refusals ("inference only") followed by the reason."""
-    c = model.cfg
-    why = None
-    if c.rnn_bidirectional:
-        why = "rnn_bidirectional (the backward direction starts at the utterance's last frame)"
-    elif c.conv_padding != "causal":
-        why = f"conv_padding = {c.conv_padding!r} (a 'same'-padded convolution reads frames that have not arrived yet)"
-    if why is not None:
-        raise NotImplementedError(f"{type(model).__name__} is inference only, and this configuration cannot be streamed: {why}")
-
-
-def check_streamable(model):
-    c = model.cfg
-    if getattr(c, "encoder", "conformer") == "deepspeech2":
-        return _check_ds2(model)
-    if getattr(c, "encoder", "conformer") == "jasper":
-        return  # causal convolutions only: streams exactly (JasperStreamState)
-    if getattr(c, "encoder", "conformer") == "transformer":
-        return _check_transformer(model)
-    if getattr(c, "encoder", "conformer") == "rnnt":
-        return  # forward LSTMs and row-wise layers only: streams exactly (RnntStreamState)
-    if getattr(c, "encoder", "conformer") != "conformer":
-        raise ValueError("streaming needs a Conformer encoder: ContextNet's squeeze-and-excite is a mean over the whole utterance")
-    if c.chunk_size is None:
-        raise ValueError("streaming needs a streaming config: chunk_size is None (full-context attention sees the whole utterance)")
-    if c.history_size is None or int(c.history_size) < 0:
-        raise ValueError("streaming needs history_size >= 0: unlimited history would need an unbounded key / value cache")
-    C, hist = int(c.chunk_size), int(c.history_size)
-    if C < 1 or C > K.STREAM_MAX_CHUNK or hist + C > K.STREAM_MAX_KEYS or model.ps.head_phys > K.STREAM_MAX_HEAD or c.kernel_size > 32:
-        raise ValueError(f"chunk_size {C} / history_size {hist} / head {model.ps.head_phys} / kernel {c.kernel_size} beyond the streaming "
-                         f"kernels' limits (chunk <= {K.STREAM_MAX_CHUNK}, history + chunk <= {K.STREAM_MAX_KEYS}, head <= "
-                         f"{K.STREAM_MAX_HEAD}, kernel <= 32)")
-
-
-def _twin(model, precision):
-    return model.inference_twin() if (precision or model.decode_precision) == "f32" else model
-
-
-@torch.no_grad()
-def encode_chunk(state, feats, nframes):
-    """One encoder step: feats [B, n <= 4C, F] (compute dtype, device), nframes [B] int32 feature frames that are real per stream: 0
-    (idle), 4C (a full chunk) or in between for a stream's last chunk -> (enc [B, C, dmodel], nvalid [B] int32 device); advances state."""
-    m = state.model
-    c, ps, dev = m.cfg, m.ps, m.device
-    B, C, hist = state.B, int(c.chunk_size), int(c.history_size)
-    H, dh, d = c.num_heads, ps.head_phys, c.dmodel
-    n0 = 4 * C
-    nf = nframes.to(dev).to(torch.int32) if isinstance(nframes, torch.Tensor) else m._h2d(list(nframes))
-    if feats.shape[0] != B or feats.shape[1] > n0:
-        raise ValueError(f"encode_chunk takes [B = {B}, <= {n0}, F] feature frames")
-    cat = torch.zeros(B, n0 + 2, c.num_feature_bins, dtype=m.dtype, device=dev)
-    cat[:, :2] = state.feat_carry
-    cat[:, 2:2 + feats.shape[1]] = feats
-    n1 = (nf + 1) // 2
-    nvalid = ((n1 + 1) // 2).to(torch.int32).contiguous()
-    two = torch.arange(2, device=dev)
-    # the carries move to the last two VALID rows (rows nf, nf + 1 of carry ++ new; nf == 0 picks the carry itself)
-    idx = (nf.long()[:, None] + two[None, :])
-    state.feat_carry.copy_(torch.gather(cat, 1, idx[:, :, None].expand(B, 2, cat.shape[2])))
-    # causal 3x3 stride-2 convs on carry(2) ++ new(n): output 0 belongs to the previous chunk, outputs 1.. are the originals
-    Cp = ps.filt_phys
-    c1 = K.conv1_fwd(cat, ps.p("enc/sub/conv0/w"), ps.p("enc/sub/conv0/b"))  # [B, 2C + 1, F1, Cp]
-    T1, F1 = c1.shape[1], c1.shape[2]
-    a1, _ = m._sub_norm_fwd(c1.view(-1, Cp), "enc/sub/bn0", False)
-    a1 = a1.view(B, T1, F1, Cp)
-    cat1 = torch.cat([state.conv_carry, a1[:, 1:]], 1).contiguous()  # [B, 2C + 2, F1, Cp]
-    idx1 = (n1.long()[:, None] + two[None, :])
-    state.conv_carry.copy_(torch.gather(cat1, 1, idx1[:, :, None, None].expand(B, 2, F1, Cp)))
-    col = K.im2col_3x3s2(cat1)
-    T2, F2 = (cat1.shape[1] + 1) // 2, (F1 + 1) // 2  # C + 1
-    c2 = K.matmul(col, ps.w2d("enc/sub/conv1/w"), bias=ps.p("enc/sub/conv1/b"))
-    a2, _ = m._sub_norm_fwd(c2, "enc/sub/bn1", False)
-    merged = a2.view(B, T2, F2 * Cp)[:, 1:].reshape(B * C, F2 * Cp)
-    x = K.matmul(merged, ps.w2d("enc/linear/w"), bias=ps.p("enc/linear/b"))  # [B*C, d]
-    scale = 1.0 / math.sqrt(c.head_size)
-    for i in range(c.num_blocks):
-        p = f"enc/block{i}/"
-        x = m._ffm_fwd(x, p + "ff1/", None, 0, False)
-        pfx = p + "mhsa/"
-        ln, _, _ = K.layernorm_fwd(x, ps.p(pfx + "ln/g"), ps.p(pfx + "ln/b"))
-        qkv = K.matmul(ln, ps.w2d(pfx + "qkv/w"), bias=ps.p(pfx + "qkv/b"))
-        ub, vb = m._uv(pfx)
-        att = K.stream_attn_fwd(qkv, ub, vb, state.pext[i], state.kcache[i], state.vcache[i], state.seen, nvalid, B, C, H, dh, hist, scale)
-        K.stream_kv_append(qkv, state.kcache[i], state.vcache[i], state.seen, nvalid, B, C, H, dh, hist)  # after every head has read the ring
-        x = K.matmul(att, ps.w2d(pfx + "o/w"), bias=ps.p(pfx + "o/b"), res=x, beta=c.mhsam_residual)
-        pfx = p + "conv/"
-        ln, _, _ = K.layernorm_fwd(x, ps.p(pfx + "ln/g"), ps.p(pfx + "ln/b"))
-        a = K.matmul(ln, ps.w2d(pfx + "pw1/w"), bias=ps.p(pfx + "pw1/b"))
-        cv = K.stream_glu_dwconv_fwd(a, state.dwstate[i], ps.p(pfx + "dw/w"), ps.p(pfx + "dw/b"), nvalid, B, C)
-        if c.convm_dw_norm == "layer":
-            yn, _, _ = K.layernorm_fwd(cv, ps.p(pfx + "bn/g"), ps.p(pfx + "bn/b"))
-            sw = K.add_act_fwd(yn, None, ACT_SWISH)
-        else:
-            sw, _ = m._bn_fwd(cv, pfx + "bn", False, ACT_SWISH)
-        x = K.matmul(sw, ps.w2d(pfx + "pw2/w"), bias=ps.p(pfx + "pw2/b"), res=x, beta=c.convm_residual)
-        x = m._ffm_fwd(x, p + "ff2/", None, 0, False)
-        x, _, _ = K.layernorm_fwd(x, ps.p(p + "ln/g"), ps.p(p + "ln/b"))
-    state.seen += nvalid
-    return x.view(B, C, d), nvalid
-
-
-class TransformerStreamState:
+class TransformerStreamState(EncoderStream):
     """Encoder state of `batch_size` Transformer streams: seen, the last 2 feature frames, the last 2 rows of the first convolution
     block's activation (after the folded BatchNorm and the ReLU), one K and one V ring [B, history_size, H * head_size] per block.  The
     absolute position table [Tcap, dmodel] f32 is a constant, not state: its rows depend on the position only, so it is grown by doubling
     (from the frame counters kept on the host) before a launch would pass its end, and it is not exported."""
 
     def __init__(self, model, batch_size):
-        check_streamable(model)
+        super().__init__(model, batch_size)
         c, dev, dt = model.cfg, model.device, model.dtype
-        self.model, self.B = model, int(batch_size)
         B, hist, HD = self.B, int(c.history_size), int(c.num_heads) * int(c.head_size)
         F1 = (c.num_feature_bins + 1) // 2
         self.seen = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -242,6 +285,26 @@ class TransformerStreamState:
         self.host_seen = [0] * B  # encoder frames per stream, as the device vector `seen` holds them
         self.pe = None
         self.reserve(4 * int(c.chunk_size))
+
+    @staticmethod
+    def check(model):
+        """A Transformer streams when its attention mask is the chunked one (use_attention_auto_mask, chunk_size, history_size >= 0) and
+        the sizes fit tfasr_stream_attn_plain_fwd; the causal flag is allowed (the kernel has it)."""
+        c = model.cfg
+        if c.chunk_size is None:
+            _refuse(model, "chunk_size is None (full-context attention sees the whole utterance)")
+        if not c.use_attention_auto_mask:
+            _refuse(model, "use_attention_auto_mask is off (no mask is computed: every frame attends over the whole utterance)")
+        if c.history_size is None or int(c.history_size) < 0:
+            _refuse(model, "unlimited history would need an unbounded key / value cache")
+        C, hist, dh = int(c.chunk_size), int(c.history_size), int(c.head_size)
+        if C < 1 or C > K.STREAM_MAX_CHUNK or hist + C > K.STREAM_MAX_KEYS or dh > K.STREAM_MAX_HEAD:
+            _refuse(model, f"chunk_size {C} / history_size {hist} / head {dh} beyond the streaming kernels' limits (chunk <= "
+                           f"{K.STREAM_MAX_CHUNK}, history + chunk <= {K.STREAM_MAX_KEYS}, head <= {K.STREAM_MAX_HEAD})")
+
+    @staticmethod
+    def step_rule(cfg, chunk_frames=None):  # the Conformer's step and frame reduction
+        return _chunked_step(cfg, chunk_frames, cfg.encoder_length)
 
     def reserve(self, rows):
         """the position table covers positions 0 .. rows - 1 at least"""
@@ -259,253 +322,343 @@ class TransformerStreamState:
     def _tensors(self):
         return [self.seen, self.feat_carry, self.conv_carry] + [t for t in self.kcache + self.vcache if t is not None]
 
-    def reset(self, rows=None):
-        StreamState.reset(self, rows)
-        for b in (range(self.B) if rows is None else rows):
+    def _host_reset(self, rows):
+        for b in rows:
             self.host_seen[b] = 0
 
-    export = StreamState.export
-
-    def load(self, tensors):
-        StreamState.load(self, tensors)
+    def _host_load(self, tensors):
         self.host_seen = [int(v) for v in self.seen.tolist()]
 
+    @torch.no_grad()
+    def encode(self, feats, nframes, final=()):
+        """One step of the streaming Transformer encoder: feats [B, n <= 4C, F] (compute dtype, device), nframes [B] feature frames that
+        are real per stream (0 = idle, 4C = a full chunk, fewer for a stream's last chunk) -> (enc [B, C, dmodel], nvalid [B] int32
+        device, nvalid on the host); advances state.  The subsampling is the Conformer's on this model's layers (_causal_stem), the position
+        rows are those of each stream's own offset (tfasr_stream_add_pe), and a block is TransformerEncoderMixin.block_fwd at T = C around
+        tfasr_stream_attn_plain_fwd, which also appends the chunk's keys and values to the rings."""
+        m = self.model
+        c, ps = m.cfg, m.ps
+        B, C, hist = self.B, int(c.chunk_size), int(c.history_size)
+        H, dh, d = int(c.num_heads), int(c.head_size), int(c.dmodel)
+        c0, c1 = m.modules["convs"]
 
-@torch.no_grad()
-def transformer_encode_chunk(state, feats, nframes):
-    """One step of the streaming Transformer encoder: feats [B, n <= 4C, F] (compute dtype, device), nframes [B] feature frames that are
-    real per stream (0 = idle, 4C = a full chunk, fewer for a stream's last chunk) -> (enc [B, C, dmodel], nvalid [B] int32 device);
-    advances state.  The subsampling is encode_chunk's on this model's layers, the position rows are those of each stream's own offset
-    (tfasr_stream_add_pe), and a block is TransformerEncoderMixin.block_fwd at T = C around tfasr_stream_attn_plain_fwd, which also
-    appends the chunk's keys and values to the rings."""
-    m = state.model
-    c, ps, dev = m.cfg, m.ps, m.device
-    B, C, hist = state.B, int(c.chunk_size), int(c.history_size)
-    H, dh, d = int(c.num_heads), int(c.head_size), int(c.dmodel)
-    n0 = 4 * C
-    host = [int(v) for v in (nframes.tolist() if isinstance(nframes, torch.Tensor) else nframes)]
-    if feats.shape[0] != B or feats.shape[1] > n0 or len(host) != B or min(host) < 0 or max(host) > feats.shape[1]:
-        raise ValueError(f"encode_chunk takes [B = {B}, <= {n0}, F] feature frames and B frame counts within them")
-    nf = m._h2d(host)
-    cat = torch.zeros(B, n0 + 2, c.num_feature_bins, dtype=m.dtype, device=dev)
-    cat[:, :2] = state.feat_carry
-    cat[:, 2:2 + feats.shape[1]] = feats
-    n1 = (nf + 1) // 2
-    nvalid = ((n1 + 1) // 2).to(torch.int32).contiguous()
-    two = torch.arange(2, device=dev)
-    # the carries move to the last two VALID rows (rows nf, nf + 1 of carry ++ new; nf == 0 picks the carry itself)
-    idx = (nf.long()[:, None] + two[None, :])
-    state.feat_carry.copy_(torch.gather(cat, 1, idx[:, :, None].expand(B, 2, cat.shape[2])))
-    # causal 3x3 stride-2 convs on carry(2) ++ new(n): output 0 belongs to the previous chunk, outputs 1.. are the originals
-    c0, c1 = m.modules["convs"]
-    a1 = K.conv1_fwd(cat, ps.p(c0["name"] + "/w"), ps.p(c0["name"] + "/b"))  # [B, 2C + 1, F1, C0]
-    a1 = K.channel_affine_fwd(a1, *m._affine(c0["bn"]), relu=True, y=a1)
-    F1, C0 = a1.shape[2], a1.shape[3]
-    cat1 = torch.cat([state.conv_carry, a1[:, 1:]], 1).contiguous()  # [B, 2C + 2, F1, C0]
-    idx1 = (n1.long()[:, None] + two[None, :])
-    state.conv_carry.copy_(torch.gather(cat1, 1, idx1[:, :, None, None].expand(B, 2, F1, C0)))
-    col = K.im2col_3x3s2(cat1)
-    T2, F2 = (cat1.shape[1] + 1) // 2, (F1 + 1) // 2  # C + 1
-    a2 = K.matmul(col, ps.w2d(c1["name"] + "/w"), bias=ps.p(c1["name"] + "/b"))
-    a2 = K.channel_affine_fwd(a2, *m._affine(c1["bn"]), relu=True, y=a2)
-    merged = a2.view(B, T2, F2 * c1["cout"])[:, 1:].reshape(B * C, F2 * c1["cout"])
-    x = K.matmul(merged, ps.w2d("enc/linear/w"), bias=ps.p("enc/linear/b"))  # [B*C, d]
-    nv_host = [-(-(-(-t // 2)) // 2) for t in host]
-    state.reserve(max(s + n for s, n in zip(state.host_seen, nv_host)))
-    x = K.stream_add_pe(x.view(B, C, d), state.pe, state.seen, nvalid).view(B * C, d)
-    scale, causal = 1.0 / math.sqrt(dh), bool(c.use_attention_causal_mask)
-    for i, p in enumerate(m.modules["blocks"]):
-        attend = lambda qkv, i=i: K.stream_attn_plain_fwd(qkv, state.kcache[i], state.vcache[i], state.seen, nvalid, B, C, H, dh, hist, scale, causal)
-        x = m.block_fwd(x, p, B, C, None, i, attend=attend)
-    state.seen += nvalid
-    state.host_seen = [s + n for s, n in zip(state.host_seen, nv_host)]
-    return x.view(B, C, d), nvalid
+        def conv_norm1(cat):
+            a1 = K.conv1_fwd(cat, ps.p(c0["name"] + "/w"), ps.p(c0["name"] + "/b"))  # [B, 2C + 1, F1, C0]
+            return K.channel_affine_fwd(a1, *m._affine(c0["bn"]), relu=True, y=a1)
+
+        def conv_norm2(col):
+            a2 = K.matmul(col, ps.w2d(c1["name"] + "/w"), bias=ps.p(c1["name"] + "/b"))
+            return K.channel_affine_fwd(a2, *m._affine(c1["bn"]), relu=True, y=a2)
+
+        x, host, nvalid = _causal_stem(self, feats, nframes, conv_norm1, conv_norm2)
+        nv_host = self._reduced(host)
+        seen = [s + n for s, n in zip(self.host_seen, nv_host)]
+        self.reserve(max(seen))
+        x = K.stream_add_pe(x.view(B, C, d), self.pe, self.seen, nvalid).view(B * C, d)
+        scale, causal = 1.0 / math.sqrt(dh), bool(c.use_attention_causal_mask)
+        for i, p in enumerate(m.modules["blocks"]):
+            attend = lambda qkv, i=i: K.stream_attn_plain_fwd(qkv, self.kcache[i], self.vcache[i], self.seen, nvalid, B, C, H, dh, hist, scale, causal)
+            x = m.block_fwd(x, p, B, C, None, i, attend=attend)
+        self.seen += nvalid
+        self.host_seen = seen
+        return x.view(B, C, d), nvalid, nv_host
 
 
-class JasperStreamState:
+class JasperStreamState(EncoderStream):
     """Encoder state of `batch_size` Jasper streams: per Conv1D layer with more than one tap, the last (K - 1) * dilation rows of its
-    input, [B, (K - 1) * dilation, Cin] in the compute type (zeros = the causal padding of a stream's start)."""
+    input, [B, (K - 1) * dilation, Cin] in the compute type (zeros = the causal padding of a stream's start).  Causal convolutions only:
+    every config streams exactly."""
+    f32_features = True
 
     def __init__(self, model, batch_size):
-        check_streamable(model)
-        self.model, self.B = model, int(batch_size)
+        super().__init__(model, batch_size)
         self.tails = [torch.zeros(self.B, (m["K"] - 1) * m["dilation"], m["cin"], dtype=model.dtype, device=model.device) if m["K"] > 1 else None
                       for m in model.layers]
+
+    step_rule = staticmethod(_strided_step)
+
+    def prepare(self, feats):
+        return self.model._scale_feats(feats)
 
     def _tensors(self):
         return [t for t in self.tails if t is not None]
 
-    reset, export, load = StreamState.reset, StreamState.export, StreamState.load
+    @torch.no_grad()
+    def encode(self, feats, nframes, final=()):
+        """One encoder step: feats [B, n, F] (compute type, device), nframes [B] feature frames that are real per stream (0 = idle; n; fewer
+        for a stream's last step; even everywhere else when the first block strides by 2) -> (enc [B, ceil(n / factor), dmodel], nvalid [B]
+        int32 device, nvalid on the host - None for a device tensor of counts, which is not read back); advances state.  Each layer
+        convolves [tail | rows] with the tail as real left context (tfasr_conv1d_fwd's `lead`), then the tail moves to the last rows that
+        are valid for the stream (tfasr_conv1d_tail_update)."""
+        m = self.model
+        if feats.shape[0] != self.B:
+            raise ValueError(f"encode_chunk takes [B = {self.B}, n, F] feature frames")
+        host, nv = _frame_counts(m, feats, nframes, keep_device=True)
+        x, residuals, starts = feats.contiguous(), [], m._block_starts()
+        for li, mod in enumerate(m.layers):
+            if li in starts:
+                residuals.append(x)
+            tail = self.tails[li]
+            if tail is None:
+                x = m._layer_fwd(x, mod, residuals)
+            else:
+                win = torch.cat([tail, x], 1)
+                x = m._layer_fwd(win, mod, residuals, lead=tail.shape[1])
+                K.conv1d_tail_update(win, nv, tail)
+            if mod["stride"] > 1:
+                nv = ((nv + (mod["stride"] - 1)) // mod["stride"]).to(torch.int32).contiguous()
+        return x, nv, self._reduced(host)
 
 
-@torch.no_grad()
-def jasper_encode_chunk(state, feats, nframes):
-    """One encoder step: feats [B, n, F] (compute type, device), nframes [B] feature frames that are real per stream (0 = idle; n; fewer
-    for a stream's last step; even everywhere else when the first block strides by 2) -> (enc [B, ceil(n / factor), dmodel], nvalid [B]
-    int32 device); advances state.  Each layer convolves [tail | rows] with the tail as real left context (tfasr_conv1d_fwd's `lead`),
-    then the tail moves to the last rows that are valid for the stream (tfasr_conv1d_tail_update)."""
-    m = state.model
-    nf = nframes.to(m.device).to(torch.int32) if isinstance(nframes, torch.Tensor) else m._h2d(list(nframes))
-    nf = nf.contiguous()
-    if feats.shape[0] != state.B:
-        raise ValueError(f"encode_chunk takes [B = {state.B}, n, F] feature frames")
-    x, residuals, starts, nv = feats.contiguous(), [], m._block_starts(), nf
-    for li, mod in enumerate(m.layers):
-        if li in starts:
-            residuals.append(x)
-        tail = state.tails[li]
-        if tail is None:
-            x = m._layer_fwd(x, mod, residuals)
-        else:
-            win = torch.cat([tail, x], 1)
-            x = m._layer_fwd(win, mod, residuals, lead=tail.shape[1])
-            K.conv1d_tail_update(win, nv, tail)
-        if mod["stride"] > 1:
-            nv = ((nv + (mod["stride"] - 1)) // mod["stride"]).to(torch.int32).contiguous()
-    return x, nv
+PERSIST_STREAMS = 64  # tfasr_lstm_infer_fwd's persistent launch takes up to 64 batch rows
 
 
-class DS2StreamState:
+class _CarriedLstm:
+    """h and c [B, P] f32 (h holds numbers of the compute type) of a stack of forward LSTMs, carried from step to step.  The recurrence
+    reads one (h, c) pair and writes another (the library refuses aliases: tfasr_lstm_infer_fwd_state), so every layer owns two pairs and
+    `cur` says which one holds the state; tensors() / reference_states() speak of that one only."""
+
+    def __init__(self, model, batch_size, units):
+        self.hc = [[tuple(torch.zeros(batch_size, P, dtype=torch.float32, device=model.device) for _ in range(2)) for _ in range(2)] for P in units]
+        self.cur = [0] * len(self.hc)
+        # in bf16 more than 64 streams run the recurrence in slices of 64: every slice stays on the persistent launch, the route the
+        # utterance alone takes (the per-step route rounds differently)
+        self.slice = PERSIST_STREAMS if model.dtype != torch.float32 else batch_size
+
+    def tensors(self):
+        return [t for pairs, cur in zip(self.hc, self.cur) for t in pairs[cur]]
+
+    def reference_states(self):
+        """[B, nlayers, 2, P] f32, states ordered (h, c): what the reference's encoders exchange through get_initial_state / call_next
+        (DeepSpeech2Encoder; RnnTransducerEncoder, encoders/rnnt.py:171-211)"""
+        return torch.stack([torch.stack(list(pairs[cur]), 1) for pairs, cur in zip(self.hc, self.cur)], 1)
+
+    def run(self, li, xg, rk, lens):
+        """layer li's recurrence over xg [B, T, 4P] for lens [B] rows per stream, continued from the carried state -> y [B, T, P]"""
+        B, T, P = xg.shape[0], xg.shape[1], xg.shape[2] // 4
+        (h0, c0), (h1, c1) = self.hc[li][self.cur[li]], self.hc[li][self.cur[li] ^ 1]
+        y = torch.empty(B, T, P, dtype=xg.dtype, device=xg.device)
+        for b0 in range(0, B, self.slice):
+            e = min(b0 + self.slice, B)
+            K.lstm_infer_fwd(xg[b0:e], rk, lens[b0:e], y=y[b0:e], state=(h0[b0:e], c0[b0:e]), state_out=(h1[b0:e], c1[b0:e]))
+        self.cur[li] ^= 1
+        return y
+
+
+class DS2StreamState(EncoderStream):
     """Encoder state of `batch_size` streams of the unidirectional DeepSpeech2.  Per stream:
         each conv block   the last kh - 1 rows of its input, [kh - 1, F_in * Cin] in the compute type (zeros = the causal padding)
-        each RnnBlock     h and c [P] f32 (h holds numbers of the compute type), and with a RowConv1D the last K - 1 rows of the LSTM's
-                          output, [K - 1, P] in the compute type
-    The recurrence reads one (h, c) pair and writes another (the library refuses aliases: tfasr_lstm_infer_fwd_state), so every RnnBlock
-    owns two pairs and `cur` says which one holds the state; export / load / reference_states speak of that one only."""
+        each RnnBlock     h and c [P] f32 (_CarriedLstm), and with a RowConv1D the last K - 1 rows of the LSTM's output, [K - 1, P] in the
+                          compute type"""
+    f32_features = True
 
     def __init__(self, model, batch_size):
-        check_streamable(model)
-        self.model, self.B = model, int(batch_size)
+        super().__init__(model, batch_size)
         B, dev, dt, mods = self.B, model.device, model.dtype, model.modules
         shapes = model.cfg.conv_shapes()
         self.conv_tails = [torch.zeros(B, kh - 1, fi * ci, dtype=dt, device=dev) if kh > 1 else None for kh, _kw, ci, _co, _st, _sf, fi, _fo in shapes]
-        self.hc = [[tuple(torch.zeros(B, r["P"], dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)] for r in mods["rnns"]]
-        self.cur = [0] * len(mods["rnns"])
+        self.lstm = _CarriedLstm(model, B, [r["P"] for r in mods["rnns"]])
         self.row_tails = [torch.zeros(B, r["K"] - 1, r["P"], dtype=dt, device=dev) if r["rowconv"] and r["K"] > 1 else None for r in mods["rnns"]]
 
-    def _tensors(self):
-        hc = [t for pairs, cur in zip(self.hc, self.cur) for t in pairs[cur]]
-        return [t for t in self.conv_tails if t is not None] + hc + [t for t in self.row_tails if t is not None]
+    @staticmethod
+    def check(model):
+        """A DeepSpeech2 streams when it is causal throughout: forward LSTMs only and causal convolutions."""
+        c = model.cfg
+        if c.rnn_bidirectional:
+            _refuse(model, "rnn_bidirectional (the backward direction starts at the utterance's last frame)")
+        if c.conv_padding != "causal":
+            _refuse(model, f"conv_padding = {c.conv_padding!r} (a 'same'-padded convolution reads frames that have not arrived yet)")
 
-    reset, export, load = StreamState.reset, StreamState.export, StreamState.load
+    @staticmethod
+    def step_rule(cfg, chunk_frames=None):
+        return _strided_step(cfg, chunk_frames, K.STREAM_MAX_CHUNK, "tfasr_stream_rowconv_fwd's limit")
 
     def reference_states(self):
-        """[B, nlayers, 2, P] f32, states ordered (h, c): what the reference's DeepSpeech2Encoder.get_initial_state / call_next exchange"""
-        return torch.stack([torch.stack(list(pairs[cur]), 1) for pairs, cur in zip(self.hc, self.cur)], 1)
+        return self.lstm.reference_states()
 
+    def prepare(self, feats):  # DeepSpeech2CTC.frontend's route: f32 out of the kernel, then the cast
+        dt = self.model.dtype
+        return feats if dt == torch.float32 else K.cast(feats, torch.empty(feats.shape, dtype=dt, device=feats.device))
 
-DS2_PERSIST_STREAMS = 64  # tfasr_lstm_infer_fwd's persistent launch takes up to 64 batch rows
+    def _tensors(self):
+        return [t for t in self.conv_tails if t is not None] + self.lstm.tensors() + [t for t in self.row_tails if t is not None]
 
-
-@torch.no_grad()
-def ds2_encode_chunk(state, feats, nframes):
-    """One encoder step of the unidirectional DeepSpeech2: feats [B, n, F] (compute type, device; n a multiple of the time reduction
-    factor), nframes [B] feature frames that are real per stream (0 = idle; n; fewer for a stream's last step) -> (enc [B, n / factor,
-    dmodel], nvalid [B] int32 device, reduced over the time strides as cfg.encoder_length does); advances state.  Each conv block
-    convolves [tail | rows] with the tail as real left context (conv2d_fwd's `lead`), then the tail moves to the last rows valid for the
-    stream; each RnnBlock is one GEMM, one recurrence continued from the carried state (tfasr_lstm_infer_fwd_state, lengths = the valid
-    rows) and one tfasr_stream_rowconv_fwd; then the FC blocks.  In bf16 more than 64 streams run the recurrence in slices of 64: every
-    slice stays on the persistent launch, the route the utterance alone takes (the per-step route rounds differently)."""
-    m = state.model
-    c, B = m.cfg, state.B
-    factor = int(c.time_reduction_factor)
-    host = [int(v) for v in (nframes.tolist() if isinstance(nframes, torch.Tensor) else nframes)]
-    if feats.dim() != 3 or feats.shape[0] != B or feats.shape[1] < factor or feats.shape[1] % factor or len(host) != B or min(host) < 0 or \
-            max(host) > feats.shape[1]:
-        raise ValueError(f"encode_chunk takes [B = {B}, n, F] feature frames, n a positive multiple of {factor}, and B frame counts within them")
-    nv = m._h2d(host)
-    x = feats.contiguous()
-    rows = x.shape[1]
-    for mod, tail in zip(m.modules["convs"], state.conv_tails):
-        w, bias, scale, shift = m._conv_consts(mod["name"])
-        shape = (mod["kh"], mod["kw"], mod["cin"], mod["cout"])
-        lead = 0 if tail is None else tail.shape[1]
-        win = x.view(B, rows, -1) if tail is None else torch.cat([tail, x.view(B, rows, -1)], 1)
-        x = K.conv2d_fwd(win.view(B, lead + rows, -1, mod["cin"]), w, shape, bias=bias, scale=scale, shift=shift, relu=True,
-                         strides=(mod["st"], mod["sf"]), padding="causal", lead=lead)
-        if tail is not None:
-            K.conv1d_tail_update(win, nv, tail)
-        if mod["st"] > 1:
-            nv = ((nv + (mod["st"] - 1)) // mod["st"]).to(torch.int32).contiguous()
+    @torch.no_grad()
+    def encode(self, feats, nframes, final=()):
+        """One encoder step of the unidirectional DeepSpeech2: feats [B, n, F] (compute type, device; n a multiple of the time reduction
+        factor), nframes [B] feature frames that are real per stream (0 = idle; n; fewer for a stream's last step) -> (enc [B, n / factor,
+        dmodel], nvalid [B] int32 device, reduced over the time strides as cfg.encoder_length does, nvalid on the host); advances state.
+        Each conv block convolves [tail | rows] with the tail as real left context (conv2d_fwd's `lead`), then the tail moves to the last
+        rows valid for the stream; each RnnBlock is one GEMM, one recurrence continued from the carried state (_CarriedLstm.run, lengths =
+        the valid rows) and one tfasr_stream_rowconv_fwd; then the FC blocks."""
+        m = self.model
+        c, B = m.cfg, self.B
+        factor = int(c.time_reduction_factor)
+        if feats.dim() != 3 or feats.shape[0] != B or feats.shape[1] < factor or feats.shape[1] % factor:
+            raise ValueError(f"encode_chunk takes [B = {B}, n, F] feature frames, n a positive multiple of {factor}")
+        host, nv = _frame_counts(m, feats, nframes)
+        x = feats.contiguous()
         rows = x.shape[1]
-    x = x.view(B, rows, -1)
-    sl = DS2_PERSIST_STREAMS if m.dtype != torch.float32 else B
-    for li, r in enumerate(m.modules["rnns"]):
-        k, b, rk = m._rnn_consts(r)
-        P = r["P"]
-        xg = K.matmul(x.view(B * rows, x.shape[2]), k, bias=b).view(B, rows, 4 * P)
-        (h0, c0), (h1, c1) = state.hc[li][state.cur[li]], state.hc[li][state.cur[li] ^ 1]
-        y = torch.empty(B, rows, P, dtype=xg.dtype, device=xg.device)
-        for b0 in range(0, B, sl):
-            e = min(b0 + sl, B)
-            K.lstm_infer_fwd(xg[b0:e], rk, nv[b0:e], y=y[b0:e], state=(h0[b0:e], c0[b0:e]), state_out=(h1[b0:e], c1[b0:e]))
-        state.cur[li] ^= 1
-        if r["rowconv"]:
-            scale, shift = m._affine(r["rowconv"] + "/bn")
-            y = K.stream_rowconv_fwd(y.view(B * rows, P), state.row_tails[li], m.ps.p(r["rowconv"] + "/conv/w"), scale, shift, nv, B, rows)
-        x = y.view(B, rows, P)
-    for f in m.modules["fcs"]:
-        w, bias = m._fc_consts(f)
-        x = K.conv1d_fwd(x, w, (1, f["din"], f["dout"]), bias=bias, relu=True)
-    return x.view(B, rows, c.dmodel), nv
+        for mod, tail in zip(m.modules["convs"], self.conv_tails):
+            w, bias, scale, shift = m._conv_consts(mod["name"])
+            shape = (mod["kh"], mod["kw"], mod["cin"], mod["cout"])
+            lead = 0 if tail is None else tail.shape[1]
+            win = x.view(B, rows, -1) if tail is None else torch.cat([tail, x.view(B, rows, -1)], 1)
+            x = K.conv2d_fwd(win.view(B, lead + rows, -1, mod["cin"]), w, shape, bias=bias, scale=scale, shift=shift, relu=True,
+                             strides=(mod["st"], mod["sf"]), padding="causal", lead=lead)
+            if tail is not None:
+                K.conv1d_tail_update(win, nv, tail)
+            if mod["st"] > 1:
+                nv = ((nv + (mod["st"] - 1)) // mod["st"]).to(torch.int32).contiguous()
+            rows = x.shape[1]
+        x = x.view(B, rows, -1)
+        for li, r in enumerate(m.modules["rnns"]):
+            k, b, rk = m._rnn_consts(r)
+            P = r["P"]
+            y = self.lstm.run(li, K.matmul(x.view(B * rows, x.shape[2]), k, bias=b).view(B, rows, 4 * P), rk, nv)
+            if r["rowconv"]:
+                scale, shift = m._affine(r["rowconv"] + "/bn")
+                y = K.stream_rowconv_fwd(y.view(B * rows, P), self.row_tails[li], m.ps.p(r["rowconv"] + "/conv/w"), scale, shift, nv, B, rows)
+            x = y.view(B, rows, P)
+        for f in m.modules["fcs"]:
+            w, bias = m._fc_consts(f)
+            x = K.conv1d_fwd(x, w, (1, f["din"], f["dout"]), bias=bias, relu=True)
+        return x.view(B, rows, c.dmodel), nv, self._reduced(host)
 
 
-class RnntStreamState:
-    """Encoder state of `batch_size` streams of the RNN-Transducer encoder.  Per stream:
-        each block       h and c [rnn_units] f32 (h holds numbers of the compute type); the recurrence reads one pair and writes another
-                         (tfasr_lstm_infer_fwd_state refuses aliases), so every block owns two pairs and `cur` says which one is the state
+def _out_rows(fb, n):
+    """rows of the output buffer of a step of n feature frames through the boundary reductions fb (the most frames one step can complete)"""
+    for f in fb:
+        n = -(-(f - 1 + n) // f) if f > 1 else n
+    return n
+
+
+class RnntStreamState(EncoderStream):
+    """Encoder state of `batch_size` streams of the RNN-Transducer encoder (forward LSTMs and row-wise layers only: every config streams
+    exactly).  Per stream:
+        each block       h and c [rnn_units] f32 (_CarriedLstm)
         each reduction   the rows that do not fill a group yet, [factor - 1, width] in the compute type, and their count: INPUT rows in
                          front of a `pre` reduction, PROJECTED rows behind a `post` one
-    The reductions are kept per block BOUNDARY (RnnEncoderMixin.boundary_factors): boundary 0 is block 0's `pre` reduction, boundary i
+    The reductions are kept per block BOUNDARY (rnnt.boundary_factors): boundary 0 is block 0's `pre` reduction, boundary i
     block i - 1's `post` times block i's `pre` (a reduction by f followed by one by g groups f g consecutive rows - zero rows pad either,
     and no layer sits between them), the last one the last block's `post`.  The counts live on the host (`cnt`, the step's launch
-    arguments are computed from them) and ride in export / load as one int32 tensor."""
+    arguments are computed from them) and ride in export / load as one int32 tensor [boundaries, B] behind the carried tensors."""
+    uses_final = True
+    host_tensors = 1
 
     def __init__(self, model, batch_size):
-        check_streamable(model)
-        self.model, self.B = model, int(batch_size)
+        super().__init__(model, batch_size)
         B, dev, dt, mods = self.B, model.device, model.dtype, model.modules
         self.fb = model.boundary_factors()
         widths = [int(model.cfg.num_feature_bins)] + [m["dout"] for m in mods]
-        self.hc = [[tuple(torch.zeros(B, m["P"], dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)] for m in mods]
-        self.cur = [0] * len(mods)
+        self.lstm = _CarriedLstm(model, B, [m["P"] for m in mods])
         self.carry = [torch.zeros(B, f - 1, w, dtype=dt, device=dev) if f > 1 else None for f, w in zip(self.fb, widths)]
         self.cnt = [[0] * B for _ in self.fb]
         self.last_nvalid = [0] * B  # encoder frames the last step gave each stream (host)
 
-    def _tensors(self):
-        hc = [t for pairs, cur in zip(self.hc, self.cur) for t in pairs[cur]]
-        return hc + [t for t in self.carry if t is not None]
+    @staticmethod
+    def step_rule(cfg, chunk_frames=None):
+        """a step is `chunk_frames` feature frames, any positive number: what does not fill a reduction's group is carried, so the encoder
+        frames a step gives depend on the state (encode's host list), out_rows(chunk_frames) at the most"""
+        n = int(chunk_frames if chunk_frames is not None else 32)
+        if n < 1:
+            raise ValueError(f"stream: chunk_frames {n} must be positive")
+        return n, _out_rows(boundary_factors(rnnt_modules(cfg)), n), cfg.encoder_length
 
-    def reset(self, rows=None):
-        StreamState.reset(self, rows)
+    def _tensors(self):
+        return self.lstm.tensors() + [t for t in self.carry if t is not None]
+
+    def _host_reset(self, rows):
         for c in self.cnt:
-            for b in (range(self.B) if rows is None else rows):
+            for b in rows:
                 c[b] = 0
 
-    def export(self):
-        """the carried tensors as one flat list (a copy): every block's (h, c), the leftover rows, and the counts [boundaries, B] int32"""
-        dev = self.model.device
-        return [t.clone() for t in self._tensors()] + [torch.tensor(self.cnt, dtype=torch.int32, device=dev)]
+    def _host_export(self):
+        return [torch.tensor(self.cnt, dtype=torch.int32, device=self.model.device)]
 
-    def load(self, tensors):
-        StreamState.load(self, tensors[:-1])
-        cnt = tensors[-1].cpu().tolist()
+    def _host_load(self, tensors):
+        cnt = tensors[0].cpu().tolist()
         if len(cnt) != len(self.fb) or any(len(r) != self.B or min(r) < 0 or max(r) >= max(f, 1) for r, f in zip(cnt, self.fb)):
             raise ValueError("encoder state of another model")
         self.cnt = [[int(v) for v in r] for r in cnt]
 
     def reference_states(self):
-        """[B, nlayers, 2, rnn_units] f32, states ordered (h, c): what the reference's RnnTransducerEncoder.get_initial_state / call_next
-        exchange (encoders/rnnt.py:171-211)"""
-        return torch.stack([torch.stack(list(pairs[cur]), 1) for pairs, cur in zip(self.hc, self.cur)], 1)
+        return self.lstm.reference_states()
 
     def out_rows(self, n):
         """rows of the step's output buffer for n feature frames (the most frames one step can complete)"""
-        rows = n
-        for f in self.fb:
-            rows = -(-(f - 1 + rows) // f) if f > 1 else rows
-        return rows
+        return _out_rows(self.fb, n)
+
+    @torch.no_grad()
+    def encode(self, feats, nframes, final=()):
+        """One encoder step of the RNN-Transducer: feats [B, n, F] (compute type, device), nframes [B] feature frames that are real per
+        stream (0 = idle .. n), final = the streams whose utterance ends with these frames -> (enc [B, out_rows(n), cfg.dmodel], nvalid [B]
+        int32 device, nvalid on the host = last_nvalid); advances state.  Every stream advances by its own number of frames: in front of
+        each reduction its carried rows and its new rows form groups, whole groups go on, the rest is carried; a final stream's last group
+        is filled with zero rows, as tf.pad fills it offline.  Per block: one GEMM, the recurrence continued from the carried state
+        (_CarriedLstm.run, lengths = the stream's groups), and tfasr_rnnt_block_tail_fwd writing each stream's rows behind the rows the next
+        reduction carries (`off`).  A boundary no tail kernel writes - block 0's `pre` reduction, the two-launch tail - is assembled by a
+        gather instead."""
+        m = self.model
+        c, B, mods, fb = m.cfg, self.B, m.modules, self.fb
+        if feats.dim() != 3 or feats.shape[0] != B or feats.shape[1] < 1:
+            raise ValueError(f"encode_chunk takes [B = {B}, n >= 1, F] feature frames")
+        host, _ = _frame_counts(m, feats, nframes, upload=False)
+        fin = [False] * B
+        for b in final:
+            fin[int(b)] = True
+        # everything the launches need is known on the host: per boundary the carried count (the tail's `off`), the rows that enter (to zero
+        # a final stream's padding), the groups that go on (the block's lengths) and where the new carry starts
+        L = len(mods)
+        plan, come = [], host
+        for i, f in enumerate(fb):
+            cnt = self.cnt[i] if f > 1 else [0] * B
+            avail = [a + b for a, b in zip(cnt, come)]
+            groups = [(-(-a // f) if fin[b] else a // f) for b, a in enumerate(avail)]
+            plan.append(dict(cnt=list(cnt), avail=avail, groups=groups, start=[g * f for g in groups]))
+            if f > 1:
+                self.cnt[i] = [0 if fin[b] else a - g * f for b, (a, g) in enumerate(zip(avail, groups))]
+            come = groups
+        vec = m._h2d(np.asarray([p[k] for p in plan for k in ("cnt", "groups", "start")], np.int32))
+        dv = lambda i, k: vec[3 * i + ("cnt", "groups", "start").index(k)]
+
+        def reduce(i, x):
+            """boundary i over x [B, R, w] (R % f == 0, each stream's carried rows in front): -> [B, R / f, f w]; moves the carry"""
+            f = fb[i]
+            if f == 1:
+                return x
+            R, w = x.shape[1], x.shape[2]
+            for b in range(B):  # tf.pad's zero rows of a last, partial group
+                lo, hi = plan[i]["avail"][b], plan[i]["start"][b]
+                if fin[b] and hi > lo:
+                    x[b, lo:hi].zero_()
+            K.conv1d_tail_update(x, dv(i, "start"), self.carry[i])
+            return x.view(B, R // f, f * w)
+
+        x = feats.contiguous()
+        if fb[0] > 1:
+            x = _place(self.carry[0], dv(0, "cnt"), x, -(-(fb[0] - 1 + x.shape[1]) // fb[0]) * fb[0])
+        for i, mod in enumerate(mods):
+            x = reduce(i, x)
+            T, P, N = x.shape[1], mod["P"], mod["dout"]
+            lens = dv(i, "groups")
+            ps, p = m.ps, mod["name"] + "/lstm"
+            xg = K.matmul(x.reshape(B * T, x.shape[2]), ps.w2d(p + "/k"), bias=ps.p(p + "/b")).view(B, T, 4 * P)
+            y = self.lstm.run(i, xg, ps.w(p + "/rk").view(1, P, 4 * P), lens)
+            f = fb[i + 1]
+            Tpad = -(-(f - 1 + T) // f) * f if f > 1 else T
+            if m._fused_tail(mod):
+                out = torch.empty(B, Tpad, N, dtype=y.dtype, device=y.device)
+                if f > 1:
+                    out[:, :f - 1].copy_(self.carry[i + 1])
+                x, _ = m.tail_fwd(y, mod, lens, Tpad, 1, off=dv(i + 1, "cnt") if f > 1 else None, out=out)
+            else:
+                x, _ = m.tail_fwd(y, mod, lens, T, 1)
+                if f > 1:
+                    x = _place(self.carry[i + 1], dv(i + 1, "cnt"), x, Tpad)
+        x = reduce(L, x)
+        self.last_nvalid = plan[L]["groups"]
+        return x.reshape(B, x.shape[1], c.dmodel), dv(L, "groups"), list(self.last_nvalid)
 
 
 def _place(carry, cnt_dev, new, R):
@@ -519,86 +672,29 @@ def _place(carry, cnt_dev, new, R):
     return torch.gather(cat, 1, idx[:, :, None].expand(B, R, w))
 
 
-RNNT_PERSIST_STREAMS = 64  # tfasr_lstm_infer_fwd's persistent launch takes up to 64 batch rows
+STREAM_STATES = {"conformer": StreamState, "transformer": TransformerStreamState, "jasper": JasperStreamState, "deepspeech2": DS2StreamState,
+                 "rnnt": RnntStreamState}
 
 
-@torch.no_grad()
-def rnnt_encode_chunk(state, feats, nframes, final=()):
-    """One encoder step of the RNN-Transducer: feats [B, n, F] (compute type, device), nframes [B] feature frames that are real per stream
-    (0 = idle .. n), final = the streams whose utterance ends with these frames -> (enc [B, state.out_rows(n), cfg.dmodel], nvalid [B]
-    int32 device); advances state.  Every stream advances by its own number of frames: in front of each reduction its carried rows and
-    its new rows form groups, whole groups go on, the rest is carried; a final stream's last group is filled with zero rows, as tf.pad
-    fills it offline.  Per block: one GEMM, the recurrence continued from the carried state (tfasr_lstm_infer_fwd_state, lengths = the
-    stream's groups), and tfasr_rnnt_block_tail_fwd writing each stream's rows behind the rows the next reduction carries (`off`).
-    A boundary no tail kernel writes - block 0's `pre` reduction, the two-launch tail - is assembled by a gather instead.
-    In bf16 more than 64 streams run the recurrence in slices of 64 (the persistent launch, the route the utterance alone takes)."""
-    m = state.model
-    c, B, mods, fb = m.cfg, state.B, m.modules, state.fb
-    host = [int(v) for v in (nframes.tolist() if isinstance(nframes, torch.Tensor) else nframes)]
-    if feats.dim() != 3 or feats.shape[0] != B or feats.shape[1] < 1 or len(host) != B or min(host) < 0 or max(host) > feats.shape[1]:
-        raise ValueError(f"encode_chunk takes [B = {B}, n >= 1, F] feature frames and B frame counts within them")
-    fin = [False] * B
-    for b in final:
-        fin[int(b)] = True
-    # everything the launches need is known on the host: per boundary the carried count (the tail's `off`), the rows that enter (to zero
-    # a final stream's padding), the groups that go on (the block's lengths) and where the new carry starts
-    L = len(mods)
-    plan, come = [], host
-    for i, f in enumerate(fb):
-        cnt = state.cnt[i] if f > 1 else [0] * B
-        avail = [a + b for a, b in zip(cnt, come)]
-        groups = [(-(-a // f) if fin[b] else a // f) for b, a in enumerate(avail)]
-        plan.append(dict(cnt=list(cnt), avail=avail, groups=groups, start=[g * f for g in groups]))
-        if f > 1:
-            state.cnt[i] = [0 if fin[b] else a - g * f for b, (a, g) in enumerate(zip(avail, groups))]
-        come = groups
-    vec = m._h2d(np.asarray([p[k] for p in plan for k in ("cnt", "groups", "start")], np.int32))
-    dv = lambda i, k: vec[3 * i + ("cnt", "groups", "start").index(k)]
+def check_streamable(model):
+    """-> the state class of the model's encoder (STREAM_STATES), after that class's refusal rule"""
+    cls = STREAM_STATES.get(getattr(model.cfg, "encoder", "conformer"))
+    if cls is None:
+        raise ValueError("streaming needs a Conformer encoder: ContextNet's squeeze-and-excite is a mean over the whole utterance")
+    cls.check(model)
+    return cls
 
-    def reduce(i, x):
-        """boundary i over x [B, R, w] (R % f == 0, each stream's carried rows in front): -> [B, R / f, f w]; moves the carry"""
-        f = fb[i]
-        if f == 1:
-            return x
-        R, w = x.shape[1], x.shape[2]
-        for b in range(B):  # tf.pad's zero rows of a last, partial group
-            lo, hi = plan[i]["avail"][b], plan[i]["start"][b]
-            if fin[b] and hi > lo:
-                x[b, lo:hi].zero_()
-        K.conv1d_tail_update(x, dv(i, "start"), state.carry[i])
-        return x.view(B, R // f, f * w)
 
-    x = feats.contiguous()
-    if fb[0] > 1:
-        x = _place(state.carry[0], dv(0, "cnt"), x, -(-(fb[0] - 1 + x.shape[1]) // fb[0]) * fb[0])
-    sl = RNNT_PERSIST_STREAMS if m.dtype != torch.float32 else B
-    for i, mod in enumerate(mods):
-        x = reduce(i, x)
-        T, P, N = x.shape[1], mod["P"], mod["dout"]
-        lens = dv(i, "groups")
-        ps, p = m.ps, mod["name"] + "/lstm"
-        xg = K.matmul(x.reshape(B * T, x.shape[2]), ps.w2d(p + "/k"), bias=ps.p(p + "/b")).view(B, T, 4 * P)
-        rk = ps.w(p + "/rk").view(1, P, 4 * P)
-        (h0, c0), (h1, c1) = state.hc[i][state.cur[i]], state.hc[i][state.cur[i] ^ 1]
-        y = torch.empty(B, T, P, dtype=xg.dtype, device=xg.device)
-        for b0 in range(0, B, sl):
-            e = min(b0 + sl, B)
-            K.lstm_infer_fwd(xg[b0:e], rk, lens[b0:e], y=y[b0:e], state=(h0[b0:e], c0[b0:e]), state_out=(h1[b0:e], c1[b0:e]))
-        state.cur[i] ^= 1
-        f = fb[i + 1]
-        Tpad = -(-(f - 1 + T) // f) * f if f > 1 else T
-        if m._fused_tail(mod):
-            out = torch.empty(B, Tpad, N, dtype=y.dtype, device=y.device)
-            if f > 1:
-                out[:, :f - 1].copy_(state.carry[i + 1])
-            x, _ = m.tail_fwd(y, mod, lens, Tpad, 1, off=dv(i + 1, "cnt") if f > 1 else None, out=out)
-        else:
-            x, _ = m.tail_fwd(y, mod, lens, T, 1)
-            if f > 1:
-                x = _place(state.carry[i + 1], dv(i + 1, "cnt"), x, Tpad)
-    x = reduce(L, x)
-    state.last_nvalid = list(plan[L]["groups"])
-    return x.reshape(B, x.shape[1], c.dmodel), dv(L, "groups")
+def _twin(model, precision):
+    return model.inference_twin() if (precision or model.decode_precision) == "f32" else model
+
+
+def encode_chunk(state, feats, nframes, final=()):
+    """One encoder step of any state (its `encode`, without the host list): -> (enc, nvalid [B] int32 device); advances state."""
+    return state.encode(feats, nframes, final)[:2]
+
+
+transformer_encode_chunk = jasper_encode_chunk = ds2_encode_chunk = rnnt_encode_chunk = encode_chunk
 
 
 def check_stream_args(batch_size=1, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
@@ -688,43 +784,10 @@ class StreamingRecognizer:
         self.B = int(batch_size)
         self.max_tokens_per_frame = int(max_tokens_per_frame)
         c = model.cfg
-        self.jasper = getattr(c, "encoder", "conformer") == "jasper"
-        self.ds2 = getattr(c, "encoder", "conformer") == "deepspeech2"
-        self.rnnt = getattr(c, "encoder", "conformer") == "rnnt"
-        self._encode = encode_chunk
-        if self.rnnt:
-            # a step is `chunk_frames` feature frames, any positive number: what does not fill a reduction's group is carried, so the
-            # encoder frames a step gives depend on the state (state.last_nvalid), state.out_rows(chunk_frames) at the most
-            self.chunk_frames = int(chunk_frames if chunk_frames is not None else 32)
-            if self.chunk_frames < 1:
-                raise ValueError(f"stream: chunk_frames {self.chunk_frames} must be positive")
-            self.state, self._encode = RnntStreamState(self.enc_model, batch_size), rnnt_encode_chunk
-            self.C = self.state.out_rows(self.chunk_frames)
-            self._reduce = c.encoder_length
-        elif self.jasper or self.ds2:
-            self._encode = jasper_encode_chunk if self.jasper else ds2_encode_chunk
-            # a step is `chunk_frames` feature frames -> chunk_frames / factor encoder frames (a stream's last step: ceil of what is left)
-            factor = int(c.time_reduction_factor)
-            self.chunk_frames = int(chunk_frames if chunk_frames is not None else 32)
-            if self.chunk_frames < factor or self.chunk_frames % factor:
-                raise ValueError(f"stream: chunk_frames {self.chunk_frames} must be a positive multiple of the time reduction factor {factor}")
-            if self.ds2 and self.chunk_frames // factor > K.STREAM_MAX_CHUNK:
-                raise ValueError(f"stream: chunk_frames {self.chunk_frames} is more than {K.STREAM_MAX_CHUNK} encoder frames a step "
-                                 "(tfasr_stream_rowconv_fwd's limit)")
-            self.state = (JasperStreamState if self.jasper else DS2StreamState)(self.enc_model, batch_size)
-            self.C = self.chunk_frames // factor
-            self._reduce = (lambda t: -(-t // factor)) if self.jasper else c.encoder_length
-        else:
-            if chunk_frames is not None:
-                raise ValueError("stream: chunk_frames belongs to the Jasper and DeepSpeech2 sessions; a Conformer's step is 4 * chunk_size "
-                                 "feature frames")
-            if getattr(c, "encoder", "conformer") == "transformer":  # the Conformer's step and frame reduction, its own encoder state
-                self.state, self._encode = TransformerStreamState(self.enc_model, batch_size), transformer_encode_chunk
-            else:
-                self.state = StreamState(self.enc_model, batch_size)
-            self.C = int(c.chunk_size)
-            self.chunk_frames = 4 * self.C
-            self._reduce = lambda t: -(-(-(-t // 2)) // 2)
+        # everything the session knows about the encoder is its state class (EncoderStream): the refusal rule, the step rule, the state
+        cls = check_streamable(self.enc_model)
+        self.chunk_frames, self.C, self._reduce = cls.step_rule(c, chunk_frames)
+        self.state = cls(self.enc_model, batch_size)
         self.step, self.flen = int(c.frame_step), int(c.frame_length)
         self.chunk_samples = self.step * (self.chunk_frames - 1) + self.flen  # samples a full chunk's feature frames cover
         self.ctc = c.head == "ctc"
@@ -743,7 +806,7 @@ class StreamingRecognizer:
             self.emitted = [0] * B  # feature frames consumed
             self.frames = [0] * B  # encoder frames emitted
             self.finished = [False] * B
-            self.flushed = [False] * B  # (RNN-Transducer) the encoder's carried rows went out with a final step
+            self.flushed = [False] * B  # (state.uses_final) the encoder's carried rows went out with a final step
             self.beam = None
             if self.detail:  # the record of every stream since its reset: what recognized() returns
                 self.record = [_TokenRecord() for _ in range(B)]
@@ -794,19 +857,20 @@ class StreamingRecognizer:
         self.state.load(tensors)
 
     # ------------------------------------------------------------------------------------------- steps
-    def _ready(self, b, flush):
-        """feature frames stream b can give to the next chunk, and the samples they consume"""
-        n = len(self.buf[b])
+    def _take(self, n, total, emitted, flush):
+        """the chunk-taking rule: the feature frames a stream gives the next step from n buffered samples - a full chunk, or under `flush`
+        what its `total` samples still hold behind the `emitted` frames"""
         if n >= self.chunk_samples:
             return self.chunk_frames
-        if flush and not self.finished[b]:
-            left = -(-self.total[b] // self.step) - self.emitted[b]
-            return min(left, self.chunk_frames)
-        return 0
+        return min(-(-total // self.step) - emitted, self.chunk_frames) if flush else 0
+
+    def _ready(self, b, flush):
+        """feature frames stream b can give to the next chunk"""
+        return self._take(len(self.buf[b]), self.total[b], self.emitted[b], flush and not self.finished[b])
 
     @torch.no_grad()
     def _run(self, flush_rows=()):
-        m, em, dev, B = self.model, self.enc_model, self.model.device, self.B
+        m, em, dev, B, st = self.model, self.enc_model, self.model.device, self.B, self.state
         c = m.cfg
         new = [[] for _ in range(B)]
         mark = [len(r.tokens) for r in self.record] if self.detail else None  # where this call's tokens begin in the record
@@ -814,7 +878,7 @@ class StreamingRecognizer:
         while True:
             take = [self._ready(b, b in flush_rows) for b in range(B)]
             final = ()
-            if self.rnnt:  # the streams whose utterance ends with this step: their carried rows go out, the last group zero-padded
+            if st.uses_final:  # the streams whose utterance ends with this step: their carried rows go out, the last group zero-padded
                 final = [b for b in flush_rows if not self.finished[b] and not self.flushed[b]
                          and -(-self.total[b] // self.step) - self.emitted[b] - take[b] == 0]
             if max(take) == 0 and not final:
@@ -827,16 +891,13 @@ class StreamingRecognizer:
                     seg = self.buf[b][:self.chunk_samples]
                     sig[b, :len(seg)] = seg
                     nlen[b] = len(seg)
-            if max(take) == 0:  # (RNN-Transducer) nothing but carried encoder rows is left to flush: no frame is read
+            if max(take) == 0:  # (a final step) nothing but carried encoder rows is left to flush: no frame is read
                 feats = torch.zeros(B, self.chunk_frames, c.num_feature_bins, dtype=em.dtype, device=dev)
             else:
                 feats = K.logmel_stream(em._h2d(torch.from_numpy(sig), torch.float32), em._h2d(nlen), em._h2d(torch.from_numpy(self.prev.copy()), torch.float32),
                                         em._h2d(self.has_prev.copy()), self.chunk_frames, window, melw, band, c.frame_step, c.nfft, c.preemphasis,
-                                        c.epsilon, torch.float32 if self.jasper or self.ds2 else em.dtype)
-            if self.jasper:
-                feats = em._scale_feats(feats)
-            elif self.ds2 and em.dtype != torch.float32:  # DeepSpeech2CTC.frontend's route: f32 out of the kernel, then the cast
-                feats = K.cast(feats, torch.empty(feats.shape, dtype=em.dtype, device=feats.device))
+                                        c.epsilon, torch.float32 if st.f32_features else em.dtype)
+                feats = st.prepare(feats)
             for b in range(B):
                 if take[b]:
                     used = take[b] * self.step
@@ -844,14 +905,9 @@ class StreamingRecognizer:
                         self.prev[b], self.has_prev[b] = self.buf[b][used - 1], 1
                     self.buf[b] = self.buf[b][used:]
                     self.emitted[b] += take[b]
-            if self.rnnt:
-                enc, nvalid = self._encode(self.state, feats, take, final)
-                nv = list(self.state.last_nvalid)
-                for b in final:
-                    self.flushed[b] = True
-            else:
-                enc, nvalid = self._encode(self.state, feats, take)
-                nv = [self._reduce(t) for t in take]
+            enc, nvalid, nv = st.encode(feats, take, final)
+            for b in final:
+                self.flushed[b] = True
             if self.encoded_log is not None:
                 self.encoded_log.append((enc, nv))
             self.chunks_run += 1
@@ -907,12 +963,12 @@ class StreamingRecognizer:
             n, emitted, frames = len(self.buf[b]) + (more[b] if more else 0), self.emitted[b], self.frames[b]
             total = self.total[b] + (more[b] if more else 0)
             flush = b in flush_rows and not self.finished[b]
-            while True:  # the chunks _run will take from this stream (_ready's rule)
-                take = self.chunk_frames if n >= self.chunk_samples else (min(-(-total // self.step) - emitted, self.chunk_frames) if flush else 0)
+            while True:  # the chunks _run will take from this stream
+                take = self._take(n, total, emitted, flush)
                 if take <= 0:
                     break
                 n, emitted, frames = max(n - take * self.step, 0), emitted + take, frames + self._reduce(take)
-            if self.rnnt:  # a step's frames depend on the carried rows; all steps together never give more than the utterance so far
+            if self.state.uses_final:  # a step's frames depend on the carried rows; all steps together never give more than the utterance so far
                 frames = self._reduce(emitted)
             if frames > self.max_frames:
                 raise RuntimeError(f"stream {b} would pass max_frames = {self.max_frames} encoder frames ({self.frames[b]} so far, {frames} after "

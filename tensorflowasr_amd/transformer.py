@@ -100,20 +100,6 @@ class TransformerEncoderMixin:
         streaming.check_streamable(self)
         return streaming.StreamingRecognizer(self, batch_size, precision, max_tokens_per_frame, beam_width, max_frames)
 
-    def stream_state(self, batch_size=1, precision=None):
-        """Encoder state of `batch_size` streams for encode_chunk (streaming.TransformerStreamState).  precision as encode."""
-        from . import streaming
-
-        streaming.check_streamable(self)
-        return streaming.TransformerStreamState(streaming._twin(self, precision), batch_size)
-
-    def encode_chunk(self, state, feats, nframes):
-        """One chunk of the streaming encoder: feats [B, n <= 4 chunk_size, F], nframes [B] -> (enc [B, chunk_size, dmodel], nvalid [B])."""
-        from . import streaming
-
-        streaming.check_streamable(self)
-        return streaming.transformer_encode_chunk(state, feats, nframes)
-
     def _encoder_length(self, t):
         return self.cfg.encoder_length(t)
 

@@ -518,3 +518,55 @@ def test_encoder_state_travels_through_the_predict_schemas(dev):
     rec2.set_encoder_state(out.next_encoder_states)
     for a, b in zip(rec2.encoder_state(), st):
         assert torch.equal(a, b)
+
+
+# =============================================================================================== the encoder-stream interface
+class _InterfaceOnly:
+    """an encoder state that shows the session the members of streaming.EncoderStream's interface and nothing else"""
+    MEMBERS = ("check", "step_rule", "f32_features", "prepare", "encode", "uses_final", "reset", "export", "load")
+
+    def __init__(self, state):
+        self._state = state
+
+    def __getattr__(self, name):
+        if name not in self.MEMBERS:
+            raise AttributeError(f"the session asked its encoder state for {name!r}, which is not in the interface")
+        return getattr(self._state, name)
+
+
+def test_the_session_reads_its_encoder_through_the_interface_alone(dev):
+    """a Jasper session whose state is wrapped so that only the interface's members exist gives what a plain session gives: every
+    StreamOutput, the encoder frames and the encoder state, under ragged lengths and pieces of 1 and 4001 samples"""
+    from test_jasper_gpu import build
+
+    model = build(dev, torch.bfloat16)
+    model.decode_precision = "bf16"
+    rng = np.random.default_rng(5)
+    sigs = [np.clip(rng.standard_normal(n) * 0.1, -1, 1).astype(np.float32) for n in (8000, 6001)]  # 0.5 s, and a ragged end
+    for piece in (1, 4001):
+        recs = [model.stream(2, chunk_frames=8, precision="bf16") for _ in range(2)]
+        recs[0].state = _InterfaceOnly(recs[0].state)
+        with pytest.raises(AttributeError, match="not in the interface"):
+            recs[0].state.tails
+        outs = []
+        for rec in recs:
+            rec.encoded_log = []
+            got, pos = [], [0, 0]
+            while any(pos[b] < len(sigs[b]) for b in range(2)):
+                x, lens = np.zeros((2, piece), np.float32), []
+                for b in range(2):
+                    seg = sigs[b][pos[b]:pos[b] + piece]
+                    x[b, :len(seg)] = seg
+                    lens.append(len(seg))
+                    pos[b] += len(seg)
+                got.append(rec.accept(torch.from_numpy(x), lens))
+            got.append(rec.finish())
+            outs.append(got)
+        assert len(outs[0]) == len(outs[1]) and recs[0].chunks_run == recs[1].chunks_run > 4
+        for a, b in zip(*outs):
+            assert all(torch.equal(x, y) for x, y in zip(a, b))
+        assert outs[0][-1].frames.tolist() == [25, 19]  # ceil(50 / 2) and ceil(38 / 2) encoder frames
+        for (ea, na), (eb, nb) in zip(recs[0].encoded_log, recs[1].encoded_log):
+            assert na == nb and torch.equal(ea, eb)
+        sa, sb = recs[0].encoder_state(), recs[1].encoder_state()
+        assert len(sa) == len(sb) > 0 and all(torch.equal(x, y) for x, y in zip(sa, sb))
