@@ -14,7 +14,8 @@
  *     to the device that is current on this thread".  State the library keeps: (i) the four switches of the table below that it reads itself
  *     (once, function-local statics; TFASR_ATTN_BWD_QK at every call, so that one process can compare both routes); (ii) the block executor's internal second stream + events per device (tfasr_block_io.wgrad_slot), the
  *     persistent-LSTM policy (tfasr_lstm_set_persist), and one flag set around a grouped launch that shares the chip with another stream;
- *     (iii) two measurement aids: a host-side launch counter (tfasr_launch_count) and the optional event record of tfasr_block_wgrad_probe -
+ *     (iii) two measurement aids: a host-side launch counter (tfasr_launch_count) and the optional event record of tfasr_block_wgrad_probe;
+ *     (iv) per device, the compute-unit count and the dynamic-LDS limit already granted to each kernel (looked up, not asked again) -
  *     all of them assume what the rest of the design assumes anyway: ONE host thread queues the launches of a device.  Results never
  *     depend on any of it.  (The Python package also sets GPU_MAX_HW_QUEUES=8 at import unless the user chose a value - the HIP
  *     runtime's own switch.)
@@ -237,6 +238,31 @@ int tfasr_gemm(const tfasr_gemm_args* args, void* stream);
    f32, no batch, no epilogue terms; split_k is chosen for the group): the Dense-layer gradients of one Conformer block
    (models/encoders/conformer.py:101-109,209-239,366-377 under keras autodiff).  Anything else is launched one by one, in order. */
 int tfasr_gemm_group(const tfasr_gemm_args* args, int n, void* stream);
+
+/* Which kernel tfasr_gemm takes for a call (added under ABI 44; host-only queries in the manner of tfasr_block_workspace_sizes: nothing
+   is launched and no data pointer of `args` is dereferenced - only their null-ness and alignment count).  The rules themselves:
+   tensorflowasr_amd/csrc/gemm_route.h. */
+typedef enum { TFASR_GEMM_GENERIC = 0 /* gemm_kernel (gemm.hip): any alignment, f32 */, TFASR_GEMM_FAST_PERSISTENT = 1, TFASR_GEMM_FAST_ONE = 2 /* one tile per workgroup */,
+               TFASR_GEMM_FAST_SEG = 3 /* K-segments */, TFASR_GEMM_FAST_KTAB = 4 /* K-block table */, TFASR_GEMM_BIG = 5 /* 256-row tiles */ } tfasr_gemm_family_t;
+/* epilogue terms compiled into the chosen instantiation (tfasr_gemm_route_info.epi; TFASR_GEMM_E_GEN: every term behind a runtime branch) */
+enum { TFASR_GEMM_E_ACT = 1, TFASR_GEMM_E_DACT = 2, TFASR_GEMM_E_DROP = 4, TFASR_GEMM_E_RES = 8, TFASR_GEMM_E_WS = 16, TFASR_GEMM_E_CSUM = 32,
+       TFASR_GEMM_E_LSE = 64, TFASR_GEMM_E_RGRAD = 128, TFASR_GEMM_E_GEN = 256, TFASR_GEMM_E_BNS = 512, TFASR_GEMM_E_MUL = 1024 };
+typedef struct {
+  int status;               /* tfasr_status_t tfasr_gemm returns for these arguments; the other fields are meaningful for SUCCESS only */
+  int family;               /* tfasr_gemm_family_t */
+  int trans_a, trans_b;
+  int tile_n;               /* columns per tile: 64 | 128 (128-row tiles), 256 | 320 (256-row tiles) */
+  int epi;                  /* TFASR_GEMM_E_* bits */
+  int tr, seg;              /* 256-row kernels: transposed accumulators in the epilogue; K-segment variant (also set for TFASR_GEMM_FAST_SEG) */
+  int tiles_x, tiles_y, tiles_z; /* the tile grid the kernel walks: columns, rows, batches x k-slices */
+  int workgroups;           /* workgroups of the product's launch */
+  int lds_bytes;            /* dynamic LDS per workgroup */
+  int launches;             /* 1; 2 with the separate column-sum pass (generic kernels) or the workspace split-K reduce */
+} tfasr_gemm_route_info;
+/* ncu: compute units to decide for; <= 0: those of the current device.  Returns out->status (INVALID_VALUE for a null args / out). */
+int tfasr_gemm_route(const tfasr_gemm_args* args, int ncu, tfasr_gemm_route_info* out);
+/* the same for tfasr_gemm_group: its status, and in *launches the launches it queues (one per chunk of 10 that qualifies, else one by one) */
+int tfasr_gemm_group_route(const tfasr_gemm_args* args, int n, int ncu, int* launches);
 
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (keras LayerNormalization eps 1e-3: conformer.py:59-64, base_transducer.py:88-93) and

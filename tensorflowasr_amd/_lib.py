@@ -40,6 +40,16 @@ class GemmArgs(Structure):
     ]
 
 
+class GemmRouteInfo(Structure):
+    """tfasr_gemm_route_info: the kernel tfasr_gemm takes for a call (tfasr_gemm_route)"""
+    _fields_ = [
+        ("status", c_int), ("family", c_int), ("trans_a", c_int), ("trans_b", c_int), ("tile_n", c_int), ("epi", c_int), ("tr", c_int), ("seg", c_int),
+        ("tiles_x", c_int), ("tiles_y", c_int), ("tiles_z", c_int), ("workgroups", c_int), ("lds_bytes", c_int), ("launches", c_int),
+    ]
+
+
+GEMM_GENERIC, GEMM_FAST_PERSISTENT, GEMM_FAST_ONE, GEMM_FAST_SEG, GEMM_FAST_KTAB, GEMM_BIG = range(6)  # tfasr_gemm_family_t
+
 BLOCK_PARAM_NAMES = [  # order of tfasr_block_param_t (include/tfasr_hip.h); names relative to "enc/block{i}/"
     "ff1/ln/g", "ff1/ln/b", "ff1/d1/w", "ff1/d1/b", "ff1/d2/w", "ff1/d2/b",
     "ff2/ln/g", "ff2/ln/b", "ff2/d1/w", "ff2/d1/b", "ff2/d2/w", "ff2/d2/b",

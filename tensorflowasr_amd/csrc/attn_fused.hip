@@ -1453,18 +1453,13 @@ extern "C" int tfasr_relattn_fused_bwd_q3(const void* qkv, const float* ubias, c
       (lds & 7) || lddq < (long)H * dh || (lddq & 3) || ((qu == nullptr) != (qv == nullptr)) || (((uintptr_t)qu | (uintptr_t)qv) & 15))
     return TFASR_STATUS_INVALID_VALUE;
   if (dtype != TFASR_BF16 || dh != DH) return TFASR_STATUS_UNSUPPORTED;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)relattn_fused_bwd_qT_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, qt_smem(1));
-    (void)hipFuncSetAttribute((const void*)relattn_fused_bwd_qT_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, qt_smem(1));
-    attr_done = true;
-  }
   const dim3 gq(attn_grid_size(B, H, (T + BI - 1) / BI));
 #define TFASR_QT_LAUNCH(ST)                                                                                                                  \
+  tfasr_dynamic_lds<relattn_fused_bwd_qT_kernel<ST, 1>>(qt_smem(1));                                                                        \
   TFASR_KLAUNCH((relattn_fused_bwd_qT_kernel<ST, 1>), gq, dim3(256), qt_smem(1), (hipStream_t)stream_, (const bf16_t*)qkv, ubias, vbias,   \
                      (const bf16_t*)pext, lengths, (const bf16_t*)o, (const bf16_t*)dout, lse, (bf16_t*)dq, (bf16_t*)ds, dvec, B, H, T, lds, scale, \
                      use_mask, dpext, lddq, du, dv, chunk > 0 ? chunk : 0, chunk > 0 ? hist : 0, (bf16_t*)qu, (bf16_t*)qv)
-  if (chunk > 0) TFASR_QT_LAUNCH(true); else TFASR_QT_LAUNCH(false);
+  if (chunk > 0) { TFASR_QT_LAUNCH(true); } else { TFASR_QT_LAUNCH(false); }
 #undef TFASR_QT_LAUNCH
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
@@ -1493,16 +1488,11 @@ extern "C" int tfasr_relattn_fused_bwd_k(const void* qkv, const void* qu, const 
   if (!qkv || !qu || !qv || !pext || !dout || !lse || !dvec || !dqkv || B <= 0 || H <= 0 || T <= 0) return TFASR_STATUS_INVALID_VALUE;
   if (dtype != TFASR_BF16 || dh != DH) return TFASR_STATUS_UNSUPPORTED;
   const dim3 gk(attn_grid_size(B, H, (T + BJ - 1) / BJ));
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)relattn_fused_bwd_k_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD_K);
-    (void)hipFuncSetAttribute((const void*)relattn_fused_bwd_k_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD_K);
-    attr_done = true;
-  }
 #define TFASR_BK_LAUNCH(KERN, SMEM, ST, CH, HI)                                                                                         \
+  tfasr_dynamic_lds<KERN<ST>>(SMEM);                                                                                                    \
   TFASR_KLAUNCH((KERN<ST>), gk, dim3(256), SMEM, (hipStream_t)stream_, (const bf16_t*)qkv, (const bf16_t*)qu, (const bf16_t*)qv,        \
                 (const bf16_t*)pext, lengths, (const bf16_t*)dout, lse, dvec, (bf16_t*)dqkv, B, H, T, scale, use_mask, CH, HI)
-  if (chunk > 0) TFASR_BK_LAUNCH(relattn_fused_bwd_k_kernel, SMEM_BWD_K, true, chunk, hist); else TFASR_BK_LAUNCH(relattn_fused_bwd_k_kernel, SMEM_BWD_K, false, 0, 0);
+  if (chunk > 0) { TFASR_BK_LAUNCH(relattn_fused_bwd_k_kernel, SMEM_BWD_K, true, chunk, hist); } else { TFASR_BK_LAUNCH(relattn_fused_bwd_k_kernel, SMEM_BWD_K, false, 0, 0); }
 #undef TFASR_BK_LAUNCH
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
@@ -1529,18 +1519,13 @@ extern "C" int tfasr_relattn_fused_bwd_qk(const void* qkv, const float* ubias, c
       T <= 0 || lds < T || (lds & 7) || (((uintptr_t)qu | (uintptr_t)qv) & 15))
     return TFASR_STATUS_INVALID_VALUE;
   if (dtype != TFASR_BF16 || dh != DH) return TFASR_STATUS_UNSUPPORTED;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)relattn_fused_bwd_qk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD_QK);
-    (void)hipFuncSetAttribute((const void*)relattn_fused_bwd_qk_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD_QK);
-    attr_done = true;
-  }
   const unsigned nq = attn_grid_size(B, H, (T + BI - 1) / BI), nk = attn_grid_size(B, H, (T + BJ - 1) / BJ);
 #define TFASR_QK_LAUNCH(ST, CH, HI)                                                                                                          \
+  tfasr_dynamic_lds<relattn_fused_bwd_qk_kernel<ST>>(SMEM_BWD_QK);                                                                          \
   TFASR_KLAUNCH((relattn_fused_bwd_qk_kernel<ST>), dim3(nq + nk), dim3(256), SMEM_BWD_QK, (hipStream_t)stream_, (const bf16_t*)qkv, ubias, vbias, \
                 (const bf16_t*)pext, lengths, (const bf16_t*)dout, lse, (const bf16_t*)qu, (const bf16_t*)qv, dvec, order, (bf16_t*)dqkv,   \
                 (bf16_t*)ds, dpext, du, dv, B, H, T, lds, scale, use_mask, CH, HI, (int)nq)
-  if (chunk > 0) TFASR_QK_LAUNCH(true, chunk, hist); else TFASR_QK_LAUNCH(false, 0, 0);
+  if (chunk > 0) { TFASR_QK_LAUNCH(true, chunk, hist); } else { TFASR_QK_LAUNCH(false, 0, 0); }
 #undef TFASR_QK_LAUNCH
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;

@@ -376,7 +376,7 @@ extern "C" int tfasr_attn_plain_fwd(const void* qkv, const int32_t* lengths, voi
   } else {
     if (dh % 16 != 0 || dh > 128) return TFASR_STATUS_UNSUPPORTED;
     const size_t smem = (size_t)(FI * (dh + 1) + FJ * (dh + 1) + FJ * dh + FI * 33 + FI) * sizeof(float);
-    if (smem > 48 * 1024) (void)hipFuncSetAttribute((const void*)attn_plain_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (smem > 48 * 1024) tfasr_dynamic_lds<attn_plain_f32_kernel>((int)smem);
     const dim3 grid((T + FI - 1) / FI, H, B);
     TFASR_KLAUNCH(attn_plain_f32_kernel, grid, dim3(256), smem, s, (const float*)qkv, lengths, (float*)out, lse, B, H, T, dh, scale, use_mask,
                   causal ? 1 : 0, ck, hist);

@@ -201,3 +201,40 @@ __device__ __forceinline__ float logaddexpf_(float a, float b) {
     fprintf(stderr, "[tfasr_hip] %s:%d: %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); return TFASR_STATUS_EXECUTION_FAILED; } } while (0)
 
 static inline int tfasr_ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- per-device host state, indexed by the device current on the calling thread.  What a lookup costs: ONE hipGetDevice - the runtime
+// reads its thread-local current device, no driver call - plus one relaxed atomic load.  (The slot is not cached per thread here: a thread
+// may change its device between two calls, and only the runtime knows.) ----
+constexpr int TFASR_MAX_DEVICES = 64;
+inline int tfasr_device_slot(int* dev_out = nullptr) {
+  int dev = 0;
+  const bool ok = hipGetDevice(&dev) == hipSuccess;
+  if (dev_out) *dev_out = ok ? dev : -1;
+  return (ok && dev >= 0 && dev < TFASR_MAX_DEVICES) ? dev : -1;
+}
+
+// compute units of the current device (256 when the runtime cannot say), asked once per device
+inline int tfasr_num_cus() {
+  static std::atomic<int> cached[TFASR_MAX_DEVICES];
+  int dev = -1, v = 0;
+  const int slot = tfasr_device_slot(&dev);
+  int n = slot >= 0 ? cached[slot].load(std::memory_order_relaxed) : 0;
+  if (n == 0) {
+    n = (dev >= 0 && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+    if (slot >= 0) cached[slot].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
+// A kernel that takes more than 64 KB of dynamic LDS must have hipFuncAttributeMaxDynamicSharedMemorySize raised first.  The attribute
+// belongs to ONE kernel function on ONE device, so the size already granted is kept per instantiation (the template argument) and per
+// device, and raised again when a later launch asks for more; a launch within the granted size costs the lookup described above, no
+// hipFuncSetAttribute.
+template <auto KERN>
+inline void tfasr_dynamic_lds(int bytes) {
+  static std::atomic<int> granted[TFASR_MAX_DEVICES];
+  const int slot = tfasr_device_slot();
+  if (slot >= 0 && granted[slot].load(std::memory_order_relaxed) >= bytes) return;
+  if (hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess && slot >= 0)
+    granted[slot].store(bytes, std::memory_order_relaxed);
+}

@@ -288,8 +288,7 @@ extern "C" int tfasr_conv2d_fwd(const void* x, const void* w, const float* bias,
         TFASR_KLAUNCH(conv2d_bf16_kernel<true>, grid, dim3(256), smem, s, (const bf16_t*)xp, (const bf16_t*)w, bias, scale, shift, (bf16_t*)yp,
                       sh, relu);
       } else {
-        if (smem > 48 * 1024)
-          (void)hipFuncSetAttribute((const void*)conv2d_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (smem > 48 * 1024) tfasr_dynamic_lds<conv2d_bf16_kernel<false>>((int)smem);
         TFASR_KLAUNCH(conv2d_bf16_kernel<false>, grid, dim3(256), smem, s, (const bf16_t*)xp, (const bf16_t*)w, bias, scale, shift, (bf16_t*)yp,
                       sh, relu);
       }

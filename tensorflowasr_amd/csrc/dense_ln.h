@@ -300,11 +300,7 @@ __global__ __launch_bounds__(512, 2) void dense_ln_bwd_kernel(const DenseLnArgs 
 
 static int launch_dense_ln_bwd(DenseLnArgs a, int nblk, hipStream_t stream) {
   // rows per workgroup: the smallest tile that still fits the partial-sum slots and one round of workgroups (one per CU)
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
+  const int ncu = tfasr_num_cus();
   const int cap = nblk < ncu ? nblk : ncu;
   int mt = 0;
   for (int m = 2; m <= 6; m += 2)
@@ -314,13 +310,13 @@ static int launch_dense_ln_bwd(DenseLnArgs a, int nblk, hipStream_t stream) {
     mt = 6;  // more tiles than CUs: several rounds of the largest tile
   }
   a.ntiles = (int)((a.rows + 16 * mt - 1) / (16 * mt));
-  auto go = [&](auto kern, int m) {
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, dln_smem(m)); attr_done = true; }
-    TFASR_KLAUNCH(kern, dim3((unsigned)nblk), dim3(512), dln_smem(m), stream, a);
+  auto go = [&](auto m) {  // (each MT variant is a kernel function of its own: 108-132 KB of dynamic LDS)
+    constexpr int MT = decltype(m)::value;
+    tfasr_dynamic_lds<dense_ln_bwd_kernel<MT>>(dln_smem(MT));
+    TFASR_KLAUNCH(dense_ln_bwd_kernel<MT>, dim3((unsigned)nblk), dim3(512), dln_smem(MT), stream, a);
   };
-  if (mt == 2) go(dense_ln_bwd_kernel<2>, 2);
-  else if (mt == 4) go(dense_ln_bwd_kernel<4>, 4);
-  else go(dense_ln_bwd_kernel<6>, 6);
+  if (mt == 2) go(std::integral_constant<int, 2>{});
+  else if (mt == 4) go(std::integral_constant<int, 4>{});
+  else go(std::integral_constant<int, 6>{});
   return TFASR_STATUS_SUCCESS;
 }

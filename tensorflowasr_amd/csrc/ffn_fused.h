@@ -450,15 +450,16 @@ __global__ __launch_bounds__(256, WGS) void ffn_fused_fwd_kernel(const FfnArgs p
 // line, 21.76 vs 21.45 ms per step when forced everywhere: the second resident workgroup's overlap does not pay for the halved reuse of
 // the weight images).
 static int launch_ffn_fused_fwd(const FfnArgs& a, hipStream_t stream) {
-  auto go = [&](auto kern, int MR, int NBUF) {
-    const int smem = 2 * NBUF * 32768 + NBUF * 32 * MR * 128 + a.F * 4;
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr_done = true; }
-    const long tiles = (a.rows + 32 * MR - 1) / (32 * MR);
-    TFASR_KLAUNCH(kern, dim3((unsigned)tiles), dim3(256), smem, stream, a);
+  constexpr int MR = 2, NBUF = 1;
+  const int smem = 2 * NBUF * 32768 + NBUF * 32 * MR * 128 + a.F * 4;  // grows with F: the limit is raised per kernel function when a call needs more
+  const long tiles = (a.rows + 32 * MR - 1) / (32 * MR);
+  auto go = [&](auto zf, auto dense) {
+    constexpr bool ZF = decltype(zf)::value, DENSE = decltype(dense)::value;
+    tfasr_dynamic_lds<ffn_fused_fwd_kernel<MR, 2, ZF, DENSE>>(smem);
+    TFASR_KLAUNCH((ffn_fused_fwd_kernel<MR, 2, ZF, DENSE>), dim3((unsigned)tiles), dim3(256), smem, stream, a);
   };
-  if (a.y == nullptr) go(ffn_fused_fwd_kernel<2, 2, false, true>, 2, 1);  // (Dense-only mode: tfasr_ln_dense_fwd)
-  else if (a.zfactor && a.z) go(ffn_fused_fwd_kernel<2, 2, true>, 2, 1);
-  else go(ffn_fused_fwd_kernel<2, 2, false>, 2, 1);
+  if (a.y == nullptr) go(std::false_type{}, std::true_type{});  // (Dense-only mode: tfasr_ln_dense_fwd)
+  else if (a.zfactor && a.z) go(std::true_type{}, std::false_type{});
+  else go(std::false_type{}, std::false_type{});
   return TFASR_STATUS_SUCCESS;
 }

@@ -10,7 +10,7 @@
 //   f32  : __builtin_amdgcn_mfma_f32_16x16x4f32      (exact f32, 157 TFLOP/s)  -- the parity mode
 // C/D fragment map (both): col = lane & 15, row = (lane >> 4) * 4 + reg.
 #include "common.h"
-#include <stdlib.h>
+#include "gemm_route.h"
 
 namespace {
 
@@ -43,27 +43,6 @@ __device__ __forceinline__ void load_direct(bf16_t* s, const bf16_t* g, long ld,
       }
     }
     *reinterpret_cast<uint4*>(s + row * LD + kc) = v;
-  }
-}
-__device__ __forceinline__ void load_direct(float* s, const float* g, long ld, int rows0, int nrows_total, int kt,
-                                            int k_end) {
-  constexpr int BK = Cfg<float>::BK, LD = Cfg<float>::LD;
-  for (int c = threadIdx.x; c < BM * BK / 4; c += 256) {
-    const int row = c / (BK / 4), kc = (c % (BK / 4)) * 4;
-    const int gr = rows0 + row, gk = kt + kc;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (gr < nrows_total) {
-      const float* p = g + (long)gr * ld + gk;
-      if (gk + 4 <= k_end && aligned16(p)) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (gk + i < k_end) v[i] = p[i];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s[row * LD + kc + i] = v[i];
   }
 }
 
@@ -105,30 +84,9 @@ __device__ __forceinline__ void load_trans(bf16_t* s, const bf16_t* g, long ld, 
     }
   }
 }
-__device__ __forceinline__ void load_trans(float* s, const float* g, long ld, int rows0, int nrows_total, int kt,
-                                           int k_end) {
-  constexpr int BK = Cfg<float>::BK, LD = Cfg<float>::LD;
-  for (int c = threadIdx.x; c < BK * (BM / 4); c += 256) {
-    const int k = c / (BM / 4), r4 = (c % (BM / 4)) * 4;
-    const int gk = kt + k, gr = rows0 + r4;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (gk < k_end && gr < nrows_total) {
-      const float* p = g + (long)gk * ld + gr;
-      if (gr + 4 <= nrows_total && aligned16(p)) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (gr + i < nrows_total) v[i] = p[i];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s[(r4 + i) * LD + k] = v[i];
-  }
-}
 
 // f32 slabs in two steps - global -> registers, registers -> LDS - so that slab k+1 can be in flight while slab k is multiplied
-// (same element placement as load_direct / load_trans above; 128 x 16 floats = 2 float4 per thread and operand)
+// (same element placement as the bf16 load_direct / load_trans above; 128 x 16 floats = 2 float4 per thread and operand)
 struct F32Stage { float v[128 * Cfg<float>::BK / 4 / 256][4]; };
 template <int ROWS>
 __device__ __forceinline__ void fetch_direct(F32Stage& st, const float* g, long ld, int rows0, int nrows_total, int kt, int k_end) {
@@ -354,112 +312,72 @@ __global__ __launch_bounds__(256) void gemm_kernel(const tfasr_gemm_args p) {
   }
 }
 
-template <typename T>
-int launch(const tfasr_gemm_args& a, hipStream_t stream) {
-  const int split = a.split_k > 1 ? a.split_k : 1;
-  dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, a.nb1 * a.nb2 * split);
-  if (grid.y > 65535 || grid.z > 65535) return TFASR_STATUS_INVALID_VALUE;
-  dim3 block(256);
+// route -> instantiation of the generic kernel (narrow tiles: f32 only)
+template <typename T, bool TA, bool TB>
+void launch(const GemmRoute& r, const tfasr_gemm_args& a, hipStream_t stream) {
+  const dim3 grid(r.tiles_x, r.tiles_y, r.tiles_z), block(256);
   if constexpr (sizeof(T) == 4) {
-    // f32: 128 x 64 tiles while the 128-wide tiling leaves CUs without a workgroup of their own (TFASR_GEMM_F32_NARROW=0: never)
-    static const bool narrow_off = false;
-    static int ncu = 0;
-    if (ncu == 0) {
-      int dev = 0, v = 0;
-      ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-    }
-    if (!narrow_off && a.N > 64 && (long)grid.x * grid.y * grid.z < 2L * ncu) {
-      dim3 g2((a.N + 63) / 64, grid.y, grid.z);
-      if (a.trans_a) {
-        if (a.trans_b) TFASR_KLAUNCH((gemm_kernel<T, true, true, 64>), g2, block, 0, stream, a);
-        else           TFASR_KLAUNCH((gemm_kernel<T, true, false, 64>), g2, block, 0, stream, a);
-      } else {
-        if (a.trans_b) TFASR_KLAUNCH((gemm_kernel<T, false, true, 64>), g2, block, 0, stream, a);
-        else           TFASR_KLAUNCH((gemm_kernel<T, false, false, 64>), g2, block, 0, stream, a);
-      }
-      TFASR_CHECK_LAUNCH();
-      return TFASR_STATUS_SUCCESS;
-    }
+    if (r.tile_n == 64) { TFASR_KLAUNCH((gemm_kernel<T, TA, TB, 64>), grid, block, 0, stream, a); return; }
   }
-  if (a.trans_a) {
-    if (a.trans_b) TFASR_KLAUNCH((gemm_kernel<T, true, true>), grid, block, 0, stream, a);
-    else           TFASR_KLAUNCH((gemm_kernel<T, true, false>), grid, block, 0, stream, a);
-  } else {
-    if (a.trans_b) TFASR_KLAUNCH((gemm_kernel<T, false, true>), grid, block, 0, stream, a);
-    else           TFASR_KLAUNCH((gemm_kernel<T, false, false>), grid, block, 0, stream, a);
-  }
-  TFASR_CHECK_LAUNCH();
-  return TFASR_STATUS_SUCCESS;
+  TFASR_KLAUNCH((gemm_kernel<T, TA, TB>), grid, block, 0, stream, a);
+}
+template <typename T>
+void launch(const GemmRoute& r, const tfasr_gemm_args& a, hipStream_t stream) {
+  if (r.trans_a) { if (r.trans_b) launch<T, true, true>(r, a, stream); else launch<T, true, false>(r, a, stream); }
+  else { if (r.trans_b) launch<T, false, true>(r, a, stream); else launch<T, false, false>(r, a, stream); }
 }
 
 }  // namespace
 
-int tfasr_gemm_fast_try(const tfasr_gemm_args& a, hipStream_t stream);  // gemm_fast.hip (2-stage BK=64, one tile per workgroup)
+int tfasr_gemm_fast_launch(const GemmRoute& r, const tfasr_gemm_args& a, hipStream_t stream);                     // gemm_fast.hip
+int tfasr_gemm_group_launch(const GemmGroupPlan& g, const tfasr_gemm_args* a, int n, hipStream_t stream);       // gemm_fast.hip
+extern int g_gemm_big_mode, g_tfasr_group_beside;                                                                // gemm_fast.hip
 
-static bool use_fast_path() {
-  static int v = -1;
-  if (v < 0) v = 1;
-  return v == 1;
+extern "C" int tfasr_gemm_route(const tfasr_gemm_args* args, int ncu, tfasr_gemm_route_info* out) {
+  if (!args || !out) return TFASR_STATUS_INVALID_VALUE;
+  *out = gemm_route(*args, ncu > 0 ? ncu : tfasr_num_cus(), g_gemm_big_mode != 0);
+  return out->status;
 }
 
-int tfasr_gemm_group_fast_try(const tfasr_gemm_args* a, int n, hipStream_t stream);
+extern "C" int tfasr_gemm_group_route(const tfasr_gemm_args* args, int n, int ncu, int* launches) {
+  if (!launches) return TFASR_STATUS_INVALID_VALUE;
+  return gemm_group_route(args, n, ncu > 0 ? ncu : tfasr_num_cus(), g_tfasr_group_beside != 0, g_gemm_big_mode != 0, launches);
+}
 
 extern "C" int tfasr_gemm_group(const tfasr_gemm_args* args, int n, void* stream_) {
   if (!args || n <= 0) return TFASR_STATUS_INVALID_VALUE;
-  static const bool off = false;
-  int i = 0;
-  while (i < n) {
-    const int m = n - i < 10 ? n - i : 10;
-    int st = TFASR_STATUS_UNSUPPORTED;
-    if (!off && use_fast_path()) st = tfasr_gemm_group_fast_try(args + i, m, (hipStream_t)stream_);
-    if (st == TFASR_STATUS_UNSUPPORTED) {
-      for (int j = 0; j < m; ++j) {
-        st = tfasr_gemm(args + i + j, stream_);
-        if (st != TFASR_STATUS_SUCCESS) return st;
-      }
-    } else if (st != TFASR_STATUS_SUCCESS) {
-      return st;
+  for (int i = 0; i < n; i += GEMM_GROUP_MAX) {
+    const int m = n - i < GEMM_GROUP_MAX ? n - i : GEMM_GROUP_MAX;
+    const GemmGroupPlan g = gemm_group_plan(args + i, m, tfasr_num_cus(), g_tfasr_group_beside != 0);
+    if (g.status == TFASR_STATUS_SUCCESS) {
+      const int st = tfasr_gemm_group_launch(g, args + i, m, (hipStream_t)stream_);
+      if (st != TFASR_STATUS_SUCCESS) return st;
+      continue;
     }
-    i += m;
+    for (int j = 0; j < m; ++j) {  // one by one
+      const int st = tfasr_gemm(args + i + j, stream_);
+      if (st != TFASR_STATUS_SUCCESS) return st;
+    }
   }
   return TFASR_STATUS_SUCCESS;
 }
 
 extern "C" int tfasr_gemm(const tfasr_gemm_args* args, void* stream_) {
-  if (!args || !args->A || !args->B || (!args->D && !args->lse_part)) return TFASR_STATUS_INVALID_VALUE;
+  if (!args) return TFASR_STATUS_INVALID_VALUE;
+  const GemmRoute r = gemm_route(*args, tfasr_num_cus(), g_gemm_big_mode != 0);
+  if (r.status != TFASR_STATUS_SUCCESS) return r.status;
   tfasr_gemm_args a = *args;
-  if (a.rgrad_coef && (!a.row_label || !a.D || a.lse_part)) return TFASR_STATUS_INVALID_VALUE;
-  if (a.M <= 0 || a.N <= 0 || a.K <= 0) return TFASR_STATUS_INVALID_VALUE;
   if (a.nb1 < 1) a.nb1 = 1;
   if (a.nb2 < 1) a.nb2 = 1;
   if (a.split_k < 1) a.split_k = 1;
-  if (a.accumulate && !a.out_f32) return TFASR_STATUS_INVALID_VALUE;
-  if (a.split_k > 1 && !a.accumulate) return TFASR_STATUS_INVALID_VALUE;
-  if (a.split_k > 1 && (a.res || a.dact_z || a.prez || a.act != TFASR_ACT_NONE || a.drop_p > 0.f)) return TFASR_STATUS_INVALID_VALUE;
-  if (a.drop_p < 0.f || a.drop_p >= 1.f) return TFASR_STATUS_INVALID_VALUE;
-  if (a.colsum && !(a.accumulate && a.trans_a && !a.trans_b && a.nb1 * a.nb2 == 1)) return TFASR_STATUS_INVALID_VALUE;
-  if (a.row_tiles) {  // row-tile table: the K-segmented NN / NT products only, every entry count the tile grid can hold
-    if (a.n_row_tiles <= 0 || a.n_row_tiles > (a.M + 255) / 256) return TFASR_STATUS_INVALID_VALUE;
-    if (!a.seg_a_off || a.trans_a || a.accumulate || a.split_k > 1 || a.nb1 * a.nb2 != 1 || a.dtype != TFASR_BF16) return TFASR_STATUS_UNSUPPORTED;
-  }
-  if (a.k_tiles) {  // K-block table: the bf16 transposed-A weight gradient only, every entry count the K range can hold
-    if (a.n_k_tiles <= 0 || a.n_k_tiles > (a.K + 255) / 256) return TFASR_STATUS_INVALID_VALUE;
-    if (!a.trans_a || a.trans_b || !a.accumulate || a.nb1 * a.nb2 != 1 || a.dtype != TFASR_BF16 || a.seg_a_off || a.row_tiles || a.ws) return TFASR_STATUS_UNSUPPORTED;
-  }
   hipStream_t stream = (hipStream_t)stream_;
-  if (a.dtype == TFASR_BF16 && use_fast_path()) {
-    const int st = tfasr_gemm_fast_try(a, stream);
-    if (st != TFASR_STATUS_UNSUPPORTED) return st;
-  }
-  if (a.k_tiles) return TFASR_STATUS_UNSUPPORTED;  // only the bf16 fast path reads the table
-  if (a.lse_part || a.rgrad_coef || a.bns_out) return TFASR_STATUS_UNSUPPORTED;  // only the bf16 fast path's epilogues produce the row statistics / the loss gradient / the BatchNorm sums
-  if (a.seg_a_off) return TFASR_STATUS_UNSUPPORTED;  // K-segments: bf16 fast path only (the f32 host path issues one product per segment)
-  if (a.colsum) {  // the generic kernels do not fuse the bias gradient: one extra pass over B = dy
+  if (r.family != TFASR_GEMM_GENERIC) return tfasr_gemm_fast_launch(r, a, stream);
+  if (a.colsum) {  // the route's second launch: the bias gradient as a pass of its own over B = dy
     const int st = tfasr_colsum(a.B, a.ldb, a.colsum, a.K, a.N, a.alpha, a.dtype, stream_);
     if (st != TFASR_STATUS_SUCCESS) return st;
     a.colsum = nullptr;
   }
-  if (a.dtype == TFASR_BF16) return launch<bf16_t>(a, stream);
-  if (a.dtype == TFASR_F32) return launch<float>(a, stream);
-  return TFASR_STATUS_INVALID_VALUE;
+  if (a.dtype == TFASR_BF16) launch<bf16_t>(r, a, stream); else launch<float>(r, a, stream);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
 }

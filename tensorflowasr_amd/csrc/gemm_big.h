@@ -740,68 +740,17 @@ _Pragma("unroll")
   }
 }
 
-int g_gemm_big_mode = -1;  // probes / tests: 0 = never, 1 = default rule; -1 = TFASR_GEMM_BIG from the environment
-
-// eligibility + launch; UNSUPPORTED -> the caller continues with the 128-row tiles
-template <bool TB>
-int launch_big(const tfasr_gemm_args& a, bool generic, int need, bool tanh_out, hipStream_t stream) {
-  static const bool env_off = false;
-  const bool off = g_gemm_big_mode < 0 ? env_off : g_gemm_big_mode == 0;
-  if (off || generic || need != 0 || a.accumulate || a.split_k > 1 || a.nb1 * a.nb2 != 1 || a.colsum || a.out_f32 || a.K < 2 * BK || (a.K & 7) || a.M < 256 || (TB && (a.N & 7))) return TFASR_STATUS_UNSUPPORTED;
-  const bool seg = a.seg_a_off != nullptr;
-  if (seg && !(a.seg_k > 0 && (a.seg_k % BK) == 0 && (a.K % a.seg_k) == 0 && a.K / BK <= 64)) return TFASR_STATUS_UNSUPPORTED;
-  // BN: 320 for N = 320 / 640 / ... (k-contiguous B only: the joint's data gradient, joint_dim 320 or 640), else 256 when the last
-  // column tile is at least 3/4 full
-  int bn = 0;
-  if (TB && !seg && !a.lse_part && (a.N % 320) == 0) bn = 320;
-  else if (a.N >= (TB ? 256 : 192) && ((a.N % 256) == 0 || (a.N % 256) >= 192)) bn = 256;
-  if (!bn) return TFASR_STATUS_UNSUPPORTED;
-  int gx = (a.N + bn - 1) / bn, gy = (a.M + 255) / 256;
-  long ntiles = (long)gx * gy;
-  static const long min_tiles = 2L * num_cus();
-  if (ntiles < min_tiles || ntiles > 0x7fffffffL) return TFASR_STATUS_UNSUPPORTED;
-  // a row-tile table never changes WHICH kernel runs (the rule above counts the full product's tiles): a listed 256-row block is
-  // computed exactly as the full product computes it
-  if (a.row_tiles) { gy = a.n_row_tiles; ntiles = (long)gx * gy; }
-  if (tanh_out && (!TB || seg || a.lse_part)) return TFASR_STATUS_UNSUPPORTED;
-  if (a.lse_part && !(a.row_label && a.pick && bn == 256 && a.lse_parts == ((a.N + 127) / 128) * 2)) return TFASR_STATUS_UNSUPPORTED;
-  if (a.rgrad_coef && (TB || seg || tanh_out || bn != 256 || !a.row_label)) return TFASR_STATUS_UNSUPPORTED;
-  if (!a.D && !a.lse_part) return TFASR_STATUS_UNSUPPORTED;
-  const int ncu = num_cus();
-  const int G = ntiles >= ncu ? (ncu & ~7) : (int)ntiles;
-  auto go = [&](auto kern, int smem) {
-    static bool attr_done = false;  // per instantiation (the lambda's static lives in the template instance)
-    if (!attr_done) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr_done = true; }
-    TFASR_KLAUNCH(kern, dim3(G), dim3(512), smem, stream, a, gx, gy, (int)ntiles);
-  };
-  constexpr int S256 = 2 * (256 * BK * 2 + 256 * BK * 2) + 8 * 8 * 68 * 4;
-  constexpr int S320 = 2 * (256 * BK * 2 + 320 * BK * 2);
-  // transposed accumulators (the kernel's TR parameter; 16-byte stores straight from the accumulators): every variant whose output rows
-  // allow them (ldd % 8 == 0, N % 8 == 0, 16-byte aligned D); TFASR_BIG_TR=0 restores the row-oriented epilogues (A/B)
-  static const bool tr_on = !(false);
-  const bool tr = tr_on && (a.ldd & 7) == 0 && (a.N & 7) == 0 && (((uintptr_t)a.D) & 15) == 0;
-  if (tanh_out) {
-    if constexpr (TB) {
-      // (320 columns: the 160 accumulators leave no register for the transposed epilogue - seen at compile time, also with the tanh-out
-      // operand requested only two fragments ahead: two spill reloads land INSIDE the slab loop, each followed by a vmcnt(0) that drains
-      // the DMA prefetch - so the 320-column kernels keep the row-oriented epilogue; tests/test_isa_guard.py watches for scratch traffic)
-      if (bn == 320) go(gemm_big_kernel<true, 320, E_DACT, false>, S320);
-      else { if (tr) go(gemm_big_kernel<true, 256, E_DACT, false, true>, S256); else go(gemm_big_kernel<true, 256, E_DACT, false>, S256); }
-    } else return TFASR_STATUS_UNSUPPORTED;
-  } else if (bn == 320) {
-    if constexpr (TB) go(gemm_big_kernel<true, 320, 0, false>, S320);
-    else return TFASR_STATUS_UNSUPPORTED;
-  } else if (a.lse_part) {
-    if constexpr (!TB) { if (tr || (tr_on && !a.D)) go(gemm_big_kernel<false, 256, E_LSE, false, true>, S256); else go(gemm_big_kernel<false, 256, E_LSE, false>, S256); }
-    else return TFASR_STATUS_UNSUPPORTED;
-  } else if (a.rgrad_coef) {
-    if constexpr (!TB) go(gemm_big_kernel<false, 256, E_RGRAD, false>, S256);
-    else return TFASR_STATUS_UNSUPPORTED;
-  } else if (seg) {
-    if (tr) go(gemm_big_kernel<TB, 256, 0, true, true>, S256); else go(gemm_big_kernel<TB, 256, 0, true>, S256);
-  } else {
-    if (tr) go(gemm_big_kernel<TB, 256, 0, false, true>, S256); else go(gemm_big_kernel<TB, 256, 0, false>, S256);
+// route -> instantiation (TFASR_GEMM_BIG_TABLE of gemm_route.h, which also holds the eligibility rules and the choice of variant).  Every
+// variant takes more than 64 KB of dynamic LDS: the limit is raised per kernel function and device (tfasr_dynamic_lds).
+inline int launch_big(const GemmRoute& r, const tfasr_gemm_args& a, hipStream_t stream) {
+  switch (gemm_big_key(r.trans_b, r.tile_n, r.epi, r.seg, r.tr)) {
+#define TFASR_X(TB, BN, EPI, SEG, TR)                                                                                                        \
+  case gemm_big_key(TB, BN, EPI, SEG, TR):                                                                                                    \
+    tfasr_dynamic_lds<gemm_big_kernel<TB, BN, EPI, SEG, TR>>(r.lds_bytes);                                                                    \
+    TFASR_KLAUNCH((gemm_big_kernel<TB, BN, EPI, SEG, TR>), dim3(r.workgroups), dim3(512), r.lds_bytes, stream, a, r.tiles_x, r.tiles_y, r.tiles_x * r.tiles_y); \
+    return TFASR_STATUS_SUCCESS;
+    TFASR_GEMM_BIG_TABLE(TFASR_X)
+#undef TFASR_X
+    default: return TFASR_STATUS_EXECUTION_FAILED;
   }
-  TFASR_CHECK_LAUNCH();
-  return TFASR_STATUS_SUCCESS;
 }

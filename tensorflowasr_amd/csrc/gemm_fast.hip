@@ -16,6 +16,7 @@
 // Requirements for this path: A,B 16-B aligned, lda/ldb % 8 == 0, batch strides % 8 == 0, and for a k-strided
 // operand its row extent (M for A, N for B) rounded up to 8 must fit inside the row stride.
 #include "common.h"
+#include "gemm_route.h"
 #include <type_traits>
 #include <string.h>
 #include <stdlib.h>
@@ -263,11 +264,7 @@ __device__ __forceinline__ float dact_f(float z, int act) {
   }
 }
 
-// EPI selects which epilogue terms are COMPILED IN.  The fully generic epilogue (every term behind a runtime branch, tanh /
-// sigmoid / f32 outputs included) is ~20k instructions and thrashes the instruction cache: a plain bias epilogue took 1700
-// cycles per 16-row strip.  The step's common combinations get lean instantiations; anything else falls back to E_GEN.
-enum : int { E_ACT = 1 /* swish(+prez) */, E_DACT = 2 /* * swish'(dact_z) */, E_DROP = 4, E_RES = 8, E_WS = 16 /* split-K partial -> workspace */, E_CSUM = 32 /* + column sums of B (bias gradient) */, E_LSE = 64 /* + log-softmax statistics of the output rows */, E_RGRAD = 128 /* re-computed logits -> RNN-T loss gradient */, E_GEN = 256, E_BNS = 512 /* + BatchNorm backward statistics of the output */, E_MUL = 1024 /* * dact_z (the stored derivative factor) */ };
-
+// EPI (the E_* bits of gemm_route.h) selects which epilogue terms are COMPILED IN.
 // Persistent workgroups (2 per CU) walk a strided list of tiles.  Measured on [23808,256]x[256,1024] (cycle counters,
 // tools/hwprobe/gemm_timing.hip): a tile spent 1900 cycles waiting for its first slab, ~2400 per further slab (the LDS-DMA
 // round trip; the 512 cycles of MFMA per slab hide nothing) and 4300 in the epilogue.  So the NEXT tile's first two slabs
@@ -275,9 +272,8 @@ enum : int { E_ACT = 1 /* swish(+prez) */, E_DACT = 2 /* * swish'(dact_z) */, E_
 // lives in its own 8.5 KiB so nothing waits for it.
 // `bid` / `G` = this workgroup's index and the number of workgroups working on THIS product (blockIdx.x / gridDim.x for a plain
 // launch; a slice of the grid inside a grouped launch, whose slices start at multiples of 8 so that bid & 7 is still the XCD).
-// NST = LDS stages: 2 (two barriers per slab: the stage just read is refilled after the MFMAs) or 3 (one barrier per slab: slab s+2
-// goes into the stage slab s-1 was read from, TWO slabs in flight under the MFMAs - for long-K products on HBM-cold operands
-// (weight gradients), whose main loop runs at the DMA round trip per slab with a single slab in flight).
+// Two LDS stages, two barriers per slab: the stage just read is refilled after the MFMAs.  (A three-stage loop - one barrier per slab, two
+// slabs in flight - was tried for the long-K grouped weight gradients and changed nothing; removed.)
 // FIXED: the caller chose this workgroup's tile itself: bid = tile index inside the gx x gy grid, G = its k-slice (grouped launch).
 // SEG: K-segments (tfasr_gemm_args.seg_*): slab s of the k loop reads its operands at a table offset instead of s * BK.
 // ONE: every workgroup owns exactly ONE tile (the grid is the tile list): no cross-tile prefetch, so the epilogue strips may lie OVER the
@@ -286,7 +282,7 @@ enum : int { E_ACT = 1 /* swish(+prez) */, E_DACT = 2 /* * swish'(dact_z) */, E_
 // KT: K-block table (tfasr_gemm_args.k_tiles; transposed-A weight gradients): the k loop runs over the COMPACTED list of 256-row blocks -
 // slab c of the compacted range reads rows k_tiles[c / 4] * 256 + (c % 4) * 64, one uniform table lookup per slab, requested in front of
 // the wait for the slab in flight.  Its own instantiations: the kernels without a table are compiled exactly as before.
-template <bool TA, bool TB, int BN_, int EPI, int NST = 2, bool FIXED = false, bool SEG = false, bool ONE = false, bool KT = false>
+template <bool TA, bool TB, int BN_, int EPI, bool FIXED = false, bool SEG = false, bool ONE = false, bool KT = false>
 __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const int gx, const int gy, const int gz, const int ntiles, const int bid, const int G) {
   constexpr bool GEN = (EPI & E_GEN) != 0;
   constexpr bool C_ACT = GEN || (EPI & E_ACT), C_DACT = GEN || (EPI & E_DACT), C_DROP = GEN || (EPI & E_DROP), C_RES = GEN || (EPI & E_RES);
@@ -484,60 +480,44 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
 #else
 #define TFASR_TICK(k)
 #endif
-    if constexpr (NST == 3) {
-      for (int s = 0; s < n; ++s) {
-        const int stage = s % 3;
-        if (s + 2 < n) kt_set(cur, s + 2);
-        if (!(drained && s < 2)) {
-          if (s + 1 < n) { if (GI == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();  // slab s is visible to every wave, and every wave is done reading slab s-1's stage
-        if (s + 2 < n) issue(cur, s + 2, (s + 2) % 3);
-        mma_slab<TA, TB, BN_, C_CS>(smem + stage * STAGE_BYTES, smem + stage * STAGE_BYTES + A_BYTES, wm, wn, lane, acc, accb, do_cs);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-    } else {
-      for (int s = 0; s < n; ++s) {
-        const int stage = s & 1;
-  #ifdef TFASR_GEMM_TIMING
-        long long tp = __builtin_readcyclecounter();
-  #endif
-        if (s + 2 < n) kt_set(cur, s + 2);
-        if (!(drained && s < 2)) {
-          // this wave's DMA pieces of slab s have landed; slab s+1 (when it exists) stays in flight
-          if (s + 1 < n) { if (GI == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        TFASR_TICK(0)
-        __builtin_amdgcn_s_barrier();
-        TFASR_TICK(1)
-#ifdef TFASR_FAST_NO_ILV
-        mma_slab<TA, TB, BN_, C_CS>(smem + stage * STAGE_BYTES, smem + stage * STAGE_BYTES + A_BYTES, wm, wn, lane, acc, accb, do_cs);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        TFASR_TICK(2)
-        __builtin_amdgcn_s_barrier();  // every wave is done reading this stage before it is refilled
-        TFASR_TICK(3)
-        if (s + 2 < n) issue(cur, s + 2, stage);
-        TFASR_TICK(4)
-#else
-        // Every fragment of the slab is read into registers FIRST; once all waves' reads have returned the stage is free, and the pieces
-        // of slab s+2 are issued BETWEEN the slab's MFMAs (a piece costs its wave ~90 clocks of issue time: 8 of them in a row after the
-        // MFMAs were a serial 730 clocks per slab next to 512 clocks of matrix work)
-        struct Hook {
-          const decltype(issue_piece)& ip; const Tile& T; int slab, stage; bool on;
-          __device__ __forceinline__ void reads_done() const {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // every wave has its fragments: the stage may be refilled
-          }
-          __device__ __forceinline__ void between(int q) const { if (on && q < GI) ip(T, slab, stage, q); }
-        };
-        const Hook hook{issue_piece, cur, s + 2, stage, s + 2 < n};
-        mma_slab<TA, TB, BN_, C_CS, Hook>(smem + stage * STAGE_BYTES, smem + stage * STAGE_BYTES + A_BYTES, wm, wn, lane, acc, accb, do_cs, hook);
-        TFASR_TICK(2)
+    for (int s = 0; s < n; ++s) {
+      const int stage = s & 1;
+#ifdef TFASR_GEMM_TIMING
+      long long tp = __builtin_readcyclecounter();
 #endif
+      if (s + 2 < n) kt_set(cur, s + 2);
+      if (!(drained && s < 2)) {
+        // this wave's DMA pieces of slab s have landed; slab s+1 (when it exists) stays in flight
+        if (s + 1 < n) { if (GI == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
+      TFASR_TICK(0)
+      __builtin_amdgcn_s_barrier();
+      TFASR_TICK(1)
+#ifdef TFASR_FAST_NO_ILV
+      mma_slab<TA, TB, BN_, C_CS>(smem + stage * STAGE_BYTES, smem + stage * STAGE_BYTES + A_BYTES, wm, wn, lane, acc, accb, do_cs);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      TFASR_TICK(2)
+      __builtin_amdgcn_s_barrier();  // every wave is done reading this stage before it is refilled
+      TFASR_TICK(3)
+      if (s + 2 < n) issue(cur, s + 2, stage);
+      TFASR_TICK(4)
+#else
+      // Every fragment of the slab is read into registers FIRST; once all waves' reads have returned the stage is free, and the pieces
+      // of slab s+2 are issued BETWEEN the slab's MFMAs (a piece costs its wave ~90 clocks of issue time: 8 of them in a row after the
+      // MFMAs were a serial 730 clocks per slab next to 512 clocks of matrix work)
+      struct Hook {
+        const decltype(issue_piece)& ip; const Tile& T; int slab, stage; bool on;
+        __device__ __forceinline__ void reads_done() const {
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_s_barrier();  // every wave has its fragments: the stage may be refilled
+        }
+        __device__ __forceinline__ void between(int q) const { if (on && q < GI) ip(T, slab, stage, q); }
+      };
+      const Hook hook{issue_piece, cur, s + 2, stage, s + 2 < n};
+      mma_slab<TA, TB, BN_, C_CS, Hook>(smem + stage * STAGE_BYTES, smem + stage * STAGE_BYTES + A_BYTES, wm, wn, lane, acc, accb, do_cs, hook);
+      TFASR_TICK(2)
+#endif
     }
     if (cur.tail) {
       char* sA = smem;
@@ -608,7 +588,7 @@ __device__ __forceinline__ void gemm_fast_body(const tfasr_gemm_args& p, const i
       constexpr int LPRW = WN / 8;        // lanes per strip row: 8 (BN 128) or 4 (BN 64), 8 columns each
       constexpr int RPP = 64 / LPRW;      // rows per pass: 8 or 16
       constexpr int NPASS = 16 / RPP;     // 2 or 1
-      float* sc = reinterpret_cast<float*>(smem + (ONE ? 0 : NST * STAGE_BYTES)) + w * (RPP * SLD);  // (ONE: over the dead stages)
+      float* sc = reinterpret_cast<float*>(smem + (ONE ? 0 : 2 * STAGE_BYTES)) + w * (RPP * SLD);  // (ONE: over the dead stages)
       const int prow = lane / LPRW, c8 = (lane % LPRW) * 8;
       const int col0 = n0 + wn * WN + c8;
       const bool vec_ok = C_WS ? ((p.N & 7) == 0) : (((p.ldd & 7) == 0) && ((((uintptr_t)p.D) & 15) == 0) && ((doff & 7) == 0));
@@ -874,18 +854,18 @@ __global__ __launch_bounds__(256, 2) void gemm_fast_kernel(const tfasr_gemm_args
 // one tile per workgroup, three workgroups per CU (64-column tiles: <= 168 registers, 48 KiB of LDS)
 template <bool TA, bool TB, int EPI>
 __global__ __launch_bounds__(256, 3) void gemm_fast_one_kernel(const tfasr_gemm_args p, const int gx, const int gy, const int gz, const int ntiles) {
-  gemm_fast_body<TA, TB, 64, EPI, 2, false, false, true>(p, gx, gy, gz, ntiles, (int)blockIdx.x, (int)gridDim.x);
+  gemm_fast_body<TA, TB, 64, EPI, false, false, true>(p, gx, gy, gz, ntiles, (int)blockIdx.x, (int)gridDim.x);
 }
 // K-segmented A / B operands (convolution taps as row shifts): same body, slab offsets from a table
 template <bool TA, bool TB>
 __global__ __launch_bounds__(256, 2) void gemm_seg_kernel(const tfasr_gemm_args p, const int gx, const int gy, const int gz, const int ntiles) {
-  gemm_fast_body<TA, TB, 128, 0, 2, false, true>(p, gx, gy, gz, ntiles, (int)blockIdx.x, (int)gridDim.x);
+  gemm_fast_body<TA, TB, 128, 0, false, true>(p, gx, gy, gz, ntiles, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // transposed-A weight gradient over a K-block table (tfasr_gemm_args.k_tiles): the persistent 128 x 128 kernel with the column-sum row
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_ktab_kernel(const tfasr_gemm_args p, const int gx, const int gy, const int gz, const int ntiles) {
-  gemm_fast_body<true, false, 128, EPI, 2, false, false, false, true>(p, gx, gy, gz, ntiles, (int)blockIdx.x, (int)gridDim.x);
+  gemm_fast_body<true, false, 128, EPI, false, false, false, true>(p, gx, gy, gz, ntiles, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -894,32 +874,26 @@ __global__ __launch_bounds__(256, 2) void gemm_ktab_kernel(const tfasr_gemm_args
 // `tiles x split` f32 atomics at a flat 320 G/s plus a launch ramp/drain - while together their ~190 tiles fill the 512
 // resident workgroup slots with a split of 2.  Every workgroup of the grid belongs to one product (a contiguous slice of
 // blockIdx.x starting at a multiple of 8) and runs gemm_fast_body on it unchanged.
-constexpr int GROUP_MAX = 10;
-constexpr int GROUP_UNITS = 20;  // (product, k-slice) units per XCD
 struct GroupArgs {
-  tfasr_gemm_args p[GROUP_MAX];
-  int gx[GROUP_MAX], gy[GROUP_MAX];
-  // XCD x (= blockIdx.x & 7) runs nunit[x] units; unit u covers slots [j0[x][u], j0[x][u+1]) of that XCD (slot = blockIdx.x >> 3)
-  short uq[8][GROUP_UNITS], uks[8][GROUP_UNITS];
-  int j0[8][GROUP_UNITS + 1];
-  int nunit[8];
+  tfasr_gemm_args p[GEMM_GROUP_MAX];
+  GemmGroupTables t;  // gx / gy per product, the (product, k-slice) units of every XCD (gemm_route.h: gemm_group_plan)
 };
 // A unit = ALL output tiles of one product for one k-slice, resident on ONE XCD at the same time: the tiles sharing an operand
 // panel march through k together, so the panel comes out of HBM once and its re-reads hit that XCD's L2.  (With the tiles of a
 // product dealt over all XCDs the panels were re-fetched per XCD: 1.5 GB of fabric traffic per block for 0.32 GB of operands,
 // and the launch ran at the fabric's rate, 156 us; 3 LDS stages instead of 2 changed nothing.)
-template <int EPI, int NST, int BN_, bool KT = false>
+template <int EPI, int BN_, bool KT = false>
 __global__ __launch_bounds__(256, 2) void wgrad_group_kernel(const GroupArgs ga) {
   const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-  const int nu = ga.nunit[x];
+  const int nu = ga.t.nunit[x];
   int u = -1;
   for (int i = 0; i < nu; ++i)
-    if (j >= ga.j0[x][i] && j < ga.j0[x][i + 1]) u = i;
+    if (j >= ga.t.j0[x][i] && j < ga.t.j0[x][i + 1]) u = i;
   u = __builtin_amdgcn_readfirstlane(u);
   if (u < 0) return;
-  const int q = ga.uq[x][u], ks = ga.uks[x][u], t = j - ga.j0[x][u];
+  const int q = ga.t.uq[x][u], ks = ga.t.uks[x][u], t = j - ga.t.j0[x][u];
   const tfasr_gemm_args* pp = ga.p + q;
-  gemm_fast_body<true, false, BN_, EPI, NST, true, false, false, KT>(*pp, ga.gx[q], ga.gy[q], 1, ga.gx[q] * ga.gy[q], t, ks);
+  gemm_fast_body<true, false, BN_, EPI, true, false, false, KT>(*pp, ga.t.gx[q], ga.t.gy[q], 1, ga.t.gx[q] * ga.t.gy[q], t, ks);
 }
 
 // second pass of the workspace split-K: D[m, n] += sum_s ws[s][m][n]
@@ -949,204 +923,23 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
-int num_cus();
-// what a product with a K-block table must be (tfasr_gemm_args.k_tiles); the entry count is checked by the callers
-inline bool ktab_eligible(const tfasr_gemm_args& a) {
-  return a.dtype == TFASR_BF16 && a.trans_a && !a.trans_b && a.accumulate && a.nb1 * a.nb2 <= 1 && !a.ws && !a.seg_a_off && !a.row_tiles && !a.lse_part &&
-         !a.rgrad_coef && !a.bns_out && a.n_k_tiles > 0 && a.n_k_tiles <= (a.K + 255) / 256;
-}
-
-int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-    else n = 256;
-  }
-  return n;
-}
-
-template <bool TA, bool TB, int BN_, int EPI>
-int launch_epi(const tfasr_gemm_args& a, dim3 tiles, hipStream_t stream) {
-  const long ntiles = (long)tiles.x * tiles.y * tiles.z;
-  // 2 resident workgroups per CU; TFASR_GEMM_SLOTS=1 is an experiment hook: one persistent workgroup per CU walking more tiles
-  static const int per_cu = 2;
-  const int slots = per_cu * num_cus();
-  if constexpr (BN_ == 64 && (EPI & (E_WS | E_CSUM | E_LSE)) == 0) {
-    // every tile its own workgroup, three per CU, when the tile list fits three per CU at once (TFASR_GEMM_ONE=0: the persistent kernel)
-    static const bool one_off = false;
-    static const long one_max = (1L << 30);  // probe: upper bound in tiles per CU
-    if (!one_off && a.split_k <= 1 && ntiles > slots && ntiles <= one_max * num_cus()) {
-      constexpr int SMEM1 = 2 * (A_BYTES + 64 * BK * 2);
-      TFASR_KLAUNCH((gemm_fast_one_kernel<TA, TB, EPI>), dim3((unsigned)ntiles), dim3(256), SMEM1, stream, a, (int)tiles.x, (int)tiles.y, (int)tiles.z, (int)ntiles);
-      TFASR_CHECK_LAUNCH();
-      return TFASR_STATUS_SUCCESS;
-    }
-  }
-  int G = (int)(ntiles < slots ? ntiles : slots);
-  if (ntiles >= slots) G &= ~7;
-  constexpr int SMEM = 2 * (A_BYTES + BN_ * BK * 2) + 4 * (64 / (BN_ / 16)) * (BN_ / 2 + 4) * 4;  // stages + 4 waves' strips
-  TFASR_KLAUNCH((gemm_fast_kernel<TA, TB, BN_, EPI>), dim3(G), dim3(256), SMEM, stream, a, (int)tiles.x, (int)tiles.y, (int)tiles.z, (int)ntiles);
-  TFASR_CHECK_LAUNCH();
-  return TFASR_STATUS_SUCCESS;
-}
-
+// ---- route -> instantiation -> launch.  WHICH kernel a call takes, its grid and its LDS are decided by gemm_route.h; nothing below chooses. ----
 #include "gemm_big.h"
 #include "ffn_fused.h"
 #include "dense_ln.h"
 
-template <bool TA, bool TB>
-int launch_one(const tfasr_gemm_args& a, hipStream_t stream) {
-  const int split = a.split_k > 1 ? a.split_k : 1;
-  if (a.k_tiles) {  // K-block table: the accumulating x^T dy product on 128-wide tiles, or nothing at all
-    if constexpr (TA && !TB) {
-      if (ktab_eligible(a) && a.out_f32) {
-        dim3 grid((a.N + 127) / 128, (a.M + BM - 1) / BM, split);
-        if ((long)grid.x * grid.y * grid.z > 0x7fffffffL) return TFASR_STATUS_INVALID_VALUE;
-        const long ntiles = (long)grid.x * grid.y * grid.z;
-        const int slots = 2 * num_cus();
-        int G = (int)(ntiles < slots ? ntiles : slots);
-        if (ntiles >= slots) G &= ~7;
-        constexpr int SMEM = 2 * (A_BYTES + 128 * BK * 2) + 4 * (64 / (128 / 16)) * (128 / 2 + 4) * 4;
-        TFASR_KLAUNCH((gemm_ktab_kernel<E_CSUM>), dim3(G), dim3(256), SMEM, stream, a, (int)grid.x, (int)grid.y, (int)grid.z, (int)ntiles);
-        TFASR_CHECK_LAUNCH();
-        return TFASR_STATUS_SUCCESS;
-      }
-    }
-    return TFASR_STATUS_UNSUPPORTED;
-  }
-  // 128x64 tiles: per-head attention products (N = head size: halves the wasted B tile) and every product whose 128x128 tiling
-  // would leave at most one workgroup per CU (the N = 256 Dense layers of a Conformer block: 190 tiles): with a single resident
-  // workgroup the DMA issue, the fragment reads and the MFMAs of a slab serialise (1530 cycles / slab measured); two 128x64
-  // workgroups per CU overlap them (14.2 vs 16.9 us on [12096,256,1024]).  TFASR_GEMM_BN64=0 restores the old rule.
-  static const bool bn64_off = false;
-  const long t128 = (long)((a.N + 127) / 128) * ((a.M + BM - 1) / BM) * a.nb1 * a.nb2 * split;
-  // Round 4: every product the one-tile kernel takes (no split-K, no accumulation / column sums; see bn64_lim below) runs as 64-column tiles, ONE per workgroup,
-  // three workgroups per CU (gemm_fast_one_kernel), whatever its size: 744 128-wide tiles on 512 persistent slots are two rounds with half
-  // the chip idle in the second, 1 488 narrow tiles on 768 dynamic slots are 1.94.  Same-box A/B: [rows,256]x[256,768|512] 17.8 -> 17.0 us,
-  // the FFN data gradient with its swish' + dropout epilogue 38.6 -> 34.3, N = 256 products 17.0 -> 16.3 / 16.2 -> 13.0; M 23.23 -> 23.01 ms/step,
-  // S 12.17 -> 12.01.  TFASR_GEMM_BN64_T=<128-wide tiles> restores a threshold (256 = round 3's rule).
-  static const long bn64_thr = (1L << 40);
-  // (above 1 x CUs only products the one-tile kernel takes)
-  // ... and with K <= 256 or N <= 256 (the Conformer's d = 256 layers: four slabs per tile, or two 128-wide column tiles).  With both >= 512
-  // (ContextNet's 512 - 1280-channel layers) the 128-wide persistent kernel amortises a tile better (cross-tile prefetch, half the operand
-  // bytes per flop): 33.3 vs 35.5 us per launch there, ContextNet-L 45.0 vs 45.4 ms/step.
-  const long bn64_lim = (split <= 1 && !a.accumulate && !a.colsum && std::min(a.K, a.N) <= 256) ? bn64_thr : std::min(bn64_thr, (long)num_cus());
-  const bool narrow = !a.lse_part && !a.seg_a_off && (a.N <= 64 || (!bn64_off && t128 <= bn64_lim && a.N > 64 && !(a.accumulate && a.ws)));
-  const int bn = narrow ? 64 : 128;
-  dim3 grid((a.N + bn - 1) / bn, (a.M + BM - 1) / BM, a.nb1 * a.nb2 * split);
-  if ((long)grid.x * grid.y * grid.z > 0x7fffffffL) return TFASR_STATUS_INVALID_VALUE;
-  // epilogue terms this call needs; accumulate (atomics from fragments) needs none of them
-  int need = 0;
-  bool generic = false;
-  if (!a.accumulate) {
-    if (a.out_f32) generic = true;
-    if (a.act != TFASR_ACT_NONE || a.prez) { if (a.act == TFASR_ACT_SWISH) need |= E_ACT; else generic = true; }
-    if (a.dact_z) { if (a.dact == TFASR_ACT_SWISH) need |= E_DACT; else if (a.dact == TFASR_ACT_FACTOR) need |= E_MUL; else generic = true; }
-    if (a.drop_p > 0.f) need |= E_DROP;
-    if (a.res) need |= E_RES;
-  }
-  if (a.bns_out) {  // BatchNorm backward statistics in the epilogue: the plain NT product on 64-column tiles, or nothing at all
-    if constexpr (!TA && TB) {
-      if (narrow && !generic && need == 0 && !a.accumulate && !a.bias && split == 1 && a.nb1 * a.nb2 == 1 && a.bns_x && a.bns_fin && (a.N & 7) == 0 && (a.ldd & 7) == 0 &&
-          (a.bns_c == 0 || (a.bns_c > 0 && (a.bns_c & 7) == 0 && a.N % a.bns_c == 0)) &&
-          (((uintptr_t)a.D | (uintptr_t)a.bns_x) & 15) == 0 && !a.colsum && !a.lse_part && !a.seg_a_off && !a.rgrad_coef)
-        return launch_epi<TA, TB, 64, E_BNS>(a, grid, stream);
-    }
-    return TFASR_STATUS_UNSUPPORTED;
-  }
-  if constexpr (!TA) {  // thousands of tiles: 256-row tiles, one 8-wave workgroup per CU (gemm_big.h)
-    const bool tanh_out = !a.accumulate && a.dact_z && a.dact == TFASR_ACT_TANH_OUT;  // the only epilogue term gemm_big knows beyond bias
-    const bool other = a.out_f32 || a.act != TFASR_ACT_NONE || a.prez || (a.dact_z && !tanh_out);
-    const int st = launch_big<TB>(a, other, need, tanh_out, stream);
-    if (st != TFASR_STATUS_UNSUPPORTED) return st;
-  }
-  if (a.rgrad_coef || !a.D) return TFASR_STATUS_UNSUPPORTED;  // gradient epilogue / statistics-only projection: 256-row kernel only
-  // (measured: NOT faster than the atomics - 34.8 vs 33.0 us on the [256,1024,19040] weight gradient, +5 ms on the step from
-  // the extra workspace traffic - so callers only pass a workspace when TFASR_SPLITK_WS=1; kept as the deterministic option)
-  if (a.accumulate && split > 1 && a.nb1 * a.nb2 == 1 && a.ws && a.ws_elems >= (long)split * a.M * a.N && !narrow && !a.colsum) {
-    const int st = launch_epi<TA, TB, 128, E_WS>(a, grid, stream);
-    if (st != TFASR_STATUS_SUCCESS) return st;
-    const long work = ((long)a.M * a.N + 3) / 4;
-    const int rg = (int)(work / 256 + 1 < 2048 ? work / 256 + 1 : 2048);
-    TFASR_KLAUNCH(splitk_reduce_kernel, dim3(rg), dim3(256), 0, stream, (const float*)a.ws, (float*)a.D, a.M, a.N, a.ldd, split);
-    TFASR_CHECK_LAUNCH();
-    return TFASR_STATUS_SUCCESS;
-  }
-  if (a.colsum) {
-    if constexpr (TA && !TB) {
-      if (a.accumulate && a.N > 64) return narrow ? launch_epi<TA, TB, 64, E_CSUM>(a, grid, stream) : launch_epi<TA, TB, 128, E_CSUM>(a, grid, stream);
-    }
-    return TFASR_STATUS_UNSUPPORTED;  // tfasr_gemm falls back to a separate column-sum pass
-  }
-  if (narrow) {
-    if (!generic && need == 0) return launch_epi<TA, TB, 64, 0>(a, grid, stream);
-    if constexpr (!TA && !TB) {
-      if (!generic && need == E_RES) return launch_epi<TA, TB, 64, E_RES>(a, grid, stream);
-      if (!generic && need == (E_RES | E_DROP)) return launch_epi<TA, TB, 64, E_RES | E_DROP>(a, grid, stream);
-    }
-    // Experiment hook (not reachable with the default threshold): 128x64 tiles for layers of MORE than one workgroup per CU need
-    // the compiled activation epilogues, or they fall to the generic one and lose (measured with TFASR_GEMM_BN64_T=1024).
-    if (t128 > num_cus() && a.N > 64 && !generic) {
-      if constexpr (!TA && !TB) {
-        if (need == E_ACT) return launch_epi<TA, TB, 64, E_ACT>(a, grid, stream);
-        if (need == (E_ACT | E_DROP)) return launch_epi<TA, TB, 64, E_ACT | E_DROP>(a, grid, stream);
-      }
-      if constexpr (!TA && TB) {
-        if (need == E_DACT) return launch_epi<TA, TB, 64, E_DACT>(a, grid, stream);
-        if (need == (E_DACT | E_DROP)) return launch_epi<TA, TB, 64, E_DACT | E_DROP>(a, grid, stream);
-        if (need == E_MUL) return launch_epi<TA, TB, 64, E_MUL>(a, grid, stream);
-      }
-    }
-    return launch_epi<TA, TB, 64, E_GEN>(a, grid, stream);
-  }
-  if (a.seg_a_off) {  // K-segmented operands: conv2 forward (NN) / data gradient (NT) over the haloed space-to-depth layout
-    if constexpr (!TA) {
-      if (!generic && need == 0 && !a.accumulate && split == 1 && a.nb1 * a.nb2 == 1 && a.seg_k > 0 && (a.seg_k % BK) == 0 && (a.K % a.seg_k) == 0 &&
-          a.K / BK <= 64 && !a.lse_part) {
-        dim3 g128((a.N + 127) / 128, a.row_tiles ? 2 * a.n_row_tiles : (a.M + BM - 1) / BM, 1);
-        const long ntiles = (long)g128.x * g128.y;
-        const int slots = 2 * num_cus();
-        int G = (int)(ntiles < slots ? ntiles : slots);
-        if (ntiles >= slots) G &= ~7;
-        constexpr int SMEM = 2 * (A_BYTES + 128 * BK * 2) + 4 * (64 / (128 / 16)) * (128 / 2 + 4) * 4;
-        TFASR_KLAUNCH((gemm_seg_kernel<TA, TB>), dim3(G), dim3(256), SMEM, stream, a, (int)g128.x, (int)g128.y, 1, (int)ntiles);
-        TFASR_CHECK_LAUNCH();
-        return TFASR_STATUS_SUCCESS;
-      }
-    }
-    return TFASR_STATUS_UNSUPPORTED;
-  }
-  if (a.lse_part) {  // joint vocabulary projection with fused log-softmax statistics
-    if constexpr (!TA && !TB) {
-      if (!generic && need == 0 && !a.accumulate && a.nb1 * a.nb2 == 1 && a.row_label && a.pick && a.lse_parts == ((a.N + 127) / 128) * 2)
-        return launch_epi<TA, TB, 128, E_LSE>(a, grid, stream);
-    }
-    return TFASR_STATUS_UNSUPPORTED;
-  }
-  if (!generic) {
-    if (need == 0) return launch_epi<TA, TB, 128, 0>(a, grid, stream);
-    if constexpr (!TA && !TB) {  // forward Dense layers
-      if (need == E_RES) return launch_epi<TA, TB, 128, E_RES>(a, grid, stream);
-      if (need == (E_RES | E_DROP)) return launch_epi<TA, TB, 128, E_RES | E_DROP>(a, grid, stream);
-      if (need == E_ACT) return launch_epi<TA, TB, 128, E_ACT>(a, grid, stream);
-      if (need == (E_ACT | E_DROP)) return launch_epi<TA, TB, 128, E_ACT | E_DROP>(a, grid, stream);
-    }
-    if constexpr (!TA && TB) {  // data gradients (dy @ W^T)
-      if (need == E_DACT) return launch_epi<TA, TB, 128, E_DACT>(a, grid, stream);
-      if (need == (E_DACT | E_DROP)) return launch_epi<TA, TB, 128, E_DACT | E_DROP>(a, grid, stream);
-      if (need == E_MUL) return launch_epi<TA, TB, 128, E_MUL>(a, grid, stream);
+template <bool TA, bool TB, int BN_, int EPI>
+int launch_fast(const GemmRoute& r, const tfasr_gemm_args& a, hipStream_t stream) {
+  const int ntiles = r.tiles_x * r.tiles_y * r.tiles_z;
+  if constexpr (BN_ == 64 && (EPI & (E_WS | E_CSUM | E_LSE)) == 0) {
+    if (r.family == TFASR_GEMM_FAST_ONE) {
+      TFASR_KLAUNCH((gemm_fast_one_kernel<TA, TB, EPI>), dim3(r.workgroups), dim3(256), r.lds_bytes, stream, a, r.tiles_x, r.tiles_y, r.tiles_z, ntiles);
+      return TFASR_STATUS_SUCCESS;
     }
   }
-  return launch_epi<TA, TB, 128, E_GEN>(a, grid, stream);
-}
-
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-bool group_eligible(const tfasr_gemm_args& a) {
-  return a.dtype == TFASR_BF16 && a.trans_a && !a.trans_b && a.accumulate && a.out_f32 && a.nb1 * a.nb2 <= 1 && !a.ws && !a.bias && !a.res &&
-         !a.dact_z && !a.prez && a.act == TFASR_ACT_NONE && a.drop_p == 0.f && al16(a.A) && al16(a.B) && !(a.lda & 7) && !(a.ldb & 7) &&
-         ((a.M + 7) & ~7) <= a.lda && ((a.N + 7) & ~7) <= a.ldb && a.K >= 8 && a.N > 64 && a.M > 0 && (!a.k_tiles || ktab_eligible(a));
+  if (r.family != TFASR_GEMM_FAST_PERSISTENT) return TFASR_STATUS_EXECUTION_FAILED;
+  TFASR_KLAUNCH((gemm_fast_kernel<TA, TB, BN_, EPI>), dim3(r.workgroups), dim3(256), r.lds_bytes, stream, a, r.tiles_x, r.tiles_y, r.tiles_z, ntiles);
+  return TFASR_STATUS_SUCCESS;
 }
 
 }  // namespace
@@ -1154,103 +947,63 @@ bool group_eligible(const tfasr_gemm_args& a) {
 // set around a launch that shares the chip with another stream's dependent chain (block.hip: the weight-gradient stream); one host thread
 // per process queues the launches of a device, so a plain global is enough
 int g_tfasr_group_beside = 0;
+int g_gemm_big_mode = -1;  // probes (tools/hwprobe/gemm_big_test.hip): 0 = never the 256-row kernels; anything else = the rule of gemm_route.h
 
-// One launch for up to GROUP_MAX weight-gradient products (see wgrad_group_kernel).  UNSUPPORTED -> the caller launches them one by one.
-int tfasr_gemm_group_fast_try(const tfasr_gemm_args* a, int n, hipStream_t stream) {
-  if (n < 2 || n > GROUP_MAX) return TFASR_STATUS_UNSUPPORTED;
-  for (int i = 0; i < n; ++i)
-    if (!group_eligible(a[i]) || (a[i].k_tiles != nullptr) != (a[0].k_tiles != nullptr)) return TFASR_STATUS_UNSUPPORTED;
-  const bool ktab = a[0].k_tiles != nullptr;
-  // K the k loop runs over: the compacted block list of a product with a K-block table
-  auto keff = [](const tfasr_gemm_args& g) -> long { return g.k_tiles ? 256L * g.n_k_tiles : (long)g.K; };
-  GroupArgs ga;
-  memset(&ga, 0, sizeof(ga));
-  long total = 0;
-  static const int bn = 128;
-  for (int i = 0; i < n; ++i) {
-    ga.gx[i] = (a[i].N + bn - 1) / bn;
-    ga.gy[i] = (a[i].M + BM - 1) / BM;
-    total += (long)ga.gx[i] * ga.gy[i];
+// Launches a route of gemm_route() that is not the generic kernels'.  `a`: the call with nb1 / nb2 / split_k >= 1.
+int tfasr_gemm_fast_launch(const GemmRoute& r, const tfasr_gemm_args& a, hipStream_t stream) {
+  const int ntiles = r.tiles_x * r.tiles_y * r.tiles_z;
+  int st = TFASR_STATUS_EXECUTION_FAILED;  // what a route without an instantiation ends in
+  switch (r.family) {
+    case TFASR_GEMM_FAST_PERSISTENT:
+    case TFASR_GEMM_FAST_ONE:
+      switch (gemm_fast_key(r.trans_a, r.trans_b, r.tile_n, r.epi)) {
+#define TFASR_X(TA, TB, BN, EPI) case gemm_fast_key(TA, TB, BN, EPI): st = launch_fast<TA, TB, BN, EPI>(r, a, stream); break;
+        TFASR_GEMM_FAST_TABLE(TFASR_X)
+#undef TFASR_X
+        default: break;
+      }
+      break;
+    case TFASR_GEMM_FAST_SEG:
+      if (r.trans_a || r.epi != 0) break;
+      if (r.trans_b) TFASR_KLAUNCH((gemm_seg_kernel<false, true>), dim3(r.workgroups), dim3(256), r.lds_bytes, stream, a, r.tiles_x, r.tiles_y, 1, ntiles);
+      else TFASR_KLAUNCH((gemm_seg_kernel<false, false>), dim3(r.workgroups), dim3(256), r.lds_bytes, stream, a, r.tiles_x, r.tiles_y, 1, ntiles);
+      st = TFASR_STATUS_SUCCESS;
+      break;
+    case TFASR_GEMM_FAST_KTAB:
+      if (!r.trans_a || r.trans_b || r.epi != E_CSUM) break;
+      TFASR_KLAUNCH((gemm_ktab_kernel<E_CSUM>), dim3(r.workgroups), dim3(256), r.lds_bytes, stream, a, r.tiles_x, r.tiles_y, r.tiles_z, ntiles);
+      st = TFASR_STATUS_SUCCESS;
+      break;
+    case TFASR_GEMM_BIG:
+      st = launch_big(r, a, stream);
+      break;
+    default: break;
   }
-  // k-split shared by the group: fill the resident slots (2 workgroups per CU) once; TFASR_GROUP_SLOTS overrides the slot count.
-  // A group that runs BESIDE another stream's dependent chain (the block executor's weight-gradient stream: g_tfasr_group_beside, set
-  // by the caller around the launch) takes 1.25 slots per CU (256 / 320 / 512 slots for those groups alone: -0.04 / -0.09 / 0 ms per step).
-  // A group of LONG products in line (the nine shifted conv2 weight gradients: K = B T2 F2 = 500 k rows, 36 tiles) also wants about one
-  // workgroup per CU: with 512 slots its 14 k-slices per tile were 8 M atomics and the slices' workgroups drifted apart in L2 - 256 / 320
-  // slots for every group of the step: -0.28 / -0.33 ms per step against 512, of which the block groups beside the chain are 0.04.
-  static const long env_slots = 0;
-  long kmax = 0;
-  for (int i = 0; i < n; ++i) kmax = keff(a[i]) > kmax ? keff(a[i]) : kmax;
-  const long slots = env_slots > 0 ? env_slots : ((g_tfasr_group_beside || kmax >= 131072) ? num_cus() * 5L / 4 : 2L * num_cus());
-  long split = slots / (total > 0 ? total : 1);
-  if (split < 1) split = 1;
-  {
-    static const bool dbg = false;
-    static int dbg_n = 0;
-    if (dbg && dbg_n < 6) { fprintf(stderr, "[group] n %d tiles %ld beside %d slots %ld split %ld\n", n, total, g_tfasr_group_beside, slots, split); ++dbg_n; }
-  }
-  // units (product, k-slice), largest first, each onto the XCD with the fewest slots taken so far
-  struct U { int q, ks, tiles; };
-  U units[GROUP_MAX * 64];
-  int nu = 0;
-  for (int i = 0; i < n; ++i) {
-    long sp = split;
-    if (keff(a[i]) / 512 < sp) sp = keff(a[i]) / 512;
-    if (sp < 1) sp = 1;
-    if (sp > 64) sp = 64;
-    ga.p[i] = a[i];
-    ga.p[i].split_k = (int)sp;
-    ga.p[i].nb1 = ga.p[i].nb2 = 1;
-    for (int k2 = 0; k2 < (int)sp; ++k2) units[nu++] = U{i, k2, ga.gx[i] * ga.gy[i]};
-  }
-  for (int i = 1; i < nu; ++i) {  // insertion sort by tiles, descending
-    const U v = units[i];
-    int j = i - 1;
-    while (j >= 0 && units[j].tiles < v.tiles) { units[j + 1] = units[j]; --j; }
-    units[j + 1] = v;
-  }
-  int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < nu; ++i) {
-    int best = 0;
-    for (int x = 1; x < 8; ++x)
-      if (load[x] < load[best]) best = x;
-    const int c = ga.nunit[best];
-    if (c >= GROUP_UNITS) return TFASR_STATUS_UNSUPPORTED;
-    ga.uq[best][c] = (short)units[i].q;
-    ga.uks[best][c] = (short)units[i].ks;
-    ga.j0[best][c] = load[best];
-    load[best] += units[i].tiles;
-    ga.j0[best][c + 1] = load[best];
-    ga.nunit[best] = c + 1;
-  }
-  int maxload = 0;
-  for (int x = 0; x < 8; ++x)
-    if (load[x] > maxload) maxload = load[x];
-  static const int nst = 2;
-  // accumulate epilogue: atomics from the fragments, no strips in LDS
-  if (bn == 64) {
-    constexpr int STAGE = A_BYTES + 64 * BK * 2;
-    if (nst == 3) TFASR_KLAUNCH((wgrad_group_kernel<E_CSUM, 3, 64>), dim3(8 * maxload), dim3(256), 3 * STAGE, stream, ga);
-    else TFASR_KLAUNCH((wgrad_group_kernel<E_CSUM, 2, 64>), dim3(8 * maxload), dim3(256), 2 * STAGE, stream, ga);
-  } else {
-    constexpr int STAGE = A_BYTES + 128 * BK * 2;
-    if (ktab) TFASR_KLAUNCH((wgrad_group_kernel<E_CSUM, 2, 128, true>), dim3(8 * maxload), dim3(256), 2 * STAGE, stream, ga);
-    else TFASR_KLAUNCH((wgrad_group_kernel<E_CSUM, 2, 128>), dim3(8 * maxload), dim3(256), 2 * STAGE, stream, ga);
+  if (st != TFASR_STATUS_SUCCESS) return st;
+  if (r.epi & E_WS) {  // the route's second launch: the k-slices' partial tiles summed into D
+    TFASR_CHECK_LAUNCH();
+    const long work = ((long)a.M * a.N + 3) / 4;
+    const int rg = (int)(work / 256 + 1 < 2048 ? work / 256 + 1 : 2048);
+    TFASR_KLAUNCH(splitk_reduce_kernel, dim3(rg), dim3(256), 0, stream, (const float*)a.ws, (float*)a.D, a.M, a.N, a.ldd, a.split_k);
   }
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
 
-// returns TFASR_STATUS_UNSUPPORTED when the fast path's preconditions do not hold (caller falls back)
-int tfasr_gemm_fast_try(const tfasr_gemm_args& a, hipStream_t stream) {
-  if (a.dtype != TFASR_BF16) return TFASR_STATUS_UNSUPPORTED;
-  if (!al16(a.A) || !al16(a.B) || (a.lda & 7) || (a.ldb & 7)) return TFASR_STATUS_UNSUPPORTED;
-  if ((a.sA1 & 7) || (a.sA2 & 7) || (a.sB1 & 7) || (a.sB2 & 7)) return TFASR_STATUS_UNSUPPORTED;
-  if (a.trans_a && ((a.M + 7) & ~7) > a.lda) return TFASR_STATUS_UNSUPPORTED;  // 16-B chunks must stay inside the row
-  if (!a.trans_b && ((a.N + 7) & ~7) > a.ldb) return TFASR_STATUS_UNSUPPORTED;
-  if (a.K < 8) return TFASR_STATUS_UNSUPPORTED;
-  if (a.trans_a) return a.trans_b ? launch_one<true, true>(a, stream) : launch_one<true, false>(a, stream);
-  return a.trans_b ? launch_one<false, true>(a, stream) : launch_one<false, false>(a, stream);
+// One launch for the products of a gemm_group_plan() (see wgrad_group_kernel).
+int tfasr_gemm_group_launch(const GemmGroupPlan& g, const tfasr_gemm_args* a, int n, hipStream_t stream) {
+  GroupArgs ga;
+  memset(&ga, 0, sizeof(ga));
+  for (int i = 0; i < n; ++i) {
+    ga.p[i] = a[i];
+    ga.p[i].split_k = g.split[i];
+    ga.p[i].nb1 = ga.p[i].nb2 = 1;
+  }
+  ga.t = g.t;
+  if (g.ktab) TFASR_KLAUNCH((wgrad_group_kernel<E_CSUM, 128, true>), dim3(g.workgroups), dim3(256), g.lds_bytes, stream, ga);
+  else TFASR_KLAUNCH((wgrad_group_kernel<E_CSUM, 128>), dim3(g.workgroups), dim3(256), g.lds_bytes, stream, ga);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -673,20 +673,12 @@ extern "C" int tfasr_layernorm_fwd(const void* x, const float* gamma, const floa
   return TFASR_STATUS_SUCCESS;
 }
 
-static int num_cus_norm() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    n = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return n;
-}
 // blocks of the vectorised backward for a shape; the partial-sum variant has no atomic tail to limit, so it takes every CU
 static int ln_bwd_vec_grid(long rows, int C, bool part) {
   const int rpw = C <= 256 ? 2 : 1;
   if (!part) return std::max(1, fat_grid(rows, rpw));
   const long per_block = 8L * rpw;  // rows per block pass (8 waves)
-  return (int)std::max<long>(1, std::min<long>(rows / (2 * per_block) + 1, (long)num_cus_norm()));
+  return (int)std::max<long>(1, std::min<long>(rows / (2 * per_block) + 1, (long)tfasr_num_cus()));
 }
 static int ln_bwd_vec_launch(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* add, void* dx,
                              float* dgamma, float* dbeta, void* dx_dropped, float drop_p, long drop_seed, long rows, int C, float* part,

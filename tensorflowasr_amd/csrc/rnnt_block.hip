@@ -271,14 +271,12 @@ extern "C" int tfasr_rnnt_block_tail_fwd(const void* y, long ld_y, const int32_t
   hipStream_t s = (hipStream_t)stream_;
   if (dtype == TFASR_F32) {
     const int smem = FM * (P + 4) * (int)sizeof(float);
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)tail_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FM * (MAX_P + 4) * (int)sizeof(float)); attr_done = true; }
+    tfasr_dynamic_lds<tail_f32_kernel>(smem);
     TFASR_KLAUNCH(tail_f32_kernel, dim3((Tpad + FM - 1) / FM, B), dim3(256), (size_t)smem, s, (const float*)y, ld_y, lengths, off, gamma, beta,
                   (const float*)W, bias, (float*)out, out_lengths, T, Tpad, P, N, factor, eps);
   } else {
     const int smem = BM * (P + PAD) * (int)sizeof(bf16_t), Np = (N + 63) / 64 * 64;
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)tail_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BM * (MAX_P + PAD) * (int)sizeof(bf16_t)); attr_done = true; }
+    tfasr_dynamic_lds<tail_bf16_kernel>(smem);
     TFASR_KLAUNCH(tail_bf16_kernel, dim3((Tpad + BM - 1) / BM, B), dim3(256), (size_t)smem, s, (const bf16_t*)y, ld_y, lengths, off, gamma, beta,
                   (const bf16_t*)W, bias, (bf16_t*)out, out_lengths, T, Tpad, P, N, Np, factor, eps);
   }

@@ -283,32 +283,31 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, bias=N
     epilogue stores the RNN-T loss gradient instead (tfasr_gemm_args.rgrad_coef).  k_tiles: i32 device tensor, the ascending 256-row blocks
     of K a transposed-A weight gradient sums over (tfasr_gemm_args.k_tiles; raises TfasrUnsupported for any other product)."""
     a = _gemm_args(A, B, out, M, N, K, lda, ldb, ldd, trans_a, trans_b, bias, res, dact_z, prez, alpha, beta, act, dact, nb1, nb2, sA, sB, sD,
-                   accumulate, split_k, drop_p, drop_seed, colsum, k_tiles)
-    if rgrad is not None:
-        coef, row_label = rgrad
-        assert coef.dtype == torch.float32 and coef.is_contiguous() and row_label.dtype == torch.int32
-        a.rgrad_coef, a.row_label = coef.data_ptr(), row_label.data_ptr()
-    if seg is not None:  # (seg_a_off i64 device tensor, seg_b_off or None, seg_k): K-segmented operands
-        a.seg_a_off, a.seg_b_off, a.seg_k = seg[0].data_ptr(), (seg[1].data_ptr() if seg[1] is not None else None), int(seg[2])
-        assert seg[0].dtype == torch.int64 and seg[0].is_cuda
-    if row_tiles is not None:  # i32 device tensor: the 256-row blocks of `out` to compute (tfasr_gemm_args.row_tiles; K-segmented products only)
-        assert seg is not None and row_tiles.dtype == torch.int32 and row_tiles.is_cuda and row_tiles.is_contiguous()
-        a.row_tiles, a.n_row_tiles = row_tiles.data_ptr(), row_tiles.numel()
-    if bns is not None:
-        bx, bfin, bout = bns[:3]
-        bc = int(bns[3]) if len(bns) > 3 else N   # channels (the columns are (position, channel) pairs when < N)
-        assert bfin.dtype == torch.float32 and bout.dtype == torch.float32 and bout.is_contiguous()
-        a.bns_x, a.bns_fin, a.bns_out, a.bns_copies = bx.data_ptr(), bfin.data_ptr(), bout.data_ptr(), bout.numel() // (2 * bc)
-        a.bns_c = 0 if bc == N else bc
-    if lse is not None:
-        part, row_label, pick = lse
-        assert part.dtype == torch.float32 and pick.dtype == torch.float32 and row_label.dtype == torch.int32
-        a.lse_part, a.lse_parts, a.row_label, a.pick = part.data_ptr(), part.shape[1], row_label.data_ptr(), pick.data_ptr()
+                   accumulate, split_k, drop_p, drop_seed, colsum, k_tiles, lse, seg, rgrad, bns, row_tiles)
     st = _lib.load().tfasr_gemm(ctypes.byref(a), _stream())
     if (lse is not None or seg is not None or rgrad is not None or bns is not None or k_tiles is not None) and st == _lib.STATUS_UNSUPPORTED:
         raise _lib.TfasrUnsupported("gemm: fused row statistics / K-segments / gradient epilogue / K-block table are not available for this product")
     check(st, "gemm")
     return out
+
+
+def gemm_route(ncu=0, **kw):
+    """The kernel tfasr_gemm takes for gemm(**kw) on a part with `ncu` compute units (0: the current device), as the library itself says
+    (tfasr_gemm_route; the rules: csrc/gemm_route.h): a _lib.GemmRouteInfo - status, family, layout, tile width, epilogue bits, grid, LDS,
+    launch count.  Nothing is launched."""
+    info = _lib.GemmRouteInfo()
+    _lib.load().tfasr_gemm_route(ctypes.byref(_gemm_args(**kw)), int(ncu), ctypes.byref(info))
+    return info
+
+
+def gemm_group_route(calls, ncu=0):
+    """(status, launches) of gemm_group(calls) (tfasr_gemm_group_route); nothing is launched"""
+    arr = (GemmArgs * len(calls))()
+    for i, kw in enumerate(calls):
+        arr[i] = _gemm_args(**kw)
+    n = ctypes.c_int(0)
+    st = _lib.load().tfasr_gemm_group_route(arr, len(calls), int(ncu), ctypes.byref(n))
+    return st, n.value
 
 
 def gemm_group(calls):
@@ -326,7 +325,8 @@ def gemm_group(calls):
 
 def _gemm_args(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, bias=None, res=None, dact_z=None,
                prez=None, alpha=1.0, beta=1.0, act=ACT_NONE, dact=ACT_NONE, nb1=1, nb2=1, sA=(0, 0), sB=(0, 0), sD=(0, 0),
-               accumulate=False, split_k=1, drop_p=0.0, drop_seed=0, colsum=None, k_tiles=None):
+               accumulate=False, split_k=1, drop_p=0.0, drop_seed=0, colsum=None, k_tiles=None, lse=None, seg=None, rgrad=None, bns=None,
+               row_tiles=None):
     a = GemmArgs()
     a.A, a.B, a.D = A.data_ptr(), B.data_ptr(), (out.data_ptr() if out is not None else None)
     a.bias = bias.data_ptr() if bias is not None else None
@@ -355,6 +355,26 @@ def _gemm_args(A, B, out, M, N, K, lda, ldb, ldd, trans_a=False, trans_b=False, 
         if _SPLITK_WS and split_k > 1 and nb1 * nb2 == 1 and k_tiles is None:  # opt-in: k-slices reduce through a workspace (deterministic sums)
             ws = workspace(4 * split_k * M * N, out.device, "splitk_%d" % (_raw_stream(torch.cuda.current_device()) if _raw_stream else 0))
             a.ws, a.ws_elems = ws.data_ptr(), ws.numel() // 4
+    if rgrad is not None:
+        coef, row_label = rgrad
+        assert coef.dtype == torch.float32 and coef.is_contiguous() and row_label.dtype == torch.int32
+        a.rgrad_coef, a.row_label = coef.data_ptr(), row_label.data_ptr()
+    if seg is not None:  # (seg_a_off i64 device tensor, seg_b_off or None, seg_k): K-segmented operands
+        a.seg_a_off, a.seg_b_off, a.seg_k = seg[0].data_ptr(), (seg[1].data_ptr() if seg[1] is not None else None), int(seg[2])
+        assert seg[0].dtype == torch.int64 and seg[0].is_cuda
+    if row_tiles is not None:  # i32 device tensor: the 256-row blocks of `out` to compute (tfasr_gemm_args.row_tiles; K-segmented products only)
+        assert seg is not None and row_tiles.dtype == torch.int32 and row_tiles.is_cuda and row_tiles.is_contiguous()
+        a.row_tiles, a.n_row_tiles = row_tiles.data_ptr(), row_tiles.numel()
+    if bns is not None:
+        bx, bfin, bout = bns[:3]
+        bc = int(bns[3]) if len(bns) > 3 else N   # channels (the columns are (position, channel) pairs when < N)
+        assert bfin.dtype == torch.float32 and bout.dtype == torch.float32 and bout.is_contiguous()
+        a.bns_x, a.bns_fin, a.bns_out, a.bns_copies = bx.data_ptr(), bfin.data_ptr(), bout.data_ptr(), bout.numel() // (2 * bc)
+        a.bns_c = 0 if bc == N else bc
+    if lse is not None:
+        part, row_label, pick = lse
+        assert part.dtype == torch.float32 and pick.dtype == torch.float32 and row_label.dtype == torch.int32
+        a.lse_part, a.lse_parts, a.row_label, a.pick = part.data_ptr(), part.shape[1], row_label.data_ptr(), pick.data_ptr()
     return a
 
 

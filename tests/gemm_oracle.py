@@ -1,15 +1,19 @@
 """One tfasr_gemm call restated plainly in float64 torch on the CPU, the dispatcher's choice of kernel restated in plain Python, and the
 table of cases that pins every route of csrc/gemm.hip, csrc/gemm_fast.hip and csrc/gemm_big.h (tests/test_gemm_routes_gpu.py runs it on the
-GPU; tests/test_gemm_oracle.py checks this file on the CPU).
+GPU; tests/test_gemm_oracle.py checks this file on the CPU; tests/test_gemm_route.py holds route() against the library's own answer).
 
 reference()  the terms in the order the epilogue of gemm_kernel (csrc/gemm.hip) defines:
                  v = alpha * acc + bias;  prez = v;  v = act(v);  v *= dact(dact_z);  v = keep ? v / (1 - p) : 0;  v = res + beta * v;
                  D = v   (accumulate: D = start + v);  colsum = colsum_start + alpha * sum_k B[k, :]
              The dropout mask `keep` is an argument: the hash is not restated here.  Operands, dact_z, res and keep are FLAT buffers read
              through the strides of the call, exactly as the kernels read them.
-route()      what tfasr_gemm / tfasr_gemm_fast_try / launch_one / launch_epi / launch_big / launch<T> choose for a call on a part with
-             `cus` compute units.  The library has no call that says which kernel ran: a test asserts the label its case was written for
-             (and the launch count), so on a part where the rule picks another kernel the test fails instead of testing something else.
+route()      what gemm_route() of csrc/gemm_route.h chooses for a call on a part with `cus` compute units, restated independently.  A test
+             asserts the label its case was written for (and the launch count), so on a part where the rule picks another kernel the test
+             fails instead of testing something else.
+library_route() / label_of()   the same answer from the library itself (tfasr_gemm_route), brought to a label: tests/test_gemm_route.py
+             holds the two against each other on the CPU, tests/test_gemm_routes_gpu.py at the live CU count.
+gemm_args()  the tfasr_gemm_args of a case as kernels._gemm_args fills them, over FAKE addresses (the route looks at null-ness and
+             alignment only).
 cases()      the case table, with M sized from the CU count wherever the route depends on it.
 
 Labels   ("fast", 64 | 128, "persist" | "one", epilogue)   gemm_fast_kernel / gemm_fast_one_kernel <TA, TB, BN, EPI>
@@ -17,12 +21,15 @@ Labels   ("fast", 64 | 128, "persist" | "one", epilogue)   gemm_fast_kernel / ge
          ("generic", "bf16" | "f32", 64 | 128)              gemm_kernel<T, TA, TB, BN>
          ("generic+colsum", "bf16" | "f32", 64 | 128)       tfasr_colsum, then gemm_kernel (two launches)
          ("group", 128, "E_CSUM") / ("one by one",)         tfasr_gemm_group
-Out of scope (their own tests): K-segments, row_tiles, k_tiles, lse, rgrad, bns, the split-K workspace, ffn_fused, dense_ln."""
+         ("seg", 128) / ("ktab", 128, "E_CSUM") / ("big-seg", 256, "0", "tr" | "rows") / ("status", 1 | 3)   route_full() only
+route_full() restates the ROUTE (status, kernel, launch count) of calls with K-segments, row_tiles, k_tiles, lse, rgrad, bns and the split-K
+workspace as well; their results stay out of scope here (their own tests), as do ffn_fused and dense_ln."""
 import math
 from dataclasses import dataclass, replace
 
 import torch
 
+from tensorflowasr_amd import _lib
 from tensorflowasr_amd._lib import ACT_FACTOR, ACT_NONE, ACT_SIGMOID, ACT_SWISH, ACT_TANH, ACT_TANH_OUT
 
 F64 = torch.float64
@@ -76,6 +83,16 @@ class Case:
     colsum: bool = False
     kinds: tuple = ("exact", "random")
     launches: int = 1
+    # the optional parts of the struct that only the route is restated for (route_full(); their results have tests of their own)
+    seg_k: int = 0           # != 0: the call has a seg_a_off table with this seg_k
+    row_tiles: int = 0       # != 0: a row-tile table with this n_row_tiles
+    k_tiles: int = 0         # != 0: a K-block table with this n_k_tiles
+    lse: int = 0             # 1: lse_part / row_label / pick with lse_parts = ceil(N / 128) * 2; 2: with lse_parts one too many
+    no_D: bool = False       # D is NULL
+    rgrad: bool = False      # rgrad_coef and row_label
+    bns: bool = False        # bns_out / bns_x / bns_fin, channels bns_c
+    bns_c: int = 0
+    ws: bool = False         # a split-K workspace that is large enough
 
     # ---- what the struct of the call holds
     @property
@@ -314,7 +331,7 @@ INF = 1 << 40
 
 
 def _fast_refusal(c):
-    """tfasr_gemm_fast_try: why the bf16 fast path hands the call back (None: it takes it)"""
+    """why the bf16 LDS-DMA kernels hand the call back to the generic ones (None: they take it)"""
     if c.f32:
         return "dtype"
     if c.a_off % 8 or c.b_off % 8:  # (buffers start on 256 bytes)
@@ -333,16 +350,19 @@ def _fast_refusal(c):
 
 
 def _launch_epi(c, bn, epi, tiles, cus):
-    if bn == 64 and epi != "E_CSUM" and c.split_k <= 1 and tiles > 2 * cus:
+    if bn == 64 and epi not in ("E_CSUM", "E_WS", "E_LSE") and c.split_k <= 1 and tiles > 2 * cus:
         return ("fast", 64, "one", epi)
     return ("fast", bn, "persist", epi)
 
 
 def _launch_big(c, generic, need, tanh_out, cus):
-    """gemm_big.h launch_big (None: UNSUPPORTED)"""
+    """the 256-row kernels of gemm_big.h (None: not eligible)"""
     if generic or need or c.accumulate or c.split_k > 1 or c.nb != 1 or c.colsum or c.out_f32 or c.K < 128 or c.K % 8 or c.M < 256 or (c.tb and c.N % 8):
         return None
-    if c.tb and c.N % 320 == 0:
+    seg = c.seg_k != 0
+    if seg and not (c.seg_k > 0 and c.seg_k % 64 == 0 and c.K % c.seg_k == 0 and c.K // 64 <= 64):
+        return None
+    if c.tb and not seg and not c.lse and c.N % 320 == 0:
         bn = 320
     elif c.N >= (256 if c.tb else 192) and (c.N % 256 == 0 or c.N % 256 >= 192):
         bn = 256
@@ -350,20 +370,36 @@ def _launch_big(c, generic, need, tanh_out, cus):
         return None
     if ceil_div(c.N, bn) * ceil_div(c.M, 256) < 2 * cus:
         return None
-    if tanh_out and not c.tb:
+    if tanh_out and (not c.tb or seg or c.lse):
         return None
-    tr = c.ldd % 8 == 0 and c.N % 8 == 0 and c.d_off % 8 == 0
+    if c.lse and not (bn == 256 and c.lse == 1):
+        return None
+    if c.rgrad and (c.tb or seg or tanh_out or bn != 256):
+        return None
+    if c.no_D and not c.lse:
+        return None
+    tr = c.ldd % 8 == 0 and c.N % 8 == 0 and (c.no_D or c.d_off % 8 == 0)
     if tanh_out:
         return ("big", bn, "E_DACT", "tr" if (tr and bn == 256) else "rows")
-    return ("big", bn, "0", "tr" if (tr and bn == 256) else "rows")
+    if bn == 320:
+        return ("big", bn, "0", "rows")
+    if c.lse:  # (the statistics kernel has no K-segment variant: a table that came this far is ignored)
+        return None if c.tb else ("big", 256, "E_LSE", "tr" if (tr or c.no_D) else "rows")
+    if c.rgrad:
+        return ("big", 256, "E_RGRAD", "rows")
+    return ("big-seg" if seg else "big", bn, "0", "tr" if tr else "rows")
 
 
 def _launch_one(c, cus):
-    """gemm_fast.hip launch_one<TA, TB> (None: UNSUPPORTED)"""
+    """the bf16 kernels of gemm_fast.hip / gemm_big.h (None: left to the generic ones)"""
     split = max(c.split_k, 1)
+    if c.k_tiles:  # K-block table: the accumulating x^T dy product on 128-wide tiles, or nothing
+        ok = (c.ta and not c.tb and c.accumulate and c.nb == 1 and not c.ws and not c.seg_k and not c.row_tiles and not c.lse and not c.rgrad and
+              not c.bns and 0 < c.k_tiles <= ceil_div(c.K, 256) and c.d_f32)
+        return ("ktab", 128, "E_CSUM") if ok else None
     t128 = ceil_div(c.N, 128) * ceil_div(c.M, 128) * c.nb * split
     lim = INF if (split <= 1 and not c.accumulate and not c.colsum and min(c.K, c.N) <= 256) else cus
-    narrow = c.N <= 64 or t128 <= lim
+    narrow = not c.lse and not c.seg_k and (c.N <= 64 or (t128 <= lim and not (c.accumulate and c.ws)))
     bn = 64 if narrow else 128
     tiles = ceil_div(c.N, bn) * ceil_div(c.M, 128) * c.nb * split
     need, generic = 0, False
@@ -386,17 +422,34 @@ def _launch_one(c, cus):
             need |= E_DROP
         if c.res:
             need |= E_RES
+    plain = not generic and need == 0
+    if c.bns:  # BatchNorm sums in the epilogue: the plain NT product on 64-column tiles, or nothing
+        ok = (not c.ta and c.tb and narrow and plain and not c.accumulate and not c.bias and split == 1 and c.nb == 1 and c.N % 8 == 0 and c.ldd % 8 == 0 and
+              (c.bns_c == 0 or (c.bns_c > 0 and c.bns_c % 8 == 0 and c.N % c.bns_c == 0)) and c.d_off % 8 == 0 and not c.no_D and
+              not c.colsum and not c.lse and not c.seg_k and not c.rgrad)
+        return _launch_epi(c, 64, "E_BNS", tiles, cus) if ok else None
     if not c.ta:
         tanh_out = not c.accumulate and dz and c.dact == ACT_TANH_OUT
         other = c.out_f32 or c.act != ACT_NONE or c.prez or (dz and not tanh_out)
         big = _launch_big(c, other, need, tanh_out, cus)
         if big:
             return big
+    if c.rgrad or c.no_D:  # gradient epilogue / statistics-only projection: 256-row kernel only
+        return None
+    if c.accumulate and split > 1 and c.nb == 1 and c.ws and not narrow and not c.colsum:
+        return ("fast", 128, "persist", "E_WS")
     if c.colsum:
         if c.ta and not c.tb and c.accumulate and c.N > 64:
             return _launch_epi(c, bn, "E_CSUM", tiles, cus)
         return None
     nn, nt = not c.ta and not c.tb, not c.ta and c.tb
+    if c.seg_k:  # K-segments: the plain NN / NT product on 128-wide tiles, without statistics
+        ok = (not c.ta and plain and not c.accumulate and split == 1 and c.nb == 1 and c.seg_k > 0 and c.seg_k % 64 == 0 and c.K % c.seg_k == 0 and
+              c.K // 64 <= 64 and not c.lse)
+        return ("seg", 128) if ok else None
+    if c.lse:
+        ok = nn and plain and not c.accumulate and c.nb == 1 and c.lse == 1
+        return ("fast", 128, "persist", "E_LSE") if ok else None
     if not generic:
         compiled = need == 0 or (nn and need in (E_RES, E_RES | E_DROP))
         if not narrow or (t128 > cus and c.N > 64):
@@ -411,9 +464,41 @@ def route(c, cus):
     label = None if _fast_refusal(c) else _launch_one(c, cus)
     if label:
         return label
-    tiles = ceil_div(c.N, 128) * ceil_div(c.M, 128) * c.nb * max(c.split_k, 1)  # gemm.hip launch<T>
+    tiles = ceil_div(c.N, 128) * ceil_div(c.M, 128) * c.nb * max(c.split_k, 1)  # the generic kernels of gemm.hip
     width = 64 if (c.f32 and c.N > 64 and tiles < 2 * cus) else 128
     return ("generic+colsum" if c.colsum else "generic", c.dtype, width)
+
+
+def route_full(c, cus):
+    """(label, launches) of ANY call, the optional tables / statistics / gradient epilogue / BatchNorm sums / workspace included, restated from
+    tfasr_gemm as it stood before csrc/gemm_route.h; a refused call gives (("status", 1 | 3), None)"""
+    INVALID, UNSUPPORTED = (("status", 1), None), (("status", 3), None)
+    split = max(c.split_k, 1)
+    if (c.no_D and not c.lse) or (c.rgrad and (c.no_D or c.lse)) or min(c.M, c.N, c.K) <= 0:
+        return INVALID
+    if (c.accumulate and not c.d_f32) or (split > 1 and not c.accumulate):
+        return INVALID
+    if split > 1 and (c.res or c.dact != ACT_NONE or c.prez or c.act != ACT_NONE or c.drop_p > 0):
+        return INVALID
+    if not 0 <= c.drop_p < 1 or (c.colsum and not (c.accumulate and c.ta and not c.tb and c.nb == 1)):
+        return INVALID
+    if c.row_tiles:
+        if c.row_tiles <= 0 or c.row_tiles > ceil_div(c.M, 256):
+            return INVALID
+        if not c.seg_k or c.ta or c.accumulate or split > 1 or c.nb != 1 or c.f32:
+            return UNSUPPORTED
+    if c.k_tiles:
+        if c.k_tiles <= 0 or c.k_tiles > ceil_div(c.K, 256):
+            return INVALID
+        if not c.ta or c.tb or not c.accumulate or c.nb != 1 or c.f32 or c.seg_k or c.row_tiles or c.ws:
+            return UNSUPPORTED
+    label = None if _fast_refusal(c) else _launch_one(c, cus)
+    if label:
+        return label, (2 if label[-1] == "E_WS" else 1)
+    if c.k_tiles or c.lse or c.rgrad or c.bns or c.seg_k:
+        return UNSUPPORTED
+    label = route(c, cus)
+    return label, (2 if c.colsum else 1)
 
 
 def route_group(cs, cus):
@@ -427,6 +512,86 @@ def route_group(cs, cus):
         units = sum(min(64, max(1, min(split, c.K // 512))) for c in cs)
         ok = units <= 8 * 20 // 2  # (far from the list limit: the exact dealing is not restated)
     return ("group", 128, "E_CSUM") if ok else ("one by one",)
+
+
+# ------------------------------------------------------------------------------------------------- the library's own answer
+BASE = 0x7F0000000000  # a 256-byte aligned address nothing reads: operands, D, res, dact_z, prez each get a region of their own
+REGION = 1 << 36
+E_LABELS = {**E_NAMES, 16: "E_WS", 32: "E_CSUM", 64: "E_LSE", 128: "E_RGRAD", 256: "E_GEN", 512: "E_BNS"}
+
+
+def gemm_args(c):
+    """tfasr_gemm_args of the case as kernels._gemm_args fills them; every pointer = its region's base + the case's element offset"""
+    esz, dsz = (4 if c.f32 else 2), (4 if c.d_f32 else 2)
+    at = lambda region, off, size: BASE + region * REGION + off * size
+    a = _lib.GemmArgs()
+    a.A, a.B, a.D = at(0, c.a_off, esz), at(1, c.b_off, esz), at(2, c.d_off, dsz)
+    a.bias = at(3, 0, 4) if c.bias else None
+    a.res = at(4, c.d_off, esz) if c.res else None
+    a.dact_z = at(5, c.d_off, esz) if c.dact != ACT_NONE else None
+    a.prez = at(6, c.d_off, esz) if c.prez else None
+    a.colsum = at(7, 0, 4) if c.colsum else None
+    a.M, a.N, a.K, a.lda, a.ldb, a.ldd = c.M, c.N, c.K, c.lda, c.ldb, c.ldd
+    a.trans_a, a.trans_b, a.nb1, a.nb2 = int(c.ta), int(c.tb), c.nb1, c.nb2
+    (a.sA1, a.sA2), (a.sB1, a.sB2), (a.sD1, a.sD2) = c.sA, c.sB, c.sD
+    a.alpha, a.beta, a.act, a.dact = c.alpha, c.beta, c.act, c.dact
+    a.dtype = _lib.TFASR_F32 if c.f32 else _lib.TFASR_BF16
+    a.out_f32, a.accumulate, a.split_k = int(c.d_f32), int(c.accumulate), c.split_k
+    a.drop_p, a.drop_seed = c.drop_p, 1
+    if c.no_D:
+        a.D = None
+    if c.seg_k:
+        a.seg_a_off, a.seg_k = at(8, 0, 8), c.seg_k
+    if c.row_tiles:
+        a.row_tiles, a.n_row_tiles = at(9, 0, 4), c.row_tiles
+    if c.k_tiles:
+        a.k_tiles, a.n_k_tiles = at(10, 0, 4), c.k_tiles
+    if c.lse:
+        a.lse_part, a.row_label, a.pick, a.lse_parts = at(11, 0, 4), at(12, 0, 4), at(13, 0, 4), ceil_div(c.N, 128) * 2 + (c.lse - 1)
+    if c.rgrad:
+        a.rgrad_coef, a.row_label = at(14, 0, 4), at(12, 0, 4)
+    if c.bns:
+        a.bns_x, a.bns_fin, a.bns_out, a.bns_copies, a.bns_c = at(15, 0, esz), at(16, 0, 4), at(17, 0, 4), 1, c.bns_c
+    if c.ws:
+        a.ws, a.ws_elems = at(18, 0, 4), max(c.split_k, 1) * c.M * c.N
+    return a
+
+
+def label_of(info, c):
+    """the label of a tfasr_gemm_route_info (None: a route outside the labels of this file)"""
+    if info.status != 0:
+        return ("status", info.status)
+    if info.family in (_lib.GEMM_FAST_PERSISTENT, _lib.GEMM_FAST_ONE):
+        return ("fast", info.tile_n, "persist" if info.family == _lib.GEMM_FAST_PERSISTENT else "one", E_LABELS.get(info.epi))
+    if info.family == _lib.GEMM_BIG:
+        return ("big-seg" if info.seg else "big", info.tile_n, E_LABELS.get(info.epi), "tr" if info.tr else "rows")
+    if info.family == _lib.GEMM_FAST_SEG:
+        return ("seg", info.tile_n)
+    if info.family == _lib.GEMM_FAST_KTAB:
+        return ("ktab", info.tile_n, E_LABELS.get(info.epi))
+    if info.family == _lib.GEMM_GENERIC:
+        return ("generic+colsum" if info.launches == 2 else "generic", c.dtype, info.tile_n)
+    return None
+
+
+def library_route(c, cus):
+    """(label, launches) of the call `c` on `cus` compute units as tfasr_gemm_route gives them"""
+    import ctypes
+
+    info = _lib.GemmRouteInfo()
+    st = _lib.load().tfasr_gemm_route(ctypes.byref(gemm_args(c)), cus, ctypes.byref(info))
+    assert st == info.status
+    return label_of(info, c), (info.launches if st == 0 else None)
+
+
+def library_route_group(cs, cus):
+    """the label of tfasr_gemm_group on the calls `cs` as tfasr_gemm_group_route counts its launches"""
+    import ctypes
+
+    arr = (_lib.GemmArgs * len(cs))(*[gemm_args(c) for c in cs])
+    n = ctypes.c_int(-1)
+    assert _lib.load().tfasr_gemm_group_route(arr, len(cs), cus, ctypes.byref(n)) == 0
+    return ("group", 128, "E_CSUM") if n.value == ceil_div(len(cs), 10) else ("one by one",)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the case table

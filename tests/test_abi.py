@@ -117,8 +117,9 @@ def test_ctypes_structures_have_the_header_sizes(tmp_path):
         pytest.skip("gcc not available")
     src = tmp_path / "sz.c"
     src.write_text('#include <stdio.h>\n#include "tfasr_hip.h"\nint main(void) { printf("%zu %zu %zu %zu\\n", sizeof(tfasr_block_io), '
-                   'sizeof(tfasr_block_cfg), sizeof(tfasr_block_params), sizeof(tfasr_gemm_args)); return 0; }\n')
+                   'sizeof(tfasr_block_cfg), sizeof(tfasr_block_params), sizeof(tfasr_gemm_args)); printf("%zu\\n", sizeof(tfasr_gemm_route_info)); return 0; }\n')
     exe = tmp_path / "sz"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     sizes = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert sizes == [ctypes.sizeof(_lib.BlockIO), ctypes.sizeof(_lib.BlockCfg), ctypes.sizeof(_lib.BlockParams), ctypes.sizeof(_lib.GemmArgs)]
+    assert sizes == [ctypes.sizeof(_lib.BlockIO), ctypes.sizeof(_lib.BlockCfg), ctypes.sizeof(_lib.BlockParams), ctypes.sizeof(_lib.GemmArgs),
+                     ctypes.sizeof(_lib.GemmRouteInfo)]

@@ -1,7 +1,7 @@
 """tfasr_gemm and tfasr_gemm_group on every dispatch route and epilogue against the float64 restatement of tests/gemm_oracle.py.
 
-Every case first asserts that gemm_oracle.route(), the Python restatement of the dispatcher, gives the label the case was written for at
-the LIVE compute-unit count (the library cannot say which kernel ran), then the launch count of the call (1; 2 for the column-sum
+Every case first asserts that gemm_oracle.route(), the Python restatement of the dispatcher, AND the library's own route (tfasr_gemm_route)
+give the label the case was written for at the LIVE compute-unit count, then the launch count of the call (1; 2 for the column-sum
 fallback), then the results.  Inputs are rounded to the storage type first; operand buffers hold NaN wherever the product must not read
 (row padding, the k tail of a padded row, the element in front of an operand that starts off 16 bytes); D and prez are pre-filled with NaN,
 guard columns (ldd > N), a guard row and the gaps between batches included, and everything outside the M x N views must come back bit for
@@ -93,6 +93,7 @@ def _case(dev, name):
         _TABLES[cus] = GO.cases(cus)
     c = _TABLES[cus][name]
     assert GO.route(c, cus) == c.label, f"{name}: on {cus} CUs the dispatcher takes {GO.route(c, cus)}, the case was written for {c.label}"
+    assert GO.library_route(c, 0) == (c.label, c.launches), f"{name}: the library takes {GO.library_route(c, 0)}, the case was written for {c.label}"
     return c
 
 
@@ -224,6 +225,7 @@ def test_grouped_weight_gradients(dev, kind):
     not zero) in ONE launch, each held to its own float64 reference"""
     cs = GO.group_cases()
     assert GO.route_group(cs, _cus(dev)) == ("group", 128, "E_CSUM")
+    assert GO.library_route_group(cs, 0) == ("group", 128, "E_CSUM")
     runs = []
     for c0 in cs:
         c, x = GO.make_inputs(c0, kind)

@@ -4,6 +4,12 @@
 #define TFASR_GEMM_TIMING 1
 #endif
 #include "../../tensorflowasr_amd/csrc/gemm_fast.hip"
+// the library's bf16 path without the generic kernels of gemm.hip: the route of gemm_route.h, launched (UNSUPPORTED: the generic kernels' call)
+static int tfasr_gemm_fast_try(const tfasr_gemm_args& a, hipStream_t s) {
+  const GemmRoute r = gemm_route(a, tfasr_num_cus(), g_gemm_big_mode != 0);
+  if (r.status != TFASR_STATUS_SUCCESS) return r.status;
+  return r.family == TFASR_GEMM_GENERIC ? TFASR_STATUS_UNSUPPORTED : tfasr_gemm_fast_launch(r, a, s);
+}
 #include <vector>
 std::atomic<size_t> g_tfasr_launch_count{0};
 #include <stdio.h>

@@ -2,6 +2,12 @@
 //   ./gemm_ws_test [M] [N] [K] [mul]      D[M,N] = A[M,K] @ Wt[N,K]^T (* mul[M,N])
 // prints us/launch of both, max abs difference, and checks a sample of entries against a host f64 sum.
 #include "../../tensorflowasr_amd/csrc/gemm_fast.hip"
+// the library's bf16 path without the generic kernels of gemm.hip: the route of gemm_route.h, launched (UNSUPPORTED: the generic kernels' call)
+static int tfasr_gemm_fast_try(const tfasr_gemm_args& a, hipStream_t s) {
+  const GemmRoute r = gemm_route(a, tfasr_num_cus(), g_gemm_big_mode != 0);
+  if (r.status != TFASR_STATUS_SUCCESS) return r.status;
+  return r.family == TFASR_GEMM_GENERIC ? TFASR_STATUS_UNSUPPORTED : tfasr_gemm_fast_launch(r, a, s);
+}
 #include "gemm_ws.h"
 #include <string.h>
 #include <stdlib.h>
