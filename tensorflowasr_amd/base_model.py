@@ -79,7 +79,7 @@ def optimizer_from_config(cfg, dmodel):
 
 
 class BaseModel:
-    """Mixin of the concrete models (ConformerTransducer, ConformerCTC, ContextNetTransducer)."""
+    """Base of model.AsrModel, and through it of every concrete model."""
 
     _tokenizer = None
     gwn_config = None

@@ -1,13 +1,14 @@
-"""Conformer-Transducer on MI355X: explicit forward / backward over the HIP kernels of libtfasr_hip.so.
+"""The Conformer encoder on MI355X: explicit forward / backward over the HIP kernels of libtfasr_hip.so, and the Conformer-Transducer.
 
 Mirrors the reference's model surface for this path:
     tensorflow_asr.models.transducer.conformer.Conformer        (models/transducer/conformer.py:22-143)
-    Transducer.call / call_next / recognize*                    (models/transducer/base_transducer.py:427-712)
-    BaseModel.train_step / _train_step / _apply_gradients       (models/base_model.py:149-198)
+    ConformerEncoder.call / Conv2dSubsampling / ConformerBlock  (models/encoders/conformer.py)
 but is NOT a Keras graph: every module has a hand-written backward that reuses the forward's saved tensors, the
-residual additions / biases / activations are fused into GEMM epilogues, and the whole step is a fixed sequence of
-C-ABI kernel launches on one HIP stream (prediction network on a second stream, overlapped with the encoder).
+residual additions / biases / activations are fused into GEMM epilogues, and the encoder is a fixed sequence of
+C-ABI kernel launches on one HIP stream (what leaves the blocks' dependent chain runs on the block executor's side stream).
 PyTorch only owns device memory and streams here.  There is no CPU / eager fallback.
+
+ConformerEncoderMixin goes in front of a head (model.AsrModel's docstring): ConformerTransducer here, ConformerCTC in ctc_model.py.
 """
 import math
 import os
@@ -16,61 +17,29 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .base_model import BaseModel
-from .kernels import ACT_NONE, ACT_SWISH, ACT_TANH_OUT
-from .params import ParamStore
-from .schemas import AlignOutput, PredictInput, PredictOutput, RecognizeOutput, TrainData, TrainInput, TrainOutput
+from .kernels import ACT_SWISH
+from .model import SingleProcess, _mel_weight_matrix, _split_k  # noqa: F401  (imported from here by the tools and the tests)
+from .transducer import TransducerModel
 
 
-class SingleProcess:
-    """Collective hooks for one GPU (tensorflowasr_amd.dp.DataParallel implements them over RCCL)."""
+class ConformerEncoderMixin:
+    """frontend's tail bookkeeping, Conv2dSubsampling on both layouts, the Conformer blocks (Python path and native executor, hoists,
+    deferred gradients), encoder_fwd / encoder_bwd and the chunked streaming session; mixed in front of TransducerModel / CtcModel"""
 
-    world = 1
-    rank = 0
+    encoder_kind = "conformer"
 
-    def allreduce_stats_(self, t):  # sync-BN statistics (sum over replicas)
-        return t
-
-    def set_reduce(self, on):  # gradient accumulation: only the apply micro-step exchanges gradients
-        pass
-
-    def grads_ready(self, lo, hi):  # gradient slice [lo, hi) of the flat buffer is final
-        pass
-
-    def finish_grads(self):
-        pass
-
-
-def _split_k(M, N, Kd):
-    tiles = -(-M // 128) * -(-N // 128)
-    if tiles >= 512 or Kd <= 2048:
-        return 1
-    v = int(max(1, min(-(-1024 // tiles), Kd // 1024, 64)))
-    return (v + 4) // 8 * 8 if v >= 12 else v  # whole k-slices per XCD (gemm_fast.hip split-K mapping needs split % 8 == 0)
-
-
-class ConformerTransducer(BaseModel):
-    def __init__(self, cfg, device=None, dtype=torch.bfloat16, seed=0, dp=None):
-        if not torch.cuda.is_available():
-            raise K._lib.TfasrError("ConformerTransducer needs an MI355X (HIP) device; there is no CPU fallback")
-        self.cfg = cfg
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.dtype = dtype
+    def _param_options(self, cfg, dtype):
         # bf16 models store attention heads narrower than 64 zero-padded to 64 (ParamStore.__init__): the reference's shipped head sizes
         # (36, 44) then run on the fused LDS-staged attention kernels, results unchanged
-        pad = (dtype == torch.bfloat16 and cfg.head_size < 64 and getattr(cfg, "encoder", "conformer") == "conformer"
-               and os.environ.get("TFASR_HEAD_PAD", "1") != "0")
+        pad = dtype == torch.bfloat16 and cfg.head_size < 64 and os.environ.get("TFASR_HEAD_PAD", "1") != "0"
         # ... and the convolutional subsampling's channels padded to a multiple of 64 (144 -> 192): conv2 then runs as K-segmented GEMMs
         # over the space-to-depth layout with conv1 + BatchNorm recomputed, like the 256-filter model (Conformer-S: 14.3 -> 13.6 ms/step)
         # (a LayerNormalization in the subsampling - `norms: layer`, small-streaming.yml.j2 - normalises over the channel axis: no padding)
-        cpad = (dtype == torch.bfloat16 and cfg.filters % 64 != 0 and getattr(cfg, "encoder", "conformer") == "conformer"
+        cpad = (dtype == torch.bfloat16 and cfg.filters % 64 != 0
                 and getattr(cfg, "sub_norm", "batch") == "batch" and os.environ.get("TFASR_FILTER_PAD", "1") != "0")
-        self.ps = ParamStore(cfg, self.device, dtype, seed, head_phys=64 if pad else None, filt_phys=-(-cfg.filters // 64) * 64 if cpad else None)
-        self.dp = dp or SingleProcess()
-        self.blank = cfg.blank
-        self.time_reduction_factor = cfg.time_reduction_factor
-        self.step = 0
-        self._consts = {}
+        return dict(head_phys=64 if pad else None, filt_phys=-(-cfg.filters // 64) * 64 if cpad else None)
+
+    def _init_encoder(self):
         self._bn1_sums_in_gemm = True  # subsampling BatchNorm1 backward sums in the linear layer's data gradient
         self._bn_stats_copies = 8  # ConvModule BatchNorm statistics inside the depthwise conv, atomics spread over this many copies; 1: the two launches (tests)
         self._conv1_gram = True  # conv1 / BatchNorm0 sums through the patch Gram matrix (one backward pass); False: the two-pass kernels (tests)
@@ -80,30 +49,9 @@ class ConformerTransducer(BaseModel):
         # ... and the subsampling's backward folds the gradient of each utterance's padded tail into three rows
         self._sub_tail_bwd = os.environ.get("TFASR_SUB_TAIL_BWD", "1") != "0"
         self._front_tail = None
-        # SpecAugment draws and dropout masks are per replica (MirroredStrategy draws independent randomness on every
-        # replica); the parameter initialisation seed above is shared by all ranks
-        self._rng = np.random.default_rng([seed + 1000, int(self.dp.rank)])
-        # Streams = hardware queues, and on this chip the step time depends on how many are live (with eight queues a
-        # data-parallel rank ran 38 instead of 23 ms).  HIP never lets streams of DIFFERENT priority share a queue, so the three streams of the
-        # step sit on three priority levels - the encoder chain on the default stream, the prediction network (hundreds of tiny launches the
-        # joint network waits for) on a HIGH-priority stream, everything nothing on the chain waits for on the executor's LOW-priority stream -
-        # which keeps them on separate queues whatever GPU_MAX_HW_QUEUES is and whatever streams RCCL adds.
-        prio = -1
-        self.pred_stream = torch.cuda.Stream(device=self.device, priority=prio)
-        self.use_pred_stream = os.environ.get("TFASR_NO_PRED_STREAM", "0") != "1"
         # probe (bench.py --dp-hooks): take the world > 1 route of the block executor - two phases per block and direction around the sync-BN
         # all-reduce - with a one-rank group, so everything of a multi-GPU step except the wire time can be measured on one GPU
         self._dp_force_split = os.environ.get("TFASR_DP_FORCE_SPLIT", "0") == "1" and not isinstance(self.dp, SingleProcess)
-        # prediction-network recurrence: the persistent one-launch kernels are faster in isolation but hold P/16 CUs for ~2 ms per step;
-        # beside the encoder on the other stream the per-step kernels make the whole step 0.2 ms faster (measured on M and S), so:
-        # persistent only when the prediction network has the device to itself.  TFASR_LSTM_PERSIST=0/1 in the environment overrides.
-        self._lstm_persist_auto = os.environ.get("TFASR_LSTM_PERSIST") is None
-        self.optimizer = dict(beta1=0.9, beta2=0.98, eps=1e-9, weight_decay=1e-6, schedule=dict(
-            dmodel=cfg.dmodel, warmup_steps=10000, scale=2.0, max_lr=0.05 / math.sqrt(cfg.dmodel)))
-        self.ga_steps = 1
-        self.prefetched_inputs = False  # True: every batch handed to train_step is complete in HBM (see _forward: early front end)
-        self._ga_count = 0
-        self._drop_epoch = 0  # bumped once per forward pass so every step draws fresh dropout masks
         # one native call per Conformer block (csrc/block.hip) instead of ~70 per-kernel calls from Python
         self.native_blocks = os.environ.get("TFASR_NATIVE_BLOCK", "1") != "0"
         # grouped weight gradients of a block on the executor's second stream (tfasr_block_io.wgrad_slot), beside the next block's
@@ -115,8 +63,6 @@ class ConformerTransducer(BaseModel):
         # 8 / 12: 39 ms, profiles/r05_dp_queue_sweep.txt) - and merged the two into one low-priority stream: a data-parallel rank runs it too.
         self.wgrad_stream = {"0": False, "1": True}.get(os.environ.get("TFASR_WGRAD_STREAM"), None)
         self._wgrad_keep = []
-        self._blk_params, self._blk_sizes = {}, {}
-        self._zero_pool = {}
         # Launches that do not belong to the blocks' dependent chain leave it (a kernel boundary costs 2.65 us on this chip, tools/hwprobe/
         # anyorder_test, and hipExtAnyOrderLaunch is a no-op on gfx9): every block's positional projection pe @ Wpos + bpos is computed on a
         # third stream while the subsampling runs (tfasr_block_io.pext_pre), and the projections' gradients and the LayerNorm gamma / beta
@@ -127,8 +73,6 @@ class ConformerTransducer(BaseModel):
         # ... and with the gradients deferred, the kernel that accumulates a block's table gradient from dS (tfasr_relattn_dpext, 37 us per
         # block, only the deferred products wait for it) runs on the auxiliary stream beside the next block's backward (attribute False: in line).
         self.dpext_aux = True
-        self.joint_wgrad_aux = False  # (measured no gain: the vocabulary weight gradient on the auxiliary stream)
-        self._aux_pending = False
         # the auxiliary stream IS the block executor's second stream (one queue for the grouped weight gradients, the positional tables ahead
         # of the chain and the table gradients beside the next block; a fourth stream of its own measured slower, profiles/r05_dp_queue_sweep.txt)
         if self.device.type != "cuda":
@@ -137,37 +81,20 @@ class ConformerTransducer(BaseModel):
             with torch.cuda.device(self.device):
                 self.aux_stream = torch.cuda.ExternalStream(K.block_side_stream(), device=self.device)
         self._hoisted = {}
-        self.fuse_joint_stats = True
-        # Joint + loss WITHOUT materialised lattice logits (SURVEY section 7 step 8 / 8(d) "report both"): the projection emits only the
-        # log-softmax statistics, the gradient pass re-computes the logit tile and turns it into the loss gradient in its epilogue
-        # (tfasr_gemm_args.rgrad_coef).  Trades two passes over the [cells, V] tensor for one more vocabulary product: measured SLOWER
-        # than the materialised route on MI355X (bench.py reports both), so opt-in: TFASR_JOINT_RECOMPUTE=1.
-        self.joint_recompute = os.environ.get("TFASR_JOINT_RECOMPUTE", "0") == "1"
-        self._after_encoder = "pred/emb" if cfg.head == "transducer" else "dec/logits/w"  # first regularised variable after the encoder
-        self.timers = None  # optional dict name -> list[(start_event, end_event)] filled by bench.py
-        self.timer_work = {}
-        self.time_sections = False  # per-module section timers (bench.py TFASR_BENCH_SECTIONS) need the per-kernel Python path
-        # Greedy search: the reference's tokens come from its f32 CPU path and the north star asks for bit-exact token indices, which a
-        # bf16 encoder cannot promise (near-tied arg-max decisions flip).  Inference therefore runs on the f32 master weights with the
-        # exact-f32 MFMA kernels by default, whatever the training storage type ("bf16" = the training kernels, faster, not token-exact)
-        self.decode_precision = os.environ.get("TFASR_DECODE_PRECISION", "f32")
-        self.decode_fused = True  # the fused search step (4 launches per iteration, queued from C); False: the per-kernel loop (tests)
-        self._twin = None
 
-    # =================================================================================== constants
-    def _frontend_consts(self):
-        if "fe" not in self._consts:
-            c = self.cfg
-            n = c.frame_length
-            window = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)).astype(np.float32)  # periodic Hann
-            melw = _mel_weight_matrix(c.num_feature_bins, c.nfft // 2 + 1, c.sample_rate, c.lower_edge_hertz, c.upper_edge_hertz)
-            band = np.zeros((melw.shape[1], 2), np.int32)
-            for m in range(melw.shape[1]):
-                nz = np.nonzero(melw[:, m])[0]
-                band[m] = (nz[0], nz[-1]) if len(nz) else (0, -1)
-            dev = self.device
-            self._consts["fe"] = (torch.from_numpy(window).to(dev), torch.from_numpy(melw).to(dev), torch.from_numpy(band).to(dev))
-        return self._consts["fe"]
+    def _reset_caches(self):
+        super()._reset_caches()
+        self._blk_params, self._blk_sizes = {}, {}  # the native executor's parameter structs and workspace sizes
+        self._zero_pool = {}
+
+    # =================================================================================== front end, constants
+    def frontend(self, signals, signals_length, training=False, masks=None):
+        """the base's front end + where each utterance's feature map turns constant (the subsampling's padded-tail tables read it)"""
+        if training and masks is None:
+            masks = self.draw_specaugment([-(-int(n) // self.cfg.frame_step) for n in signals_length])
+        feats, flen = super().frontend(signals, signals_length, training, masks)
+        self._front_tail = (feats, self._feature_tail(signals_length, masks[1] if training else None))
+        return feats, flen
 
     def _pe_ext(self, T):
         """Relative sinusoid table for length T: rows r=0..2T-2 <-> positions T-1..-(T-1) (positional_encoding.py:119-121,
@@ -182,64 +109,6 @@ class ConformerTransducer(BaseModel):
             pe = np.concatenate([pe, np.zeros((1, d), np.float32)], 0)
             self._consts[key] = torch.from_numpy(pe).to(self.device).to(self.dtype).contiguous()
         return self._consts[key]
-
-    # =================================================================================== dropout bookkeeping
-    def _drop(self, site, training):
-        """(rate, seed) of dropout site `site` for the current step; masks are a pure function of (seed, element index), so
-        the backward regenerates them instead of storing them (keras Dropout sites: conformer.py:80-87,197,358,681)."""
-        p = float(self.cfg.dropout) if training else 0.0
-        if p <= 0.0:
-            return 0.0, 0
-        return p, (self._drop_epoch_eff() * 8192 + site) & 0x7FFFFFFFFFFF
-
-    def _drop_epoch_eff(self):
-        """Mask epoch with the data-parallel rank folded into bits 40..46 of the seed (epoch * 8192 + site stays below 2^40
-        for 2^27 forward passes): replicas draw different dropout masks; the native block executor forms the same seed."""
-        return self._drop_epoch + ((int(self.dp.rank) & 0x7F) << 27)
-
-    def _mask_grad(self, dy, drop):
-        return K.dropout(dy, drop[0], drop[1]) if drop[0] > 0.0 else dy
-
-    # =================================================================================== dense helpers
-    def _dense_bwd(self, dy, x, wname, bname, alpha=1.0, dact_z=None, dact=ACT_NONE, need_dx=True, drop=(0.0, 0)):
-        """dx = alpha * (dy @ W^T) [* dact'(z)];  gW += alpha * x^T dy;  gb += alpha * colsum(dy)."""
-        ps = self.ps
-        W = ps.w2d(wname)
-        rows = dy.shape[0]
-        din, dout = W.shape
-        # weight gradient; the bias gradient (column sums of dy) rides in the same launch
-        K.gemm(x, dy, ps.g2d(wname), din, dout, rows, x.stride(0), dy.stride(0), dout, trans_a=True, accumulate=True,
-               split_k=_split_k(din, dout, rows), alpha=alpha, colsum=ps.g(bname) if bname is not None else None)
-        if not need_dx:
-            return None
-        return K.matmul(dy, W, trans_b=True, alpha=alpha, dact_z=dact_z, dact=dact, drop_p=drop[0], drop_seed=drop[1])
-
-    def _h2d(self, x, dtype=torch.int32):
-        """Small host array -> device through PINNED staging: a pageable hipMemcpyAsync makes the host wait until the stream
-        has drained up to the copy, which stops the host from queueing kernels ahead of the GPU several times per step."""
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-        t = t.to(dtype)
-        if t.device.type == "cpu":
-            if self.device.type == "cuda":
-                t = t.pin_memory()
-            t = t.to(self.device, non_blocking=True)
-        return t
-
-    # =================================================================================== frontend
-    def frontend(self, signals, signals_length, training=False, masks=None):
-        """FeatureExtraction.call (feature_extraction.py:255-303) -> features [B,T0,F] (compute dtype), feature lengths (host)."""
-        c = self.cfg
-        window, melw, band = self._frontend_consts()
-        feats = K.logmel(signals, window, melw, band, c.frame_step, c.nfft, c.preemphasis, c.epsilon, self.dtype)
-        flen = [-(-int(n) // c.frame_step) for n in signals_length]
-        if training:
-            if masks is None:
-                masks = self.draw_specaugment(flen)
-            fm, tm = masks
-            if fm is not None or tm is not None:
-                K.specaugment(feats, None if fm is None else self._h2d(fm), None if tm is None else self._h2d(tm), 0.0)
-        self._front_tail = (feats, self._feature_tail(signals_length, masks[1] if training else None))
-        return feats, flen
 
     def _feature_tail(self, signals_length, tm):
         """Per utterance the first frame from which the feature map is constant in time, or None when that is not known on the host.
@@ -330,86 +199,6 @@ class ConformerTransducer(BaseModel):
             del self._consts[k]
         self._consts[key] = out
         return out
-
-    def draw_specaugment(self, flen):
-        """Random draws of FreqMasking/TimeMasking.augment (specaugment.py:72-77,122-131; freq before time:
-        augmentation.py:95; TimeMasking ignores mask_factor)."""
-        c = self.cfg
-        fcfg, tcfg = c.freq_masking, c.time_masking
-        B = len(flen)
-        rng = self._rng
-        nf = fcfg.get("num_masks", 0) if fcfg else 0
-        nt = tcfg.get("num_masks", 0) if tcfg else 0
-        fm = np.zeros((B, nf, 2), np.int32) if nf > 0 else None
-        tm = np.zeros((B, nt, 2), np.int32) if nt > 0 else None
-        nb = c.num_feature_bins
-        # the reference's consumption order: utterance by utterance (tf.map_fn, augmentation.py:78-90), frequency masks before time
-        # masks, and per mask (prob, width, start) are drawn unconditionally and multiplied by do_apply afterwards
-        # (hot host loop, ~1 000 generator calls per batch: lookups hoisted; rng.random() is uniform(0, 1) - same stream, same values)
-        rnd, rint = rng.random, rng.integers
-        fprob = fcfg.get("prob", 1.0) if fcfg else 1.0
-        fmax = max(1, int(fcfg["mask_factor"])) if nf > 0 else 1
-        tprob = tcfg.get("prob", 1.0) if tcfg else 1.0
-        tup = np.float32(tcfg.get("p_upperbound", 1.0)) if tcfg else np.float32(1.0)
-        for b in range(B):
-            ln = int(flen[b])
-            for k in range(nf):
-                do = 1 if rnd() <= fprob else 0
-                f = do * min(int(rint(0, fmax)), nb)
-                fm[b, k] = (do * int(rint(0, max(1, nb - f))), f)
-            if nt > 0:
-                Tb = max(1, int(math.floor(np.float32(ln) * tup)))
-            for k in range(nt):
-                do = 1 if rnd() <= tprob else 0
-                # tf.random.uniform(maxval=0) is an InvalidArgumentError in the reference (fewer than 20 frames at 0.05):
-                # a zero-width mask here
-                t = do * min(int(rint(0, Tb)), ln)
-                tm[b, k] = (do * int(rint(0, max(1, ln - t))), t)
-        return (None if fm is None else torch.from_numpy(fm)), (None if tm is None else torch.from_numpy(tm))
-
-    # =================================================================================== batch norm
-    def _zeros_f32(self, n):
-        """n zeroed f32 accumulators for one launch (BN sums): slices of an arena cleared by ONE fill per ~1 MB instead of one fill
-        launch per use (the ContextNet step had 300 of them).  An exhausted arena is replaced, never re-cleared, so slices that are
-        still referenced stay valid."""
-        n = (n + 63) // 64 * 64
-        size = max(1 << 18, n)
-        arena, cur = self._consts.get("zero_arena", (None, 0))
-        if arena is None or cur + n > arena.numel():
-            arena, cur = torch.zeros(size, dtype=torch.float32, device=self.device), 0
-        self._consts["zero_arena"] = (arena, cur + n)
-        return arena[cur:cur + n]
-
-    def _bn_fwd(self, x2d, name, training, act, rows=None, y=None):
-        """rows: number of REAL rows when x2d carries exactly-zero padding rows (haloed layouts): zeros change neither sum."""
-        ps = self.ps
-        C = x2d.shape[1]
-        fin = torch.empty(4 * C, dtype=torch.float32, device=self.device)
-        if training:
-            stats = self._zeros_f32(2 * C + 1)[:2 * C + 1]
-            K.bn_stats(x2d, stats)
-            count = (x2d.shape[0] if rows is None else rows) * self.dp.world
-            self.dp.allreduce_stats_(stats[:2 * C])
-        else:
-            stats, count = None, x2d.shape[0]
-        # statistics -> coefficients (+ moving statistics) -> normalise + activation in ONE launch where the row kernel applies
-        got = K.bn_finalize_apply_fwd(x2d, stats, count if training else 1, ps.p(name + "/g"), ps.p(name + "/b"), fin, ps.state[name + "/mm"],
-                                      ps.state[name + "/mv"], act, y=y, training=training)
-        if got is None:
-            K.bn_finalize(stats, count if training else 1, ps.p(name + "/g"), ps.p(name + "/b"), fin, ps.state[name + "/mm"], ps.state[name + "/mv"],
-                          0.99, 1e-3, training)
-            got = K.bn_apply_fwd(x2d, fin, act, y=y)
-        return got, (fin, count)
-
-    def _bn_bwd(self, x2d, dy2d, name, saved, act, dx=None):
-        fin, count = saved
-        ps = self.ps
-        C = x2d.shape[1]
-        bstats = self._zeros_f32(2 * C)[:2 * C]
-        K.bn_bwd_stats(x2d, dy2d, fin, bstats, act)
-        self.dp.allreduce_stats_(bstats)
-        # bstats = (sum dz, sum dz*xhat) over the GLOBAL batch = the beta / gamma gradients; the flat-gradient all-reduce sums over ranks again
-        return K.bn_apply_bwd(x2d, dy2d, fin, bstats, count, act, dx=dx, dgamma=ps.g(name + "/g"), dbeta=ps.g(name + "/b"), grad_scale=1.0 / self.dp.world)
 
     # =================================================================================== subsampling
     # ---- conv2 without a patch matrix: haloed space-to-depth layout (csrc/conv2d.hip, include/tfasr_hip.h) -----------------
@@ -1236,566 +1025,6 @@ class ConformerTransducer(BaseModel):
         hi = self.ps.offsets[f"enc/block{i + 1}/ff1/d1/w"] if i + 1 < self.cfg.num_blocks else self.ps.defer_lo
         self.dp.grads_ready(lo, hi)
 
-    # =================================================================================== prediction network
-    def prediction_fwd(self, tokens_dev, plen_dev, ctx, h0=None, c0=None):
-        """TransducerPrediction.call (base_transducer.py:123-132): Embedding -> LSTM -> LayerNorm. tokens [B,U1] int32."""
-        ps, c = self.ps, self.cfg
-        B, U1 = tokens_dev.shape
-        E, P = c.embed_dim, c.rnn_units
-        emb = K.embedding_fwd(tokens_dev, ps.p("pred/emb"), self.dtype).view(B * U1, E)
-        xg = K.matmul(emb, ps.w2d("pred/lstm/k"), bias=ps.p("pred/lstm/b")).view(B, U1, 4 * P)
-        gates = torch.empty(B, U1, 4 * P, dtype=self.dtype, device=self.device)
-        cseq = torch.empty(B, U1, P, dtype=torch.float32, device=self.device)
-        hseq = torch.empty(B, U1, P, dtype=self.dtype, device=self.device)
-        yseq = torch.empty(B, U1, P, dtype=self.dtype, device=self.device)
-        hr = torch.empty(B, 4 * P, dtype=torch.float32, device=self.device)
-        Wrk = ps.w2d("pred/lstm/rk")
-        if self._lstm_persist_auto:
-            K.lstm_set_persist(0 if (self.use_pred_stream and torch.cuda.current_stream(self.device) == self.pred_stream) else 1)
-        K.lstm_seq_fwd(xg, Wrk, h0, c0, plen_dev, gates, cseq, hseq, yseq, hr)  # the U1 steps queued from C (one host call)
-        y2 = yseq.view(B * U1, P)
-        if c.prediction_layer_norm:
-            pred, mean, rstd = K.layernorm_fwd(y2, ps.p("pred/ln/g"), ps.p("pred/ln/b"))
-        else:  # prediction_layer_norm: False (contextnet/small.yml.j2)
-            pred, mean, rstd = y2, None, None
-        if ctx is not None:
-            ctx["pred"] = dict(tokens=tokens_dev, plen=plen_dev, emb=emb, gates=gates, cseq=cseq, hseq=hseq, y2=y2, mean=mean, rstd=rstd, B=B, U1=U1)
-        return pred  # [B*U1, P]
-
-    # ---- the prediction network queued in SLICES between the encoder blocks --------------------------------------------------------------
-    # Its recurrence is ~2 x U1 tiny launches per direction on a stream of its own.  Queued in one go, a host that is slower than the GPU
-    # (under rocprofv3: tools/prof_streams.py, profiles/r05_streams_single_slices0.txt) blocks in hipLaunchKernel on that stream's full launch
-    # queue and starves the ENCODER's stream meanwhile - the main queue idles for the whole duration of the prediction network, once per
-    # direction, 21 % of the traced span.  A slice per encoder block keeps both queues fed: traced span 155 -> 128 ms for six steps.
-    # Unprofiled the host runs ~3 steps ahead of the GPU (6.5 ms of pure host time per 21.7-ms step), so the gain there is small:
-    # 21.75 -> 21.68 ms/step (two interleaved pairs, profiles/r05_dp_queue_sweep.txt).  TFASR_PRED_SLICES=0: in one go.
-    def _pred_nslices(self, U1):
-        n = int(os.environ.get("TFASR_PRED_SLICES", "8"))
-        return max(1, min(n, U1))
-
-    def _prediction_fwd_gen(self, tokens_dev, plen_dev, ctx):
-        """prediction_fwd as a generator: every next() queues one slice (on the current stream); the last one sets self._side_result"""
-        ps, c = self.ps, self.cfg
-        B, U1 = tokens_dev.shape
-        E, P = c.embed_dim, c.rnn_units
-        emb = K.embedding_fwd(tokens_dev, ps.p("pred/emb"), self.dtype).view(B * U1, E)
-        xg = K.matmul(emb, ps.w2d("pred/lstm/k"), bias=ps.p("pred/lstm/b")).view(B, U1, 4 * P)
-        gates = torch.empty(B, U1, 4 * P, dtype=self.dtype, device=self.device)
-        cseq = torch.empty(B, U1, P, dtype=torch.float32, device=self.device)
-        hseq = torch.empty(B, U1, P, dtype=self.dtype, device=self.device)
-        yseq = torch.empty(B, U1, P, dtype=self.dtype, device=self.device)
-        hr = torch.empty(B, 4 * P, dtype=torch.float32, device=self.device)
-        Wrk = ps.w2d("pred/lstm/rk")
-        step = -(-U1 // self._pred_nslices(U1))
-        for t0 in range(0, U1, step):
-            K.lstm_seq_fwd_range(xg, Wrk, None, None, plen_dev, gates, cseq, hseq, yseq, hr, t0, min(U1, t0 + step))
-            if t0 + step < U1:
-                yield
-        y2 = yseq.view(B * U1, P)
-        if c.prediction_layer_norm:
-            pred, mean, rstd = K.layernorm_fwd(y2, ps.p("pred/ln/g"), ps.p("pred/ln/b"))
-        else:
-            pred, mean, rstd = y2, None, None
-        if ctx is not None:
-            ctx["pred"] = dict(tokens=tokens_dev, plen=plen_dev, emb=emb, gates=gates, cseq=cseq, hseq=hseq, y2=y2, mean=mean, rstd=rstd, B=B, U1=U1)
-        self._side_result = pred
-
-    def _prediction_bwd_gen(self, dpred, ctx):
-        """prediction_bwd as a generator (slices of the backward recurrence in descending time order, then the weight gradients)"""
-        ps, c = self.ps, self.cfg
-        s = ctx["pred"]
-        B, U1 = s["B"], s["U1"]
-        E, P = c.embed_dim, c.rnn_units
-        if c.prediction_layer_norm:
-            dy = K.layernorm_bwd(dpred, s["y2"], ps.p("pred/ln/g"), s["mean"], s["rstd"], ps.g("pred/ln/g"), ps.g("pred/ln/b")).view(B, U1, P)
-        else:
-            dy = dpred.view(B, U1, P)
-        dy = dy.contiguous()
-        dz = torch.empty(B, U1, 4 * P, dtype=self.dtype, device=self.device)
-        dh_carry = torch.zeros(B, P, dtype=torch.float32, device=self.device)
-        dc_carry = torch.zeros(B, P, dtype=torch.float32, device=self.device)
-        dhr = torch.empty(B, P, dtype=torch.float32, device=self.device)
-        Wrk = ps.w2d("pred/lstm/rk")
-        step = -(-U1 // self._pred_nslices(U1))
-        t1 = U1
-        while t1 > 0:
-            t0 = max(0, t1 - step)
-            K.lstm_seq_bwd_range(dy, Wrk, s["gates"], s["cseq"], s["plen"], dz, dh_carry, dc_carry, dhr, t0, t1)
-            t1 = t0
-            yield
-        dz2 = dz.view(B * U1, 4 * P)
-        if U1 > 1:
-            K.gemm(s["hseq"], dz[:, 1:], ps.g2d("pred/lstm/rk"), P, 4 * P, U1 - 1, P, 4 * P, 4 * P, trans_a=True, nb1=B,
-                   sA=(U1 * P, 0), sB=(U1 * 4 * P, 0), sD=(0, 0), accumulate=True)
-        demb = self._dense_bwd(dz2, s["emb"], "pred/lstm/k", "pred/lstm/b")
-        K.embedding_bwd(s["tokens"], demb, ps.g("pred/emb"))
-
-    def _side_tick(self):
-        """queue the next slice of the prediction network (if one is pending) on its stream"""
-        g = getattr(self, "_side_gen", None)
-        if g is None:
-            return
-        with torch.cuda.stream(self.pred_stream):
-            try:
-                next(g)
-            except StopIteration:
-                self._side_gen = None
-
-    def _side_drain(self):
-        while getattr(self, "_side_gen", None) is not None:
-            self._side_tick()
-
-    def _pred_sliced(self):
-        # the per-step kernels are what the overlapped step runs (see _lstm_persist_auto); a forced persistent launch has nothing to slice
-        return self.use_pred_stream and self._lstm_persist_auto and os.environ.get("TFASR_PRED_SLICES", "8") != "0"
-
-    def prediction_bwd(self, dpred, ctx):
-        ps, c = self.ps, self.cfg
-        s = ctx["pred"]
-        B, U1 = s["B"], s["U1"]
-        E, P = c.embed_dim, c.rnn_units
-        if c.prediction_layer_norm:
-            dy = K.layernorm_bwd(dpred, s["y2"], ps.p("pred/ln/g"), s["mean"], s["rstd"], ps.g("pred/ln/g"), ps.g("pred/ln/b")).view(B, U1, P)
-        else:
-            dy = dpred.view(B, U1, P)
-        dz = torch.empty(B, U1, 4 * P, dtype=self.dtype, device=self.device)
-        dh_carry = torch.zeros(B, P, dtype=torch.float32, device=self.device)
-        dc_carry = torch.zeros(B, P, dtype=torch.float32, device=self.device)
-        dhr = torch.empty(B, P, dtype=torch.float32, device=self.device)
-        Wrk = ps.w2d("pred/lstm/rk")
-        if self._lstm_persist_auto:
-            K.lstm_set_persist(0 if (self.use_pred_stream and torch.cuda.current_stream(self.device) == self.pred_stream) else 1)
-        K.lstm_seq_bwd(dy.contiguous(), Wrk, s["gates"], s["cseq"], s["plen"], dz, dh_carry, dc_carry, dhr)
-        dz2 = dz.view(B * U1, 4 * P)
-        # recurrent kernel: gR += sum_b h[b, :-1]^T @ dz[b, 1:]
-        if U1 > 1:
-            K.gemm(s["hseq"], dz[:, 1:], ps.g2d("pred/lstm/rk"), P, 4 * P, U1 - 1, P, 4 * P, 4 * P, trans_a=True, nb1=B,
-                   sA=(U1 * P, 0), sB=(U1 * 4 * P, 0), sD=(0, 0), accumulate=True)
-        demb = self._dense_bwd(dz2, s["emb"], "pred/lstm/k", "pred/lstm/b")
-        K.embedding_bwd(s["tokens"], demb, ps.g("pred/emb"))
-
-    # =================================================================================== joint + loss
-    def joint_fwd(self, enc, pred, B, T, U1, ctx):
-        """TransducerJoint.call (base_transducer.py:280-293) -> logits [B,T,U1,V]."""
-        ps, c = self.ps, self.cfg
-        J, V = c.joint_dim, c.vocab_size
-        e = K.matmul(enc, ps.w2d("joint/enc/w"), bias=ps.p("joint/enc/b"))
-        p = K.matmul(pred, ps.w2d("joint/pred/w"), bias=ps.p("joint/pred/b"))
-        h = K.joint_fwd(e.view(B, T, J), p.view(B, U1, J))
-        t0 = self._tick("joint_vocab_gemm")
-        logits = K.matmul(h.view(B * T * U1, J), ps.w2d("joint/vocab/w"), bias=ps.p("joint/vocab/b")).view(B, T, U1, V)
-        self._tock("joint_vocab_gemm", t0, 2.0 * B * T * U1 * J * V)
-        if ctx is not None:
-            ctx["joint"] = dict(enc=enc, pred=pred, h=h, B=B, T=T, U1=U1)
-        return logits
-
-    def joint_bwd(self, dlogits, ctx):
-        ps, c = self.ps, self.cfg
-        s = ctx["joint"]
-        B, T, U1 = s["B"], s["T"], s["U1"]
-        J, V = c.joint_dim, c.vocab_size
-        h2 = s["h"].view(B * T * U1, J)
-        dh = self._dense_bwd(dlogits.view(B * T * U1, V), h2, "joint/vocab/w", "joint/vocab/b")
-        de, dp = K.joint_bwd(s["h"], dh.view(B, T, U1, J))
-        denc = self._dense_bwd(de.view(B * T, J), s["enc"], "joint/enc/w", "joint/enc/b")
-        dpred = self._dense_bwd(dp.view(B * U1, J), s["pred"], "joint/pred/w", "joint/pred/b")
-        return denc, dpred
-
-    # =================================================================================== public API
-    def __call__(self, inputs: TrainInput, training=False):
-        """Transducer.call (base_transducer.py:427-435)."""
-        logits, elen, _ = self._forward(inputs, training, None)
-        return TrainOutput(logits=logits, logits_length=torch.tensor(elen, dtype=torch.int32))
-
-    def _forward(self, inputs: TrainInput, training, ctx, masks=None, joint=True):
-        dev = self.device
-        self._drop_epoch += 1
-        sig = inputs.inputs.to(dev, non_blocking=True)
-        slen = [int(v) for v in inputs.inputs_length.tolist()]
-        tokens = inputs.predictions.to(dev, non_blocking=True).to(torch.int32).contiguous()
-        plen = inputs.predictions_length.to(dev, non_blocking=True).to(torch.int32)
-        B, U1 = tokens.shape
-        main = torch.cuda.current_stream()
-        # Host order: the launch queue holds only ~1 ms of work, so (1) the ~1 ms of Python that draws the SpecAugment masks runs FIRST,
-        # while the previous step's tail is still executing (between log-mel and the mask kernel it left the main stream idle for 0.85 ms
-        # per step under the profiler's slower host; neutral in an unprofiled same-box A/B: 23.81 vs 23.85 ms), and (2) the main stream
-        # gets its front end BEFORE the ~170 launches of the prediction network go to the second stream.
-        if training and masks is None:
-            masks = self.draw_specaugment([-(-int(n) // self.cfg.frame_step) for n in slen])
-        # The front end (log-mel + SpecAugment) reads nothing a previous step wrote - no parameters, only this batch's samples - so it does
-        # not have to queue behind the previous step's tail on the main stream (subsampling backward + optimizer, ~1.8 ms): it goes to the
-        # prediction network's stream, idle at this point, and the main stream picks the features up (round 5; TFASR_FRONT_EARLY=0: in line).
-        # Only when the CALLER says its batches are complete in HBM before train_step is called (`prefetched_inputs`, what a double-buffered
-        # input pipeline - the reference's tf.data prefetch - provides and what bench.py does): a batch still being produced by earlier work
-        # on the current stream would otherwise be read too early.
-        if (self.prefetched_inputs and self.use_pred_stream and os.environ.get("TFASR_FRONT_EARLY", "1") != "0"
-                and inputs.inputs.device.type == "cuda" and inputs.inputs.device == sig.device):
-            sig.record_stream(self.pred_stream)
-            with torch.cuda.stream(self.pred_stream):
-                feats, flen = self.frontend(sig, slen, training, masks)
-            main.wait_stream(self.pred_stream)
-            feats.record_stream(main)
-        else:
-            feats, flen = self.frontend(sig, slen, training, masks)
-        self._side_gen = None
-        if self.use_pred_stream:
-            self.pred_stream.wait_stream(main)
-            tokens.record_stream(self.pred_stream)
-            plen.record_stream(self.pred_stream)
-            if self._pred_sliced():
-                K.lstm_set_persist(0)
-                self._side_gen = self._prediction_fwd_gen(tokens, plen, ctx)
-                self._side_tick()  # embedding, input product and the first slice now; the rest between the encoder blocks
-            else:
-                with torch.cuda.stream(self.pred_stream):
-                    pred = self.prediction_fwd(tokens, plen, ctx)
-                pred.record_stream(main)
-        enc, T, elen, elen_dev = self.encoder_fwd(feats, flen, training, ctx)
-        if self.use_pred_stream:
-            if self._side_gen is not None or getattr(self, "_side_result", None) is not None:
-                self._side_drain()
-                pred, self._side_result = self._side_result, None
-                pred.record_stream(main)
-            main.wait_stream(self.pred_stream)
-        else:
-            pred = self.prediction_fwd(tokens, plen, ctx)
-        if not joint:
-            return enc, pred, (B, T, U1), elen, elen_dev
-        logits = self.joint_fwd(enc, pred, B, T, U1, ctx)
-        return logits, elen, elen_dev
-
-    def loss_and_backward(self, data: TrainData, training=True, masks=None, want_backward=True, packed=True, reduce=True):
-        """BaseModel._train_step (base_model.py:149-183): forward, RnntLoss (mean over the batch, rnnt_loss.py:34) and
-        the full backward into the flat gradient buffer (gradients ACCUMULATE; zero_grad() first).
-
-        packed=True evaluates the joint network and the loss only on the valid lattice nodes (t < logit_len_b,
-        u <= label_len_b): padded nodes carry exactly zero gradient in the reference (impl/rnnt.py:218-224), so skipping them
-        changes no result while removing the padding's share of the largest GEMMs of the step.
-
-        reduce=False keeps this micro-step's gradients local (train_step_ga, base_model.py:200-209: the replicas exchange
-        gradients only when the accumulated gradient is applied)."""
-        self.dp.set_reduce(bool(reduce))
-        ctx = {} if want_backward else None
-        dev = self.device
-        ps, c = self.ps, self.cfg
-        enc, pred, (B, T, U1), elen, elen_dev = self._forward(data.inputs, training, ctx, masks, joint=False)
-        J, V = c.joint_dim, c.vocab_size
-        labels = data.labels.labels.to(dev, non_blocking=True).to(torch.int32).contiguous()
-        llen_host = [int(v) for v in data.labels.labels_length.tolist()]
-        # BaseLoss.call: logit_length = max(logit_length, label_length)  (losses/base_loss.py:36)
-        tl = [min(max(int(a), b), T) for a, b in zip(elen, llen_host)]
-        ul = [min(b, U1 - 1) for b in llen_host]
-        tl_dev = self._h2d(tl)
-        ul_dev = self._h2d(ul)
-        gkey = ("gscale", B, self.dp.world)
-        if gkey not in self._consts:
-            self._consts[gkey] = torch.full((B,), 1.0 / (B * self.dp.world), dtype=torch.float32, device=dev)
-        gscale = self._consts[gkey]
-        if not packed:
-            logits = self.joint_fwd(enc, pred, B, T, U1, ctx)
-            t0 = self._tick("rnnt_loss")
-            costs, dlogits = K.rnnt_loss_fwd_bwd(logits, labels, ul_dev, tl_dev, grad_scale=gscale, grads=logits, want_grads=want_backward)
-            self._tock("rnnt_loss", t0)
-            if not want_backward:
-                return costs
-            denc, dpred = self.joint_bwd(dlogits, ctx)
-        else:
-            off = np.zeros(B + 1, np.int64)
-            off[1:] = np.cumsum([t * (u + 1) for t, u in zip(tl, ul)])
-            total = int(off[-1])
-            off_dev = self._h2d(off, torch.int64)
-            e = K.matmul(enc, ps.w2d("joint/enc/w"), bias=ps.p("joint/enc/b"))
-            p = K.matmul(pred, ps.w2d("joint/pred/w"), bias=ps.p("joint/pred/b"))
-            h = K.joint_fwd_packed(e.view(B, T, J), p.view(B, U1, J), off_dev, ul_dev, total)
-            # The vocabulary projection's epilogue also emits the log-softmax statistics of every lattice row (max / sum-exp per
-            # 64-column slice, blank and label logits) from its f32 accumulators, so the loss skips its first pass over the logits
-            # (impl/rnnt.py:211 tf.nn.log_softmax + the gathers of :94-105).  bf16 fast path only; otherwise the plain route.
-            stats = None
-            logits = None
-            if self.dtype == torch.bfloat16 and self.fuse_joint_stats:
-                parts = -(-V // 128) * 2
-                lse_part = torch.empty(total, parts, 2, dtype=torch.float32, device=dev)
-                pick = torch.empty(total, 2, dtype=torch.float32, device=dev)
-                row_label = K.rnnt_row_labels(labels, ul_dev, tl_dev, off_dev, total, T, V)
-                t0 = self._tick("joint_vocab_gemm")
-                if self.joint_recompute and want_backward:
-                    try:
-                        K.gemm(h, ps.w2d("joint/vocab/w"), None, total, V, J, J, V, V, bias=ps.p("joint/vocab/b"), lse=(lse_part, row_label, pick))
-                        self._tock("joint_vocab_gemm", t0, 2.0 * total * J * V)
-                        t0 = self._tick("rnnt_loss")
-                        costs, coef = K.rnnt_loss_packed_coef(labels, ul_dev, tl_dev, off_dev, total, T, V, (lse_part, pick), grad_scale=gscale)
-                        dlogits = torch.empty(total, V, dtype=self.dtype, device=dev)
-                        K.gemm(h, ps.w2d("joint/vocab/w"), dlogits, total, V, J, J, V, V, bias=ps.p("joint/vocab/b"), rgrad=(coef, row_label))
-                        # algorithmic bytes of this variant: the gradient tensor is written once (the logits never exist)
-                        self._tock("rnnt_loss", t0, 1.0 * total * V * dlogits.element_size())
-                        return self._joint_backward_tail(costs, dlogits, h, enc, pred, off_dev, ul_dev, tl_dev, B, T, U1, ctx)
-                    except K._lib.TfasrUnsupported:
-                        t0 = self._tick("joint_vocab_gemm")  # shapes outside the 256-row kernel: the materialised route below
-                try:
-                    logits = torch.empty(total, V, dtype=self.dtype, device=dev)
-                    K.gemm(h, ps.w2d("joint/vocab/w"), logits, total, V, J, J, V, V, bias=ps.p("joint/vocab/b"), lse=(lse_part, row_label, pick))
-                    stats = (lse_part, pick)
-                    self._tock("joint_vocab_gemm", t0, 2.0 * total * J * V)
-                except K._lib.TfasrUnsupported:
-                    logits = None
-                    if self.timers is not None:  # (keep the section timers paired: ADVICE r02)
-                        self._tock("joint_vocab_gemm", t0, 0.0)
-            if logits is None:
-                t0 = self._tick("joint_vocab_gemm")
-                logits = K.matmul(h, ps.w2d("joint/vocab/w"), bias=ps.p("joint/vocab/b"))  # [total, V]
-                self._tock("joint_vocab_gemm", t0, 2.0 * total * J * V)
-            t0 = self._tick("rnnt_loss")
-            costs, dlogits = K.rnnt_loss_packed(logits, labels, ul_dev, tl_dev, off_dev, total, T, grad_scale=gscale, grads=logits,
-                                                want_grads=want_backward, stats=stats)
-            self._tock("rnnt_loss", t0, 2.0 * total * V * logits.element_size())
-            if not want_backward:
-                return costs
-            return self._joint_backward_tail(costs, dlogits, h, enc, pred, off_dev, ul_dev, tl_dev, B, T, U1, ctx)
-        return self._backward_from_joint(costs, denc, dpred, ctx)
-
-    def _joint_backward_tail(self, costs, dlogits, h, enc, pred, off_dev, ul_dev, tl_dev, B, T, U1, ctx):
-        """packed lattice: gradient of the lattice logits -> gradients of the joint network's inputs (+ its weight gradients)"""
-        J = self.cfg.joint_dim
-        ps = self.ps
-        # tanh' folded into the data gradient's epilogue (dact = TANH_OUT: times 1 - h^2): the segment sums read one tensor, not two
-        if self.joint_wgrad_aux and self.aux_stream is not None and isinstance(self.dp, SingleProcess) and self.dtype == torch.bfloat16:
-            # one GPU: the vocabulary projection's weight gradient (nothing waits for it before the optimizer) on the auxiliary stream,
-            # beside its data gradient and the start of the backward chain
-            main = torch.cuda.current_stream()
-            self.aux_stream.wait_stream(main)
-            W = ps.w2d("joint/vocab/w")
-            din, dout = W.shape
-            rows = dlogits.shape[0]
-            for t in (dlogits, h):
-                t.record_stream(self.aux_stream)
-            with torch.cuda.stream(self.aux_stream):
-                K.gemm(h, dlogits, ps.g2d("joint/vocab/w"), din, dout, rows, h.stride(0), dlogits.stride(0), dout, trans_a=True, accumulate=True,
-                       split_k=_split_k(din, dout, rows), colsum=ps.g("joint/vocab/b"))
-            self._aux_pending = True
-            dh = K.matmul(dlogits, W, trans_b=True, dact_z=h, dact=ACT_TANH_OUT)
-        else:
-            dh = self._dense_bwd(dlogits, h, "joint/vocab/w", "joint/vocab/b", dact_z=h, dact=ACT_TANH_OUT)
-        de, dp = K.joint_bwd_packed(None, dh, off_dev, ul_dev, tl_dev, B, T, U1)
-        denc = self._dense_bwd(de.view(B * T, J), enc, "joint/enc/w", "joint/enc/b")
-        dpred = self._dense_bwd(dp.view(B * U1, J), pred, "joint/pred/w", "joint/pred/b")
-        return self._backward_from_joint(costs, denc, dpred, ctx)
-
-    def _backward_from_joint(self, costs, denc, dpred, ctx):
-        main = torch.cuda.current_stream()
-        self.dp.grads_ready(self.ps.offsets["joint/enc/w"], self.ps.n_reg)
-        self._side_gen = None
-        if self.use_pred_stream:
-            self.pred_stream.wait_stream(main)
-            dpred.record_stream(self.pred_stream)
-            if self._pred_sliced():
-                K.lstm_set_persist(0)
-                self._side_gen = self._prediction_bwd_gen(dpred, ctx)
-                self._side_tick()
-            else:
-                with torch.cuda.stream(self.pred_stream):
-                    self.prediction_bwd(dpred, ctx)
-        else:
-            self.prediction_bwd(dpred, ctx)
-        self.encoder_bwd(denc, ctx)
-        if self.use_pred_stream:
-            self._side_drain()
-            main.wait_stream(self.pred_stream)
-        if getattr(self, "_aux_pending", False):
-            main.wait_stream(self.aux_stream)
-            self._aux_pending = False
-        self.dp.finish_grads()
-        return costs
-
-    def zero_grad(self):
-        self.ps.grad.zero_()
-
-    def learning_rate(self, step):
-        s = self.optimizer["schedule"]
-        if isinstance(s, (int, float)):
-            return float(s)
-        from .configs import transformer_schedule
-
-        return transformer_schedule(step, **s)
-
-    def apply_gradients(self, grad_scale=1.0):
-        """BaseModel._apply_gradients -> keras Adam (base_model.py:185-192; small.yml.j2:73-87) + L2 regulariser gradient."""
-        o = self.optimizer
-        self._gradient_noise()  # gradn_config (base_model.py:185-191): no-op unless compiled with one
-        self.step += 1
-        # keras evaluates the schedule at `iterations` BEFORE the increment (0 at the first update: the reference's first step has
-        # lr = 0 with TransformerSchedule) and bias-corrects with iterations + 1 [ext: keras BaseOptimizer._get_current_learning_rate,
-        # Adam.update_step]
-        lr = self.learning_rate(self.step - 1)
-        ps = self.ps
-        # bf16 models: the optimizer writes the bf16 shadow of the parameters itself
-        fused = ps.shadow is not ps.flat and ps.shadow.dtype == torch.bfloat16
-        K.adam(ps.flat, ps.grad, ps.adam_m, ps.adam_v, ps.n_reg, lr, self.step, o["beta1"], o["beta2"], o["eps"], o["weight_decay"],
-               self.cfg.l2, grad_scale, shadow=ps.shadow if fused else None)
-        if not fused:
-            ps.refresh_shadow()
-        return lr
-
-    def regularization_loss(self):
-        out = torch.zeros(1, dtype=torch.float32, device=self.device)
-        K.sumsq(self.ps.flat, self.ps.n_reg, out)
-        return out * self.cfg.l2
-
-    def train_step(self, data: TrainData, masks=None):
-        """BaseModel.train_step / train_step_ga (base_model.py:194-209): returns {'loss': per-utterance costs [B]}.
-        With ga_steps > 1 the optimizer is applied every ga_steps-th call with (sum of micro-grads)/ga_steps
-        (optimizers/accumulation.py:64-70)."""
-        if self._ga_count == 0:
-            self.zero_grad()
-        # the flat buffer accumulates LOCAL micro-gradients; it is all-reduced once, on the apply micro-step, where the
-        # bucketed slices still overlap that micro-step's backward (base_model.py:200-209)
-        original_weights = self.apply_gwn()  # gwn_config (base_model.py:156-159): no-op unless compiled with one
-        costs = self.loss_and_backward(data, True, masks, reduce=self._ga_count + 1 >= self.ga_steps)
-        self.remove_gwn(original_weights)
-        self._ga_count += 1
-        if self._ga_count >= self.ga_steps:
-            self.apply_gradients(1.0 / self.ga_steps)
-            self._ga_count = 0
-        return {"loss": costs}
-
-    # =================================================================================== greedy inference
-    def get_initial_decoder_states(self, batch_size=1):
-        """TransducerPrediction.get_initial_state (base_transducer.py:109-121): zeros [B, num_rnns=1, 2 (h,c), P]."""
-        return torch.zeros(batch_size, 1, 2, self.cfg.rnn_units, dtype=torch.float32, device=self.device)
-
-    def get_initial_tokens(self, batch_size=1):
-        return torch.full((batch_size, 1), self.blank, dtype=torch.int32, device=self.device)
-
-    def inference_twin(self):
-        """This model in f32 parity mode over the SAME parameter buffers (f32 master weights, BatchNorm moving statistics): no copy,
-        always current.  The twin of an f32 model is the model itself."""
-        if self.dtype == torch.float32:
-            return self
-        if self._twin is None:
-            t = object.__new__(type(self))
-            t.__dict__.update(self.__dict__)
-            t.dtype, t.ps = torch.float32, self.ps.alias(torch.float32)
-            t._consts, t._blk_params, t._blk_sizes, t._zero_pool, t._twin = {}, {}, {}, {}, None
-            t.timers, t.timer_work = None, {}
-            self._twin = t
-        return self._twin
-
-    @torch.no_grad()
-    def encode(self, signals, signals_length, precision=None):
-        """frontend + ConformerEncoder.call_next (conformer.py:703-718), inference mode (moving BN statistics).
-        precision "f32" (default, self.decode_precision) runs it on the f32 master weights; "bf16" on the training kernels."""
-        if (precision or self.decode_precision) == "f32" and self.dtype != torch.float32:
-            return self.inference_twin().encode(signals, signals_length)
-        sig = signals.to(self.device, non_blocking=True)
-        slen = [int(v) for v in signals_length.tolist()]
-        feats, flen = self.frontend(sig, slen, training=False)
-        enc, T, elen, _ = self.encoder_fwd(feats, flen, False, None)
-        return enc.view(sig.shape[0], T, self.cfg.dmodel), elen
-
-    @property
-    def seconds_per_frame(self):
-        return self.cfg.time_reduction_factor * self.cfg.stride_ms / 1000.0
-
-    @torch.no_grad()
-    def align(self, data: TrainData, precision=None):
-        """Forced alignment of data.labels to the audio: the best path through the lattice the loss sums over (csrc/align.hip) and the
-        encoder frame at which it emits each label -> AlignOutput.  Inference mode; `precision` as in encode.  On a tie a
-        label is emitted as late as possible.  Unlike the loss, the number of frames is NOT raised to the label length."""
-        if (precision or self.decode_precision) == "f32" and self.dtype != torch.float32:
-            return self.inference_twin().align(data, "f32")
-        enc, elen = self.encode(data.inputs.inputs, data.inputs.inputs_length, "f32" if self.dtype == torch.float32 else "bf16")
-        return self.align_encoded(enc, elen, data.inputs.predictions, data.labels.labels, data.labels.labels_length)
-
-    @torch.no_grad()
-    def align_encoded(self, enc, elen, predictions, labels, labels_length):
-        """align() on encoder output enc [B, T', dmodel] (this model's storage type) with lengths elen: prediction network over the
-        blank-prepended labels `predictions` [B, U+1], the joint network on the valid lattice nodes only, then the walk.  A bf16 model
-        takes the log-probabilities from the vocabulary product's statistics epilogue (where its 256-row kernel applies the logits never
-        exist); f32, or a shape that epilogue does not hold, walks materialised logits: the choices loss_and_backward makes."""
-        ps, c, dev = self.ps, self.cfg, self.device
-        B, T, d = enc.shape
-        J, V = c.joint_dim, c.vocab_size
-        tokens = predictions.to(dev).to(torch.int32).contiguous()
-        no_labels = tokens.shape[1] == 1  # nothing to align anywhere: one padding column keeps the label arrays non-empty
-        if no_labels:
-            tokens = torch.cat([tokens, torch.full((B, 1), self.blank, dtype=torch.int32, device=dev)], 1)
-        U1 = tokens.shape[1]
-        lab = labels.to(dev).to(torch.int32)
-        if lab.shape[1] != U1 - 1:  # labels padded to another width than the predictions
-            fit = torch.zeros(B, U1 - 1, dtype=torch.int32, device=dev)
-            w = min(U1 - 1, lab.shape[1])
-            fit[:, :w] = lab[:, :w]
-            lab = fit
-        lab = lab.contiguous()
-        tl = [min(max(int(v), 0), T) for v in elen]
-        ul = [min(max(int(v), 0), U1 - 1) for v in labels_length.tolist()]
-        tl_dev, ul_dev = self._h2d(tl), self._h2d(ul)
-        plen = self._h2d([u + 1 for u in ul])
-        enc2 = enc.reshape(B * T, d)
-        if enc2.dtype != self.dtype or not enc2.is_contiguous():
-            enc2 = K.cast(enc2.contiguous(), torch.empty(B * T, d, dtype=self.dtype, device=dev))
-        pred = self.prediction_fwd(tokens, plen, None)
-        off = np.zeros(B + 1, np.int64)
-        off[1:] = np.cumsum([t * (u + 1) for t, u in zip(tl, ul)])
-        total = int(off[-1])
-        if total == 0:  # no utterance has a frame
-            return AlignOutput(torch.full((B, U1 - 1), -1, dtype=torch.int32, device=dev), None, torch.zeros(B, U1 - 1, device=dev),
-                               torch.full((B,), float("-inf"), device=dev), self.seconds_per_frame)
-        off_dev = self._h2d(off, torch.int64)
-        e = K.matmul(enc2, ps.w2d("joint/enc/w"), bias=ps.p("joint/enc/b"))
-        p = K.matmul(pred, ps.w2d("joint/pred/w"), bias=ps.p("joint/pred/b"))
-        h = K.joint_fwd_packed(e.view(B, T, J), p.view(B, U1, J), off_dev, ul_dev, total)
-        out = None
-        if self.dtype == torch.bfloat16 and self.fuse_joint_stats:
-            parts = -(-V // 128) * 2
-            lse_part = torch.empty(total, parts, 2, dtype=torch.float32, device=dev)
-            pick = torch.empty(total, 2, dtype=torch.float32, device=dev)
-            row_label = K.rnnt_row_labels(lab, ul_dev, tl_dev, off_dev, total, T, V)
-            # statistics only (the 256-row kernel), else statistics beside materialised logits (the 128-row kernel: the walk still skips its
-            # pass over them), else the plain route below: the order loss_and_backward tries them in
-            for materialise in (False, True):
-                try:
-                    logits = torch.empty(total, V, dtype=self.dtype, device=dev) if materialise else None
-                    K.gemm(h, ps.w2d("joint/vocab/w"), logits, total, V, J, J, V, V, bias=ps.p("joint/vocab/b"), lse=(lse_part, row_label, pick))
-                    out = K.rnnt_align_stats((lse_part, pick), lab, ul_dev, tl_dev, T, V, cell_off=off_dev, blank=self.blank)
-                    break
-                except K._lib.TfasrUnsupported:
-                    out = None
-        if out is None:
-            logits = K.matmul(h, ps.w2d("joint/vocab/w"), bias=ps.p("joint/vocab/b"))  # [total, V]
-            out = K.rnnt_align(logits, lab, ul_dev, tl_dev, T=T, cell_off=off_dev, blank=self.blank)
-        frames, label_lp, score = out
-        if no_labels:
-            frames, label_lp = frames[:, :0], label_lp[:, :0]
-        return AlignOutput(frames, None, label_lp, score, self.seconds_per_frame)
-
-    @torch.no_grad()
-    def recognize(self, inputs: PredictInput, max_tokens_per_frame=3, check_every=16, precision=None):
-        """Transducer.recognize (base_transducer.py:474-494): batch size 1 -> recognize_single (<=3 symbols per frame),
-        otherwise recognize_batch — the two variants are NOT equivalent in the reference and both are reproduced."""
-        enc, elen = self.encode(inputs.inputs, inputs.inputs_length, precision)
-        out = self.recognize_encoded(enc, elen, inputs.previous_tokens, inputs.previous_decoder_states, max_tokens_per_frame,
-                                     check_every)
-        if inputs.previous_encoder_states is not None:  # a streaming session's encoder state (streaming.StreamState.export) rides along
-            out = out._replace(next_encoder_states=inputs.previous_encoder_states)
-        return out
-
-    # =================================================================================== streaming (streaming.py, csrc/stream.hip)
-    def stream_state(self, batch_size=1, precision=None):
-        """Encoder state of `batch_size` streams for encode_chunk (the class streaming.STREAM_STATES names for the encoder, after its refusal
-        rule).  precision as encode: "f32" (default) = the inference twin."""
-        from . import streaming
-
-        return streaming.check_streamable(self)(streaming._twin(self, precision), batch_size)
-
-    def encode_chunk(self, state, feats, nframes, final=()):
-        """One step of the streaming encoder (the state's `encode`): feats [B, n, F] (the Conformer: n <= 4 chunk_size), nframes [B], final
-        = the streams that end with these frames (RnntStreamState) -> (enc [B, rows, dmodel] (the Conformer: chunk_size rows), nvalid [B])."""
-        from . import streaming
-
-        if not isinstance(state, streaming.check_streamable(self)):
-            raise ValueError("encoder state of another model")
-        return streaming.encode_chunk(state, feats, nframes, final)
-
     def stream(self, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000):
         """Incremental recognition session (streaming.StreamingRecognizer): accept(pcm) ... finish().  Refused, with the reason, for a
         full-context config, unlimited history, and sizes beyond the streaming attention kernel.  beam_width >= 1: every stream carries
@@ -1805,216 +1034,6 @@ class ConformerTransducer(BaseModel):
 
         return streaming.StreamingRecognizer(self, batch_size, precision, max_tokens_per_frame, beam_width, max_frames)
 
-    def stream_detailed(self, *args, **kwargs):
-        """stream(...) of this class with the same arguments, opened as a detail session (greedy only; a beam raises ValueError): the
-        outputs also say when each token was spoken and how sure the model was (streaming.StreamDetailOutput, rec.recognized(),
-        DESIGN.md 4b-3).  One method for every streamable class: their stream() signatures differ and stay as they are."""
-        return self.stream(*args, **kwargs).detailed()
 
-    def recognize_beam(self, inputs: PredictInput, beam_width=10, device_search=False, precision=None, **kw):
-        """The reference's recognize_beam falls back to greedy (base_transducer.py:841-842), and so does this one by default.
-        device_search=True runs the modified beam search on the device (csrc/rnnt_beam.hip: at most one symbol per frame, equal label
-        sequences merged) and returns its best path: tokens [B, T'] blank padded, next_tokens [B, 1], next_decoder_states [B, 1, 2, P]."""
-        if not device_search:
-            return self.recognize(inputs, precision=precision, **kw)
-        enc, elen = self.encode(inputs.inputs, inputs.inputs_length, precision)
-        tokens, _, _, next_tok, states = self.recognize_beam_encoded(enc, elen, beam_width, 1, inputs.previous_tokens,
-                                                                     inputs.previous_decoder_states)
-        return PredictOutput(tokens=tokens[:, 0], next_tokens=next_tok[:, :1], next_encoder_states=None, next_decoder_states=states[:, 0])
-
-    def recognize_nbest(self, inputs: PredictInput, beam_width=10, top_paths=4, precision=None):
-        """n-best list of the device beam search: (tokens [B, NP, T'] blank padded, lengths [B, NP], scores [B, NP]), best first; paths
-        past the last live hypothesis are empty with score -inf (the shapes of ConformerCTC.recognize_nbest)."""
-        enc, elen = self.encode(inputs.inputs, inputs.inputs_length, precision)
-        tokens, lengths, scores, _, _ = self.recognize_beam_encoded(enc, elen, beam_width, top_paths, inputs.previous_tokens,
-                                                                    inputs.previous_decoder_states)
-        return tokens, lengths, scores
-
-    @torch.no_grad()
-    def recognize_beam_encoded(self, enc, elen, beam_width=10, top_paths=1, previous_tokens=None, previous_decoder_states=None):
-        """The device beam search on encoder output enc [B, T', dmodel] with lengths elen: (tokens [B, NP, T'], lengths [B, NP], scores
-        [B, NP] f32, next_tokens [B, NP], next_decoder_states [B, NP, 1, 2, P]).  Path p continues from next_tokens[:, p:p+1] and
-        next_decoder_states[:, p] (the greedy search's convention: the path's last label, or the initial token, and the prediction
-        state before it is fed).  f32 on the f32 master weights whatever the model's storage type, as recognize_encoded."""
-        ps, c, dev = self.ps, self.cfg, self.device
-        B, T, d = enc.shape
-        P, J = c.rnn_units, c.joint_dim
-        f32 = torch.float32
-        lens = [min(max(int(v), 0), T) for v in elen]
-        Tm = max(max(lens), 1)  # frames past every utterance are never searched
-        enc32 = enc[:, :Tm].reshape(B * Tm, d)
-        if enc32.dtype != f32 or not enc32.is_contiguous():
-            enc32 = K.cast(enc32.contiguous(), torch.empty(B * Tm, d, dtype=f32, device=dev))
-        encj = K.matmul(enc32, ps.p2d("joint/enc/w"), bias=ps.p("joint/enc/b")).view(B, Tm, J)
-        init_tok = None if previous_tokens is None else previous_tokens.to(dev).to(torch.int32).reshape(B).contiguous()
-        init_h = init_c = None
-        if previous_decoder_states is not None:
-            st = previous_decoder_states.to(dev)
-            init_h, init_c = st[:, 0, 0].float().contiguous(), st[:, 0, 1].float().contiguous()
-        lng, lnb = (ps.p("pred/ln/g"), ps.p("pred/ln/b")) if c.prediction_layer_norm else (None, None)
-        Wk, Wrk, Wjp, Wv = ps.p2d("pred/lstm/k"), ps.p2d("pred/lstm/rk"), ps.p2d("joint/pred/w"), ps.p2d("joint/vocab/w")
-        toks, lengths, scores, next_tok, next_h, next_c = K.rnnt_beam_search(
-            ps.p("pred/emb"), Wk, Wrk, ps.p("pred/lstm/b"), lng, lnb, Wjp, ps.p("joint/pred/b"), Wv, ps.p("joint/vocab/b"), encj,
-            torch.tensor(lens, dtype=torch.int32), beam_width, top_paths, self.blank, init_tok, init_h, init_c)
-        if Tm < T:
-            full = torch.full((B, toks.shape[1], T), self.blank, dtype=torch.int32, device=dev)
-            full[:, :, :Tm] = toks
-            toks = full
-        states = torch.stack([next_h, next_c], dim=2).unsqueeze(2)  # [B, NP, 1, 2, P]
-        return toks, lengths, scores, next_tok, states
-
-    @torch.no_grad()
-    def recognize_encoded(self, enc, elen, previous_tokens=None, previous_decoder_states=None, max_tokens_per_frame=3,
-                          check_every=16):
-        return self._greedy_search(enc, elen, previous_tokens, previous_decoder_states, max_tokens_per_frame, check_every, False)[0]
-
-    @torch.no_grad()
-    def recognize_detailed(self, inputs: PredictInput, max_tokens_per_frame=3, check_every=16, precision=None):
-        """recognize that also says when each token was spoken and how sure the model was -> RecognizeOutput (schemas.token_times,
-        token_confidences, word_details read it).  Same search, same tokens: the bookkeeping kernel keeps, next to every symbol it writes,
-        the frame, the log-probability and the entropy of the decision (tfasr_decode_update_detail) - no second pass over the encoder."""
-        enc, elen = self.encode(inputs.inputs, inputs.inputs_length, precision)
-        out = self.recognize_encoded_detailed(enc, elen, inputs.previous_tokens, inputs.previous_decoder_states, max_tokens_per_frame,
-                                              check_every)
-        if inputs.previous_encoder_states is not None:
-            out = out._replace(predict=out.predict._replace(next_encoder_states=inputs.previous_encoder_states))
-        return out
-
-    @torch.no_grad()
-    def recognize_encoded_detailed(self, enc, elen, previous_tokens=None, previous_decoder_states=None, max_tokens_per_frame=3,
-                                   check_every=16):
-        """recognize_encoded -> RecognizeOutput: frames / log_probs / entropies [B, W] column-aligned with predict.tokens (a batch: symbols
-        from column 2; -1 / 0 where no symbol sits), ends None, scores [B] = the sum of the emitted tokens' log-probabilities."""
-        out, (frames, logp, ent) = self._greedy_search(enc, elen, previous_tokens, previous_decoder_states, max_tokens_per_frame,
-                                                       check_every, True)
-        scores = torch.where(frames >= 0, logp, torch.zeros_like(logp)).sum(1)
-        return RecognizeOutput(out, frames, None, logp, ent, scores, self.seconds_per_frame, self.cfg.vocab_size)
-
-    def _greedy_search(self, enc, elen, previous_tokens, previous_decoder_states, max_tokens_per_frame, check_every, detail):
-        """The greedy search of recognize_encoded -> (PredictOutput, None), or with `detail` (PredictOutput, (tok_frames, tok_logp,
-        tok_entropy)): the same launches with the detail variant of the bookkeeping kernel."""
-        ps, c, dev = self.ps, self.cfg, self.device
-        B, T, d = enc.shape
-        E, P, J, V = c.embed_dim, c.rnn_units, c.joint_dim, c.vocab_size
-        mode = 1 if B == 1 else 0
-        # The search arithmetic (embedding, LSTM cell, LayerNorm, joint, vocabulary projection, log-softmax, arg-max) runs in
-        # f32 on the f32 master weights whatever the model's storage type: the GEMMs of one step are [B, <=640] x [640, <=2560]
-        # (launch-bound, not MFMA-bound), and every token decision then carries the reference's f32 arithmetic
-        # (base_transducer.py:437-464) - a bf16 model's tokens are bit-exact against the reference search applied to ITS
-        # encoder output (tests/test_parity_baseline_gpu.py).
-        f32 = torch.float32
-        nframes = torch.tensor([int(v) for v in elen], dtype=torch.int32).to(dev)
-        enc32 = enc.reshape(B * T, d)
-        if enc32.dtype != f32:
-            enc32 = K.cast(enc32.contiguous(), torch.empty(B * T, d, dtype=f32, device=dev))
-        encj = K.matmul(enc32, ps.p2d("joint/enc/w"), bias=ps.p("joint/enc/b")).view(B, T, J)
-        max_tokens = int(elen[0]) * max_tokens_per_frame if mode == 1 else 2 * T + 1
-        tokens = torch.full((B, max(max_tokens, 1)), self.blank, dtype=torch.int32, device=dev)
-        det = ()  # detail buffers, shaped like `tokens`
-        if detail:
-            det = (torch.full_like(tokens, -1), torch.zeros(tokens.shape, dtype=f32, device=dev), torch.zeros(tokens.shape, dtype=f32, device=dev))
-        steps, update = (K.decode_steps_detail, K.decode_update_detail) if detail else (K.decode_steps, K.decode_update)
-        frame_idx = torch.zeros(B, dtype=torch.int32, device=dev)
-        tok_idx = torch.full((B,), -1 if mode == 1 else 1, dtype=torch.int32, device=dev)
-        prev_tok = (torch.full((B,), self.blank, dtype=torch.int32, device=dev) if previous_tokens is None
-                    else previous_tokens.to(dev).to(torch.int32).reshape(B).clone())  # (updated in place by the search: never the caller's tensor)
-        if previous_decoder_states is None:
-            h = torch.zeros(B, P, dtype=f32, device=dev)
-            cst = torch.zeros(B, P, dtype=f32, device=dev)
-        else:
-            st = previous_decoder_states.to(dev)
-            h = st[:, 0, 0].float().clone()
-            cst = st[:, 0, 1].float().clone()
-        per_frame = torch.zeros(max(int(elen[0]), 1), dtype=torch.int32, device=dev) if mode == 1 else None
-        active = torch.ones(1, dtype=torch.int32, device=dev)
-        ecur = torch.empty(B, J, dtype=f32, device=dev)
-        xg = torch.empty(B, 4 * P, dtype=f32, device=dev)
-        hr = torch.empty(B, 4 * P, dtype=f32, device=dev)
-        h_new = torch.empty(B, P, dtype=f32, device=dev)
-        c_new = torch.empty(B, P, dtype=f32, device=dev)
-        pj = torch.empty(B, J, dtype=f32, device=dev)
-        logits = torch.empty(B, V, dtype=f32, device=dev)
-        Wk, Wrk, Wjp, Wv = ps.p2d("pred/lstm/k"), ps.p2d("pred/lstm/rk"), ps.p2d("joint/pred/w"), ps.p2d("joint/vocab/w")
-        # every useful iteration advances a frame or appends a token; the reference's while_loop is unbounded and can
-        # spin forever once a sample saturates its token buffer (SURVEY.md A.4 item 6) — cap the trip count instead
-        max_iters = T + max_tokens + 2
-        it = 0
-        zbuf = torch.empty(B, J, dtype=f32, device=dev)
-        lng, lnb = (ps.p("pred/ln/g"), ps.p("pred/ln/b")) if c.prediction_layer_norm else (None, None)
-        fused = B <= 64 and self.decode_fused
-        packed = K.decode_pack(ps.p("pred/emb"), Wk, Wrk, Wjp, Wv) if fused else None  # tile order of the MFMA step kernels
-        # Iterations queued per host check (fused route).  A row leaves the loop only after it has consumed its frames, one per blank, so
-        # max_b(frames left) iterations are certain to be needed: that many are queued without looking (the first batch is ~T' long), then
-        # the counters are read back ONCE per batch (one device -> host sync) - 4-5 syncs per search instead of one per 64 iterations; the
-        # no-op tail of the last batch is at most `check_every` iterations.
-        need = int(elen[0]) - 1 if mode == 1 else max(int(v) for v in elen) - 1
-        while it < max_iters:
-            n = min(max(need, check_every) if fused else check_every, max_iters - it)
-            if fused:
-                # `n` iterations = 3 skinny-product launches + the bookkeeping kernel each (csrc/decode_step.hip), queued by one host call
-                fused = steps(ps.p("pred/emb"), Wk, Wrk, ps.p("pred/lstm/b"), lng, lnb, Wjp, ps.p("joint/pred/b"), Wv,
-                              ps.p("joint/vocab/b"), encj, nframes, frame_idx, tok_idx, prev_tok, h, cst, active, h_new, c_new, zbuf,
-                              logits, tokens, per_frame, *det, max_tokens, self.blank, mode, max_tokens_per_frame, n, packed=packed)
-                if fused:
-                    it += n
-                    left = (nframes - 1 - frame_idx).clamp_(min=0).max()
-                    act_h, need = (int(v) for v in torch.stack([active[0], left]).tolist())  # (one sync)
-                    if act_h == 0:
-                        break
-                    continue
-            for _ in range(n):
-                K.decode_prepare(encj, nframes, frame_idx, tok_idx, active, ecur, max_tokens, mode)
-                emb = K.embedding_fwd(prev_tok, ps.p("pred/emb"), f32)
-                K.matmul(emb, Wk, bias=ps.p("pred/lstm/b"), out=xg)
-                K.gemm(h, Wrk, hr, B, 4 * P, P, P, 4 * P, 4 * P)
-                K.lstm_step_fwd(xg, hr, h, cst, None, 0, None, c_new, h_new, None, B, P)
-                if c.prediction_layer_norm:
-                    y, _, _ = K.layernorm_fwd(h_new, ps.p("pred/ln/g"), ps.p("pred/ln/b"), save_stats=False)
-                else:  # prediction_layer_norm: False (contextnet/small.yml.j2), as prediction_fwd
-                    y = h_new
-                K.matmul(y, Wjp, bias=ps.p("joint/pred/b"), out=pj)
-                z = K.joint_fwd(ecur.view(B, 1, J), pj.view(B, 1, J))
-                K.matmul(z.view(B, J), Wv, bias=ps.p("joint/vocab/b"), out=logits)
-                update(logits, active, nframes, frame_idx, prev_tok, tok_idx, tokens, per_frame, h_new, c_new, h, cst, *det,
-                       max_tokens, self.blank, mode, max_tokens_per_frame)
-                it += 1
-            if int(active.item()) == 0:
-                break
-        self.last_search_iterations = it  # (queued iterations incl. the no-op tail of the last batch; bench.py reports it)
-        states = torch.stack([h, cst], dim=1).unsqueeze(1)  # [B, 1, 2, P]
-        out = PredictOutput(tokens=tokens[:, :max_tokens], next_tokens=prev_tok.view(B, 1), next_encoder_states=None,
-                            next_decoder_states=states)
-        return out, (tuple(t[:, :max_tokens] for t in det) if detail else None)
-
-    # ----------------------------------------------------------------- timing hooks (bench.py)
-    def _tick(self, name):
-        if self.timers is None:
-            return None
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
-
-    def _tock(self, name, start, work=0.0):
-        if self.timers is None:
-            return
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        self.timers.setdefault(name, []).append((start, e))
-        self.timer_work.setdefault(name, []).append(work)
-
-
-def _mel_weight_matrix(num_mel_bins, num_spectrogram_bins, sample_rate, lower, upper):
-    """tf.signal.linear_to_mel_weight_matrix semantics (feature_extraction.py:222-229): HTK mel scale, DC row zero,
-    un-normalised triangles, float32 arithmetic."""
-    f32 = np.float32
-
-    def mel(f):
-        return (f32(1127.0) * np.log(f32(1.0) + np.asarray(f, f32) / f32(700.0))).astype(f32)
-
-    nyquist = f32(sample_rate) / f32(2.0)
-    linear = np.linspace(f32(0.0), nyquist, num_spectrogram_bins, dtype=f32)[1:]
-    spec_mel = mel(linear)[:, None]
-    edges = np.linspace(mel(lower), mel(upper), num_mel_bins + 2, dtype=f32)
-    lo, ce, hi = edges[:-2][None, :], edges[1:-1][None, :], edges[2:][None, :]
-    w = np.maximum(f32(0.0), np.minimum((spec_mel - lo) / (ce - lo), (hi - spec_mel) / (hi - ce))).astype(f32)
-    return np.pad(w, [[1, 0], [0, 0]]).astype(f32)
+class ConformerTransducer(ConformerEncoderMixin, TransducerModel):
+    _config_error = "ConformerTransducer needs a ConformerConfig with head='transducer' (configs.conformer_s())"

@@ -7,7 +7,7 @@ Conformer path: the encoder of tensorflow_asr/models/encoders/contextnet.py:40-3
     ContextNetEncoder = reshape [B,T,F,1] -> [B,T,F], then the blocks; time reduction = product of the strides   (:301-341)
 
 with an explicit hand-written backward.  The frontend, prediction network, joint network, RNN-T loss, optimizer, decoding
-and data-parallel hooks are inherited from ConformerTransducer (models/transducer/contextnet.py wires the same pieces).
+and data-parallel hooks are TransducerModel's / AsrModel's (models/transducer/contextnet.py wires the same pieces).
 
 Kernel mapping: depthwise part = tfasr_dwconv_* (causal, stride 1; a strided causal conv is the stride-1 one sampled every
 `stride` frames: tfasr_rows_subsample_*), pointwise part = tfasr_gemm (bias fused, weight + bias gradients in one launch),
@@ -19,20 +19,21 @@ import os
 import torch
 
 from . import kernels as K
-from .conformer import ConformerTransducer, _split_k
 from .kernels import ACT_NONE, ACT_SIGMOID, ACT_SWISH
+from .model import SingleProcess, _split_k
 from .params import contextnet_modules
+from .transducer import TransducerModel
 
 _ACT = {"swish": ACT_SWISH, "none": ACT_NONE}
 
 
-class ContextNetTransducer(ConformerTransducer):
-    def __init__(self, cfg, device=None, dtype=torch.bfloat16, seed=0, dp=None):
-        if cfg.encoder != "contextnet":
-            raise ValueError("ContextNetTransducer needs a config with encoder='contextnet' (configs.contextnet())")
-        super().__init__(cfg, device, dtype, seed, dp)
-        self.blocks = contextnet_modules(cfg)
-        self.native_blocks = False  # the native executor (csrc/block.hip) is the Conformer block
+class ContextNetEncoderMixin:
+    """encoder_fwd / encoder_bwd, the grouped weight gradients and the refusal to stream; mixed in front of TransducerModel"""
+
+    encoder_kind = "contextnet"
+
+    def _init_encoder(self):
+        self.blocks = contextnet_modules(self.cfg)
 
     def stream(self, *a, **k):
         raise NotImplementedError("ContextNet cannot stream: its squeeze-and-excite is a mean over the whole utterance")
@@ -196,7 +197,6 @@ class ContextNetTransducer(ConformerTransducer):
         self._wg_queue = []
         # one GPU: the depthwise weight gradients of all layers batched by shape after the loop (a data-parallel group releases a block's
         # gradient range right behind the block); dw_batch=False: per layer
-        from .conformer import SingleProcess
         self._dw_queue = [] if (isinstance(self.dp, SingleProcess) and getattr(self, "dw_batch", True)) else None
         try:
             for i in reversed(range(len(self.blocks))):
@@ -212,3 +212,7 @@ class ContextNetTransducer(ConformerTransducer):
             self._wg_queue = None  # the prediction / joint networks' gradients are issued directly
             self._dw_queue = None
         # (the input features need no gradient)
+
+
+class ContextNetTransducer(ContextNetEncoderMixin, TransducerModel):
+    _config_error = "ContextNetTransducer needs a config with encoder='contextnet' (configs.contextnet())"

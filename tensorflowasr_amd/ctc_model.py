@@ -5,27 +5,26 @@ Mirrors  tensorflow_asr.models.ctc.conformer.Conformer      (models/ctc/conforme
          CtcModel.call / recognize / recognize_beam         (models/ctc/base_ctc.py:74-149)
          CtcLoss.call                                       (losses/ctc_loss.py:47-66: tf.nn.ctc_loss, blank 0, mean over the batch)
 
-The log-mel frontend, SpecAugment, subsampling, Conformer blocks (native block executor), optimizer, gradient accumulation
-and the data-parallel hooks are inherited from ConformerTransducer; this class replaces the prediction / joint networks and the
-RNN-T loss by the Dense decoder and tfasr_ctc_loss, with a hand-written backward.  Decoding: tfasr_ctc_greedy_decode (device)
-and tfasr_ctc_beam_search_host (host routine, as tf.nn.ctc_beam_search_decoder is; the default of recognize_beam) or
+CtcModel is the CTC head over any encoder (model.AsrModel's docstring): the Dense decoder and tfasr_ctc_loss with a hand-written backward
+around encoder_fwd / encoder_bwd; the log-mel frontend, SpecAugment, optimizer, gradient accumulation and the data-parallel hooks are
+AsrModel's, the subsampling and the Conformer blocks (native block executor) ConformerEncoderMixin's.  Decoding: tfasr_ctc_greedy_decode
+(device) and tfasr_ctc_beam_search_host (host routine, as tf.nn.ctc_beam_search_decoder is; the default of recognize_beam) or
 tfasr_ctc_beam_search (the same search on the device, with the n-best list: recognize_beam(device_search=True), recognize_nbest).
 No CPU fallback.
 """
 import torch
 
 from . import kernels as K
-from .conformer import ConformerTransducer
+from .conformer import ConformerEncoderMixin
+from .model import AsrModel
 from .schemas import AlignOutput, PredictInput, PredictOutput, RecognizeOutput, TrainData, TrainInput, TrainOutput
 
 
-class ConformerCTC(ConformerTransducer):
-    def __init__(self, cfg, device=None, dtype=torch.bfloat16, seed=0, dp=None):
-        if cfg.head != "ctc":
-            raise ValueError("ConformerCTC needs a config with head='ctc' (configs.conformer_ctc_s())")
-        super().__init__(cfg, device, dtype, seed, dp)
-        self.time_reduction_factor = cfg.time_reduction_factor
-        self.use_pred_stream = False  # there is no prediction network to overlap
+class CtcModel(AsrModel):
+    head_kind = "ctc"
+
+    def get_initial_decoder_states(self, batch_size=1):
+        return None  # a CTC decoder carries nothing from call to call (the decoders' call_next return None, models/ctc/deepspeech2.py:129-130)
 
     # ------------------------------------------------------------------------------------------- forward
     def _forward_ctc(self, inputs: TrainInput, training, ctx, masks=None):
@@ -183,3 +182,12 @@ class ConformerCTC(ConformerTransducer):
 
     def recognize_beam_encoded(self, *a, **k):
         raise NotImplementedError("transducer beam search does not apply to a CTC model")
+
+
+class ConformerCTC(ConformerEncoderMixin, CtcModel):
+    _config_error = "ConformerCTC needs a config with head='ctc' (configs.conformer_ctc_s())"
+
+    def get_initial_decoder_states(self, batch_size=1):
+        """As before the heads were split: the zero state of the transducer's prediction LSTM [B, 1, 2, cfg.rnn_units], not the None of
+        the other CTC models (the reference's CtcModel returns [], base_ctc.py:97-98)."""
+        return torch.zeros(batch_size, 1, 2, self.cfg.rnn_units, dtype=torch.float32, device=self.device)

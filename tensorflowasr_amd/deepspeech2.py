@@ -27,7 +27,7 @@ alone; that is the reference's behaviour on a padded batch and is reproduced, no
 such path: there a batch row equals the utterance alone.
 
 The CTC decoders (greedy, host and device beam search, n-best), forced alignment, evaluate, the precision switch (f32 twin by default,
-bf16 opt-in) and the .npz checkpoints are ConformerCTC's.  feature_type "spectrogram" (feature_extraction.py:233-235: ln(|STFT|^2 + eps),
+bf16 opt-in) and the .npz checkpoints are CtcModel's / AsrModel's.  feature_type "spectrogram" (feature_extraction.py:233-235: ln(|STFT|^2 + eps),
 first num_feature_bins bins) runs on the log-mel kernel with the first F columns of the identity as its weight matrix.  Training,
 GRU / SimpleRNN, conv_type conv1d and .weights.h5 import are not built: train_step / loss_and_backward / compile raise.
 
@@ -46,27 +46,20 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .ctc_model import ConformerCTC
+from .ctc_model import CtcModel
+from .inference_only import InferenceOnlyEncoder
 from .params import deepspeech2_modules
 
-_BN_EPS = 1e-3  # keras.layers.BatchNormalization default
 
+class DeepSpeech2EncoderMixin(InferenceOnlyEncoder):
+    """the front end (log-mel or spectrogram), encoder_fwd and the causal variant's streaming session; mixed in front of CtcModel"""
 
-class DeepSpeech2CTC(ConformerCTC):
-    def __init__(self, cfg, device=None, dtype=torch.bfloat16, seed=0, dp=None):
-        if getattr(cfg, "encoder", None) != "deepspeech2":
-            raise ValueError("DeepSpeech2CTC needs a DeepSpeech2Config (configs.deepspeech2() / configs.deepspeech2_from_reference(mapping))")
-        super().__init__(cfg, device, dtype, seed, dp)
-        self.modules = deepspeech2_modules(cfg)
-        self.native_blocks = False  # the native executor (csrc/block.hip) is the Conformer block
-        self._derived = {"epoch": -1}  # folded BatchNorm pairs, packed / concatenated kernels, per (layer, type); shared with the f32 twin
+    encoder_kind = "deepspeech2"
+    _not_built = "the Conv2D / LSTM gradients and BatchNorm in batch-statistics mode are not built"
 
-    # ------------------------------------------------------------------------------------------- inference only
-    def _inference_only(self, *a, **k):
-        raise NotImplementedError("DeepSpeech2CTC is inference only: the Conv2D / LSTM gradients and BatchNorm in batch-statistics mode are "
-                                  "not built (weights arrive through load_weights)")
-
-    train_step = loss_and_backward = compile = _inference_only
+    def _init_encoder(self):
+        super()._init_encoder()
+        self.modules = deepspeech2_modules(self.cfg)
 
     # ------------------------------------------------------------------------------------------- streaming (the causal variant)
     def stream(self, batch_size=1, chunk_frames=32, beam_width=0, max_frames=3000, precision=None):
@@ -78,29 +71,7 @@ class DeepSpeech2CTC(ConformerCTC):
         streaming.check_streamable(self)
         return streaming.StreamingRecognizer(self, batch_size, precision, 1, beam_width, max_frames, chunk_frames=chunk_frames)
 
-    def _encoder_length(self, t):
-        return self.cfg.encoder_length(t)
-
-    def get_initial_decoder_states(self, batch_size=1):
-        return None  # DeepSpeech2.get_initial_decoder_states (models/ctc/deepspeech2.py:129-130)
-
     # ------------------------------------------------------------------------------------------- constants derived from the weights
-    def _cache(self):
-        d = self._derived
-        if d["epoch"] != self.ps.epoch[0]:
-            d.clear()
-            d["epoch"] = self.ps.epoch[0]
-        return d
-
-    def _affine(self, bn):
-        d, ps = self._cache(), self.ps
-        aff = d.get((bn, "affine"))
-        if aff is None:
-            scale = (ps.p(bn + "/g") / torch.sqrt(ps.state[bn + "/mv"] + _BN_EPS)).contiguous()
-            shift = (ps.p(bn + "/b") - ps.state[bn + "/mm"] * scale).contiguous()
-            aff = d[(bn, "affine")] = (scale, shift)
-        return aff
-
     def _conv_consts(self, name):
         d, ps = self._cache(), self.ps
         got = d.get((name, self.dtype))
@@ -145,9 +116,7 @@ class DeepSpeech2CTC(ConformerCTC):
             self._consts["fe"] = (torch.from_numpy(window).to(dev), torch.from_numpy(melw).to(dev), torch.from_numpy(band).to(dev))
         return self._consts["fe"]
 
-    def frontend(self, signals, signals_length, training=False, masks=None):
-        if training:
-            self._inference_only()
+    def _features(self, signals, signals_length):
         c = self.cfg
         window, melw, band = self._frontend_consts()
         feats = K.logmel(signals, window, melw, band, c.frame_step, c.nfft, c.preemphasis, c.epsilon, torch.float32)
@@ -196,6 +165,10 @@ class DeepSpeech2CTC(ConformerCTC):
             w, bias = self._fc_consts(f)
             x = K.conv1d_fwd(x, w, (1, f["din"], f["dout"]), bias=bias, relu=True)
         return x.view(B * T, self.cfg.dmodel), T, lens, lens_dev
+
+
+class DeepSpeech2CTC(DeepSpeech2EncoderMixin, CtcModel):
+    _config_error = "DeepSpeech2CTC needs a DeepSpeech2Config (configs.deepspeech2() / configs.deepspeech2_from_reference(mapping))"
 
 
 def spectrogram_weights(F, bins=257):

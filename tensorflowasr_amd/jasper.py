@@ -19,7 +19,7 @@ Padded frames need no masking: every layer is causal and the BatchNorm is affine
 only - what lies behind an utterance's end in a batch row cannot reach a valid frame, and a batch row equals the utterance run alone.
 
 The front end, the CTC decoders (greedy, host and device beam search, n-best), forced alignment, evaluate, the precision switch (f32
-twin by default, bf16 opt-in) and the .npz checkpoints are ConformerCTC's.  The feature logarithm is base 10 where the config says so
+twin by default, bf16 opt-in) and the .npz checkpoints are CtcModel's / AsrModel's.  The feature logarithm is base 10 where the config says so
 (speech_config.log_base, feature_extraction.py:214-218): the natural-log features times 1 / ln 10.  Training (Conv1D gradients,
 BatchNorm batch statistics) is not built: train_step / loss_and_backward / compile raise.
 """
@@ -28,49 +28,29 @@ import math
 import torch
 
 from . import kernels as K
-from .ctc_model import ConformerCTC
+from .ctc_model import CtcModel
+from .inference_only import InferenceOnlyEncoder
 from .params import jasper_modules
 
-_BN_EPS = 1e-3  # keras.layers.BatchNormalization default
 
+class JasperEncoderMixin(InferenceOnlyEncoder):
+    """the front end in the config's log base, encoder_fwd and the streaming session; mixed in front of CtcModel"""
 
-class JasperCTC(ConformerCTC):
-    def __init__(self, cfg, device=None, dtype=torch.bfloat16, seed=0, dp=None):
-        if getattr(cfg, "encoder", None) != "jasper":
-            raise ValueError("JasperCTC needs a JasperConfig (configs.jasper() / configs.jasper_from_reference(mapping))")
-        super().__init__(cfg, device, dtype, seed, dp)
-        self.layers = jasper_modules(cfg)
-        self.native_blocks = False  # the native executor (csrc/block.hip) is the Conformer block
-        self._derived = {"epoch": -1}  # folded BatchNorm pairs and packed kernels, per (layer, type); shared with the f32 twin
+    encoder_kind = "jasper"
+    _not_built = "the Conv1D data / weight gradients and BatchNorm in batch-statistics mode are not built"
 
-    # ------------------------------------------------------------------------------------------- inference only
-    def _inference_only(self, *a, **k):
-        raise NotImplementedError("JasperCTC is inference only: the Conv1D data / weight gradients and BatchNorm in batch-statistics mode "
-                                  "are not built (weights arrive through load_weights)")
-
-    train_step = loss_and_backward = compile = _inference_only
-
-    def _encoder_length(self, t):
-        return self.cfg.encoder_length(t)
-
-    def get_initial_decoder_states(self, batch_size=1):
-        return None  # a CTC decoder carries nothing from call to call (JasperDecoder.call_next returns None)
+    def _init_encoder(self):
+        super()._init_encoder()
+        self.layers = jasper_modules(self.cfg)
 
     # ------------------------------------------------------------------------------------------- constants derived from the weights
     def _layer_consts(self, conv, bn):
         """(kernel in the compute type's layout, bias, scale, shift) of one Conv1D + BatchNormalization pair"""
-        ps, d = self.ps, self._derived
-        if d["epoch"] != ps.epoch[0]:
-            d.clear()
-            d["epoch"] = ps.epoch[0]
+        ps, d = self.ps, self._cache()
         key = (conv, self.dtype)
         got = d.get(key)
         if got is None:
-            aff = d.get((bn, "affine"))
-            if aff is None:
-                scale = (ps.p(bn + "/g") / torch.sqrt(ps.state[bn + "/mv"] + _BN_EPS)).contiguous()
-                shift = (ps.p(bn + "/b") - ps.state[bn + "/mm"] * scale).contiguous()
-                aff = d[(bn, "affine")] = (scale, shift)
+            aff = self._affine(bn)
             w = ps.p(conv + "/w")
             if self.dtype != torch.float32:
                 w = K.conv1d_pack_weight(w)
@@ -101,9 +81,7 @@ class JasperCTC(ConformerCTC):
             feats32 = K.cast(feats32, torch.empty(feats32.shape, dtype=self.dtype, device=feats32.device))
         return feats32
 
-    def frontend(self, signals, signals_length, training=False, masks=None):
-        if training:
-            self._inference_only()
+    def _features(self, signals, signals_length):
         c = self.cfg
         window, melw, band = self._frontend_consts()
         feats = K.logmel(signals, window, melw, band, c.frame_step, c.nfft, c.preemphasis, c.epsilon, torch.float32)
@@ -136,3 +114,7 @@ class JasperCTC(ConformerCTC):
         from . import streaming
 
         return streaming.StreamingRecognizer(self, batch_size, precision, 1, beam_width, max_frames, chunk_frames=chunk_frames)
+
+
+class JasperCTC(JasperEncoderMixin, CtcModel):
+    _config_error = "JasperCTC needs a JasperConfig (configs.jasper() / configs.jasper_from_reference(mapping))"

@@ -26,7 +26,7 @@ reduced frame of a shorter batch row the group mixes valid frames with beta . W 
 zeros.  A padded batch row is therefore NOT the utterance alone (the reference's own classes pin this: tests/golden/rnnt_wiring.npz).
 
 The prediction and joint networks, the decoders (greedy, host and device beam search, n-best), forced alignment, evaluate, the precision
-switch (f32 twin by default, bf16 opt-in) and the .npz checkpoints are ConformerTransducer's; time_reduction_factor is the product of
+switch (f32 twin by default, bf16 opt-in) and the .npz checkpoints are TransducerModel's / AsrModel's; time_reduction_factor is the product of
 the blocks' factors.  A `post` reduction in the LAST block widens the encoder's output rows to factor * dmodel (cfg.dmodel), on which the
 joint network's encoder projection is built, as keras builds it.
 
@@ -44,8 +44,9 @@ projection and .weights.h5 import are not built: train_step / loss_and_backward 
 import torch
 
 from . import kernels as K
-from .conformer import ConformerTransducer
+from .inference_only import InferenceOnlyEncoder
 from .params import rnnt_modules
+from .transducer import TransducerModel
 
 _LN_EPS = 1e-3  # keras.layers.LayerNormalization default
 
@@ -62,8 +63,11 @@ def boundary_factors(mods):
     return [pre[0]] + [post[i] * pre[i + 1] for i in range(len(mods) - 1)] + [post[-1]]
 
 
-class RnnEncoderMixin:
-    """encoder_fwd and what it needs; mixed in front of ConformerTransducer"""
+class RnnEncoderMixin(InferenceOnlyEncoder):
+    """encoder_fwd and what it needs; mixed in front of TransducerModel"""
+
+    encoder_kind = "rnnt"
+    _not_built = "the encoder's LSTM and block-tail gradients are not built"
 
     # "fused": tfasr_rnnt_block_tail_fwd; "unfused": tfasr_layernorm_fwd + tfasr_gemm + the zero fill; "auto": the faster of the two as
     # measured (profiles/rnnt_timing.json, small config, 32 x 10 s) - which is the two launches in BOTH types: on layer 0's rows the one
@@ -71,19 +75,9 @@ class RnnEncoderMixin:
     # `recognize` do not tell the routes apart (the recurrence is 99 % of them), a session step is 3 - 6 % slower on the one launch
     tail_route = "auto"
 
-    def _init_rnnt(self):
-        if getattr(self.cfg, "encoder", None) != "rnnt":
-            raise ValueError(f"{type(self).__name__} needs an RnnTransducerConfig (configs.rnnt() / configs.rnnt_from_reference(mapping))")
+    def _init_encoder(self):
+        super()._init_encoder()
         self.modules = rnnt_modules(self.cfg)
-        self.native_blocks = False  # the native executor (csrc/block.hip) is the Conformer block
-        self._derived = {"epoch": -1}  # packed projection kernels per (block, type); shared with the f32 twin
-
-    # ------------------------------------------------------------------------------------------- inference only
-    def _inference_only(self, *a, **k):
-        raise NotImplementedError(f"{type(self).__name__} is inference only: the encoder's LSTM and block-tail gradients are not built "
-                                  "(weights arrive through load_weights)")
-
-    train_step = loss_and_backward = compile = _inference_only
 
     # ------------------------------------------------------------------------------------------- streaming (tensorflowasr_amd/streaming.py)
     def stream(self, batch_size=1, chunk_frames=32, beam_width=0, max_frames=3000, precision=None, max_tokens_per_frame=3):
@@ -98,17 +92,7 @@ class RnnEncoderMixin:
     def boundary_factors(self):
         return boundary_factors(self.modules)
 
-    def _encoder_length(self, t):
-        return self.cfg.encoder_length(t)
-
     # ------------------------------------------------------------------------------------------- constants derived from the weights
-    def _cache(self):
-        d = self._derived
-        if d["epoch"] != self.ps.epoch[0]:
-            d.clear()
-            d["epoch"] = self.ps.epoch[0]
-        return d
-
     def _fused_tail(self, m):
         route = self.tail_route
         if route == "auto":
@@ -204,15 +188,6 @@ class RnnEncoderMixin:
         # (a `pre` reduction of a block that does not exist cannot be pending here: g = 1 for the last block)
         return x.reshape(B * T, x.shape[2]), T, lens, lens_dev
 
-    def frontend(self, signals, signals_length, training=False, masks=None):
-        if training:
-            self._inference_only()
-        return super().frontend(signals, signals_length, False, None)
 
-
-class RnnTransducer(RnnEncoderMixin, ConformerTransducer):
-    def __init__(self, cfg, device=None, dtype=torch.bfloat16, seed=0, dp=None):
-        if getattr(cfg, "encoder", None) != "rnnt" or cfg.head != "transducer":
-            raise ValueError("RnnTransducer needs an RnnTransducerConfig (configs.rnnt() / configs.rnnt_from_reference(mapping))")
-        super().__init__(cfg, device, dtype, seed, dp)
-        self._init_rnnt()
+class RnnTransducer(RnnEncoderMixin, TransducerModel):
+    _config_error = "RnnTransducer needs an RnnTransducerConfig (configs.rnnt() / configs.rnnt_from_reference(mapping))"

@@ -44,11 +44,10 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .conformer import ConformerTransducer
-from .ctc_model import ConformerCTC
+from .ctc_model import CtcModel
+from .inference_only import InferenceOnlyEncoder
 from .params import transformer_modules
-
-_BN_EPS = 1e-3  # keras.layers.BatchNormalization default
+from .transducer import TransducerModel
 
 
 def sinusoid_table(T, d, interleave):
@@ -64,8 +63,11 @@ def sinusoid_table(T, d, interleave):
     return np.concatenate([np.sin(ang), np.cos(ang)], -1).astype(np.float32)
 
 
-class TransformerEncoderMixin:
-    """encoder_fwd and what it needs; mixed in front of ConformerCTC / ConformerTransducer"""
+class TransformerEncoderMixin(InferenceOnlyEncoder):
+    """encoder_fwd and what it needs; mixed in front of CtcModel / TransducerModel"""
+
+    encoder_kind = "transformer"
+    _not_built = "the plain-attention backward and BatchNorm in batch-statistics mode are not built"
 
     # "fused": tfasr_attn_plain_fwd; "unfused": batched GEMMs + the softmax kernel with a zero position tensor (unfused_attention below);
     # "auto": the faster of the two as measured (profiles/transformer_timing.json, base config at T' = 250 and 875): in bf16 the fused
@@ -74,19 +76,9 @@ class TransformerEncoderMixin:
     # under the causal mask, which only the fused kernel has
     attention_route = "auto"
 
-    def _init_transformer(self):
-        if getattr(self.cfg, "encoder", None) != "transformer":
-            raise ValueError(f"{type(self).__name__} needs a TransformerConfig (configs.transformer() / configs.transformer_from_reference(mapping))")
+    def _init_encoder(self):
+        super()._init_encoder()
         self.modules = transformer_modules(self.cfg)
-        self.native_blocks = False  # the native executor (csrc/block.hip) is the Conformer block
-        self._derived = {"epoch": -1}  # folded BatchNorm pairs, packed kernels, scaled LayerNorm pairs; shared with the f32 twin
-
-    # ------------------------------------------------------------------------------------------- inference only
-    def _inference_only(self, *a, **k):
-        raise NotImplementedError(f"{type(self).__name__} is inference only: the plain-attention backward and BatchNorm in batch-statistics "
-                                  "mode are not built (weights arrive through load_weights)")
-
-    train_step = loss_and_backward = compile = _inference_only
 
     # ------------------------------------------------------------------------------------------- streaming (tensorflowasr_amd/streaming.py)
     # A config that cannot be streamed (full context, no auto mask, unlimited history, sizes beyond the kernel) is refused by
@@ -100,28 +92,7 @@ class TransformerEncoderMixin:
         streaming.check_streamable(self)
         return streaming.StreamingRecognizer(self, batch_size, precision, max_tokens_per_frame, beam_width, max_frames)
 
-    def _encoder_length(self, t):
-        return self.cfg.encoder_length(t)
-
     # ------------------------------------------------------------------------------------------- constants derived from the weights
-    def _cache(self):
-        d = self._derived
-        if d["epoch"] != self.ps.epoch[0]:
-            d.clear()
-            d["epoch"] = self.ps.epoch[0]
-        return d
-
-    def _affine(self, bn):
-        if bn is None:
-            return None, None
-        d, ps = self._cache(), self.ps
-        aff = d.get((bn, "affine"))
-        if aff is None:
-            scale = (ps.p(bn + "/g") / torch.sqrt(ps.state[bn + "/mv"] + _BN_EPS)).contiguous()
-            shift = (ps.p(bn + "/b") - ps.state[bn + "/mm"] * scale).contiguous()
-            aff = d[(bn, "affine")] = (scale, shift)
-        return aff
-
     def _ffn1_consts(self, p):
         d, ps, c = self._cache(), self.ps, self.cfg
         got = d.get((p, "ffn_1", self.dtype))
@@ -228,11 +199,6 @@ class TransformerEncoderMixin:
             x = self.block_fwd(x, p, B, T, lens_dev, i)
         return x, T, lens, lens_dev
 
-    def frontend(self, signals, signals_length, training=False, masks=None):
-        if training:
-            self._inference_only()
-        return super().frontend(signals, signals_length, False, None)
-
 
 def unfused_attention(qkv, lens_dev, B, H, T, dh, scale, use_mask=True, chunk_size=None, history_size=None):
     """The same attention on the kernels the library had before csrc/attn_plain.hip: batched tfasr_gemm for scale * Q K^T, the
@@ -251,20 +217,9 @@ def unfused_attention(qkv, lens_dev, B, H, T, dh, scale, use_mask=True, chunk_si
     return out
 
 
-class TransformerCTC(TransformerEncoderMixin, ConformerCTC):
-    def __init__(self, cfg, device=None, dtype=torch.bfloat16, seed=0, dp=None):
-        if getattr(cfg, "encoder", None) != "transformer" or cfg.head != "ctc":
-            raise ValueError("TransformerCTC needs a TransformerConfig with head='ctc' (configs.transformer() / transformer_from_reference)")
-        super().__init__(cfg, device, dtype, seed, dp)
-        self._init_transformer()
-
-    def get_initial_decoder_states(self, batch_size=1):
-        return None  # TransformerDecoder.call_next returns None (models/ctc/transformer.py:45-47)
+class TransformerCTC(TransformerEncoderMixin, CtcModel):
+    _config_error = "TransformerCTC needs a TransformerConfig with head='ctc' (configs.transformer() / transformer_from_reference)"
 
 
-class TransformerTransducer(TransformerEncoderMixin, ConformerTransducer):
-    def __init__(self, cfg, device=None, dtype=torch.bfloat16, seed=0, dp=None):
-        if getattr(cfg, "encoder", None) != "transformer" or cfg.head != "transducer":
-            raise ValueError("TransformerTransducer needs a TransformerConfig with head='transducer' (configs.transformer(head='rnnt'))")
-        super().__init__(cfg, device, dtype, seed, dp)
-        self._init_transformer()
+class TransformerTransducer(TransformerEncoderMixin, TransducerModel):
+    _config_error = "TransformerTransducer needs a TransformerConfig with head='transducer' (configs.transformer(head='rnnt'))"

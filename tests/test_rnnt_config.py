@@ -79,11 +79,13 @@ def test_class_name_resolves(fixture, monkeypatch):
     monkeypatch.setattr(rnnt_mod, "RnnTransducer", Fake)
     m = base_model.model_from_config(fixture)
     assert isinstance(m, Fake) and seen["cfg"] == configs.rnnt(vocab_size=1000) and seen["dtype"] == torch.bfloat16
-    from tensorflowasr_amd.conformer import ConformerTransducer
+    from tensorflowasr_amd.conformer import ConformerEncoderMixin
+    from tensorflowasr_amd.transducer import TransducerModel
 
     assert issubclass(rnnt_mod.RnnEncoderMixin, object) and rnnt_mod.RnnTransducer is Fake
     monkeypatch.undo()
-    assert issubclass(rnnt_mod.RnnTransducer, ConformerTransducer) and issubclass(rnnt_mod.RnnTransducer, rnnt_mod.RnnEncoderMixin)
+    assert issubclass(rnnt_mod.RnnTransducer, TransducerModel) and not issubclass(rnnt_mod.RnnTransducer, ConformerEncoderMixin)
+    assert issubclass(rnnt_mod.RnnTransducer, rnnt_mod.RnnEncoderMixin)
     for name in ("train_step", "loss_and_backward", "compile"):
         assert getattr(rnnt_mod.RnnTransducer, name) is rnnt_mod.RnnEncoderMixin._inference_only
     with pytest.raises(NotImplementedError):

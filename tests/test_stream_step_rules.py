@@ -61,7 +61,7 @@ def test_deepspeech2(cfg):
 def test_rnn_transducer(cfg):
     model = object.__new__(RnnTransducer)  # boundary_factors reads the module list only
     model.cfg = cfg
-    model._init_rnnt()
+    model._init_encoder()
     fb = model.boundary_factors()
     assert len(fb) == int(cfg.nlayers) + 1
     for n in (1, 7, 32):
