@@ -827,6 +827,36 @@ int tfasr_ctc_beam_commit(const int32_t* final_mask, int32_t* committed, int32_t
 int tfasr_ctc_beam_nbest(int B, int C, int Tcap, int V, int beam_width, int top_paths, int width, int32_t* tokens, int32_t* tokens_len,
                          float* log_prob, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Commit horizon and trie compaction of the beam streams (declarations added under ABI 44, nothing existing changes).
+ *
+ * horizon_state [B, 4 + 2 * (horizon + 1)] int32 is owned by the caller, zeroed when a stream is reset and written by these entries
+ * alone: the frames the stream has consumed since its reset, the frame counter it was last brought up to, and a ring of horizon + 1
+ * prune points (frames consumed, trie node count), one per call that found new frames.  1 <= horizon <= TFASR_BEAM_MAX_HORIZON frames.
+ *   _commit_horizon  what _commit does, and at a prune point: with X the node count logged at the latest point at least `horizon`
+ *             frames back (none: the plain commit), target = the deepest ancestor-or-self of the best live row's node with id < X (a
+ *             label sequence that existed `horizon` frames ago).  If target is deeper than the live rows' common ancestor, the live
+ *             rows that do not descend from it leave the carried beam (the rest move up in their order) and the commit goes up to
+ *             target; otherwise it goes up to the common ancestor.  final_mask streams commit their whole best row, as _commit.
+ *   _compact  the streams with mask[b] != 0 (mask required) shed the trie above and beside their live rows, in place: new root = the
+ *             ancestor of the live rows' common ancestor at depth min(committed[b], its depth); kept = the nodes on the paths from it
+ *             to the live rows, in their old order, depths rebased; the root keeps its label; the (parent, label) table is rebuilt, the
+ *             rows' nodes and the horizon state's node counts are remapped, committed[b] loses the dropped depth, the node counter
+ *             becomes the number kept and the frame counter the depth of the deepest live row (so nodes <= 1 + beam_width * frames and
+ *             depth <= frames hold as before).  out [B,3] = (dropped depth, nodes kept, frame counter) per stream, (0, nodes, frames)
+ *             for the others.  horizon_state may be NULL (then horizon = 0) for streams that never ran _commit_horizon.  _nbest
+ *             afterwards gives the label sequences below the root. */
+#define TFASR_BEAM_MAX_HORIZON 4096
+int tfasr_rnnt_beam_commit_horizon(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens,
+                                   int32_t* horizon_state, int horizon, int B, int Tcap, int U, int J, int V, int beam_width, int width,
+                                   int blank, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_rnnt_beam_compact(const int32_t* mask, int32_t* committed, int32_t* horizon_state, int horizon, int32_t* out, int B, int Tcap,
+                            int U, int J, int V, int beam_width, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_ctc_beam_commit_horizon(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens,
+                                  int32_t* horizon_state, int horizon, int B, int C, int Tcap, int V, int beam_width, int width,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_ctc_beam_compact(const int32_t* mask, int32_t* committed, int32_t* horizon_state, int horizon, int32_t* out, int B, int C,
+                           int Tcap, int V, int beam_width, void* workspace, size_t workspace_bytes, void* stream);
+
 /* N-gram LM shallow fusion in the CTC prefix beam search (declarations added under ABI 44, nothing existing changes;
  * csrc/ctc_beam.hip, csrc/ngram_lm.h).  The search maximises log P_ctc(y | x) + lm(y) over label sequences y.
  *

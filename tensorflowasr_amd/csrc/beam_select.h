@@ -17,7 +17,8 @@
 //    exact, so ranks are distinct.  The trie is walked only on an exact tie of totals.
 // 4. grow_trie: one node per label sequence for the whole utterance, so a prefix that leaves the beam and comes back keeps its mass:
 //    the search looks the winners up in the (parent, label) table, the missing ones become nodes numbered in rank order.
-// write_paths, commit_stream and clear_stream are the n-best output, the stable-prefix commit and the reset of the searches in pieces.
+// write_paths, commit_stream and clear_stream are the n-best output, the stable-prefix commit and the reset of the searches in pieces;
+// horizon_point / horizon_target / descends_from are the commit horizon's rule and compact_stream the trie compaction.
 #pragma once
 #include "beam_trie.h"
 #include <algorithm>
@@ -175,6 +176,126 @@ __device__ __forceinline__ void commit_stream(const Trie& tr, int node, bool liv
   int target = 0;
   if (nb > 0) target = best >= 0 ? __shfl(node, best, 64) : beam_trie::common_ancestor(tr, node, live);
   beam_trie::commit_labels(tr, target, lane, committed, out, count, width, pad);
+}
+
+// ---- the commit horizon (tfasr_*_beam_commit_horizon) --------------------------------------------------------------------------------
+// Horizon state of one stream, int32 [horizon_stride(H)], owned by the caller and written by the horizon commit and the compaction
+// alone: HS_ABS the frames the stream has consumed since its reset (never rebased), HS_SEEN the stream's CNT_FRAMES when HS_ABS was
+// last brought up to date, then a ring of R = H + 1 prune points (frame count, trie node count), HS_HEAD the next slot, HS_FILL how
+// many hold a point.  A point is logged by every call that finds new frames, so the logged frame counts are distinct integers: at most
+// H of them lie in (now - H, now], the current one included, and the latest point at or before now - H is the one logged just before
+// those - among the last H + 1.
+enum { HS_ABS = 0, HS_SEEN = 1, HS_HEAD = 2, HS_FILL = 3, HS_RING = 4 };
+__device__ __forceinline__ int horizon_stride(int H) { return HS_RING + 2 * (H + 1); }
+
+// One wave.  Brings the state up to the stream's counters; when the stream has consumed frames since the last call this is a prune
+// point: it is logged, and the node count X logged at the latest point at least H frames back is returned (>= 1), -1 when there is
+// none or this is no prune point.  A node with id < X was in the trie H frames ago.
+__device__ __forceinline__ int horizon_point(int32_t* hs, int H, const int* cnt, int lane) {
+  int X = -1;
+  if (lane == 0) {
+    const int fr = cnt[CNT_FRAMES], d = fr - hs[HS_SEEN];
+    hs[HS_SEEN] = fr;
+    if (d > 0) {
+      const int R = H + 1, now = hs[HS_ABS] + d;
+      int head = min(max(hs[HS_HEAD], 0), R - 1);
+      const int fill = min(max(hs[HS_FILL], 0) + 1, R);
+      hs[HS_ABS] = now;
+      hs[HS_RING + 2 * head] = now; hs[HS_RING + 2 * head + 1] = cnt[CNT_NODES];
+      for (int i = 1; i < fill; ++i) {  // from the point before this one backwards
+        const int slot = (head - i + R) % R;
+        if (hs[HS_RING + 2 * slot] <= now - H) { X = max(hs[HS_RING + 2 * slot + 1], 1); break; }
+      }
+      hs[HS_HEAD] = (head + 1) % R;
+      hs[HS_FILL] = fill;
+    }
+  }
+  return __shfl(X, 0, 64);
+}
+// the deepest ancestor-or-self of `node` with id < X (X >= 1; ids grow from parent to child)
+__device__ __forceinline__ int horizon_target(const Trie& tr, int node, int X) {
+  while (node >= X) node = tr.parent[node];
+  return node;
+}
+__device__ __forceinline__ bool descends_from(const Trie& tr, int node, int anc) {
+  for (int d = tr.depth[node], da = tr.depth[anc]; d > da; --d) node = tr.parent[node];
+  return node == anc;
+}
+
+// ---- compaction of one stream's trie (tfasr_*_beam_compact), the whole workgroup, in place -------------------------------------------
+// New root = the ancestor of the live rows' common ancestor at depth min(*committed, its depth); kept = the nodes on the paths from the
+// root to the live rows' nodes, in their old order (ids stay creation ordered, parent < child), depths rebased, the root keeps its LABEL
+// (parent -1, depth 0).  The table doubles as scratch while it is empty of meaning: hv[i] = kept nodes below old id i (bit-inverted for
+// a dropped node), the keys' bytes stage the kept (parent, label, depth) triples (3 nk <= 4 nmax <= 2 hcap ints) - then the table is
+// rebuilt.  node_at(i) / set_node(i, n) read and write live row i's node; `hs` (may be NULL) is the stream's horizon state, whose logged
+// node counts are remapped; out3 = (dropped depth, nodes kept, new CNT_FRAMES = the deepest live row).
+template <class NodeAt, class SetNode>
+__device__ __forceinline__ void compact_stream(const Trie& tr, unsigned long long* hk, int* hv, unsigned hcap, int* cnt, int nb,
+                                               int32_t* committed, int32_t* hs, int H, int32_t* out3, int tid, NodeAt node_at,
+                                               SetNode set_node) {
+  __shared__ int sums[THREADS];
+  __shared__ int s_root, s_drop, s_maxdep;
+  const int n = cnt[CNT_NODES], frames_old = cnt[CNT_FRAMES], have = max(*committed, 0);
+  if (nb < 1) {  // (a stream always holds a row; nothing to anchor a root on otherwise)
+    if (tid == 0) { out3[0] = 0; out3[1] = n; out3[2] = frames_old; }
+    return;
+  }
+  const int my = tid < nb ? node_at(tid) : 0;
+  if (tid < 64) {
+    const bool live = tid < nb;
+    int md = live ? tr.depth[my] : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) md = max(md, __shfl_xor(md, o, 64));
+    int root = beam_trie::common_ancestor(tr, my, live);
+    if (tid == 0) {
+      const int rd = min(have, tr.depth[root]);
+      for (int d = tr.depth[root]; d > rd; --d) root = tr.parent[root];
+      s_root = root; s_drop = rd; s_maxdep = md;
+    }
+  }
+  for (int i = tid; i < n; i += THREADS) hv[i] = 0;
+  __syncthreads();
+  const int root = s_root, drop = s_drop;
+  if (tid < nb)  // mark the path up to the root, or up to a node another row has marked (that row goes on from there)
+    for (int x = my; x >= root && atomicExch(&hv[x], 1) == 0 && x != root;) x = tr.parent[x];  // (ids fall towards the root)
+  __syncthreads();
+  const int chunk = (n + THREADS - 1) / THREADS, lo = min(tid * chunk, n), hi = min(lo + chunk, n);
+  int c = 0;
+  for (int i = lo; i < hi; ++i) c += hv[i];
+  sums[tid] = c;
+  __syncthreads();
+  int base = 0, nk = 0;
+  for (int j = 0; j < THREADS; ++j) { if (j == tid) base = nk; nk += sums[j]; }
+  for (int i = lo; i < hi; ++i) { const int m = hv[i]; hv[i] = m ? base : ~base; base += m; }
+  __syncthreads();
+  int* stage = (int*)hk;
+  for (int i = tid; i < n; i += THREADS) {
+    const int j = hv[i];
+    if (j < 0) continue;
+    stage[3 * j] = i == root ? -1 : hv[tr.parent[i]];  // (the kept set is closed towards the root)
+    stage[3 * j + 1] = tr.label[i];
+    stage[3 * j + 2] = tr.depth[i] - drop;
+  }
+  const int mine = tid < nb ? hv[my] : 0;
+  if (hs)
+    for (int k = tid; k < H + 1; k += THREADS) {
+      const int v = hs[HS_RING + 2 * k + 1];
+      hs[HS_RING + 2 * k + 1] = v >= n ? nk : v < 0 ? 0 : hv[v] >= 0 ? hv[v] : ~hv[v];
+    }
+  __syncthreads();
+  for (int j = tid; j < nk; j += THREADS) { tr.parent[j] = stage[3 * j]; tr.label[j] = stage[3 * j + 1]; tr.depth[j] = stage[3 * j + 2]; }
+  __syncthreads();
+  for (unsigned i = tid; i < hcap; i += THREADS) hk[i] = beam_trie::EMPTY;
+  __syncthreads();
+  for (int j = 1 + tid; j < nk; j += THREADS) beam_trie::insert(hk, hv, hcap, tr.parent[j], tr.label[j], j);
+  if (tid < nb) set_node(tid, mine);
+  if (tid == 0) {
+    const int frames = s_maxdep - drop;
+    cnt[CNT_NODES] = nk; cnt[CNT_FRAMES] = frames;
+    if (hs) hs[HS_SEEN] = frames - (frames_old - hs[HS_SEEN]);  // frames no commit has seen yet stay unseen
+    *committed = have - drop;
+    out3[0] = drop; out3[1] = nk; out3[2] = frames;
+  }
 }
 
 }  // namespace beam_select

@@ -1,6 +1,7 @@
 // Label-sequence trie of the device beam searches (ctc_beam.hip, rnnt_beam.hip): one node per label sequence of an utterance
-// (node 0 = the empty sequence), found by an open-addressing (parent node, label) -> node table, and the sequence order of the
-// searches' exact-tie rule (lexicographic, a proper prefix first).  Written and read by one workgroup: plain (non-restrict)
+// (node 0 = the empty sequence; after a compaction, beam_select.h, the root of what is left, which keeps its label), found by an
+// open-addressing (parent node, label) -> node table, and the sequence order of the searches' exact-tie rule (lexicographic, a proper
+// prefix first).  Written and read by one workgroup: plain (non-restrict)
 // pointers, ordered by __syncthreads.
 #pragma once
 #include "common.h"

@@ -358,7 +358,8 @@ extern "C" int tfasr_ctc_beam_search_lm_host(const float* logits, const int32_t*
 //
 // The search in pieces (tfasr_ctc_beam_reset / _advance / _commit / _nbest, streaming sessions) is the same two kernels: the search
 // kernel loads its LDS beam from the workspace's carry area instead of starting from the empty prefix, runs the chunk's frames and
-// stores the beam back; the n-best of a carried beam is the same kernel over zero frames.
+// stores the beam back; the n-best of a carried beam is the same kernel over zero frames.  tfasr_ctc_beam_commit_horizon and
+// tfasr_ctc_beam_compact (commit horizon, trie compaction: DESIGN.md 4a) work on the carry area and the trie between two advances.
 // ================================================================================================================================
 namespace {
 
@@ -676,6 +677,18 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_reset_kernel(const int32_t* 
   }
 }
 
+// lane of the best live row in the n-best order (total desc, then the smaller label sequence); lane i holds the node of live row i
+__device__ __forceinline__ int ctc_best_lane(const Trie& tr, const CtcCarry& cy, long c0, int nb, int lane, int node, bool live) {
+  const float tq = live ? lae(cy.pb[c0 + lane], cy.pnb[c0 + lane]) : -INFINITY;
+  bool best = live;
+  for (int p = 0; p < nb && best; ++p) {
+    const float tp = lae(cy.pb[c0 + p], cy.pnb[c0 + p]);
+    if (tp > tq || (tp == tq && p != lane && seq_less(tr, Seq{cy.node[c0 + p], -1}, Seq{node, -1}))) best = false;
+  }
+  const unsigned long long m = __ballot(best);
+  return m ? __ffsll((long long)m) - 1 : 0;
+}
+
 // ---- tfasr_ctc_beam_commit: one wave per stream, a lane per live row; `fin` streams commit their best row (the n-best order) ----
 __global__ __launch_bounds__(64) void ctc_beam_commit_kernel(int* trie_parent, int* trie_label, int* trie_depth, CtcCarry cy,
                                                             const int32_t* __restrict__ fin, int32_t* __restrict__ committed,
@@ -688,17 +701,74 @@ __global__ __launch_bounds__(64) void ctc_beam_commit_kernel(int* trie_parent, i
   const long c0 = (long)b * W;
   const int node = live ? cy.node[c0 + lane] : 0;
   int best_lane = -1;
-  if (nb > 0 && fin && fin[b]) {
-    const float tq = live ? lae(cy.pb[c0 + lane], cy.pnb[c0 + lane]) : -INFINITY;
-    bool best = live;
-    for (int p = 0; p < nb && best; ++p) {
-      const float tp = lae(cy.pb[c0 + p], cy.pnb[c0 + p]);
-      if (tp > tq || (tp == tq && p != lane && seq_less(tr, Seq{cy.node[c0 + p], -1}, Seq{node, -1}))) best = false;
-    }
-    const unsigned long long m = __ballot(best);
-    best_lane = m ? __ffsll((long long)m) - 1 : 0;
-  }
+  if (nb > 0 && fin && fin[b]) best_lane = ctc_best_lane(tr, cy, c0, nb, lane, node, live);
   commit_stream(tr, node, live, nb, best_lane, lane, committed + b, tokens + (long)b * width, ntokens + b, width, 0);
+}
+
+// ---- tfasr_ctc_beam_commit_horizon: the same, and at a prune point (beam_select.h) the rows that do not descend from the best row's
+// deepest node older than the horizon leave the carried beam: the survivors move up in their order, the commit goes up to that node ----
+__global__ __launch_bounds__(64) void ctc_beam_commit_horizon_kernel(int* trie_parent, int* trie_label, int* trie_depth, CtcCarry cy,
+                                                                    const int32_t* __restrict__ fin, int32_t* __restrict__ committed,
+                                                                    int32_t* __restrict__ tokens, int32_t* __restrict__ ntokens,
+                                                                    int32_t* hstate, int H, int W, int width, long nmax) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int* cnt = cy.cnt + b * CNT_N;
+  const int nb = min(max(cnt[CNT_LIVE], 0), W);
+  const Trie tr = trie_at(trie_parent, trie_label, trie_depth, (long)b * nmax);
+  const bool live = lane < nb;
+  const long c0 = (long)b * W;
+  const int node = live ? cy.node[c0 + lane] : 0;
+  const int X = horizon_point(hstate + (long)b * horizon_stride(H), H, cnt, lane);
+  const bool final = fin && fin[b];
+  int best_lane = -1;
+  if (nb > 0 && (final || X >= 0)) best_lane = ctc_best_lane(tr, cy, c0, nb, lane, node, live);
+  if (nb > 0 && !final && X >= 0) {
+    int target = horizon_target(tr, __shfl(node, best_lane, 64), X);
+    const int ca = beam_trie::common_ancestor(tr, node, live);
+    if (tr.depth[target] > tr.depth[ca]) {
+      const bool keep = live && descends_from(tr, node, target);
+      const unsigned long long mask = __ballot(keep);
+      const int par = live ? cy.par[c0 + lane] : 0, lab = live ? cy.lab[c0 + lane] : 0, dep = live ? cy.dep[c0 + lane] : 0;
+      const float pb = live ? cy.pb[c0 + lane] : 0.f, pnb = live ? cy.pnb[c0 + lane] : 0.f;
+      __syncthreads();  // (one wave: every row is read before any is written)
+      if (keep) {
+        const long q = c0 + __popcll(mask & ((1ull << lane) - 1ull));
+        cy.node[q] = node; cy.par[q] = par; cy.lab[q] = lab; cy.dep[q] = dep; cy.pb[q] = pb; cy.pnb[q] = pnb;
+      }
+      if (lane == 0) cnt[CNT_LIVE] = __popcll(mask);
+    } else {
+      target = ca;
+    }
+    beam_trie::commit_labels(tr, target, lane, committed + b, tokens + (long)b * width, ntokens + b, width, 0);
+    return;
+  }
+  commit_stream(tr, node, live, nb, final ? best_lane : -1, lane, committed + b, tokens + (long)b * width, ntokens + b, width, 0);
+}
+
+// ---- tfasr_ctc_beam_compact: one workgroup per stream named by `mask`.  The search tells "this row has a last label" by par >= 0 and
+// finds a row's parent ROW by comparing par with the rows' nodes: a live row that is the new root keeps its last label, so its par is
+// CTC_ROOT_PAR, a value no node id takes (ids stay below nmax < 2^28), unless the root is still the empty sequence (label -1) ----
+constexpr int CTC_ROOT_PAR = 0x7fffffff;
+__global__ __launch_bounds__(THREADS) void ctc_beam_compact_kernel(const int32_t* __restrict__ mask, int* trie_parent, int* trie_label,
+                                                                   int* trie_depth, unsigned long long* hkeys, int* hvals, CtcCarry cy,
+                                                                   int32_t* __restrict__ committed, int32_t* hstate, int H,
+                                                                   int32_t* __restrict__ out, int W, long nmax, unsigned hcap) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int* cnt = cy.cnt + b * CNT_N;
+  if (!mask[b]) {
+    if (tid == 0) { out[3 * b] = 0; out[3 * b + 1] = cnt[CNT_NODES]; out[3 * b + 2] = cnt[CNT_FRAMES]; }
+    return;
+  }
+  const Trie tr = trie_at(trie_parent, trie_label, trie_depth, (long)b * nmax);
+  const long c0 = (long)b * W;
+  const int nb = min(max(cnt[CNT_LIVE], 0), W);
+  compact_stream(tr, hkeys + (long)b * hcap, hvals + (long)b * hcap, hcap, cnt, nb, committed + b,
+                 hstate ? hstate + (long)b * horizon_stride(H) : nullptr, H, out + 3 * b, tid,
+                 [&](int i) { return cy.node[c0 + i]; },
+                 [&](int i, int n) {
+                   cy.node[c0 + i] = n; cy.lab[c0 + i] = tr.label[n]; cy.dep[c0 + i] = tr.depth[n];
+                   cy.par[c0 + i] = n > 0 ? tr.parent[n] : tr.label[0] >= 0 ? CTC_ROOT_PAR : -1;
+                 });
 }
 
 struct BeamLayout : Geometry {
@@ -885,4 +955,34 @@ extern "C" int tfasr_ctc_beam_nbest(int B, int C, int Tcap, int V, int beam_widt
   // the search kernel over zero frames: load the beam, rank it, write the paths
   return beam_launch<float>(L, w, nullptr, nullptr, B, C, Tcap, V, beam_width, top_paths, 0, BEAM_LOAD | BEAM_OUTPUT, width, tokens, tokens_len,
                             log_prob, (hipStream_t)stream_);
+}
+
+// ---- the commit horizon and the compaction: the horizon state [B, 4 + 2 (horizon + 1)] int32 is the caller's ----
+extern "C" int tfasr_ctc_beam_commit_horizon(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens,
+                                             int32_t* horizon_state, int horizon, int B, int C, int Tcap, int V, int beam_width, int width,
+                                             void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!committed || !tokens || !ntokens || !horizon_state || !workspace || !stream_shape_ok(B, C, Tcap, V, beam_width) || width < 1 ||
+      horizon < 1 || horizon > TFASR_BEAM_MAX_HORIZON)
+    return TFASR_STATUS_INVALID_VALUE;
+  const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  const BeamWs w = beam_carve(L, workspace, B, beam_width);
+  TFASR_KLAUNCH(ctc_beam_commit_horizon_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream_, w.par, w.lab, w.dep, w.cy, final_mask, committed,
+                tokens, ntokens, horizon_state, horizon, beam_width, width, L.nmax);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_compact(const int32_t* mask, int32_t* committed, int32_t* horizon_state, int horizon, int32_t* out, int B, int C,
+                                      int Tcap, int V, int beam_width, void* workspace, size_t workspace_bytes, void* stream_) {
+  // horizon_state NULL (then horizon must be 0): a stream that never ran a horizon commit
+  if (!mask || !committed || !out || !workspace || !stream_shape_ok(B, C, Tcap, V, beam_width)) return TFASR_STATUS_INVALID_VALUE;
+  if (horizon_state ? (horizon < 1 || horizon > TFASR_BEAM_MAX_HORIZON) : horizon != 0) return TFASR_STATUS_INVALID_VALUE;
+  const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  const BeamWs w = beam_carve(L, workspace, B, beam_width);
+  TFASR_KLAUNCH(ctc_beam_compact_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream_, mask, w.par, w.lab, w.dep, w.hk, w.hv, w.cy, committed,
+                horizon_state, horizon, out, beam_width, L.nmax, L.hcap);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
 }

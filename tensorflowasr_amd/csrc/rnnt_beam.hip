@@ -18,7 +18,8 @@
 // The search in pieces (tfasr_rnnt_beam_reset / _advance / _commit / _nbest_states, streaming sessions): the workspace sized with
 // T = Tcap is the carried state of B streams, rb_frames is the one frame loop (the one-shot search = begin + rb_frames over all T
 // frames + n-best).  Between two advances a beam is what the select leaves - node, total, token, gathered pre-state - and the
-// advance starts with the prediction step, which rebuilds the rest with the same bits.
+// advance starts with the prediction step, which rebuilds the rest with the same bits.  tfasr_rnnt_beam_commit_horizon (which moves
+// exactly those four when it drops rows) and tfasr_rnnt_beam_compact are the commit horizon and the trie compaction of DESIGN.md 4a.
 // Arithmetic: products f32 on the f32 master weights; totals, merges (max + log1p(exp(-|a-b|))) and comparisons f64; scores f32.
 #include "beam_select.h"
 #include <string.h>
@@ -349,6 +350,73 @@ __global__ __launch_bounds__(64) void rb_commit_kernel(Ws s, const int32_t* __re
                 tokens + (long)b * width, ntokens + b, width, blank);
 }
 
+// ---- tfasr_rnnt_beam_commit_horizon: the same, and at a prune point (beam_select.h) the rows that do not descend from the deepest
+// node of row 0 (the best) older than the horizon leave the beam: the survivors move up in their order (node, total, token and the
+// gathered pre-state, all a beam holds between two advances), the freed rows become dead rows as the select leaves them ----
+__global__ __launch_bounds__(64) void rb_commit_horizon_kernel(Ws s, const int32_t* __restrict__ fin, int32_t* __restrict__ committed,
+                                                              int32_t* __restrict__ tokens, int32_t* __restrict__ ntokens, int32_t* hstate,
+                                                              int H, int W, int U, int width, int blank, long nmax) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int* cnt = s.cnt + b * CNT_N;
+  const int nb = min(max(cnt[CNT_LIVE], 0), W);
+  const bool live = lane < nb;
+  const long r0 = (long)b * W;
+  const int node = live ? s.node[r0 + lane] : 0;
+  const Trie tr = trie_at(s.par, s.lab, s.dep, (long)b * nmax);
+  const int X = horizon_point(hstate + (long)b * horizon_stride(H), H, cnt, lane);
+  const bool final = fin && fin[b];
+  if (nb > 0 && !final && X >= 0) {
+    int target = horizon_target(tr, __shfl(node, 0, 64), X);
+    const int ca = beam_trie::common_ancestor(tr, node, live);
+    if (tr.depth[target] > tr.depth[ca]) {
+      const bool keep = live && descends_from(tr, node, target);
+      const unsigned long long mask = __ballot(keep);
+      const int nk = __popcll(mask);
+      const double tot = live ? s.tot[r0 + lane] : 0.0;
+      const int tok = live ? s.tok[r0 + lane] : 0;
+      __syncthreads();  // (one wave: every row is read before any is written)
+      if (keep) {
+        const long q = r0 + __popcll(mask & ((1ull << lane) - 1ull));
+        s.node[q] = node; s.tot[q] = tot; s.tok[q] = tok;
+      }
+      if (lane >= nk && lane < W) { s.node[r0 + lane] = 0; s.tot[r0 + lane] = -INFINITY; }
+      // pre-states: destination q <= source, in rising order, every lane its own columns: a source row is read before it is overwritten
+      unsigned long long rest = mask;
+      for (int q = 0; q < nk; ++q) {
+        const int src = __ffsll((long long)rest) - 1;
+        rest &= rest - 1;
+        if (src == q) continue;
+        for (int u = lane; u < U; u += 64) {
+          s.hnx[(r0 + q) * U + u] = s.hnx[(r0 + src) * U + u];
+          s.cnx[(r0 + q) * U + u] = s.cnx[(r0 + src) * U + u];
+        }
+      }
+      if (lane == 0) cnt[CNT_LIVE] = nk;
+    } else {
+      target = ca;
+    }
+    beam_trie::commit_labels(tr, target, lane, committed + b, tokens + (long)b * width, ntokens + b, width, blank);
+    return;
+  }
+  commit_stream(tr, node, live, nb, final ? 0 : -1, lane, committed + b, tokens + (long)b * width, ntokens + b, width, blank);
+}
+
+// ---- tfasr_rnnt_beam_compact: one workgroup per stream named by `mask` (a row's last token travels in s.tok, not in the trie) ----
+__global__ __launch_bounds__(THREADS) void rb_compact_kernel(Ws s, const int32_t* __restrict__ mask, int32_t* __restrict__ committed,
+                                                            int32_t* hstate, int H, int32_t* __restrict__ out, int W, long nmax,
+                                                            unsigned hcap) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int* cnt = s.cnt + b * CNT_N;
+  if (!mask[b]) {
+    if (tid == 0) { out[3 * b] = 0; out[3 * b + 1] = cnt[CNT_NODES]; out[3 * b + 2] = cnt[CNT_FRAMES]; }
+    return;
+  }
+  const long r0 = (long)b * W;
+  compact_stream(trie_at(s.par, s.lab, s.dep, (long)b * nmax), s.hk + (long)b * hcap, s.hv + (long)b * hcap, hcap, cnt,
+                 min(max(cnt[CNT_LIVE], 0), W), committed + b, hstate ? hstate + (long)b * horizon_stride(H) : nullptr, H, out + 3 * b, tid,
+                 [&](int i) { return s.node[r0 + i]; }, [&](int i, int n) { s.node[r0 + i] = n; });
+}
+
 int rb_gemm(const float* A, const float* Bm, const float* bias, float* D, int M, int N, int Kd, hipStream_t st) {
   tfasr_gemm_args ga;
   memset(&ga, 0, sizeof(ga));
@@ -541,4 +609,33 @@ extern "C" int tfasr_rnnt_beam_nbest_states(int B, int Tcap, int U, int J, int V
   if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
   return rb_nbest(L, rb_carve(L, workspace, B), B, width, U, beam_width, top_paths, blank, tokens, tokens_len, score, next_tok, next_h, next_c,
                   (hipStream_t)stream);
+}
+
+// ---- the commit horizon and the compaction: the horizon state [B, 4 + 2 (horizon + 1)] int32 is the caller's ----
+extern "C" int tfasr_rnnt_beam_commit_horizon(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens,
+                                              int32_t* horizon_state, int horizon, int B, int Tcap, int U, int J, int V, int beam_width,
+                                              int width, int blank, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!committed || !tokens || !ntokens || !horizon_state || !workspace || !rb_shape_ok(B, Tcap, U, J, V, beam_width) || width < 1 ||
+      blank < 0 || blank >= V || horizon < 1 || horizon > TFASR_BEAM_MAX_HORIZON)
+    return TFASR_STATUS_INVALID_VALUE;
+  const RbLayout L = rb_layout(B, Tcap, U, J, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t st = (hipStream_t)stream;
+  TFASR_KLAUNCH(rb_commit_horizon_kernel, dim3(B), dim3(64), 0, st, rb_carve(L, workspace, B), final_mask, committed, tokens, ntokens,
+                horizon_state, horizon, beam_width, U, width, blank, L.nmax);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_rnnt_beam_compact(const int32_t* mask, int32_t* committed, int32_t* horizon_state, int horizon, int32_t* out, int B,
+                                       int Tcap, int U, int J, int V, int beam_width, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!mask || !committed || !out || !workspace || !rb_shape_ok(B, Tcap, U, J, V, beam_width)) return TFASR_STATUS_INVALID_VALUE;
+  if (horizon_state ? (horizon < 1 || horizon > TFASR_BEAM_MAX_HORIZON) : horizon != 0) return TFASR_STATUS_INVALID_VALUE;
+  const RbLayout L = rb_layout(B, Tcap, U, J, V, beam_width);
+  if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t st = (hipStream_t)stream;
+  TFASR_KLAUNCH(rb_compact_kernel, dim3(B), dim3(THREADS), 0, st, rb_carve(L, workspace, B), mask, committed, horizon_state, horizon, out,
+                beam_width, L.nmax, L.hcap);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
 }

@@ -1451,6 +1451,9 @@ def rnnt_beam_nbest(seam, top_paths=None):
     return seam.nbest(top_paths)
 
 
+MAX_HORIZON = 4096  # TFASR_BEAM_MAX_HORIZON
+
+
 def _row_mask(rows, B, dev):
     """rows (None = all) -> [B] int32 device mask, or None"""
     if rows is None:
@@ -1466,14 +1469,21 @@ def _row_mask(rows, B, dev):
 
 class _BeamStream:
     """What RnntBeamStream and CtcBeamStream share: the host's frame counts (the capacity check needs no device round trip), the
-    committed depths and the commit call."""
+    committed depths, the commit calls and the compaction.
+
+    commit(horizon=H) prunes as well as commits (tfasr_*_beam_commit_horizon); its per-stream horizon state is made at the
+    first such call, and one object keeps one H.  compact() sheds the trie above and beside the live rows; after it `frames` counts the
+    frames a stream's trie still answers for (the depth of its deepest live row), nbest() returns the label sequences below the new
+    root, and dropped[b] holds the labels in front of them."""
 
     def _init_common(self, B, Tcap, V, beam_width, device):
         self.B, self.Tcap, self.V = int(B), int(Tcap), int(V)
         if self.B < 1 or self.Tcap < 1:
             raise ValueError(f"{self.what}: B {self.B} and Tcap {self.Tcap} must be >= 1")
-        self.frames = [0] * self.B  # frames consumed per stream since its reset
+        self.frames = [0] * self.B  # frames per stream since its reset (or, after a compaction, the depth of its deepest live row)
         self.committed = torch.zeros(self.B, dtype=torch.int32, device=device)
+        self.horizon, self.hstate = None, None  # commit(horizon=H): H, and the [B, 4 + 2 (H + 1)] int32 state the kernels keep
+        self.dropped = [[] for _ in range(self.B)]  # the labels compact() has taken out of each stream's trie
 
     def _take(self, nvalid, C):
         """check a chunk's nvalid (host values) against C and the capacity BEFORE anything is queued -> (list, frames_max_after)"""
@@ -1489,25 +1499,64 @@ class _BeamStream:
     def _reset_host(self, rows):
         for b in (range(self.B) if rows is None else rows):
             self.frames[int(b)] = 0
+            self.dropped[int(b)] = []
         if rows is None:
             self.committed.zero_()
+            if self.hstate is not None:
+                self.hstate.zero_()
         elif len(rows):
-            self.committed[torch.as_tensor([int(b) for b in rows], dtype=torch.long, device=self.committed.device)] = 0
+            r = torch.as_tensor([int(b) for b in rows], dtype=torch.long, device=self.committed.device)
+            self.committed[r] = 0
+            if self.hstate is not None:
+                self.hstate[r] = 0
 
     def _width(self):
         return max(max(self.frames), 1)  # a hypothesis is never longer than the frames consumed
 
-    def commit(self, final_rows=()):
+    def commit(self, final_rows=(), horizon=None):
         """-> (tokens [B, width] padded with the search's pad value (transducer: blank, CTC: 0), ntokens [B]) device tensors: the
         labels new in the streams' stable prefixes (the part every live hypothesis shares); the streams in final_rows commit their
-        whole best hypothesis"""
+        whole best hypothesis.  horizon=H (encoder frames, >= 1): a stream that has consumed frames since the previous call also drops
+        the rows that disagree with what its best row held H frames ago, and commits up to there."""
         dev, width = self.ws.device, self._width()
         final_rows = list(final_rows)
+        if horizon is not None:
+            self._horizon_state(horizon)
         fin = _row_mask(final_rows, self.B, dev) if final_rows else None
         tokens = torch.empty(self.B, width, dtype=torch.int32, device=dev)
         n = torch.empty(self.B, dtype=torch.int32, device=dev)
-        self._commit(_p(fin), _p(tokens), _p(n), width)
+        if horizon is None:
+            self._commit(_p(fin), _p(tokens), _p(n), width)
+        else:
+            self._commit_horizon(_p(fin), _p(tokens), _p(n), width)
         return tokens, n
+
+    def _horizon_state(self, horizon):
+        horizon = int(horizon)
+        if not 1 <= horizon <= MAX_HORIZON:
+            raise ValueError(f"{self.what}: horizon {horizon} outside [1, {MAX_HORIZON}] encoder frames")
+        if self.horizon is None:
+            self.horizon = horizon
+            self.hstate = torch.zeros(self.B, 4 + 2 * (horizon + 1), dtype=torch.int32, device=self.ws.device)
+        elif horizon != self.horizon:
+            raise ValueError(f"{self.what}: this stream object runs horizon {self.horizon}, not {horizon} (its prune-point ring has that size)")
+
+    def compact(self, rows=None):
+        """Shed the trie nodes above and beside the live rows of the given streams (default: all), in place -> per stream the list
+        [labels dropped from the front, trie nodes kept, frames]: `frames` (also self.frames[b]) is the depth of the deepest live row,
+        what the capacity check counts from now on.  The dropped labels are committed ones and go to self.dropped[b].  One
+        device-to-host read."""
+        dev = self.ws.device
+        mask = _row_mask(range(self.B) if rows is None else list(rows), self.B, dev)
+        head = self.nbest(1)[0][:, 0, :]  # the labels in front of the new root are the first ones of every live row
+        out = torch.empty(self.B, 3, dtype=torch.int32, device=dev)
+        self._compact(_p(mask), _p(self.hstate), self.horizon or 0, _p(out))
+        host = torch.cat([out, head], 1).cpu()
+        res = host[:, :3].tolist()
+        for b, (drop, _, frames) in enumerate(res):
+            self.dropped[b] += host[b, 3:3 + drop].tolist()
+            self.frames[b] = frames
+        return res
 
 
 class RnntBeamStream(_BeamStream):
@@ -1554,6 +1603,14 @@ class RnntBeamStream(_BeamStream):
     def _commit(self, fin, tokens, n, width):
         check(_L().tfasr_rnnt_beam_commit(fin, _p(self.committed), tokens, n, *self._dims(), width, self.blank, _p(self.ws),
                                           self.ws.numel(), _stream()), "rnnt_beam_commit")
+
+    def _commit_horizon(self, fin, tokens, n, width):
+        check(_L().tfasr_rnnt_beam_commit_horizon(fin, _p(self.committed), tokens, n, _p(self.hstate), self.horizon, *self._dims(), width,
+                                                  self.blank, _p(self.ws), self.ws.numel(), _stream()), "rnnt_beam_commit_horizon")
+
+    def _compact(self, mask, hstate, horizon, out):
+        check(_L().tfasr_rnnt_beam_compact(mask, _p(self.committed), hstate, horizon, out, *self._dims(), _p(self.ws), self.ws.numel(),
+                                           _stream()), "rnnt_beam_compact")
 
     def nbest(self, top_paths=None):
         """the current beams as rnnt_beam_search returns them: (tokens [B, NP, L], lengths, scores, next_tok, next_h, next_c), L = the
@@ -1612,6 +1669,14 @@ class CtcBeamStream(_BeamStream):
     def _commit(self, fin, tokens, n, width):
         check(_L().tfasr_ctc_beam_commit(fin, _p(self.committed), tokens, n, *self._dims(), width, _p(self.ws), self.ws.numel(),
                                          _stream()), "ctc_beam_commit")
+
+    def _commit_horizon(self, fin, tokens, n, width):
+        check(_L().tfasr_ctc_beam_commit_horizon(fin, _p(self.committed), tokens, n, _p(self.hstate), self.horizon, *self._dims(), width,
+                                                 _p(self.ws), self.ws.numel(), _stream()), "ctc_beam_commit_horizon")
+
+    def _compact(self, mask, hstate, horizon, out):
+        check(_L().tfasr_ctc_beam_compact(mask, _p(self.committed), hstate, horizon, out, *self._dims(), _p(self.ws), self.ws.numel(),
+                                          _stream()), "ctc_beam_compact")
 
     def nbest(self, top_paths=None):
         """the current beams as ctc_beam_search_device returns them: (tokens [B, P, L] 0 padded, lengths [B, P], log_prob [B, P])"""

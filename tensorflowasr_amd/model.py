@@ -396,6 +396,13 @@ class AsrModel(BaseModel):
         DESIGN.md 4b-3).  One method for every streamable class: their stream() signatures differ and stay as they are."""
         return self.stream(*args, **kwargs).detailed()
 
+    def stream_horizon(self, commit_horizon, *args, **kwargs):
+        """stream(...) of this class with the same arguments (beam_width >= 1 among them), opened with a commit horizon of
+        `commit_horizon` encoder frames: an endless beam session whose committed text trails the audio by about the horizon, at the
+        price of a pruning rule (streaming.StreamingRecognizer).  One method for every streamable class, as
+        stream_detailed: their stream() signatures differ and stay as they are."""
+        return self.stream(*args, **kwargs).with_commit_horizon(commit_horizon)
+
     # ----------------------------------------------------------------- timing hooks (bench.py)
     def _tick(self, name):
         if self.timers is None:

@@ -712,6 +712,18 @@ def check_stream_args(batch_size=1, max_tokens_per_frame=3, beam_width=0, max_fr
     return batch_size, max_tokens_per_frame, beam_width, max_frames
 
 
+def check_commit_horizon(commit_horizon, beam_width):
+    """commit_horizon (None = no horizon) against the session's beam_width -> None or the horizon in encoder frames"""
+    if commit_horizon is None:
+        return None
+    if int(beam_width) < 1:
+        raise ValueError("stream: commit_horizon belongs to a beam session (beam_width >= 1): the greedy searches commit every token at once")
+    h = int(commit_horizon)
+    if not 1 <= h <= K.MAX_HORIZON:
+        raise ValueError(f"stream: commit_horizon {h} outside [1, {K.MAX_HORIZON}] encoder frames")
+    return h
+
+
 class _TokenRecord:
     """The tokens of one stream of a detail session since its reset, on the host: class, frame (CTC: the first frame of the run), end (CTC:
     one past the run's last frame, -1 while the run is open; transducer: frame + 1), log-probability, entropy."""
@@ -747,6 +759,20 @@ class StreamingRecognizer:
     beam emits one symbol per frame at most, a beam_width=1 session equals the greedy session made with max_tokens_per_frame=1, not the
     default greedy session.  The CTC head's beam session treats class V-1 as blank, as recognize_beam does.
     max_frames bounds the encoder frames of one stream between resets (a chunk past it raises RuntimeError; reset() frees the slot).
+
+    commit_horizon = H (beam sessions) makes the session endless and its committed text prompt, at a price in accuracy: a
+    label that the best hypothesis has held for H encoder frames is final, and the hypotheses that disagree with it leave the beam.  It
+    is a pruning rule: the result can differ from the offline search's.  The commit then runs after EVERY chunk (the prune points are the
+    chunk boundaries, which the config fixes: the tokens do not depend on how the samples arrive), a call returns its chunks' commits
+    in a row, and max_frames bounds only the UNCOMMITTED part of a stream: before a chunk that would take a stream's trie past it the
+    session compacts that stream (K.*BeamStream.compact: everything above and beside the live hypotheses goes; compact() does it on
+    demand), keeps the dropped labels on the host, and goes on.  Only when the stream still does not fit - its uncommitted part alone is
+    too long - the chunk raises RuntimeError, naming the stream and the lengths.  That is decided chunk by chunk, not before the call as
+    without a horizon: the chunks before the refused one have been consumed and searched, their commits are in committed_tokens and in
+    hypotheses(); the refused chunk's samples and all later ones stay buffered (for an RNN-Transducer encoder, whose frames per step
+    depend on carried rows, a refusal can also come after the step's encoder pass, which has then consumed its samples); reset(rows=[b])
+    frees the slot.  hypotheses() returns full hypotheses (committed prefix + what the trie holds), StreamOutput.frames counts from the
+    stream's reset.  Open it with model.stream_horizon(H, ...) (then stream()'s arguments), or with commit_horizon=H here.
     Beam memory per stream, with W = beam_width, N = 1 + W * max_frames trie nodes and H = the power of two >= 2 N table slots:
         transducer  12 N + 12 H + W * (4 V + 44 U + 8 J + 12 min(2 W, V - 1) + 28) bytes   (U = rnn_units, J = joint_dim)
         CTC         12 N + 12 H + 24 W + 8 chunk_size * (1 + min(2 W, V - 1)) bytes
@@ -775,9 +801,10 @@ class StreamingRecognizer:
     open run with the final flag."""
 
     def __init__(self, model, batch_size=1, precision=None, max_tokens_per_frame=3, beam_width=0, max_frames=3000, chunk_frames=None,
-                 detail=False):
+                 commit_horizon=None, detail=False):
         batch_size, max_tokens_per_frame, self.beam_width, self.max_frames = check_stream_args(batch_size, max_tokens_per_frame, beam_width,
                                                                                              max_frames)
+        self.commit_horizon = check_commit_horizon(commit_horizon, self.beam_width)
         self.detail = self._check_detail(detail)
         self.model = model
         self.enc_model = _twin(model, precision)
@@ -808,6 +835,7 @@ class StreamingRecognizer:
             self.finished = [False] * B
             self.flushed = [False] * B  # (state.uses_final) the encoder's carried rows went out with a final step
             self.beam = None
+            self.committed_tokens = [[] for _ in range(B)]  # (horizon sessions) everything a stream has committed since its reset
             if self.detail:  # the record of every stream since its reset: what recognized() returns
                 self.record = [_TokenRecord() for _ in range(B)]
             if self.beam_width:
@@ -829,6 +857,7 @@ class StreamingRecognizer:
             self.prev[b], self.has_prev[b] = 0.0, 0
             self.total[b] = self.emitted[b] = self.frames[b] = 0
             self.finished[b] = self.flushed[b] = False
+            self.committed_tokens[b] = []
         r = torch.as_tensor(rows, dtype=torch.long, device=dev)
         if self.detail:
             for b in rows:
@@ -898,6 +927,8 @@ class StreamingRecognizer:
                                         em._h2d(self.has_prev.copy()), self.chunk_frames, window, melw, band, c.frame_step, c.nfft, c.preemphasis,
                                         c.epsilon, torch.float32 if st.f32_features else em.dtype)
                 feats = st.prepare(feats)
+            if self.commit_horizon:
+                self._make_room([self._reduce(t) if t else 0 for t in take])  # before anything of the chunk is consumed
             for b in range(B):
                 if take[b]:
                     used = take[b] * self.step
@@ -912,17 +943,22 @@ class StreamingRecognizer:
                 self.encoded_log.append((enc, nv))
             self.chunks_run += 1
             if self.beam is not None:
+                if self.commit_horizon:
+                    self._make_room(nv)  # (exact now; differs from the estimate only for encoders with carried rows)
                 self._advance_beam(enc, nv)
+                if self.commit_horizon:
+                    self._take_commit(new, self.beam.commit(horizon=self.commit_horizon))
             else:
                 toks = self._search_ctc(enc, nvalid) if self.ctc else self._search(enc, nvalid, nv)
             for b in range(B):
                 self.frames[b] += nv[b]
                 if self.beam is None:
                     new[b].extend(toks[b])
-        if self.beam is not None:  # one commit per call: the labels that became stable, and the rest of the best row for flushed streams
-            ct, cn = self.beam.commit(final_rows=sorted(flush_rows))
-            th, tl = ct.cpu(), cn.cpu()
-            new = [th[b, :int(tl[b])].tolist() for b in range(B)]
+        if self.commit_horizon:  # every chunk has committed; the flushed streams commit the rest of their best row
+            if flush_rows:
+                self._take_commit(new, self.beam.commit(final_rows=sorted(flush_rows), horizon=self.commit_horizon))
+        elif self.beam is not None:  # one commit per call: the labels that became stable, and the rest of the best row for flushed streams
+            self._take_commit(new, self.beam.commit(final_rows=sorted(flush_rows)))
         if self.detail and self.ctc:
             closing = [b for b in flush_rows if not self.finished[b] and self.record[b].open]
             if closing:  # the utterance is over: close the run that reached its last frame (a call without frames, the final flag alone)
@@ -954,10 +990,49 @@ class StreamingRecognizer:
                    ps.p("joint/pred/b"), ps.p2d("joint/vocab/w"), ps.p("joint/vocab/b"))
         return K.RnntBeamStream(weights, self.B, self.max_frames, self.beam_width, blank=m.blank)
 
+    def _take_commit(self, new, commit):
+        """a commit's (tokens, counts) -> appended to the call's tokens and to the streams' committed tokens"""
+        th, tl = commit[0].cpu(), commit[1].cpu()
+        for b in range(self.B):
+            t = th[b, :int(tl[b])].tolist()
+            new[b] += t
+            self.committed_tokens[b] += t
+
+    def _make_room(self, need):
+        """(horizon sessions) need[b] more frames for stream b's trie: compact the streams they would take past max_frames; refuse when
+        one still does not fit"""
+        over = [b for b in range(self.B) if self.beam.frames[b] + need[b] > self.max_frames]
+        if not over:
+            return
+        self.beam.compact(over)
+        for b in over:
+            if self.beam.frames[b] + need[b] > self.max_frames:
+                raise RuntimeError(f"stream {b}: its uncommitted hypotheses alone are {self.beam.frames[b]} labels deep after {self.frames[b]} "
+                                   f"frames ({len(self.beam.dropped[b])} labels committed and dropped) and the next chunk adds {need[b]} frames, past "
+                                   f"max_frames = {self.max_frames}: reset it, or open the session with a larger max_frames or a shorter "
+                                   "commit_horizon")
+
+    def compact(self, rows=None):
+        """Compact the beam tries of the given streams (default: all) now -> per stream [labels dropped, trie nodes kept, trie frames]
+        (K.*BeamStream.compact).  A horizon session does it by itself when a stream reaches max_frames."""
+        if self.beam is None:
+            raise ValueError("compact() needs a beam session: open it with model.stream(beam_width >= 1)")
+        return self.beam.compact(rows)
+
+    def with_commit_horizon(self, commit_horizon):
+        """This session, which has taken no audio yet, as a horizon session (what model.stream_horizon returns) -> self."""
+        if any(self.total) or self.chunks_run:
+            raise RuntimeError("stream: with_commit_horizon() comes before the first accept()")
+        if self.detail:
+            raise ValueError("stream: commit_horizon belongs to a beam session; detail sessions are greedy")
+        self.commit_horizon = check_commit_horizon(commit_horizon, self.beam_width)
+        return self
+
     def _check_capacity(self, flush_rows=(), more=None):
         """refuse a call (more[b] further samples, or the flush of some streams) whose chunks would take a stream past max_frames, before
-        anything of it is buffered or queued: the session stays as it was"""
-        if self.beam is None:
+        anything of it is buffered or queued: the session stays as it was.  (A horizon session compacts as it goes and decides chunk by
+        chunk: _make_room.)"""
+        if self.beam is None or self.commit_horizon:
             return
         for b in range(self.B):
             n, emitted, frames = len(self.buf[b]) + (more[b] if more else 0), self.emitted[b], self.frames[b]
@@ -991,7 +1066,23 @@ class StreamingRecognizer:
         finish, until reset."""
         if self.beam is None:
             raise ValueError("hypotheses() needs a beam session: open it with model.stream(beam_width >= 1)")
-        return tuple(self.beam.nbest(top_paths)[:3])
+        toks, lens, scores = self.beam.nbest(top_paths)[:3]
+        dropped = self.beam.dropped
+        if not any(dropped):
+            return toks, lens, scores
+        # compacted streams: the labels their tries dropped go back in front of every live row
+        th, lh, live = toks.cpu(), lens.cpu(), (scores != -float("inf")).cpu()
+        P = th.shape[1]
+        full = torch.full((self.B, P, max(max(self.frames), 1)), 0 if self.ctc else self.model.blank, dtype=torch.int32)
+        for b in range(self.B):
+            d = torch.tensor(dropped[b], dtype=torch.int32)
+            for p in range(P):
+                if live[b, p]:
+                    n = int(lh[b, p])
+                    full[b, p, :len(d)] = d
+                    full[b, p, len(d):len(d) + n] = th[b, p, :n]
+                    lh[b, p] = len(d) + n
+        return full.to(toks.device), lh.to(lens.device), scores
 
     def _enc32(self, enc):
         B, C, d = enc.shape
@@ -1134,6 +1225,8 @@ class StreamingRecognizer:
 
     # ------------------------------------------------------------------------------------------- detail sessions
     def _check_detail(self, detail):
+        if detail and getattr(self, "commit_horizon", None):
+            raise ValueError("stream: a detail session is greedy and takes no commit_horizon")
         if detail and self.beam_width:
             raise ValueError("stream: detail=True belongs to the greedy session (beam_width=0): beam sessions keep their outputs, their "
                              "searches record no token times or confidences")
