@@ -902,6 +902,53 @@ int tfasr_ctc_beam_search_lm(const void* logits, const int32_t* logit_len, int B
                              int blank_index, int dtype, const tfasr_ngram_lm_t* lm, int32_t* tokens, int32_t* tokens_len, float* score,
                              float* log_prob, float* lm_score, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The fused search in pieces (declarations added under ABI 44, nothing existing changes; DESIGN.md 4b-4 "in streaming sessions"):
+ * tfasr_ctc_beam_reset / _advance / _commit / _commit_horizon / _compact / _nbest one for one, with the n-gram LM of
+ * tfasr_ctc_beam_search_lm.  The contracts of the plain entries hold word for word: all pointers are device pointers (`lm` is a host
+ * struct of device arrays), nothing synchronises with the host, every argument is checked on the host before any launch, a stream with
+ * nvalid[b] == 0 keeps every bit of its state, frames_max_after > Tcap is INVALID_VALUE.  1 <= beam_width <= TFASR_CTC_LM_MAX_BEAM, a
+ * larger width is TFASR_STATUS_UNSUPPORTED; a table struct that fails the checks of tfasr_ctc_beam_search_lm is INVALID_VALUE.
+ *
+ * The caller passes THE SAME tables to every call of a session: the carried LM states are node ids of those tables, and the carried
+ * lm sums were taken from their weights.
+ *
+ * Workspace = the layout of tfasr_ctc_beam_stream_workspace_size, then two arrays [B, 1 + beam_width * Tcap]: per trie node lm of its
+ * label sequence (float, the absolute sum from `start`) and the LM state after it (int32), written when the node is created.  A beam
+ * row has no LM values of its own: when an advance loads the beam, a row's lm and state are read from its node's entries - the values
+ * the one-shot search holds for that row.  _reset writes lm 0 and state `start` for the root.
+ *
+ * After any sequence of _lm_advance calls (any chunk sizes, any nvalid pattern, whatever the other streams do) stream b holds the beam
+ * tfasr_ctc_beam_search_lm holds after the same frames, and _lm_nbest with final_mask[b] != 0 returns that search's tokens, tokens_len,
+ * score, log_prob and lm_score bit for bit.
+ *
+ * final_mask (_lm_nbest, _lm_commit, _lm_commit_horizon; NULL: no stream): a stream in the mask has ended, its rows rank by
+ * float(acoustic total + (lm + end-of-sentence term)), the one-shot search's final order, and lm_score includes the term.  A stream
+ * not in the mask is still running: its rows rank by float(acoustic total + lm), the key they were selected by, and lm_score = lm.
+ * Exact ties go to the smaller label sequence.  "The best live row" of _commit and _commit_horizon is the best row in THIS order
+ * (a final stream commits it whole; at a prune point the horizon's target is taken on the running-order best row's path), not the
+ * acoustically best one; everything else in them is the plain rule.
+ *
+ * _lm_compact is tfasr_ctc_beam_compact with the two per-node arrays moved along with the kept nodes.  The lm values stay absolute
+ * sums from `start` (nothing is rebased, so the bits stay those of the one-shot search); in an endless session they grow without
+ * bound in magnitude, as the acoustic totals do. */
+int tfasr_ctc_beam_lm_stream_workspace_size(int B, int C, int Tcap, int V, int beam_width, size_t* bytes);
+int tfasr_ctc_beam_lm_reset(const int32_t* mask, int B, int C, int Tcap, int V, int beam_width, const tfasr_ngram_lm_t* lm, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int tfasr_ctc_beam_lm_advance(const void* logits, const int32_t* nvalid, int B, int C, int Cn, int Tcap, int V, int beam_width,
+                              int blank_index, int dtype, int frames_max_after, const tfasr_ngram_lm_t* lm, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int tfasr_ctc_beam_lm_commit(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens, int B, int C, int Tcap,
+                             int V, int beam_width, int width, const tfasr_ngram_lm_t* lm, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int tfasr_ctc_beam_lm_commit_horizon(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens,
+                                     int32_t* horizon_state, int horizon, int B, int C, int Tcap, int V, int beam_width, int width,
+                                     const tfasr_ngram_lm_t* lm, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_ctc_beam_lm_compact(const int32_t* mask, int32_t* committed, int32_t* horizon_state, int horizon, int32_t* out, int B, int C,
+                              int Tcap, int V, int beam_width, void* workspace, size_t workspace_bytes, void* stream);
+int tfasr_ctc_beam_lm_nbest(const int32_t* final_mask, int B, int C, int Tcap, int V, int beam_width, int top_paths, int width,
+                            int32_t* tokens, int32_t* tokens_len, float* score, float* log_prob, float* lm_score,
+                            const tfasr_ngram_lm_t* lm, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Forced alignment on the device (ABI 44 addition; csrc/align.hip): the best single path through the lattice the loss sums over,
  * and when it emits each label.  All pointers are device pointers, label_len / logit_len [B] int32 are clamped to the padded
  * sizes, nothing synchronises with the host, and every argument is checked on the host before any launch.

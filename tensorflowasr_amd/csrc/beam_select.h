@@ -229,10 +229,14 @@ __device__ __forceinline__ bool descends_from(const Trie& tr, int node, int anc)
 // a dropped node), the keys' bytes stage the kept (parent, label, depth) triples (3 nk <= 4 nmax <= 2 hcap ints) - then the table is
 // rebuilt.  node_at(i) / set_node(i, n) read and write live row i's node; `hs` (may be NULL) is the stream's horizon state, whose logged
 // node counts are remapped; out3 = (dropped depth, nodes kept, new CNT_FRAMES = the deepest live row).
-template <class NodeAt, class SetNode>
+// `payload` is what a search keeps per node beside the trie's three arrays (default: nothing): Payload::WORDS <= 3 ints per node,
+// get(old id, dst) / put(new id, src).  It moves in a pass of its own, staged in the same key bytes once the triples are back in the
+// trie (WORDS nk <= 3 nk ints) and before the table is rebuilt, while hv still maps old ids to new ones.
+struct NoPayload { static constexpr int WORDS = 0; };
+template <class NodeAt, class SetNode, class Payload = NoPayload>
 __device__ __forceinline__ void compact_stream(const Trie& tr, unsigned long long* hk, int* hv, unsigned hcap, int* cnt, int nb,
                                                int32_t* committed, int32_t* hs, int H, int32_t* out3, int tid, NodeAt node_at,
-                                               SetNode set_node) {
+                                               SetNode set_node, Payload payload = Payload{}) {
   __shared__ int sums[THREADS];
   __shared__ int s_root, s_drop, s_maxdep;
   const int n = cnt[CNT_NODES], frames_old = cnt[CNT_FRAMES], have = max(*committed, 0);
@@ -285,6 +289,14 @@ __device__ __forceinline__ void compact_stream(const Trie& tr, unsigned long lon
   __syncthreads();
   for (int j = tid; j < nk; j += THREADS) { tr.parent[j] = stage[3 * j]; tr.label[j] = stage[3 * j + 1]; tr.depth[j] = stage[3 * j + 2]; }
   __syncthreads();
+  if constexpr (Payload::WORDS > 0) {
+    static_assert(Payload::WORDS <= 3, "the staging space holds 3 ints per kept node");
+    for (int i = tid; i < n; i += THREADS)
+      if (hv[i] >= 0) payload.get(i, stage + Payload::WORDS * hv[i]);
+    __syncthreads();
+    for (int j = tid; j < nk; j += THREADS) payload.put(j, stage + Payload::WORDS * j);
+    __syncthreads();
+  }
   for (unsigned i = tid; i < hcap; i += THREADS) hk[i] = beam_trie::EMPTY;
   __syncthreads();
   for (int j = 1 + tid; j < nk; j += THREADS) beam_trie::insert(hk, hv, hcap, tr.parent[j], tr.label[j], j);

@@ -419,9 +419,18 @@ __global__ __launch_bounds__(256) void ctc_beam_frame_kernel(const T* __restrict
 struct CtcCarry { int *node, *par, *lab, *dep; float *pb, *pnb; int* cnt; };
 enum { BEAM_LOAD = 1, BEAM_STORE = 2, BEAM_OUTPUT = 4 };  // one-shot search: BEAM_OUTPUT alone
 
-// LM fusion (the LM = true instantiation, one-shot searches only): the tables, per trie node lm of its sequence and the LM state after
-// it (written when the node is created, beside the trie's three arrays), and the two extra outputs
-struct LmDev { ngram_lm::Tables t; float* node_lm; int* node_state; float *score, *lm_score; };
+// LM fusion (the LM = true instantiations): the tables, per trie node lm of its sequence and the LM state after it (written when the
+// node is created, beside the trie's three arrays: they ARE the carried LM state of a stream, a beam row reads its own from its node),
+// the two extra outputs, and which streams have ended: those rank with the end-of-sentence term (all_final: every stream, the one-shot
+// search; else the streams with fin[b] != 0, fin NULL: none)
+struct LmDev { ngram_lm::Tables t; float* node_lm; int* node_state; float *score, *lm_score; const int32_t* fin; int all_final; };
+
+// the LM part of the key a carried row ranks by: lm of its node's sequence, with the end-of-sentence term when its stream has ended
+__device__ __forceinline__ float lm_rank_term(const LmDev& lmd, const float* node_lm, const int* node_state, long nmax, int node, bool ended) {
+  const long n = min(max((long)node, 0L), nmax - 1);
+  const float lm = node_lm[n];
+  return ended ? lm + ngram_lm::end_of_sentence(lmd.t, ngram_lm::clamp_node(node_state[n], lmd.t.nodes)) : lm;
+}
 
 template <typename T, bool LM>
 __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
@@ -469,6 +478,10 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
     if (tid < nb0) {
       bnode[tid] = cy.node[c0 + tid]; bpar[tid] = cy.par[c0 + tid]; blab[tid] = cy.lab[c0 + tid]; bdep[tid] = cy.dep[c0 + tid];
       bpb[tid] = cy.pb[c0 + tid]; bpnb[tid] = cy.pnb[c0 + tid];
+      if constexpr (LM) {  // a row's lm and state are its node's: the values the one-shot search holds in LDS at this frame
+        const long n = min(max((long)bnode[tid], 0L), nmax - 1);
+        blm[tid] = node_lm[n]; blms[tid] = ngram_lm::clamp_node(node_state[n], lmd.t.nodes);
+      }
     }
     if (tid == 0) { s_nb = nb0; s_ntrie = cnt[CNT_NODES]; }
     frames0 = cnt[CNT_FRAMES];
@@ -618,10 +631,12 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
   if (!(mode & BEAM_OUTPUT)) return;
   const long obase = (long)b * P;
   if constexpr (LM) {
-    // final beam by score = acoustic total + (lm + the end-of-sentence term), ties: smaller label sequence
+    // final beam by score = acoustic total + (lm + the end-of-sentence term), ties: smaller label sequence; a stream that has not
+    // ended ranks by acoustic total + lm, the key its rows were selected by
+    const bool ended = lmd.all_final || (lmd.fin && lmd.fin[b]);
     if (tid < nb) {
       bptot[tid] = lae(bpb[tid], bpnb[tid]);
-      nlm[tid] = blm[tid] + ngram_lm::end_of_sentence(lmd.t, blms[tid]);
+      nlm[tid] = ended ? blm[tid] + ngram_lm::end_of_sentence(lmd.t, blms[tid]) : blm[tid];
       spb[tid] = bptot[tid] + nlm[tid];
     }
     __syncthreads();
@@ -663,9 +678,11 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_search_kernel(
 }
 
 // ---- tfasr_ctc_beam_reset: the streams named by `mask` (NULL: all) hold the empty prefix alone ----
+// (LM: the root's lm and LM state as well, lm_start = the state a sequence begins in)
+template <bool LM>
 __global__ __launch_bounds__(THREADS) void ctc_beam_reset_kernel(const int32_t* __restrict__ mask, int* trie_parent, int* trie_label,
                                                                  int* trie_depth, unsigned long long* hkeys, CtcCarry cy, int W, long nmax,
-                                                                 unsigned hcap) {
+                                                                 unsigned hcap, float* node_lm, int* node_state, int lm_start) {
   const int b = blockIdx.x, tid = threadIdx.x;
   if (mask && !mask[b]) return;
   clear_stream(trie_at(trie_parent, trie_label, trie_depth, (long)b * nmax), hkeys + (long)b * hcap, hcap, tid);
@@ -674,15 +691,24 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_reset_kernel(const int32_t* 
     cy.node[c0] = 0; cy.par[c0] = -1; cy.lab[c0] = -1; cy.dep[c0] = 0; cy.pb[c0] = 0.f; cy.pnb[c0] = -INFINITY;
     int* cnt = cy.cnt + b * CNT_N;
     cnt[CNT_LIVE] = 1; cnt[CNT_NODES] = 1; cnt[CNT_FRAMES] = 0;
+    if constexpr (LM) { node_lm[(long)b * nmax] = 0.f; node_state[(long)b * nmax] = lm_start; }
   }
 }
 
-// lane of the best live row in the n-best order (total desc, then the smaller label sequence); lane i holds the node of live row i
-__device__ __forceinline__ int ctc_best_lane(const Trie& tr, const CtcCarry& cy, long c0, int nb, int lane, int node, bool live) {
-  const float tq = live ? lae(cy.pb[c0 + lane], cy.pnb[c0 + lane]) : -INFINITY;
+// lane of the best live row in the n-best order (total desc, then the smaller label sequence); lane i holds the node of live row i.
+// LM: the order of the fused n-best, float(total + lm), lm with the end-of-sentence term when the stream has `ended`.
+template <bool LM>
+__device__ __forceinline__ int ctc_best_lane(const Trie& tr, const CtcCarry& cy, long c0, int nb, int lane, int node, bool live,
+                                             const LmDev& lmd, long n0, long nmax, bool ended) {
+  auto key = [&](int p, int nd) {
+    const float t = lae(cy.pb[c0 + p], cy.pnb[c0 + p]);
+    if constexpr (LM) return t + lm_rank_term(lmd, lmd.node_lm + n0, lmd.node_state + n0, nmax, nd, ended);
+    else return t;
+  };
+  const float tq = live ? key(lane, node) : -INFINITY;
   bool best = live;
   for (int p = 0; p < nb && best; ++p) {
-    const float tp = lae(cy.pb[c0 + p], cy.pnb[c0 + p]);
+    const float tp = key(p, cy.node[c0 + p]);
     if (tp > tq || (tp == tq && p != lane && seq_less(tr, Seq{cy.node[c0 + p], -1}, Seq{node, -1}))) best = false;
   }
   const unsigned long long m = __ballot(best);
@@ -690,10 +716,11 @@ __device__ __forceinline__ int ctc_best_lane(const Trie& tr, const CtcCarry& cy,
 }
 
 // ---- tfasr_ctc_beam_commit: one wave per stream, a lane per live row; `fin` streams commit their best row (the n-best order) ----
+template <bool LM>
 __global__ __launch_bounds__(64) void ctc_beam_commit_kernel(int* trie_parent, int* trie_label, int* trie_depth, CtcCarry cy,
                                                             const int32_t* __restrict__ fin, int32_t* __restrict__ committed,
                                                             int32_t* __restrict__ tokens, int32_t* __restrict__ ntokens, int W, int width,
-                                                            long nmax) {
+                                                            long nmax, LmDev lmd) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nb = min(max(cy.cnt[b * CNT_N + CNT_LIVE], 0), W);
   const Trie tr = trie_at(trie_parent, trie_label, trie_depth, (long)b * nmax);
@@ -701,16 +728,17 @@ __global__ __launch_bounds__(64) void ctc_beam_commit_kernel(int* trie_parent, i
   const long c0 = (long)b * W;
   const int node = live ? cy.node[c0 + lane] : 0;
   int best_lane = -1;
-  if (nb > 0 && fin && fin[b]) best_lane = ctc_best_lane(tr, cy, c0, nb, lane, node, live);
+  if (nb > 0 && fin && fin[b]) best_lane = ctc_best_lane<LM>(tr, cy, c0, nb, lane, node, live, lmd, (long)b * nmax, nmax, true);
   commit_stream(tr, node, live, nb, best_lane, lane, committed + b, tokens + (long)b * width, ntokens + b, width, 0);
 }
 
 // ---- tfasr_ctc_beam_commit_horizon: the same, and at a prune point (beam_select.h) the rows that do not descend from the best row's
 // deepest node older than the horizon leave the carried beam: the survivors move up in their order, the commit goes up to that node ----
+template <bool LM>
 __global__ __launch_bounds__(64) void ctc_beam_commit_horizon_kernel(int* trie_parent, int* trie_label, int* trie_depth, CtcCarry cy,
                                                                     const int32_t* __restrict__ fin, int32_t* __restrict__ committed,
                                                                     int32_t* __restrict__ tokens, int32_t* __restrict__ ntokens,
-                                                                    int32_t* hstate, int H, int W, int width, long nmax) {
+                                                                    int32_t* hstate, int H, int W, int width, long nmax, LmDev lmd) {
   const int b = blockIdx.x, lane = threadIdx.x;
   int* cnt = cy.cnt + b * CNT_N;
   const int nb = min(max(cnt[CNT_LIVE], 0), W);
@@ -721,7 +749,7 @@ __global__ __launch_bounds__(64) void ctc_beam_commit_horizon_kernel(int* trie_p
   const int X = horizon_point(hstate + (long)b * horizon_stride(H), H, cnt, lane);
   const bool final = fin && fin[b];
   int best_lane = -1;
-  if (nb > 0 && (final || X >= 0)) best_lane = ctc_best_lane(tr, cy, c0, nb, lane, node, live);
+  if (nb > 0 && (final || X >= 0)) best_lane = ctc_best_lane<LM>(tr, cy, c0, nb, lane, node, live, lmd, (long)b * nmax, nmax, final);
   if (nb > 0 && !final && X >= 0) {
     int target = horizon_target(tr, __shfl(node, best_lane, 64), X);
     const int ca = beam_trie::common_ancestor(tr, node, live);
@@ -749,10 +777,20 @@ __global__ __launch_bounds__(64) void ctc_beam_commit_horizon_kernel(int* trie_p
 // finds a row's parent ROW by comparing par with the rows' nodes: a live row that is the new root keeps its last label, so its par is
 // CTC_ROOT_PAR, a value no node id takes (ids stay below nmax < 2^28), unless the root is still the empty sequence (label -1) ----
 constexpr int CTC_ROOT_PAR = 0x7fffffff;
+// what a kept node takes along under LM fusion: lm of its sequence (the absolute sum from `start`, never rebased) and the LM state
+struct LmPayload {
+  static constexpr int WORDS = 2;
+  float* node_lm;
+  int* node_state;
+  __device__ void get(int node, int* dst) const { dst[0] = __float_as_int(node_lm[node]); dst[1] = node_state[node]; }
+  __device__ void put(int node, const int* src) const { node_lm[node] = __int_as_float(src[0]); node_state[node] = src[1]; }
+};
+template <bool LM>
 __global__ __launch_bounds__(THREADS) void ctc_beam_compact_kernel(const int32_t* __restrict__ mask, int* trie_parent, int* trie_label,
                                                                    int* trie_depth, unsigned long long* hkeys, int* hvals, CtcCarry cy,
                                                                    int32_t* __restrict__ committed, int32_t* hstate, int H,
-                                                                   int32_t* __restrict__ out, int W, long nmax, unsigned hcap) {
+                                                                   int32_t* __restrict__ out, int W, long nmax, unsigned hcap,
+                                                                   float* node_lm, int* node_state) {
   const int b = blockIdx.x, tid = threadIdx.x;
   int* cnt = cy.cnt + b * CNT_N;
   if (!mask[b]) {
@@ -762,13 +800,17 @@ __global__ __launch_bounds__(THREADS) void ctc_beam_compact_kernel(const int32_t
   const Trie tr = trie_at(trie_parent, trie_label, trie_depth, (long)b * nmax);
   const long c0 = (long)b * W;
   const int nb = min(max(cnt[CNT_LIVE], 0), W);
-  compact_stream(tr, hkeys + (long)b * hcap, hvals + (long)b * hcap, hcap, cnt, nb, committed + b,
-                 hstate ? hstate + (long)b * horizon_stride(H) : nullptr, H, out + 3 * b, tid,
-                 [&](int i) { return cy.node[c0 + i]; },
-                 [&](int i, int n) {
-                   cy.node[c0 + i] = n; cy.lab[c0 + i] = tr.label[n]; cy.dep[c0 + i] = tr.depth[n];
-                   cy.par[c0 + i] = n > 0 ? tr.parent[n] : tr.label[0] >= 0 ? CTC_ROOT_PAR : -1;
-                 });
+  auto node_at = [&](int i) { return cy.node[c0 + i]; };
+  auto set_node = [&](int i, int n) {
+    cy.node[c0 + i] = n; cy.lab[c0 + i] = tr.label[n]; cy.dep[c0 + i] = tr.depth[n];
+    cy.par[c0 + i] = n > 0 ? tr.parent[n] : tr.label[0] >= 0 ? CTC_ROOT_PAR : -1;
+  };
+  int32_t* hs = hstate ? hstate + (long)b * horizon_stride(H) : nullptr;
+  if constexpr (LM)
+    compact_stream(tr, hkeys + (long)b * hcap, hvals + (long)b * hcap, hcap, cnt, nb, committed + b, hs, H, out + 3 * b, tid, node_at, set_node,
+                   LmPayload{node_lm + (long)b * nmax, node_state + (long)b * nmax});
+  else
+    compact_stream(tr, hkeys + (long)b * hcap, hvals + (long)b * hcap, hcap, cnt, nb, committed + b, hs, H, out + 3 * b, tid, node_at, set_node);
 }
 
 struct BeamLayout : Geometry {
@@ -880,7 +922,7 @@ extern "C" int tfasr_ctc_beam_search_lm(const void* logits, const int32_t* logit
   if (workspace_bytes < L.total + 2 * nb) return TFASR_STATUS_INVALID_VALUE;
   const BeamWs w = beam_carve(L, workspace, B, beam_width);
   char* extra = (char*)workspace + L.total;
-  const LmDev lmd{ngram_lm::tables_of(*lm), (float*)extra, (int*)(extra + nb), score, lm_score};
+  const LmDev lmd{ngram_lm::tables_of(*lm), (float*)extra, (int*)(extra + nb), score, lm_score, nullptr, 1};
   hipStream_t s = (hipStream_t)stream_;
   if (dtype == TFASR_F32)
     return beam_launch<float, true>(L, w, logits, logit_len, B, T, T, V, beam_width, top_paths, blank_index, BEAM_OUTPUT, T, tokens, tokens_len,
@@ -907,8 +949,8 @@ extern "C" int tfasr_ctc_beam_reset(const int32_t* mask, int B, int C, int Tcap,
   const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
   if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
   const BeamWs w = beam_carve(L, workspace, B, beam_width);
-  TFASR_KLAUNCH(ctc_beam_reset_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream_, mask, w.par, w.lab, w.dep, w.hk, w.cy, beam_width,
-                L.nmax, L.hcap);
+  TFASR_KLAUNCH(ctc_beam_reset_kernel<false>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream_, mask, w.par, w.lab, w.dep, w.hk, w.cy,
+                beam_width, L.nmax, L.hcap, (float*)nullptr, (int*)nullptr, 0);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
@@ -938,8 +980,8 @@ extern "C" int tfasr_ctc_beam_commit(const int32_t* final_mask, int32_t* committ
   const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
   if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
   const BeamWs w = beam_carve(L, workspace, B, beam_width);
-  TFASR_KLAUNCH(ctc_beam_commit_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream_, w.par, w.lab, w.dep, w.cy, final_mask, committed, tokens,
-                ntokens, beam_width, width, L.nmax);
+  TFASR_KLAUNCH(ctc_beam_commit_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream_, w.par, w.lab, w.dep, w.cy, final_mask, committed,
+                tokens, ntokens, beam_width, width, L.nmax, LmDev{});
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
@@ -967,8 +1009,8 @@ extern "C" int tfasr_ctc_beam_commit_horizon(const int32_t* final_mask, int32_t*
   const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
   if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
   const BeamWs w = beam_carve(L, workspace, B, beam_width);
-  TFASR_KLAUNCH(ctc_beam_commit_horizon_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream_, w.par, w.lab, w.dep, w.cy, final_mask, committed,
-                tokens, ntokens, horizon_state, horizon, beam_width, width, L.nmax);
+  TFASR_KLAUNCH(ctc_beam_commit_horizon_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream_, w.par, w.lab, w.dep, w.cy, final_mask,
+                committed, tokens, ntokens, horizon_state, horizon, beam_width, width, L.nmax, LmDev{});
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }
@@ -981,8 +1023,121 @@ extern "C" int tfasr_ctc_beam_compact(const int32_t* mask, int32_t* committed, i
   const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
   if (workspace_bytes < L.total) return TFASR_STATUS_INVALID_VALUE;
   const BeamWs w = beam_carve(L, workspace, B, beam_width);
-  TFASR_KLAUNCH(ctc_beam_compact_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream_, mask, w.par, w.lab, w.dep, w.hk, w.hv, w.cy, committed,
-                horizon_state, horizon, out, beam_width, L.nmax, L.hcap);
+  TFASR_KLAUNCH(ctc_beam_compact_kernel<false>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream_, mask, w.par, w.lab, w.dep, w.hk, w.hv, w.cy,
+                committed, horizon_state, horizon, out, beam_width, L.nmax, L.hcap, (float*)nullptr, (int*)nullptr);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
+}
+
+// ---- the fused search in pieces (tfasr_ctc_beam_lm_*): the entries above on the LM = true instantiations.  The workspace is the plain
+// stream layout, then lm and LM state per trie node; a beam row carries no LM values of its own (it reads its node's) ----
+namespace {
+struct LmStreamWs { BeamLayout L{Geometry(1, 2, 1)}; BeamWs w; float* node_lm; int* node_state; };
+
+// the checks every fused stream entry shares -> SUCCESS and the carved workspace
+inline int lm_stream_ws(int B, int C, int Tcap, int V, int W, void* workspace, size_t workspace_bytes, LmStreamWs* out) {
+  if (!workspace || !stream_shape_ok(B, C, Tcap, V, W)) return TFASR_STATUS_INVALID_VALUE;
+  if (W > TFASR_CTC_LM_MAX_BEAM) return TFASR_STATUS_UNSUPPORTED;
+  out->L = beam_layout(B, C, Tcap, V, W);
+  const size_t nb = lm_node_bytes(B, out->L);
+  if (workspace_bytes < out->L.total + 2 * nb) return TFASR_STATUS_INVALID_VALUE;
+  out->w = beam_carve(out->L, workspace, B, W);
+  char* extra = (char*)workspace + out->L.total;
+  out->node_lm = (float*)extra;
+  out->node_state = (int*)(extra + nb);
+  return TFASR_STATUS_SUCCESS;
+}
+}  // namespace
+
+extern "C" int tfasr_ctc_beam_lm_stream_workspace_size(int B, int C, int Tcap, int V, int beam_width, size_t* bytes) {
+  if (!bytes || !stream_shape_ok(B, C, Tcap, V, beam_width)) return TFASR_STATUS_INVALID_VALUE;
+  if (beam_width > TFASR_CTC_LM_MAX_BEAM) return TFASR_STATUS_UNSUPPORTED;
+  const BeamLayout L = beam_layout(B, C, Tcap, V, beam_width);
+  *bytes = L.total + 2 * lm_node_bytes(B, L);
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_lm_reset(const int32_t* mask, int B, int C, int Tcap, int V, int beam_width, const tfasr_ngram_lm_t* lm,
+                                       void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!ngram_lm::tables_ok(lm)) return TFASR_STATUS_INVALID_VALUE;
+  LmStreamWs x;
+  if (const int st = lm_stream_ws(B, C, Tcap, V, beam_width, workspace, workspace_bytes, &x)) return st;
+  TFASR_KLAUNCH(ctc_beam_reset_kernel<true>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream_, mask, x.w.par, x.w.lab, x.w.dep, x.w.hk, x.w.cy,
+                beam_width, x.L.nmax, x.L.hcap, x.node_lm, x.node_state, (int)lm->start);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_lm_advance(const void* logits, const int32_t* nvalid, int B, int C, int Cn, int Tcap, int V, int beam_width,
+                                         int blank_index, int dtype, int frames_max_after, const tfasr_ngram_lm_t* lm, void* workspace,
+                                         size_t workspace_bytes, void* stream_) {
+  if (!logits || !nvalid || !ngram_lm::tables_ok(lm) || Cn < 1 || Cn > C || blank_index < 0 || blank_index >= V || frames_max_after < 0 ||
+      frames_max_after > Tcap)
+    return TFASR_STATUS_INVALID_VALUE;
+  if (dtype != TFASR_F32 && dtype != TFASR_BF16) return TFASR_STATUS_INVALID_VALUE;
+  LmStreamWs x;
+  if (const int st = lm_stream_ws(B, C, Tcap, V, beam_width, workspace, workspace_bytes, &x)) return st;
+  const LmDev lmd{ngram_lm::tables_of(*lm), x.node_lm, x.node_state, nullptr, nullptr, nullptr, 0};
+  hipStream_t s = (hipStream_t)stream_;
+  const int mode = BEAM_LOAD | BEAM_STORE;
+  if (dtype == TFASR_F32)
+    return beam_launch<float, true>(x.L, x.w, logits, nvalid, B, Cn, Tcap, V, beam_width, 1, blank_index, mode, 1, nullptr, nullptr, nullptr, s,
+                                    lmd);
+  return beam_launch<bf16_t, true>(x.L, x.w, logits, nvalid, B, Cn, Tcap, V, beam_width, 1, blank_index, mode, 1, nullptr, nullptr, nullptr, s,
+                                   lmd);
+}
+
+extern "C" int tfasr_ctc_beam_lm_commit(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens, int B, int C,
+                                        int Tcap, int V, int beam_width, int width, const tfasr_ngram_lm_t* lm, void* workspace,
+                                        size_t workspace_bytes, void* stream_) {
+  if (!committed || !tokens || !ntokens || !ngram_lm::tables_ok(lm) || width < 1) return TFASR_STATUS_INVALID_VALUE;
+  LmStreamWs x;
+  if (const int st = lm_stream_ws(B, C, Tcap, V, beam_width, workspace, workspace_bytes, &x)) return st;
+  const LmDev lmd{ngram_lm::tables_of(*lm), x.node_lm, x.node_state, nullptr, nullptr, final_mask, 0};
+  TFASR_KLAUNCH(ctc_beam_commit_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream_, x.w.par, x.w.lab, x.w.dep, x.w.cy, final_mask,
+                committed, tokens, ntokens, beam_width, width, x.L.nmax, lmd);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_lm_commit_horizon(const int32_t* final_mask, int32_t* committed, int32_t* tokens, int32_t* ntokens,
+                                                int32_t* horizon_state, int horizon, int B, int C, int Tcap, int V, int beam_width, int width,
+                                                const tfasr_ngram_lm_t* lm, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!committed || !tokens || !ntokens || !horizon_state || !ngram_lm::tables_ok(lm) || width < 1 || horizon < 1 ||
+      horizon > TFASR_BEAM_MAX_HORIZON)
+    return TFASR_STATUS_INVALID_VALUE;
+  LmStreamWs x;
+  if (const int st = lm_stream_ws(B, C, Tcap, V, beam_width, workspace, workspace_bytes, &x)) return st;
+  const LmDev lmd{ngram_lm::tables_of(*lm), x.node_lm, x.node_state, nullptr, nullptr, final_mask, 0};
+  TFASR_KLAUNCH(ctc_beam_commit_horizon_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream_, x.w.par, x.w.lab, x.w.dep, x.w.cy, final_mask,
+                committed, tokens, ntokens, horizon_state, horizon, beam_width, width, x.L.nmax, lmd);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_lm_compact(const int32_t* mask, int32_t* committed, int32_t* horizon_state, int horizon, int32_t* out, int B,
+                                         int C, int Tcap, int V, int beam_width, void* workspace, size_t workspace_bytes, void* stream_) {
+  // (no tables: the per-node lm and state move as they are)
+  if (!mask || !committed || !out) return TFASR_STATUS_INVALID_VALUE;
+  if (horizon_state ? (horizon < 1 || horizon > TFASR_BEAM_MAX_HORIZON) : horizon != 0) return TFASR_STATUS_INVALID_VALUE;
+  LmStreamWs x;
+  if (const int st = lm_stream_ws(B, C, Tcap, V, beam_width, workspace, workspace_bytes, &x)) return st;
+  TFASR_KLAUNCH(ctc_beam_compact_kernel<true>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream_, mask, x.w.par, x.w.lab, x.w.dep, x.w.hk, x.w.hv,
+                x.w.cy, committed, horizon_state, horizon, out, beam_width, x.L.nmax, x.L.hcap, x.node_lm, x.node_state);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_beam_lm_nbest(const int32_t* final_mask, int B, int C, int Tcap, int V, int beam_width, int top_paths, int width,
+                                       int32_t* tokens, int32_t* tokens_len, float* score, float* log_prob, float* lm_score,
+                                       const tfasr_ngram_lm_t* lm, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!tokens || !tokens_len || !score || !log_prob || !lm_score || !ngram_lm::tables_ok(lm) || top_paths < 1 || top_paths > beam_width ||
+      width < 1 || width > Tcap)
+    return TFASR_STATUS_INVALID_VALUE;
+  LmStreamWs x;
+  if (const int st = lm_stream_ws(B, C, Tcap, V, beam_width, workspace, workspace_bytes, &x)) return st;
+  const LmDev lmd{ngram_lm::tables_of(*lm), x.node_lm, x.node_state, score, lm_score, final_mask, 0};
+  // the search kernel over zero frames: load the beam, rank it by the fused score, write the paths
+  return beam_launch<float, true>(x.L, x.w, nullptr, nullptr, B, C, Tcap, V, beam_width, top_paths, 0, BEAM_LOAD | BEAM_OUTPUT, width, tokens,
+                                  tokens_len, log_prob, (hipStream_t)stream_, lmd);
 }

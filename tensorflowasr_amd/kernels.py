@@ -1688,6 +1688,75 @@ class CtcBeamStream(_BeamStream):
         return tokens, lengths, log_prob
 
 
+class CtcLmBeamStream(_BeamStream):
+    """The fused prefix beam search of ctc_beam_search_lm in pieces (tfasr_ctc_beam_lm_reset / _advance / _commit / _commit_horizon /
+    _compact / _nbest): CtcBeamStream's interface with the n-gram tables `tables` = NGramLM.tables(alpha, beta), which every call of
+    this object passes on (the carried LM states are node ids of these tables).  After any sequence of advances stream b holds the
+    beam ctc_beam_search_lm holds after the same frames.  blank_index is the model's blank (the tables were built for it), never
+    defaulted to V-1.  The streams in `final_rows` (commit, nbest) have ended and rank with the end-of-sentence term; the others rank
+    by acoustic total + lm.  1 <= beam_width <= 32."""
+    what = "tfasr_ctc_beam_lm_advance"
+
+    def __init__(self, B, C, Tcap, V, beam_width, tables, blank_index=0, device="cuda"):
+        self.C = int(C)
+        self.beam_width, _, self.blank_index = _lm_beam_args(self.what, V, beam_width, 1, blank_index, tables)
+        if not 1 <= self.C <= int(Tcap):
+            raise ValueError(f"{self.what}: chunk capacity {self.C} outside [1, Tcap = {Tcap}]")
+        self._init_common(B, Tcap, V, beam_width, device)
+        self.tables = tables
+        n = ctypes.c_size_t(0)
+        check(_L().tfasr_ctc_beam_lm_stream_workspace_size(*self._dims(), ctypes.byref(n)), "ctc_beam_lm_stream_ws")
+        self.ws = torch.empty(n.value, dtype=torch.uint8, device=device)
+        self._lm = ctypes.addressof(_lm_device(tables, self.ws.device))
+        self.reset()
+
+    def _dims(self):
+        return self.B, self.C, self.Tcap, self.V, self.beam_width
+
+    def reset(self, rows=None):
+        rows = None if rows is None else list(rows)
+        mask = _row_mask(rows, self.B, self.ws.device)
+        check(_L().tfasr_ctc_beam_lm_reset(_p(mask), *self._dims(), self._lm, _p(self.ws), self.ws.numel(), _stream()), "ctc_beam_lm_reset")
+        self._reset_host(rows)
+
+    def advance(self, logits, nvalid):
+        """logits [B, Cn <= C, V] f32 / bf16 (device), nvalid [B] host values in [0, Cn]"""
+        if logits.dim() != 3 or logits.shape[0] != self.B or logits.shape[2] != self.V or not 1 <= logits.shape[1] <= self.C:
+            raise ValueError(f"ctc_beam_lm_advance: logits {tuple(logits.shape)}, expected [{self.B}, <= {self.C}, {self.V}]")
+        Cn = int(logits.shape[1])
+        nv, after = self._take(nvalid, Cn)
+        logits = logits.contiguous()
+        B, C, Tcap, V, W = self._dims()
+        check(_L().tfasr_ctc_beam_lm_advance(_p(logits), _p(_i32(nv, self.ws.device)), B, C, Cn, Tcap, V, W, self.blank_index, _dt(logits),
+                                             after, self._lm, _p(self.ws), self.ws.numel(), _stream()), "ctc_beam_lm_advance")
+        self.frames = [f + v for f, v in zip(self.frames, nv)]
+
+    def _commit(self, fin, tokens, n, width):
+        check(_L().tfasr_ctc_beam_lm_commit(fin, _p(self.committed), tokens, n, *self._dims(), width, self._lm, _p(self.ws), self.ws.numel(),
+                                            _stream()), "ctc_beam_lm_commit")
+
+    def _commit_horizon(self, fin, tokens, n, width):
+        check(_L().tfasr_ctc_beam_lm_commit_horizon(fin, _p(self.committed), tokens, n, _p(self.hstate), self.horizon, *self._dims(), width,
+                                                    self._lm, _p(self.ws), self.ws.numel(), _stream()), "ctc_beam_lm_commit_horizon")
+
+    def _compact(self, mask, hstate, horizon, out):
+        check(_L().tfasr_ctc_beam_lm_compact(mask, _p(self.committed), hstate, horizon, out, *self._dims(), _p(self.ws), self.ws.numel(),
+                                             _stream()), "ctc_beam_lm_compact")
+
+    def nbest(self, top_paths=None, final_rows=None):
+        """the current beams as ctc_beam_search_lm returns them: (tokens [B, P, L] 0 padded, lengths, score, log_prob, lm_score [B, P]);
+        final_rows = the streams that have ended (None / empty: none)"""
+        _, top_paths, _ = _beam_args("tfasr_ctc_beam_lm_nbest", self.V, self.beam_width, top_paths or self.beam_width, self.blank_index)
+        dev, width, B = self.ws.device, self._width(), self.B
+        final_rows = list(final_rows) if final_rows is not None else []
+        fin = _row_mask(final_rows, B, dev) if final_rows else None
+        tokens, lengths, score = _paths(B, top_paths, width, dev)
+        log_prob, lm_score = torch.empty_like(score), torch.empty_like(score)
+        check(_L().tfasr_ctc_beam_lm_nbest(_p(fin), *self._dims(), top_paths, width, _p(tokens), _p(lengths), _p(score), _p(log_prob),
+                                           _p(lm_score), self._lm, _p(self.ws), self.ws.numel(), _stream()), "ctc_beam_lm_nbest")
+        return tokens, lengths, score, log_prob, lm_score
+
+
 def ctc_greedy_decode(logits, logit_len, blank=0):
     B, T, V = logits.shape
     am = torch.empty(B * T, dtype=torch.int32, device=logits.device)

@@ -401,7 +401,27 @@ class AsrModel(BaseModel):
         `commit_horizon` encoder frames: an endless beam session whose committed text trails the audio by about the horizon, at the
         price of a pruning rule (streaming.StreamingRecognizer).  One method for every streamable class, as
         stream_detailed: their stream() signatures differ and stay as they are."""
+        lm = {k: kwargs.pop(k) for k in ("lm", "lm_alpha", "lm_beta") if k in kwargs}  # (stream_lm's keywords, accepted here too)
+        if lm.get("lm") is not None:
+            return self.stream_lm(lm.pop("lm"), *args, **lm, **kwargs).with_commit_horizon(commit_horizon)
         return self.stream(*args, **kwargs).with_commit_horizon(commit_horizon)
+
+    def stream_lm(self, lm, *args, lm_alpha=0.5, lm_beta=0.0, **kwargs):
+        """stream(...) of this class with the same arguments (1 <= beam_width <= 32 among them), opened with the n-gram model `lm`
+        (lm.NGramLM) fused into the carried CTC beam: the beam of recognize_nbest_lm(alpha=lm_alpha, beta=lm_beta), carried from chunk
+        to chunk, on the model's own blank self.blank - not the V-1 convention of the plain beam session (streaming.StreamingRecognizer,
+        DESIGN.md 4b-4).  lm=None: stream(...) itself.  One method for every streamable class, as stream_horizon: their stream()
+        signatures differ and stay as they are.  A transducer head raises NotImplementedError; beam_width 0 or > 32 and a detail
+        session ValueError - judged from the arguments, before the session is opened."""
+        if lm is not None:
+            import inspect
+
+            from . import streaming
+
+            bound = inspect.signature(self.stream).bind(*args, **kwargs)
+            bound.apply_defaults()
+            streaming.check_stream_lm(self, lm, lm_alpha, lm_beta, bound.arguments.get("beam_width", 0))
+        return self.stream(*args, **kwargs).with_lm(lm, lm_alpha, lm_beta)
 
     # ----------------------------------------------------------------- timing hooks (bench.py)
     def _tick(self, name):

@@ -724,6 +724,26 @@ def check_commit_horizon(commit_horizon, beam_width):
     return h
 
 
+def check_stream_lm(model, lm, lm_alpha, lm_beta, beam_width, detail=False):
+    """A session's n-gram LM (None = none) against the model and the session, before any device work -> None, or the tables
+    NGramLM.tables(lm_alpha, lm_beta) the fused beam runs on."""
+    if lm is None:
+        return None
+    if model.cfg.head != "ctc":
+        raise NotImplementedError(f"{type(model).__name__}.stream(lm=...): LM shallow fusion exists for the CTC prefix beam search only; a "
+                                  "transducer's prediction network is its LM")
+    if detail:
+        raise ValueError("stream: lm belongs to a beam session; detail sessions are greedy")
+    if int(beam_width) < 1:
+        raise ValueError("stream: lm belongs to a beam session (beam_width >= 1): the greedy search takes one class per frame and has no "
+                         "hypotheses for a language model to rank")
+    if int(beam_width) > K.CTC_LM_MAX_BEAM:
+        raise ValueError(f"stream: beam_width {int(beam_width)} with lm is outside [1, {K.CTC_LM_MAX_BEAM}] (the fused candidate list of a "
+                         "frame lives in one workgroup's LDS)")
+    model._check_lm(lm)
+    return lm.tables(lm_alpha, lm_beta)
+
+
 class _TokenRecord:
     """The tokens of one stream of a detail session since its reset, on the host: class, frame (CTC: the first frame of the run), end (CTC:
     one past the run's last frame, -1 while the run is open; transducer: frame + 1), log-probability, entropy."""
@@ -758,6 +778,14 @@ class StreamingRecognizer:
     hypothesis, so the concatenation of a stream's outputs is its best path.  hypotheses() gives the current n-best in full.  Because the
     beam emits one symbol per frame at most, a beam_width=1 session equals the greedy session made with max_tokens_per_frame=1, not the
     default greedy session.  The CTC head's beam session treats class V-1 as blank, as recognize_beam does.
+    model.stream_lm(lm, ..., lm_alpha=0.5, lm_beta=0.0) (then stream()'s arguments; the stream() signatures are pinned and stay as they
+    are), model.stream_horizon(H, ..., lm=lm, lm_alpha=, lm_beta=) or rec.with_lm(lm, lm_alpha, lm_beta) before the first accept, with
+    lm = an lm.NGramLM (CTC heads, 1 <= beam_width <= 32; lm_alpha, lm_beta as recognize_beam_lm's alpha, beta): the beam is the fused
+    search's (K.CtcLmBeamStream on lm.tables(lm_alpha, lm_beta)), stream b holds the beam recognize_nbest_lm holds after
+    the same encoder frames, and the blank is the model's OWN, self.blank, as recognize_beam_lm uses - NOT the V-1 convention of the
+    plain beam session above.  Commits follow the LM-ranked best row; a running stream ranks without the end-of-sentence term, a
+    finished one with it.  hypotheses() keeps its three values (scores = the fused score), hypotheses_lm() adds log_prob and lm_score.
+    lm with beam_width 0, beam_width > 32 or a detail session is a ValueError, with a transducer head NotImplementedError.
     max_frames bounds the encoder frames of one stream between resets (a chunk past it raises RuntimeError; reset() frees the slot).
 
     commit_horizon = H (beam sessions) makes the session endless and its committed text prompt, at a price in accuracy: a
@@ -805,6 +833,7 @@ class StreamingRecognizer:
         batch_size, max_tokens_per_frame, self.beam_width, self.max_frames = check_stream_args(batch_size, max_tokens_per_frame, beam_width,
                                                                                              max_frames)
         self.commit_horizon = check_commit_horizon(commit_horizon, self.beam_width)
+        self.lm_tables = None  # with_lm(): the tables of the session's n-gram LM
         self.detail = self._check_detail(detail)
         self.model = model
         self.enc_model = _twin(model, precision)
@@ -983,6 +1012,9 @@ class StreamingRecognizer:
     def _new_beam(self):
         m = self.model
         ps, c = m.ps, m.cfg
+        if self.ctc and self.lm_tables is not None:
+            return K.CtcLmBeamStream(self.B, self.C, self.max_frames, c.vocab_size, self.beam_width, self.lm_tables, blank_index=m.blank,
+                                     device=m.device)
         if self.ctc:
             return K.CtcBeamStream(self.B, self.C, self.max_frames, c.vocab_size, self.beam_width, blank_index=None, device=m.device)
         lng, lnb = (ps.p("pred/ln/g"), ps.p("pred/ln/b")) if c.prediction_layer_norm else (None, None)
@@ -1018,6 +1050,19 @@ class StreamingRecognizer:
         if self.beam is None:
             raise ValueError("compact() needs a beam session: open it with model.stream(beam_width >= 1)")
         return self.beam.compact(rows)
+
+    def with_lm(self, lm, lm_alpha=0.5, lm_beta=0.0):
+        """This beam session, which has taken no audio yet, with the n-gram model `lm` fused into its carried beam (what model.stream_lm
+        returns; lm=None: the session as it is) -> self.  The beam becomes a K.CtcLmBeamStream on lm.tables(lm_alpha, lm_beta) and the
+        model's own blank.  Refused with the reason: a transducer head (NotImplementedError); a greedy or detail session, beam_width >
+        32, an lm of another vocabulary (ValueError)."""
+        if lm is None:
+            return self
+        if any(self.total) or self.chunks_run:
+            raise RuntimeError("stream: with_lm() comes before the first accept()")
+        self.lm_tables = check_stream_lm(self.model, lm, lm_alpha, lm_beta, self.beam_width, self.detail)
+        self.beam = self._new_beam()
+        return self
 
     def with_commit_horizon(self, commit_horizon):
         """This session, which has taken no audio yet, as a horizon session (what model.stream_horizon returns) -> self."""
@@ -1064,12 +1109,26 @@ class StreamingRecognizer:
         """The current n-best of every stream in full, committed part included: (tokens [B, P, L] blank padded (CTC: 0 padded), lengths
         [B, P], scores [B, P]) device tensors, best first; P = top_paths (default: beam_width).  Valid after every accept and after
         finish, until reset."""
+        return self._hypotheses(top_paths)[:3]
+
+    def hypotheses_lm(self, top_paths=None):
+        """hypotheses() of a session opened with lm=...: (tokens, lengths, score, log_prob, lm_score), as recognize_nbest_lm returns them.
+        The streams that have been finished rank with the end-of-sentence term (lm_score includes it); running ones rank by log_prob +
+        lm, without it."""
+        if self.lm_tables is None:
+            raise ValueError("hypotheses_lm() needs a beam session with a language model: open it with model.stream(beam_width >= 1, lm=...)")
+        return self._hypotheses(top_paths)
+
+    def _hypotheses(self, top_paths):
         if self.beam is None:
             raise ValueError("hypotheses() needs a beam session: open it with model.stream(beam_width >= 1)")
-        toks, lens, scores = self.beam.nbest(top_paths)[:3]
+        if self.lm_tables is not None:
+            toks, lens, scores, *rest = self.beam.nbest(top_paths, final_rows=[b for b in range(self.B) if self.finished[b]])
+        else:
+            (toks, lens, scores), rest = self.beam.nbest(top_paths)[:3], []
         dropped = self.beam.dropped
         if not any(dropped):
-            return toks, lens, scores
+            return (toks, lens, scores, *rest)
         # compacted streams: the labels their tries dropped go back in front of every live row
         th, lh, live = toks.cpu(), lens.cpu(), (scores != -float("inf")).cpu()
         P = th.shape[1]
@@ -1082,7 +1141,7 @@ class StreamingRecognizer:
                     full[b, p, :len(d)] = d
                     full[b, p, len(d):len(d) + n] = th[b, p, :n]
                     lh[b, p] = len(d) + n
-        return full.to(toks.device), lh.to(lens.device), scores
+        return (full.to(toks.device), lh.to(lens.device), scores, *rest)
 
     def _enc32(self, enc):
         B, C, d = enc.shape
@@ -1227,6 +1286,8 @@ class StreamingRecognizer:
     def _check_detail(self, detail):
         if detail and getattr(self, "commit_horizon", None):
             raise ValueError("stream: a detail session is greedy and takes no commit_horizon")
+        if detail and getattr(self, "lm_tables", None) is not None:
+            raise ValueError("stream: lm belongs to a beam session; detail sessions are greedy")
         if detail and self.beam_width:
             raise ValueError("stream: detail=True belongs to the greedy session (beam_width=0): beam sessions keep their outputs, their "
                              "searches record no token times or confidences")
