@@ -990,9 +990,9 @@ __global__ __launch_bounds__(256, 2) void relattn_dpext_kernel(
     __builtin_amdgcn_s_barrier();
     const bf16_t* sT = reinterpret_cast<const bf16_t*>(smem + buf * DPX_BUF);
     const char* sQ = smem + buf * DPX_BUF + DPX_TILE_BYTES;
-    const int off = cur.jmin - cur.jb0;                   // tile column of key jmin
-    // a clamped source column shifts the row's content: rows whose first column was clamped (jb0 < 0) are addressed from column 0
-    const int cshift = cur.jb0 < 0 ? cur.jb0 : 0;         // source column of tile column 0 is max(jb0, 0) = jb0 - cshift
+    // Tile column of key j is j - jb0 whatever the sign of jb0: the DMA clamps the ORIGIN of a 16-byte chunk, not the row, so a chunk of
+    // keys >= 0 (origin jb0 + 8 ch >= 0, jb0 a multiple of 8) lands unshifted; only chunks that lie wholly below key 0 (or from lds on)
+    // hold other columns' values, and their pairs do not exist (j < 0 or j >= T: masked below).
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
       const int c = c0 + (2 * w + ct) * 16 + r;           // this lane's table row (A row)
@@ -1006,8 +1006,6 @@ __global__ __launch_bounds__(256, 2) void relattn_dpext_kernel(
           const int il = kk * 32 + g * 8 + t;
           const int j = cur.jmin + (c - c0) + il;          // real key index: pairs outside [0, T) do not exist
           const bool ok = cvalid && j >= 0 && j < T && cur.i0 + il < T;
-          // tile column of key j: chunk (j - jb0) / 8 was fetched from source column clamp(jb0 + 8*chunk): inside [0, T) the clamp is
-          // the identity except when jb0 < 0, where every chunk with a negative origin reads from column 0 (masked: j < 0)
           const int col = j - cur.jb0;
           a[t] = ok ? (short)sT[il * DPX_TLD + col] : (short)0;
         }
@@ -1016,7 +1014,6 @@ __global__ __launch_bounds__(256, 2) void relattn_dpext_kernel(
           acc[ct][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, frag_kt(sQ, n * 16, kk * 32 + g * 8, r), acc[ct][n], 0, 0, 0);
       }
     }
-    (void)off; (void)cshift;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                          // everyone is done with this buffer before the tile after next lands in it
     cur = nxt;

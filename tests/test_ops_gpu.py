@@ -615,6 +615,7 @@ def test_logmel_no_preemphasis_and_bf16_output(dev):
     assert torch.equal(out16, out.to(torch.bfloat16))  # same f32 value, rounded once
 
 
+# (every launch branch of csrc/attn_fused.hip against a float64 oracle with derived bounds: tests/test_relattn_fused_gpu.py)
 def _relattn_reference(qkv, u, v, pext, lens, B, H, T, dh, scale, use_mask=True):
     """f32 reference of the fused kernel from the same (bf16-rounded) inputs, via the gather identity of attention.hip."""
     HD = H * dh
