@@ -994,6 +994,28 @@ int tfasr_ctc_align(const void* logits, const int32_t* labels, const int32_t* la
                     int U, int V, int blank, int dtype, int normalized, int32_t* start, int32_t* end, float* label_lp, float* score,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* Token times and confidences of a beam search's n-best list (declarations added under ABI 44, nothing existing changes; csrc/align.hip,
+ * DESIGN.md 4b-5): the P hypotheses of an utterance are aligned to ONE copy of its logits, in one pass over what the search read.
+ *
+ * tfasr_row_lse_entropy: per row of x [rows, V] (f32 | bf16, f32 arithmetic) lse[r] = max + log(sum_v e_v), e_v = exp(x_v - max), and
+ * entropy[r] = H = -sum_v p_v log p_v in nats = log(sum_v e_v) + sum_v e_v (max - x_v) / sum_v e_v, a class with e_v == 0 left out: a
+ * frame's definitions in tfasr_ctc_greedy_decode_detail (the same device function), and lse[r] is bit for bit the lse tfasr_ctc_align
+ * subtracts.  entropy may be NULL.
+ *
+ * tfasr_ctc_nbest_align: row r = b * P + p aligns labels[r * ldl .. r * ldl + U) (ldl >= U: a search's [B, P, T] token array is read in
+ * place) to logits[b] [T, V] over logit_len[b] frames; the lse and the entropy of a frame are computed once per utterance.  For
+ * 0 <= label_len[r] <= U, start / end / label_lp [B, P, U] and score [B, P] are bit for bit tfasr_ctc_align(normalized = 0)'s for
+ * (logits[b], that label row, logit_len[b]): the same walk, tie rule and clamps, score -inf and -1 everywhere for labels that do not fit
+ * or a row without frames.  label_entropy [B, P, U]: the mean of the frame entropy over [start, end), added in frame order in f32 and
+ * then divided (tok_entropy of tfasr_ctc_greedy_decode_detail); 0 where no label sits.  label_len[r] < 0 (a dead path) or > U (too long
+ * to align): score -inf, spans -1, zeros; such a row is never clamped and never walked.  U > TFASR_ALIGN_CTC_MAX_U:
+ * TFASR_STATUS_UNSUPPORTED.  Every argument is checked on the host before any launch; nothing synchronises with the host. */
+int tfasr_row_lse_entropy(const void* x, long rows, int V, int dtype, float* lse, float* entropy, void* stream);
+int tfasr_ctc_nbest_align_workspace_size(int B, int P, int T, int U, int V, size_t* bytes);
+int tfasr_ctc_nbest_align(const void* logits, const int32_t* logit_len, const int32_t* labels, long ldl, const int32_t* label_len,
+                          int B, int P, int T, int U, int V, int blank, int dtype, int32_t* start, int32_t* end, float* label_lp,
+                          float* label_entropy, float* score, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Native executor of one Conformer block (ConformerBlock.call, encoders/conformer.py:430-520, and its backward):
  * queues every kernel of FFModule -> MHSAModule -> ConvModule -> FFModule -> LayerNorm on `stream` with one host call.

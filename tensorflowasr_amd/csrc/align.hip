@@ -24,6 +24,9 @@
 //                          two ballots per step record the move (0, 1, 2) of every state.
 //   5. ctc_backtrace     : lane 0 follows the moves and writes [start, end) of every label; then one lane per label adds its
 //                          log-probabilities in frame order.
+// N-best lists (tfasr_ctc_nbest_align): kernels 4 and 5 over B * P label rows, row b * P + p against the logits of utterance b - the same
+// code as the one-row-per-utterance call, so the same bits - after ONE pass for the lse and the entropy of every frame (csrc/ctc.hip,
+// ctc_frame_detail); kernel 5 then also averages the frame entropy over each label's span.
 #include "common.h"
 #include "lattice_lp.h"
 #include <algorithm>
@@ -187,38 +190,51 @@ __global__ __launch_bounds__(64) void rnnt_backtrace_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
-// grid B, blockDim = NW * 64 >= 2U+1.  lse == nullptr: the logits are log-probabilities already.
+// grid B * P, blockDim = NW * 64 >= 2U+1: row r = b * P + p walks labels[r * ldl ..) over the logits of utterance b (P = 1, ldl = U: one
+// label row per utterance, tfasr_ctc_align).  lse == nullptr: the logits are log-probabilities already.  nbest: a row with
+// label_len < 0 or > U is dead (no walk, score -inf) instead of clamped.  The P workgroups of an utterance gather from the same logit
+// rows, which they share through L2; a state's gather logit[t+1, lab_s] does not depend on the step before it and is issued ahead of
+// the step's barrier.
 template <typename T>
-__global__ void ctc_viterbi_kernel(const T* __restrict__ logits, const float* __restrict__ lse, const int32_t* __restrict__ labels,
-                                   const int32_t* __restrict__ label_len, const int32_t* __restrict__ logit_len, int Tm, int U, int V, int blank,
-                                   int NW, u64* __restrict__ dec, float* __restrict__ score, int32_t* __restrict__ final_state) {
+__global__ void ctc_viterbi_kernel(const T* __restrict__ logits, const float* __restrict__ lse, const int32_t* __restrict__ labels, long ldl,
+                                   const int32_t* __restrict__ label_len, const int32_t* __restrict__ logit_len, int P, int Tm, int U, int V,
+                                   int blank, int nbest, int NW, u64* __restrict__ dec, float* __restrict__ score,
+                                   int32_t* __restrict__ final_state) {
   extern __shared__ float sh[];
-  const int b = blockIdx.x, s = threadIdx.x, nthr = blockDim.x;
-  const int Tl = min(logit_len[b], Tm), Ul = max(min(label_len[b], U), 0);
+  const int r = blockIdx.x, b = r / P, s = threadIdx.x, nthr = blockDim.x;
+  const int ll = label_len[r];
+  const int Tl = min(logit_len[b], Tm), Ul = max(min(ll, U), 0);
+  const bool dead = nbest && (ll < 0 || ll > U);
   const int S = 2 * Ul + 1;
   float* buf0 = sh;
   float* buf1 = sh + nthr;
   buf0[s] = -INFINITY;
   buf1[s] = -INFINITY;
   __syncthreads();
-  if (Tl <= 0) { if (s == 0) { score[b] = -INFINITY; final_state[b] = -1; } return; }
+  if (Tl <= 0 || dead) { if (s == 0) { score[r] = -INFINITY; final_state[r] = -1; } return; }
   const bool act = s < S;
+  const int32_t* lb = labels + (long)r * ldl;
   int lab = blank;
   bool skip = false;  // transition s-2 -> s allowed
   if (act && (s & 1)) {  // labels and neighbours clamped as ctc_scan_kernel clamps them
-    lab = min(max(labels[(long)b * U + (s >> 1)], 0), V - 1);
-    if (s >= 2) skip = lab != min(max(labels[(long)b * U + (s >> 1) - 1], 0), V - 1);
+    lab = min(max(lb[s >> 1], 0), V - 1);
+    if (s >= 2) skip = lab != min(max(lb[(s >> 1) - 1], 0), V - 1);
   }
-  const T* lg = logits + (long)b * Tm * V;
+  const T* lg = logits + (long)b * Tm * V + lab;
   const float* ls = lse ? lse + (long)b * Tm : nullptr;
-  u64* d = dec + (long)b * Tm * NW * 2;
+  u64* d = dec + (long)r * Tm * NW * 2;
+  // the next frame's logit and lse wait in registers across the barrier; the subtraction (the only use) comes a step later
+  float nx = act ? Num<T>::ld(lg) : 0.f, nl = ls ? ls[0] : 0.f;
   for (int t = 0; t < Tl; ++t) {
     float* cur = (t & 1) ? buf1 : buf0;
     const float* prev = (t & 1) ? buf0 : buf1;
     int mv = 0;
+    const float lp = ls ? nx - nl : nx;
+    if (t + 1 < Tl) {
+      if (act) nx = Num<T>::ld(lg + (long)(t + 1) * V);
+      if (ls) nl = ls[t + 1];
+    }
     if (act) {
-      float lp = Num<T>::ld(lg + (long)t * V + lab);
-      if (ls) lp = lp - ls[t];
       float a;
       if (t == 0) a = (s <= 1) ? lp : -INFINITY;
       else {
@@ -240,32 +256,40 @@ __global__ void ctc_viterbi_kernel(const T* __restrict__ logits, const float* __
     const float* last = ((Tl - 1) & 1) ? buf1 : buf0;
     const float a1 = last[S - 1], a2 = (S >= 2) ? last[S - 2] : -INFINITY;
     const float sc = fmaxf(a1, a2);
-    score[b] = sc;
-    final_state[b] = (sc == -INFINITY) ? -1 : ((a2 > a1) ? S - 2 : S - 1);
+    score[r] = sc;
+    final_state[r] = (sc == -INFINITY) ? -1 : ((a2 > a1) ? S - 2 : S - 1);
   }
 }
 
-// grid B, 64 threads
+// grid B * P, 64 threads.  frame_ent / label_entropy (both or neither): the mean over [start, end) of the frame entropies, summed in frame
+// order and then divided, as ctc_collapse_detail_kernel (csrc/ctc.hip) forms tok_entropy.
 template <typename T>
 __global__ __launch_bounds__(64) void ctc_backtrace_kernel(const T* __restrict__ logits, const float* __restrict__ lse,
-                                                           const int32_t* __restrict__ labels, const int32_t* __restrict__ label_len,
-                                                           const int32_t* __restrict__ logit_len, int Tm, int U, int V, int NW,
-                                                           const u64* __restrict__ dec, const int32_t* __restrict__ final_state,
-                                                           int32_t* start, int32_t* end, float* __restrict__ label_lp) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const int Tl = min(logit_len[b], Tm), Ul = max(min(label_len[b], U), 0);
-  const int fs = final_state[b];
+                                                           const float* __restrict__ frame_ent, const int32_t* __restrict__ labels, long ldl,
+                                                           const int32_t* __restrict__ label_len, const int32_t* __restrict__ logit_len, int P,
+                                                           int Tm, int U, int V, int NW, const u64* __restrict__ dec,
+                                                           const int32_t* __restrict__ final_state, int32_t* start, int32_t* end,
+                                                           float* __restrict__ label_lp, float* __restrict__ label_entropy) {
+  const int r = blockIdx.x, b = r / P, lane = threadIdx.x;
+  const int Tl = min(logit_len[b], Tm), Ul = max(min(label_len[r], U), 0);
+  const int fs = final_state[r];
+  const long o = (long)r * U;
   for (int u = lane; u < U; u += 64)
-    if (u >= Ul || fs < 0) { start[(long)b * U + u] = -1; end[(long)b * U + u] = -1; label_lp[(long)b * U + u] = 0.f; }
-  if (fs < 0) return;  // no frames, or the labels do not fit them
+    if (u >= Ul || fs < 0) {
+      start[o + u] = -1;
+      end[o + u] = -1;
+      label_lp[o + u] = 0.f;
+      if (label_entropy) label_entropy[o + u] = 0.f;
+    }
+  if (fs < 0) return;  // no frames, the labels do not fit them, or a dead row
   if (lane == 0) {
-    const u64* d = dec + (long)b * Tm * NW * 2;
+    const u64* d = dec + (long)r * Tm * NW * 2;
     int s = fs, open = -1;
     for (int t = Tl - 1; t >= 0; --t) {
       if (s & 1) {
         const int u = s >> 1;
-        if (u != open) { end[(long)b * U + u] = t + 1; open = u; }
-        start[(long)b * U + u] = t;  // the last write is the earliest frame
+        if (u != open) { end[o + u] = t + 1; open = u; }
+        start[o + u] = t;  // the last write is the earliest frame
       }
       if (t > 0) {
         const long w = ((long)t * NW + (s >> 6)) * 2;
@@ -278,17 +302,33 @@ __global__ __launch_bounds__(64) void ctc_backtrace_kernel(const T* __restrict__
   __syncthreads();
   const T* lg = logits + (long)b * Tm * V;
   const float* ls = lse ? lse + (long)b * Tm : nullptr;
+  const float* fe = frame_ent ? frame_ent + (long)b * Tm : nullptr;
   for (int u = lane; u < Ul; u += 64) {
-    const int t0 = max(start[(long)b * U + u], 0), t1 = min(end[(long)b * U + u], Tl);
-    const int lab = min(max(labels[(long)b * U + u], 0), V - 1);
-    float acc = 0.f;
+    const int t0 = max(start[o + u], 0), t1 = min(end[o + u], Tl);
+    const int lab = min(max(labels[(long)r * ldl + u], 0), V - 1);
+    float acc = 0.f, ent_run = 0.f;
     for (int t = t0; t < t1; ++t) {
       float lp = Num<T>::ld(lg + (long)t * V + lab);
       if (ls) lp = lp - ls[t];
       acc = (t == t0) ? lp : acc + lp;
+      if (fe) ent_run += fe[t];
     }
-    label_lp[(long)b * U + u] = acc;
+    label_lp[o + u] = acc;
+    if (label_entropy) label_entropy[o + u] = t1 > t0 ? ent_run / (float)(t1 - t0) : 0.f;
   }
+}
+
+// the two launches of a CTC alignment: B * P label rows over B utterances
+template <typename T>
+void ctc_walk(const T* logits, const float* lse, const float* frame_ent, const int32_t* labels, long ldl, const int32_t* label_len,
+              const int32_t* logit_len, int B, int P, int Tm, int U, int V, int blank, int nbest, u64* dec, int32_t* fin, int32_t* start, int32_t* end,
+              float* label_lp, float* label_entropy, float* score, hipStream_t s) {
+  const int NW = ctc_dec_nw(U), nthr = NW * 64;
+  TFASR_KLAUNCH(ctc_viterbi_kernel<T>, dim3(B * P), dim3(nthr), 2 * nthr * sizeof(float), s, logits, lse, labels, ldl, label_len, logit_len, P, Tm, U, V,
+                blank, nbest, NW, dec, score, fin);
+  if (U > 0)
+    TFASR_KLAUNCH(ctc_backtrace_kernel<T>, dim3(B * P), dim3(64), 0, s, logits, lse, frame_ent, labels, ldl, label_len, logit_len, P, Tm, U, V, NW, dec,
+                  fin, start, end, label_lp, label_entropy);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -399,7 +439,6 @@ extern "C" int tfasr_ctc_align(const void* logits, const int32_t* labels, const 
   if (workspace_bytes < need) return TFASR_STATUS_INVALID_VALUE;
   hipStream_t s = (hipStream_t)stream_;
   char* ws = (char*)workspace;
-  const int NW = ctc_dec_nw(U);
   float* lse = (float*)ws;
   int32_t* fin = (int32_t*)(ws + align256((size_t)B * T * sizeof(float)));
   u64* dec = (u64*)(ws + align256((size_t)B * T * sizeof(float)) + align256((size_t)B * sizeof(int32_t)));
@@ -409,20 +448,54 @@ extern "C" int tfasr_ctc_align(const void* logits, const int32_t* labels, const 
   } else {
     lse = nullptr;
   }
-  const int nthr = NW * 64;
-  if (dtype == TFASR_F32) {
-    TFASR_KLAUNCH(ctc_viterbi_kernel<float>, dim3(B), dim3(nthr), 2 * nthr * sizeof(float), s, (const float*)logits, lse, labels, label_len, logit_len, T,
-                  U, V, blank, NW, dec, score, fin);
-    if (U > 0)
-      TFASR_KLAUNCH(ctc_backtrace_kernel<float>, dim3(B), dim3(64), 0, s, (const float*)logits, lse, labels, label_len, logit_len, T, U, V, NW, dec, fin,
-                    start, end, label_lp);
-  } else {
-    TFASR_KLAUNCH(ctc_viterbi_kernel<bf16_t>, dim3(B), dim3(nthr), 2 * nthr * sizeof(float), s, (const bf16_t*)logits, lse, labels, label_len, logit_len,
-                  T, U, V, blank, NW, dec, score, fin);
-    if (U > 0)
-      TFASR_KLAUNCH(ctc_backtrace_kernel<bf16_t>, dim3(B), dim3(64), 0, s, (const bf16_t*)logits, lse, labels, label_len, logit_len, T, U, V, NW, dec,
-                    fin, start, end, label_lp);
-  }
+  if (dtype == TFASR_F32)
+    ctc_walk((const float*)logits, lse, nullptr, labels, U, label_len, logit_len, B, 1, T, U, V, blank, 0, dec, fin, start, end, label_lp, nullptr, score, s);
+  else
+    ctc_walk((const bf16_t*)logits, lse, nullptr, labels, U, label_len, logit_len, B, 1, T, U, V, blank, 0, dec, fin, start, end, label_lp, nullptr, score, s);
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_row_lse_entropy(const void* x, long rows, int V, int dtype, float* lse, float* entropy, void* stream) {
+  if (!x || !lse || rows <= 0 || V <= 0 || (dtype != TFASR_F32 && dtype != TFASR_BF16)) return TFASR_STATUS_INVALID_VALUE;
+  return tfasr_detail::ctc_row_lse_entropy(x, lse, entropy, rows, V, dtype, (hipStream_t)stream);
+}
+
+extern "C" int tfasr_ctc_nbest_align_workspace_size(int B, int P, int T, int U, int V, size_t* bytes) {
+  if (!bytes || B <= 0 || P <= 0 || T <= 0 || U < 0 || V <= 0) return TFASR_STATUS_INVALID_VALUE;
+  if (U > kCtcMaxU) return TFASR_STATUS_UNSUPPORTED;
+  // lse and entropy per frame of an utterance, final state per label row, two decision bits per (label row, frame, state)
+  *bytes = 2 * align256((size_t)B * T * sizeof(float)) + align256((size_t)B * P * sizeof(int32_t)) +
+           align256((size_t)B * P * T * ctc_dec_nw(U) * 2 * sizeof(u64));
+  return TFASR_STATUS_SUCCESS;
+}
+
+extern "C" int tfasr_ctc_nbest_align(const void* logits, const int32_t* logit_len, const int32_t* labels, long ldl, const int32_t* label_len, int B,
+                                     int P, int T, int U, int V, int blank, int dtype, int32_t* start, int32_t* end, float* label_lp,
+                                     float* label_entropy, float* score, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!logits || !logit_len || !label_len || !score || !workspace || (U > 0 && (!labels || !start || !end || !label_lp || !label_entropy)))
+    return TFASR_STATUS_INVALID_VALUE;
+  if (B <= 0 || P <= 0 || T <= 0 || U < 0 || ldl < U || V <= 1 || blank < 0 || blank >= V || (dtype != TFASR_F32 && dtype != TFASR_BF16))
+    return TFASR_STATUS_INVALID_VALUE;
+  size_t need = 0;
+  const int st = tfasr_ctc_nbest_align_workspace_size(B, P, T, U, V, &need);
+  if (st != TFASR_STATUS_SUCCESS) return st;
+  if (workspace_bytes < need) return TFASR_STATUS_INVALID_VALUE;
+  hipStream_t s = (hipStream_t)stream_;
+  char* ws = (char*)workspace;
+  const size_t seg = align256((size_t)B * T * sizeof(float));
+  float* lse = (float*)ws;
+  float* ent = (float*)(ws + seg);
+  int32_t* fin = (int32_t*)(ws + 2 * seg);
+  u64* dec = (u64*)(ws + 2 * seg + align256((size_t)B * P * sizeof(int32_t)));
+  const int lst = tfasr_detail::ctc_row_lse_entropy(logits, lse, ent, (long)B * T, V, dtype, s);  // once per utterance, not per path
+  if (lst != TFASR_STATUS_SUCCESS) return lst;
+  if (dtype == TFASR_F32)
+    ctc_walk((const float*)logits, lse, ent, labels, ldl, label_len, logit_len, B, P, T, U, V, blank, 1, dec, fin, start, end, label_lp, label_entropy,
+             score, s);
+  else
+    ctc_walk((const bf16_t*)logits, lse, ent, labels, ldl, label_len, logit_len, B, P, T, U, V, blank, 1, dec, fin, start, end, label_lp,
+             label_entropy, score, s);
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;
 }

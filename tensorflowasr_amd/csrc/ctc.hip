@@ -207,6 +207,25 @@ __global__ __launch_bounds__(256) void ctc_frame_detail_kernel(const T* __restri
   }
 }
 
+// tfasr_row_lse_entropy: ctc_frame_detail per row with ctc_lse_kernel's lse next to the entropy.  The maximum is the arg-max's own logit
+// and s is ctc_lse_kernel's sum (the same terms in the same order), so lse = m + logf(s) has ctc_lse_kernel's bits.
+template <typename T>
+__global__ __launch_bounds__(256) void ctc_lse_entropy_kernel(const T* __restrict__ logits, float* __restrict__ lse, float* __restrict__ entropy,
+                                                              long rows, int V) {
+  const int lane = threadIdx.x & 63;
+  const long w0 = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (long)gridDim.x * (blockDim.x >> 6);
+  for (long r = w0; r < rows; r += nw) {
+    const T* row = logits + r * V;
+    const CtcFrame f = ctc_frame_detail(row, V, lane);
+    if (lane == 0) {
+      const float m = (f.mi >= 0 && f.mi < V) ? Num<T>::ld(row + f.mi) : -INFINITY;  // (no class above -inf: ctc_lse_kernel's m)
+      const float ls = logf(f.s);
+      lse[r] = m + ls;
+      entropy[r] = ls + f.a / f.s;
+    }
+  }
+}
+
 // tfasr_ctc_greedy_decode_carry_detail: one chunk [C, V] of a stream per workgroup, ONE launch.  The waves take the chunk's valid frames in
 // tiles of CTC_CARRY_TILE (one wave per frame, ctc_frame_detail), the tile's arg-max / log-probability / entropy wait in LDS, and after the
 // barrier thread 0 continues ctc_collapse_detail_kernel's serial loop over them from the carried state: the same additions in the same
@@ -377,6 +396,16 @@ int tfasr_detail::ctc_row_lse(const void* logits, float* lse, long rows, int V, 
   const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
   if (dtype == TFASR_F32) TFASR_KLAUNCH(ctc_lse_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)logits, lse, (int32_t*)nullptr, rows, V);
   else if (dtype == TFASR_BF16) TFASR_KLAUNCH(ctc_lse_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (const bf16_t*)logits, lse, (int32_t*)nullptr, rows, V);
+  else return TFASR_STATUS_INVALID_VALUE;
+  TFASR_CHECK_LAUNCH();
+  return TFASR_STATUS_SUCCESS;
+}
+
+int tfasr_detail::ctc_row_lse_entropy(const void* logits, float* lse, float* entropy, long rows, int V, int dtype, hipStream_t stream) {
+  if (!entropy) return ctc_row_lse(logits, lse, rows, V, dtype, stream);
+  const int grid = (int)std::max<long>(1, std::min<long>((rows + 3) / 4, 8192));
+  if (dtype == TFASR_F32) TFASR_KLAUNCH(ctc_lse_entropy_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)logits, lse, entropy, rows, V);
+  else if (dtype == TFASR_BF16) TFASR_KLAUNCH(ctc_lse_entropy_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (const bf16_t*)logits, lse, entropy, rows, V);
   else return TFASR_STATUS_INVALID_VALUE;
   TFASR_CHECK_LAUNCH();
   return TFASR_STATUS_SUCCESS;

@@ -14,4 +14,8 @@ __attribute__((visibility("hidden"))) int rnnt_lattice_logprobs(const void* logi
 // log-sum-exp of every row of logits [rows, V] (csrc/ctc.hip)
 __attribute__((visibility("hidden"))) int ctc_row_lse(const void* logits, float* lse, long rows, int V, int dtype, hipStream_t stream);
 
+// the same lse (bit for bit) with the entropy of every row, by the greedy detail decoder's frame function (csrc/ctc.hip)
+__attribute__((visibility("hidden"))) int ctc_row_lse_entropy(const void* logits, float* lse, float* entropy, long rows, int V, int dtype,
+                                                              hipStream_t stream);
+
 }  // namespace tfasr_detail

@@ -17,7 +17,7 @@ import torch
 from . import kernels as K
 from .conformer import ConformerEncoderMixin
 from .model import AsrModel
-from .schemas import AlignOutput, PredictInput, PredictOutput, RecognizeOutput, TrainData, TrainInput, TrainOutput
+from .schemas import AlignOutput, NBestOutput, PredictInput, PredictOutput, RecognizeOutput, TrainData, TrainInput, TrainOutput
 
 
 class CtcModel(AsrModel):
@@ -157,6 +157,30 @@ class CtcModel(AsrModel):
         logits, elen = self._infer_logits(inputs)
         return K.ctc_beam_search_lm(logits, self._h2d(elen), lm.tables(alpha, beta), beam_width=beam_width, top_paths=top_paths,
                                     blank_index=self.blank)
+
+    @torch.no_grad()
+    def recognize_nbest_detailed(self, inputs: PredictInput, beam_width=10, top_paths=4, lm=None, alpha=0.5, beta=0.0):
+        """recognize_nbest (or, with `lm`, recognize_nbest_lm) that also says when each token of each hypothesis was spoken and how sure the
+        model was -> NBestOutput.  One _infer_logits, the search, then ONE alignment of all B * P hypotheses against the same logits
+        (tfasr_ctc_nbest_align: the frame statistics once per utterance, the token array read in place), with the blank the search used:
+        the last class for the plain search (TF's convention, see recognize_beam), self.blank with an lm.  `search` is bit for bit what
+        recognize_nbest / recognize_nbest_lm return; a path past the last live beam (search score -inf) stays marked: path_scores -inf,
+        frames -1.  Columns past TFASR_ALIGN_CTC_MAX_U hold no times."""
+        if lm is not None:
+            self._check_lm(lm)
+        logits, elen = self._infer_logits(inputs)
+        elen_dev = self._h2d(elen)
+        if lm is None:
+            search = K.ctc_beam_search_device(logits, elen_dev, beam_width=beam_width, top_paths=top_paths, blank_index=None)
+            blank = self.cfg.vocab_size - 1
+        else:
+            search = K.ctc_beam_search_lm(logits, elen_dev, lm.tables(alpha, beta), beam_width=beam_width, top_paths=top_paths,
+                                          blank_index=self.blank)
+            blank = self.blank
+        tokens, lengths, score = search[:3]
+        live = torch.where(score == float("-inf"), torch.full_like(lengths, -1), lengths)  # dead paths, marked on the device
+        start, end, logp, ent, path = K.ctc_nbest_align(logits, elen_dev, tokens, live, blank=blank)
+        return NBestOutput(search, tokens, lengths, start, end, logp, ent, path, self.seconds_per_frame, self.cfg.vocab_size)
 
     @torch.no_grad()
     def align(self, data: TrainData, precision=None):

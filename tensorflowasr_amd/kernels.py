@@ -237,6 +237,62 @@ def ctc_align(logits, labels, label_len, logit_len, blank=0, normalized=False):
     return start, end, label_lp, score
 
 
+ALIGN_CTC_MAX_U = 511  # TFASR_ALIGN_CTC_MAX_U
+
+
+def row_lse_entropy(x):
+    """Log-sum-exp and entropy in nats of every row of x [..., V] (f32 | bf16, f32 arithmetic) -> (lse [...], entropy [...]) f32: a frame's
+    definitions in ctc_greedy_decode_detail, the lse bit for bit the one ctc_align subtracts (tfasr_row_lse_entropy)."""
+    assert x.dim() >= 1 and x.is_contiguous()
+    V = x.shape[-1]
+    rows = x.numel() // V
+    lse = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+    ent = torch.empty_like(lse)
+    check(_lib.load().tfasr_row_lse_entropy(_p(x), rows, V, _dt(x), _p(lse), _p(ent), _stream()), "row_lse_entropy")
+    return lse, ent
+
+
+def ctc_nbest_align_workspace_size(B, P, T, U, V):
+    n = ctypes.c_size_t(0)
+    _align_check(_lib.load().tfasr_ctc_nbest_align_workspace_size(B, P, T, U, V, ctypes.byref(n)), "ctc_nbest_align_workspace_size")
+    return n.value
+
+
+def ctc_nbest_align(logits, logit_len, tokens, lengths, blank=0, max_labels=None):
+    """CTC forced alignment of an n-best list to ONE copy of its utterance's logits (tfasr_ctc_nbest_align): logits [B,T,V] (f32 | bf16),
+    logit_len [B] i32, tokens [B,P,W] i32 (a search's token array, read in place through its row stride), lengths [B,P] i32.  Columns past
+    TFASR_ALIGN_CTC_MAX_U are not aligned.  -> (start, end [B,P,W] i32, label_lp, label_entropy [B,P,W] f32, score [B,P] f32): per
+    path what ctc_align gives for (logits[b], tokens[b,p], logit_len[b]), bit for bit, plus the mean frame entropy of every label's span.
+    lengths < 0 (a dead path) or > min(W, TFASR_ALIGN_CTC_MAX_U): score -inf, spans -1, zeros.  max_labels = U <= W: only the first U
+    columns are label columns (longer paths are dead) and the outputs are [B,P,U]; U > TFASR_ALIGN_CTC_MAX_U raises TfasrUnsupported.
+    max_labels is public on purpose: it is the C entry point's U beside ldl = W, for a caller who knows a bound on the hypotheses'
+    lengths (the walk runs one thread per state of the label width) or wants the C call's own refusal of a width."""
+    assert logits.dim() == 3 and tokens.dim() == 3 and tokens.dtype == torch.int32 and tokens.is_contiguous()
+    B, T, V = logits.shape
+    P, W = tokens.shape[1], tokens.shape[2]
+    assert tokens.shape[0] == B and lengths.shape == (B, P) and lengths.dtype == torch.int32 and logit_len.dtype == torch.int32
+    assert lengths.is_contiguous() and logit_len.shape == (B,)
+    dev = logits.device
+    U = min(W, ALIGN_CTC_MAX_U) if max_labels is None else int(max_labels)
+    assert 0 <= U <= W
+    start = torch.empty(B, P, U, dtype=torch.int32, device=dev)
+    end = torch.empty(B, P, U, dtype=torch.int32, device=dev)
+    label_lp = torch.empty(B, P, U, dtype=torch.float32, device=dev)
+    label_ent = torch.empty(B, P, U, dtype=torch.float32, device=dev)
+    score = torch.empty(B, P, dtype=torch.float32, device=dev)
+    ws = workspace(ctc_nbest_align_workspace_size(B, P, T, U, V), dev, "align")
+    q = (lambda t: _p(t) if U else None)
+    _align_check(_lib.load().tfasr_ctc_nbest_align(_p(logits), _p(logit_len), q(tokens), W, _p(lengths), B, P, T, U, V, blank, _dt(logits), q(start),
+                                                   q(end), q(label_lp), q(label_ent), _p(score), _p(ws), ws.numel(), _stream()), "ctc_nbest_align")
+    if max_labels is None and U < W:  # the columns no walk reaches: no label sits there
+        def wide(t, fill):
+            full = torch.full((B, P, W), fill, dtype=t.dtype, device=dev)
+            full[:, :, :U] = t
+            return full
+        start, end, label_lp, label_ent = wide(start, -1), wide(end, -1), wide(label_lp, 0.0), wide(label_ent, 0.0)
+    return start, end, label_lp, label_ent, score
+
+
 # ------------------------------------------------------------------------------------------ scoring
 def _edit_check(st, what):
     if st == _lib.STATUS_UNSUPPORTED:

@@ -66,6 +66,28 @@ class RecognizeOutput(typing.NamedTuple):
     vocab_size: int
 
 
+class NBestOutput(typing.NamedTuple):
+    """A beam search's n-best list with token times and confidences (model.recognize_nbest_detailed): every hypothesis aligned to the logits
+    the search read.  frames / ends / log_probs / entropies are aligned column by column with tokens; where no token sits, frames = ends =
+    -1 and log_probs = entropies = 0.  path(p) is hypothesis p as a RecognizeOutput."""
+    search: tuple  # what recognize_nbest / recognize_nbest_lm return for the same input, untouched
+    tokens: torch.Tensor  # [B, P, W] int32
+    lengths: torch.Tensor  # [B, P] int32
+    frames: torch.Tensor  # [B, P, W] int32: AlignOutput.frames of the hypothesis
+    ends: typing.Optional[torch.Tensor]  # [B, P, W] int32, CTC only; None for a transducer
+    log_probs: torch.Tensor  # [B, P, W] f32: AlignOutput.label_log_probs of the hypothesis
+    entropies: torch.Tensor  # [B, P, W] f32: entropy in nats of the distribution the token was read from (CTC: mean over its frames)
+    path_scores: torch.Tensor  # [B, P] f32: log-probability of the aligned path; -inf for a dead path, an over-long one, or one that does not fit
+    seconds_per_frame: float
+    vocab_size: int
+
+    def path(self, p):
+        """hypothesis p -> RecognizeOutput: token_times, token_confidences and word_details read it as they read a greedy result"""
+        predict = PredictOutput(tokens=self.tokens[:, p], next_tokens=None, next_encoder_states=None, next_decoder_states=None)
+        return RecognizeOutput(predict, self.frames[:, p], None if self.ends is None else self.ends[:, p], self.log_probs[:, p],
+                               self.entropies[:, p], self.path_scores[:, p], self.seconds_per_frame, self.vocab_size)
+
+
 def token_times(out):
     """Start time of every label in seconds, [B, U] f32 (-1 past the labels); AlignOutput or RecognizeOutput."""
     f = out.frames.to(torch.float32)

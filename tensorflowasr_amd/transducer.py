@@ -15,7 +15,7 @@ import torch
 from . import kernels as K
 from .kernels import ACT_TANH_OUT
 from .model import AsrModel, SingleProcess, _split_k
-from .schemas import AlignOutput, PredictInput, PredictOutput, RecognizeOutput, TrainData, TrainInput, TrainOutput
+from .schemas import AlignOutput, NBestOutput, PredictInput, PredictOutput, RecognizeOutput, TrainData, TrainInput, TrainOutput
 
 
 class TransducerModel(AsrModel):
@@ -517,6 +517,56 @@ class TransducerModel(AsrModel):
         tokens, lengths, scores, _, _ = self.recognize_beam_encoded(enc, elen, beam_width, top_paths, inputs.previous_tokens,
                                                                     inputs.previous_decoder_states)
         return tokens, lengths, scores
+
+    @torch.no_grad()
+    def recognize_nbest_detailed(self, inputs: PredictInput, beam_width=10, top_paths=4, precision=None):
+        """recognize_nbest that also says when each token of each hypothesis was spoken and how sure the model was -> NBestOutput (ends
+        None).  ONE encoder pass: recognize_beam_encoded on its output, then align_encoded on the same rows repeated once per path, with
+        the hypotheses as labels and their blank-prepended form as predictions - on the model align() would use (a bf16 model's f32
+        twin by default, whose encoder output `encode` already returned).  frames / log_probs are align_encoded's; entropies: the joint
+        activation of each label's emitting node (frames[u], u) is gathered, projected with the vocabulary weights (one product of
+        [B * P * U, joint_dim] rows) and reduced by tfasr_row_lse_entropy; for this the encoder projection and the prediction network of
+        the hypotheses run a second time, beside align_encoded's own.  path_scores: the alignment's score, -inf for a path past the last
+        live hypothesis.  The alignment starts from the blank and the zero state: other previous tokens or states are refused."""
+        if inputs.previous_tokens is not None or inputs.previous_decoder_states is not None:
+            raise ValueError("recognize_nbest_detailed aligns from the blank and the zero prediction state: previous_tokens / "
+                             "previous_decoder_states must be None")
+        enc, elen = self.encode(inputs.inputs, inputs.inputs_length, precision)
+        toks, lengths, scores, _, _ = self.recognize_beam_encoded(enc, elen, beam_width, top_paths)
+        al = self.inference_twin() if (precision or self.decode_precision) == "f32" else self  # align()'s rule; enc has al's type
+        dev, c = self.device, self.cfg
+        B, NP, W = toks.shape
+        T, J, V = enc.shape[1], c.joint_dim, c.vocab_size
+        R = B * NP
+        n = lengths.reshape(R).clamp(min=0)
+        U = int(n.max().item())
+        frames = torch.full((B, NP, W), -1, dtype=torch.int32, device=dev)
+        logp = torch.zeros(B, NP, W, dtype=torch.float32, device=dev)
+        ent = torch.zeros(B, NP, W, dtype=torch.float32, device=dev)
+        lab = toks.reshape(R, W)[:, :U].contiguous()
+        pred_tok = torch.cat([torch.full((R, 1), self.blank, dtype=torch.int32, device=dev), lab], 1)
+        elen_r = [int(v) for v in elen for _ in range(NP)]
+        a = al.align_encoded(enc.repeat_interleave(NP, 0), elen_r, pred_tok, lab, n.cpu())
+        dead = scores == float("-inf")
+        path = torch.where(dead, scores, a.scores.view(B, NP))
+        if U > 0:
+            fr = torch.where(dead.view(R, 1), torch.full_like(a.frames, -1), a.frames)
+            lp = torch.where(fr >= 0, a.label_log_probs, torch.zeros_like(a.label_log_probs))
+            # the emitting node of label u is (frames[u], u): encoder row b * T + frames[u], prediction row r * (U + 1) + u
+            # (all B * T encoder rows are projected: the B * P * U gathered rows are not fewer in general, and repeat rows)
+            e = K.matmul(enc.reshape(B * T, enc.shape[2]).contiguous(), al.ps.w2d("joint/enc/w"), bias=al.ps.p("joint/enc/b"))
+            p = K.matmul(al.prediction_fwd(pred_tok.contiguous(), (n + 1).to(torch.int32), None), al.ps.w2d("joint/pred/w"),
+                         bias=al.ps.p("joint/pred/b"))
+            rows = torch.arange(R, device=dev).view(R, 1)
+            ei = ((rows // NP) * T + fr.clamp(min=0)).reshape(-1)
+            pi = (rows * (U + 1) + torch.arange(U, device=dev).view(1, U)).reshape(-1)
+            h = K.joint_fwd(e.index_select(0, ei).view(R * U, 1, J), p.index_select(0, pi).view(R * U, 1, J)).view(R * U, J)
+            logits = K.matmul(h, al.ps.w2d("joint/vocab/w"), bias=al.ps.p("joint/vocab/b"))
+            h_ent = K.row_lse_entropy(logits.view(R * U, V))[1].view(R, U)
+            frames[:, :, :U] = fr.view(B, NP, U)
+            logp[:, :, :U] = lp.view(B, NP, U)
+            ent[:, :, :U] = torch.where(fr >= 0, h_ent, torch.zeros_like(h_ent)).view(B, NP, U)
+        return NBestOutput((toks, lengths, scores), toks, lengths, frames, None, logp, ent, path, self.seconds_per_frame, V)
 
     @torch.no_grad()
     def recognize_beam_encoded(self, enc, elen, beam_width=10, top_paths=1, previous_tokens=None, previous_decoder_states=None):
